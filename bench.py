@@ -2,7 +2,7 @@
 """Benchmark of the CMGAN generator forward path on MI355X (BASELINE.json metric:
 enhanced audio frames/sec, 16 kHz, 2 s clips, batch 32 per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 16k|48k]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 16k|48k] [--dump-outputs DIR]
 
 A "step" = one pass of the whole device pipeline (RMS scale -> STFT -> power compress ->
 TSCNet -> power uncompress -> ISTFT) over one batch of synthetic 2 s clips per GPU that are
@@ -403,6 +403,35 @@ def workload_48k_leg(dev, mfma_mode, steps=5):
             "value": round(sh.B * sh.T / dt, 1), "unit": "frames/s", "frames_per_clip": sh.T, "launch": "hipGraph replay"}
 
 
+DUMP_BUDGET_BYTES = 64 * 10**6
+
+
+def dump_outputs(path, audio, loss_terms, rank, world):
+    """--dump-outputs: what the last timed step returned, as float32 .npy files - enhanced_audio [B, L] (rank r > 0 of a
+    multi-rank run: enhanced_audio.rank<r>.npy, its own shard) and, from rank 0, time_loss_terms [2] (time_loss,
+    time_mse, summed over the ranks by the step's all-reduce).  An audio shard over its rank's part of the 64 MB budget
+    is cut to a fixed sample of clips (rows np.random.default_rng(0).choice(B, k, replace=False), sorted) and saved as
+    enhanced_audio_sample[.rank<r>].npy.  A directory created here gets a `*` .gitignore, like pytest's cache."""
+    import numpy as np
+    try:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        os.mkdir(path)
+        with open(os.path.join(path, ".gitignore"), "w") as f:
+            f.write("*\n")
+    except FileExistsError:
+        pass
+    suffix = f".rank{rank}" if rank > 0 else ""
+    a = audio.detach().float().cpu().numpy()
+    share = (DUMP_BUDGET_BYTES - 4096) // world
+    name = "enhanced_audio"
+    if a.nbytes > share:
+        k = max(1, share // (a.shape[1] * 4))
+        a, name = a[np.sort(np.random.default_rng(0).choice(a.shape[0], k, replace=False))], "enhanced_audio_sample"
+    np.save(os.path.join(path, name + suffix + ".npy"), a)
+    if rank == 0:
+        np.save(os.path.join(path, "time_loss_terms.npy"), loss_terms.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -427,9 +456,16 @@ def main():
     ap.add_argument("--stub-cpu", action="store_true",
                     help="launcher / collective self-test without a GPU: gloo backend, the forward replaced by a "
                          "trivial CPU op (tests/test_bench_launcher.py); prints a line marked \"stub\": true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (enhanced audio, the "
+                         "all-reduced time-loss scalars) as DIR/<name>.npy in float32, at most 64 MB in all, so that "
+                         "two builds can be compared output for output (the inputs are seeded: same arguments, same "
+                         "inputs)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args))
@@ -509,7 +545,7 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        out = step()
     sync()
     own = time.perf_counter() - t0                            # this rank's K steps
     barrier()
@@ -520,6 +556,9 @@ def main():
     if world > 1 or cdist._active():
         torch.distributed.all_gather(per_rank, et)
     elapsed = max(float(t[0]) for t in per_rank)              # MAX over ranks
+    if args.dump_outputs:
+        # before anything else runs: the graphed forward returns a static buffer that the next call overwrites
+        dump_outputs(args.dump_outputs, out, scal[2:4], rank, world)
     unit_frames = sh.B * sh.T if not args.stub_cpu else 2 * 17
     per_rank_fps = [unit_frames * args.steps / float(t[1]) for t in per_rank]
     loss_scalars = [float(v) / world for v in scal[2:4].tolist()]

@@ -52,3 +52,28 @@ def test_more_gpus_than_visible_fails_loudly_instead_of_falling_back():
     r = _run(["--gpus", str(have + 2), "--steps", "1", "--warmup", "0", "--no-cpu-baseline"])
     assert r.returncode == 2 and "refusing to fall back" in r.stderr
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_dump_outputs_writes_the_last_timed_step_and_is_reproducible(tmp_path):
+    """--dump-outputs DIR: the last timed step's outputs as float32 .npy files, identical from run to run with the same
+    arguments (seeded inputs), one audio shard per rank, in a directory that ignores itself for git."""
+    import numpy as np
+    dumps = []
+    for i, extra in enumerate((["--gpus", "2", "--steps", "3", "--warmup", "1"], ["--gpus", "2", "--steps", "2", "--warmup", "0"])):
+        d = tmp_path / f"run{i}"
+        r = _run([*extra, "--stub-cpu", "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+        assert line["steps"] == int(extra[3]) and line["ms_per_step"] > 0
+        assert sorted(os.listdir(d)) == [".gitignore", "enhanced_audio.npy", "enhanced_audio.rank1.npy", "time_loss_terms.npy"]
+        assert (d / ".gitignore").read_text() == "*\n"
+        dumps.append({n: np.load(d / n) for n in os.listdir(d) if n.endswith(".npy")})
+    for n, a in dumps[0].items():
+        assert a.dtype == np.float32 and np.array_equal(a, dumps[1][n]), n
+    assert dumps[0]["enhanced_audio.npy"].shape == (2, 1600) and dumps[0]["time_loss_terms.npy"].shape == (2,)
+    assert not np.array_equal(dumps[0]["enhanced_audio.npy"], dumps[0]["enhanced_audio.rank1.npy"])     # own shard per rank
+
+
+def test_steps_below_one_is_an_argument_error():
+    r = _run(["--steps", "0", "--stub-cpu"])
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr

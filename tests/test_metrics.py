@@ -95,21 +95,3 @@ def test_logged_scores_of_the_reference_tool_on_its_shipped_tracks(name, tmp_pat
     wavfile.write(b, 16000, noisy)
     got1 = M.compute_metrics(a, b, 0, 1, pesq_mos=pesq_mos)
     assert max(abs(a_ - b_) for a_, b_ in zip(got1[1:], want)) < 1e-6
-
-
-def test_all_shipped_tracks_against_the_log_when_the_reference_tree_is_here():
-    ref = "/root/reference/AudioSamples"
-    if not os.path.isdir(ref):
-        pytest.skip("no /root/reference here")
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
-    from make_metrics_known_answers import logged
-    from scipy.io import wavfile
-    log, worst = logged(), 0.0
-    names = sorted(os.path.splitext(f)[0] for f in os.listdir(os.path.join(ref, "noisy")))
-    assert len(names) == 25
-    for n in names:
-        got = M.compute_metrics(os.path.join(ref, "clean", n + ".wav"), os.path.join(ref, "noisy", n + ".wav"), 0, 1,
-                                pesq_mos=log[n][0])
-        worst = max(worst, max(abs(a - b) for a, b in zip(got[1:], log[n][1:])))
-    assert worst < 1e-6, worst

@@ -1,6 +1,6 @@
 """GraphedTrainStep: parity with the eager step (dropout off) and replay timing (dropout on)."""
-import sys, time, torch
-sys.path.insert(0, '/root/repo')
+import os, sys, time, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from cmgan_amd.synth import discriminator_state_dict, make_state_dict, synthetic_clips
 from cmgan_amd.training import (AdamW, DiscriminatorTrain, GeneratorTrain, GraphedTrainStep, adversarial_train_step,
                                 generator_train_step)
