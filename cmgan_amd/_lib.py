@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_longlong, c_size_t, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_longlong, c_size_t, c_void_p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # CMGAN_HIP_LIB selects an alternative BUILD of the same HIP library (cmgan_amd.build variants, used for
@@ -176,6 +176,10 @@ SIGNATURES = {
                                      c_size_t, c_void_p]),
     "cmgan_selftest_mfma": (c_int, [c_void_p, POINTER(c_float)]),
     "cmgan_selftest_mfma_x3": (c_int, [c_void_p, POINTER(c_float)]),
+    "cmgan_metrics_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "cmgan_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_double, c_void_p, c_void_p,
+                              c_void_p, c_size_t, c_void_p]),
+    "cmgan_metrics_table": (c_int, [c_int, c_int, c_void_p, c_size_t]),
     "cmgan_set_profiling": (c_int, [c_void_p, c_int]),
     "cmgan_profile_read": (c_int, [c_void_p, POINTER(KernelTime), c_int]),
 }

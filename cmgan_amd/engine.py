@@ -7,7 +7,7 @@ PyTorch is used only for device memory and streams: every method takes CUDA (ROC
 from __future__ import annotations
 
 import ctypes
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -39,6 +39,36 @@ def _on_device(fn):
         with torch.cuda.device(self.device):
             return fn(self, *a, **k)
     return wrapper
+
+
+_EPS = float(np.spacing(1.0))
+
+
+class DeviceScores(NamedTuple):
+    """Engine.metrics: float64 [B] device tensors; the first six are cmgan_amd.metrics.Scores' fields."""
+    pesq: torch.Tensor
+    csig: torch.Tensor
+    cbak: torch.Tensor
+    covl: torch.Tensor
+    ssnr: torch.Tensor
+    stoi: torch.Tensor
+    wss: torch.Tensor
+    llr: torch.Tensor
+    snr: torch.Tensor
+
+
+class FrameScores(NamedTuple):
+    """Engine.metrics(per_frame=True): per-frame WSS, LLR and clipped segmental SNR, [B, frames] float64."""
+    wss: torch.Tensor
+    llr: torch.Tensor
+    segsnr: torch.Tensor
+
+
+def metric_frames(L: int, fs: int):
+    """(WSS / segSNR frames, LLR frames) of an L-sample signal: the two counts of cmgan_amd.metrics."""
+    win = int(np.round(30 * fs / 1000))
+    hop = win // 4
+    return int(L / hop - win / hop), int((L - win) / hop)
 
 
 #: kernel families (names of _lib.MIX) that run ONE fp16 product in mfma_mode="f16mix".  The ablation
@@ -98,6 +128,7 @@ class Engine:
         self._ws: Optional[torch.Tensor] = None
         self._cws: Optional[torch.Tensor] = None
         self._bws: Optional[torch.Tensor] = None          # workspace of the two-branch form (enhance_graphed(branches=2))
+        self._mws: Optional[torch.Tensor] = None          # workspace of metrics()
         self._graphs: dict = {}          # enhance_graphed: input shape -> (graph, in, out, token)
         self._row_graphs: dict = {}      # streaming.enhance_windows: row shape -> (graph, in, out, token)
         self._stream_slots: dict = {}    # streaming.StreamState(graph=True): (B, W, Ca, La) -> state buffers + step graphs
@@ -510,6 +541,58 @@ class Engine:
                                                  self._in(out, "out").data_ptr(), self._stream()))
         return out
 
+    # ---- objective metrics ---------------------------------------------------------
+    @_on_device
+    def metrics(self, clean: torch.Tensor, enhanced: torch.Tensor, fs: int = 16000, pesq_mos=None,
+                per_frame: bool = False):
+        """Objective scores of B pairs on the GPU (cmgan_metrics; host twin: cmgan_amd.metrics.compute_metrics).
+
+        clean, enhanced: float32 device tensors [B, L] (or [L]).  Unequal lengths are handled like the reference tool:
+        both are trimmed to the shorter one and eps is added to every sample.  pesq_mos: a float or a [B] tensor (the
+        composites need it; None gives NaN composites).  Returns DeviceScores of float64 [B] device tensors (pesq, csig,
+        cbak, covl, ssnr, stoi, wss, llr, snr); with per_frame=True also FrameScores (wss [B, nf_wss], llr [B, nf_llr],
+        segsnr [B, nf_wss]).  Needs no weights and does not synchronise."""
+        clean, enhanced = self._in(clean, "clean"), self._in(enhanced, "enhanced")
+        if clean.dim() == 1:
+            clean = clean[None]
+        if enhanced.dim() == 1:
+            enhanced = enhanced[None]
+        if clean.dim() != 2 or enhanced.dim() != 2 or clean.size(0) != enhanced.size(0):
+            raise ValueError(f"expected two [B, L] tensors, got {tuple(clean.shape)} / {tuple(enhanced.shape)}")
+        offset = 0.0
+        if clean.size(1) != enhanced.size(1):                   # compute_metrics.py:41-44
+            n = min(clean.size(1), enhanced.size(1))
+            clean, enhanced = clean[:, :n].contiguous(), enhanced[:, :n].contiguous()
+            offset = _EPS
+        B, L = clean.shape
+        need = int(self.lib.cmgan_metrics_workspace_bytes(self._h, B, L, fs))
+        if need == 0:
+            rc = self.lib.cmgan_metrics_table(fs, 0, None, 0)
+            if rc < 0:
+                raise _lib.CmganError(rc, f"unsupported sample rate {fs} (16000 or 8000)")
+            raise ValueError(f"[{B}, {L}] at fs={fs} is too short to score (one 30-frame STOI window is needed)")
+        if self._mws is None or self._mws.numel() < need:
+            self._mws = None
+            self._mws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        pesq_ptr = None
+        if pesq_mos is not None:
+            if isinstance(pesq_mos, torch.Tensor):
+                pesq = pesq_mos.to(device=self.device, dtype=torch.float64).reshape(-1).expand(B).contiguous()
+            else:
+                pesq = torch.full((B,), float(pesq_mos), dtype=torch.float64, device=self.device)
+            pesq_ptr = pesq.data_ptr()
+        scores = torch.empty(B, 9, dtype=torch.float64, device=self.device)
+        nfw, nfl = metric_frames(L, fs)
+        nf = max(nfw, nfl)
+        frames = torch.empty(B, 3, nf, dtype=torch.float64, device=self.device) if per_frame else None
+        check(self._h, self.lib.cmgan_metrics(self._h, clean.data_ptr(), enhanced.data_ptr(), B, L, fs, pesq_ptr,
+                                              offset, scores.data_ptr(), frames.data_ptr() if per_frame else None,
+                                              self._mws.data_ptr(), self._mws.numel(), self._stream()))
+        out = DeviceScores(*scores.unbind(1))
+        if not per_frame:
+            return out
+        return out, FrameScores(frames[:, 0, :nfw], frames[:, 1, :nfl], frames[:, 2, :nfw])
+
     # ---- diagnostics ---------------------------------------------------------------
     @_on_device
     def selftest_mfma(self) -> float:
@@ -529,7 +612,7 @@ class Engine:
         self._graphs.clear()
         self._row_graphs.clear()
         self._stream_slots.clear()
-        self._ws = self._bws = self._cws = None
+        self._ws = self._bws = self._cws = self._mws = None
 
     def set_profiling(self, on: bool):
         check(self._h, self.lib.cmgan_set_profiling(self._h, 1 if on else 0))

@@ -1,7 +1,8 @@
 """Mirror of the reference's evaluation script (src/evaluation.py): ``enhance_one_track`` (:12-58, same
 argument meaning, same padding / >cut_len chunking rule, same output, every device op a HIP kernel; the
 host code is shape logic only) and the directory driver ``evaluation`` (:61-100) that scores the enhanced
-tracks with cmgan_amd.metrics."""
+tracks on the GPU with Engine.metrics (the kernels of cmgan_amd/csrc/metrics.hip; cmgan_amd.metrics is their
+host twin)."""
 from __future__ import annotations
 
 import math
@@ -90,7 +91,9 @@ def evaluation(model, noisy_dir: str, clean_dir: str, save_tracks: bool = False,
     `pesq` wheel lookup of cmgan_amd.metrics.  The reference imports `pesq` unconditionally and fails without
     it (compute_metrics.py:7); so does this driver (ImportError) unless `allow_missing_pesq=True`, in which case
     the four PESQ-dependent averages are NaN and a warning says so.  Saved tracks are 16-bit PCM like the
-    reference's `sf.write(path, est, sr)` default (`subtype="FLOAT"` keeps float32 samples instead)."""
+    reference's `sf.write(path, est, sr)` default (`subtype="FLOAT"` keeps float32 samples instead).  Each track is scored
+on the GPU (`model.engine.metrics`, float64 arithmetic on the float32 device samples); the enhanced track is copied to
+the host only when it is saved or `pesq_fn` needs it."""
     from . import metrics
     n_fft = 400
     if isinstance(model, (str, os.PathLike)):
@@ -112,27 +115,32 @@ def evaluation(model, noisy_dir: str, clean_dir: str, save_tracks: bool = False,
     names = sorted((f for f in os.listdir(noisy_dir) if f.lower().endswith(".wav")), key=_natural_key)
     if not names:
         raise ValueError(f"no .wav files in {noisy_dir}")
-    total = np.zeros(6)
-    dev = torch.device(model.engine.device)
+    eng = model.engine
+    dev = torch.device(eng.device)
+    fn = pesq_fn if pesq_fn is not None else metrics._default_pesq()
+    total = torch.zeros(6, dtype=torch.float64, device=dev)       # per-track scores summed on the device, in order
     for name in names:
         noisy, sr = _read_wav(os.path.join(noisy_dir, name))
         if sr != 16000:
             raise ValueError(f"{name}: expected 16 kHz audio, got {sr}")           # evaluation.py:19
         est = enhance_one_track(model, torch.from_numpy(noisy).to(dev, torch.float32)[None, :],
-                                16000 * 16, n_fft, n_fft // 4).cpu().numpy().astype(np.float64)
+                                16000 * 16, n_fft, n_fft // 4)
+        est_host = est.cpu().numpy().astype(np.float64) if (save_tracks or fn is not None) else None
         if save_tracks:
             from scipy.io import wavfile
             if subtype == "PCM_16":     # libsndfile's float -> int16 conversion: scale by 2^15, round, clip
-                pcm = np.clip(np.rint(est * 32768.0), -32768, 32767).astype(np.int16)
+                pcm = np.clip(np.rint(est_host * 32768.0), -32768, 32767).astype(np.int16)
                 wavfile.write(os.path.join(saved_dir, name), sr, pcm)
             else:
-                wavfile.write(os.path.join(saved_dir, name), sr, est.astype(np.float32))
+                wavfile.write(os.path.join(saved_dir, name), sr, est_host.astype(np.float32))
         clean, sr_c = _read_wav(os.path.join(clean_dir, name))
         if sr_c != 16000:
             raise ValueError(f"{name}: clean file is not 16 kHz")
-        mos = None if pesq_fn is None else float(pesq_fn(sr, clean, est))
-        total += np.array(metrics.compute_metrics(clean, est, sr, 0, pesq_mos=mos))
-    avg = metrics.Scores(*(total / len(names)))
+        mos = None if fn is None else float(fn(sr, clean, est_host))
+        # scored on the GPU (cmgan_metrics); unequal lengths are trimmed with the reference's eps offset
+        s = eng.metrics(torch.from_numpy(clean).to(dev, torch.float32)[None, :], est[None, :], sr, pesq_mos=mos)
+        total += torch.stack(tuple(s[:6]), dim=1)[0]
+    avg = metrics.Scores(*(total / len(names)).tolist())
     if verbose:
         print("pesq: ", avg.pesq, "csig: ", avg.csig, "cbak: ", avg.cbak, "covl: ", avg.covl,
               "ssnr: ", avg.ssnr, "stoi: ", avg.stoi)

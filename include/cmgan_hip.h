@@ -514,6 +514,29 @@ int cmgan_selftest_mfma(cmgan_handle* h, float* max_err_host);
 /* Same for the f16 16x16x32 MFMA + split-product images of the F16X3 mode. */
 int cmgan_selftest_mfma_x3(cmgan_handle* h, float* max_err_host);
 
+/* ---- Objective speech metrics (src/tools/compute_metrics.py; host twin: cmgan_amd/metrics.py) --------------------
+ * Scores B equal-length float32 pairs [B, L] (clean, enhanced) in float64: per row
+ *   scores_dev[b][9] = pesq csig cbak covl ssnr stoi wss llr snr
+ * (wss / llr: the 95 % trimmed means; snr: the overall SNR in dB; csig / cbak / covl from the caller's PESQ,
+ * pesq_dev[b], or NaN when pesq_dev is NULL - PESQ itself is not computed here).  frames_dev, when not NULL, receives
+ * [B][3][nf] per-frame WSS, LLR and clipped segmental SNR, nf = max(nf_wss, nf_llr) with
+ * nf_wss = int(L / hop - win / hop), nf_llr = int((L - win) / hop) (win / hop = 480 / 120 at 16 kHz, 240 / 60 at
+ * 8 kHz); entries past a measure's own count are NaN.  `offset` is added to every widened sample (the reference adds
+ * eps to both signals when it trims unequal lengths; 0 otherwise).  fs = 16000 or 8000, else CMGAN_E_UNSUPPORTED.
+ * CMGAN_E_BADSHAPE when L < win or L is too short for one 30-frame STOI window (at least 31 frames of 256 samples at
+ * 10 kHz).  Difference from the host: a row whose STOI silence removal keeps fewer than 31 frames (so no 30-frame
+ * window) gets stoi = NaN where the host tool raises.  Workspace: cmgan_metrics_workspace_bytes (h may be NULL; 0 for
+ * an invalid shape), 256-byte aligned.  No synchronisation; graph-capturable.                                   */
+size_t cmgan_metrics_workspace_bytes(const cmgan_handle* h, int B, int L, int fs);
+int cmgan_metrics(cmgan_handle* h, const float* clean_dev, const float* enh_dev, int B, int L, int fs,
+                  const double* pesq_dev, double offset, double* scores_dev, double* frames_dev,
+                  void* workspace_dev, size_t workspace_bytes, void* stream);
+/* Host-side export of the tables the metric kernels build (same C++ code), for tests: which = 0 analysis taper [win],
+ * 1 WSS bank [25 first bins, 25 counts, 25 x 64 weights], 2 STOI bands [kept, then (first, end) bin pairs],
+ * 3 STOI inner Hann window [256], 4 resample_poly FIR to 10 kHz [zero pre-pad + taps].  out_host NULL: returns the
+ * count; otherwise writes it (cap >= count) and returns it.  Negative CMGAN_E_* on error.                          */
+int cmgan_metrics_table(int fs, int which, double* out_host, size_t cap);
+
 /* Names + durations (ms) of the kernels of the most recent forward when
  * profiling is enabled with cmgan_set_profiling(h, 1): HIP events are recorded
  * around every launch on the caller's stream.  cmgan_profile_read synchronises
