@@ -2,7 +2,7 @@
 """Benchmark of the CMGAN generator forward path on MI355X (BASELINE.json metric:
 enhanced audio frames/sec, 16 kHz, 2 s clips, batch 32 per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 16k|48k] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 16k|48k] [--dump-outputs DIR] [--full]
 
 A "step" = one pass of the whole device pipeline (RMS scale -> STFT -> power compress ->
 TSCNet -> power uncompress -> ISTFT) over one batch of synthetic 2 s clips per GPU that are
@@ -16,6 +16,11 @@ the reference's mp.spawn in src/train.py:294-297) unless it is already running a
 such a launch (WORLD_SIZE set by the driver); a world size that differs from --gpus, or fewer
 visible GPUs than requested, is a hard error - never a silent 1-GPU run.  Rank 0 prints one
 JSON line.
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: the headline figure
+and what follows from it without another run (path TFLOP/s, csrc_digest).  `--full` adds the legs that take runs of
+their own: the live per-kernel table and rooflines, the f32 / f16x1 / f16mix modes, BASELINE configs[3] (48 kHz) and
+configs[4] (streaming), the training step (configs[2]) and the CPU baseline; the --no-* options skip single legs of it.
 """
 import argparse
 import json
@@ -439,15 +444,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="16k")
     ap.add_argument("--batch", type=int, default=None, help="clips per GPU (default: the workload's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every secondary leg of the line: per-kernel table and rooflines, "
+                         "f32 / f16x1 / f16mix modes, configs[3] and [4], the training step, the CPU baseline "
+                         "(the --no-* options below skip single legs of a --full run)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline leg")
     ap.add_argument("--no-f16x1", action="store_true",
-                    help="skip the reduced-precision (single fp16 product) mode leg of the line")
-    ap.add_argument("--no-f32", action="store_true", help="skip the bit-exact fp32-MFMA mode leg of the line")
+                    help="--full: skip the reduced-precision (single fp16 product) mode leg of the line")
+    ap.add_argument("--no-f32", action="store_true", help="--full: skip the bit-exact fp32-MFMA mode leg of the line")
     ap.add_argument("--no-train", action="store_true",
-                    help="skip the training-step leg (BASELINE configs[2]: adversarial train steps at 32 clips per GPU "
-                         "with the gradient all-reduces over the flat buckets)")
+                    help="--full: skip the training-step leg (BASELINE configs[2]: adversarial train steps at 32 clips per "
+                         "GPU with the gradient all-reduces over the flat buckets)")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the configs[3] (48 kHz) and configs[4] (10 s clip in 400-frame windows) legs of the line")
+                    help="--full: skip the configs[3] (48 kHz) and configs[4] (10 s clip in 400-frame windows) legs of "
+                         "the line")
     ap.add_argument("--train-batch", type=int, default=32, help="clips per GPU of the training-step leg (configs[2]: 32)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
     ap.add_argument("--mfma-mode", choices=["f16x3", "f32"], default="f16x3",
@@ -484,6 +494,7 @@ def main():
         wl["batch"] = args.batch
     sh = Shape(wl)
     x3 = args.mfma_mode == "f16x3"
+    peak_tf = F16_MFMA_PEAK_TF if x3 else FP32_MFMA_PEAK_TF
 
     if args.stub_cpu:
         dev = torch.device("cpu")
@@ -589,20 +600,21 @@ def main():
         if args.stub_cpu:
             line["stub"] = True
             line["config"]["workload"] = "launcher self-test (CPU stub, gloo)"
+        else:
+            total_flop = path_flops_per_clip(sh) * sh.B                  # algorithmic, fusion-independent
+            line["csrc_digest"] = csrc_digest()
+            line["path_tflops"] = round(total_flop / (ms_per_step * 1e-3) / 1e12, 2)
+            line["path_frac_of_mfma_peak"] = round(total_flop / (ms_per_step * 1e-3) / 1e12 / peak_tf, 4)
 
-    if not args.stub_cpu:
+    # ---- --full: the secondary legs, each a run of its own after the headline --------------------------------------
+    if args.full and not args.stub_cpu:
         kern = kernel_table(eng, wav)
         if rank == 0:
-            total_flop = path_flops_per_clip(sh) * sh.B                  # algorithmic, fusion-independent
-            peak_tf = F16_MFMA_PEAK_TF if x3 else FP32_MFMA_PEAK_TF
             pmc, src, why = load_pmc_traffic(x3, sh, args.workload)
             roof, dom = roofline_of(kern, sh, x3, pmc, src)
             if pmc is None:
                 roof["traffic_note"] = why
             fl, hb = flops_per_clip(sh), hbm_bytes_per_clip(sh)
-            line["csrc_digest"] = csrc_digest()
-            line["path_tflops"] = round(total_flop / (ms_per_step * 1e-3) / 1e12, 2)
-            line["path_frac_of_mfma_peak"] = round(total_flop / (ms_per_step * 1e-3) / 1e12 / peak_tf, 4)
             line["roofline"] = roof
             line["kernels_ms_per_step"] = {k: round(v["ms_per_step"], 4)
                                            for k, v in sorted(kern.items(), key=lambda kv: -kv[1]["ms_per_step"])}
@@ -711,7 +723,7 @@ def main():
                 line["train_step"] = tr
         if rank == 0 and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(sd, sh)
-    elif not args.no_train:
+    elif args.full and not args.no_train:
         # launcher self-test of the same collective shape: a flat gradient bucket averaged over the gloo ranks
         b = cdist.FlatBucket({"w": (1000,), "b": (7,)})
         b.flat.fill_(float(rank + 1))

@@ -18,7 +18,7 @@ def _run(args, env_extra=None, drop=("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER
 
 
 def test_gpus_2_launches_two_ranks_and_reports_them():
-    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--stub-cpu"])
+    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--stub-cpu", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout                       # rank 0 only
@@ -38,6 +38,19 @@ def test_single_process_stub_line():
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert d["n_gpus"] == 1 and d["collective"]["ranks_seen"] == 1
+
+
+def test_plain_run_leaves_the_secondary_legs_to_full():
+    """Without --full the run is the headline alone: no leg that takes a run of its own (here the training leg's
+    collective self-test) is in the line; --no-* options only trim a --full run."""
+    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--stub-cpu"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert d["n_gpus"] == 2 and d["steps"] == 2 and d["ms_per_step"] > 0 and "train_step" not in d
+    r = _run(["--steps", "2", "--warmup", "1", "--stub-cpu", "--full", "--no-train"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert "train_step" not in d
 
 
 def test_world_size_mismatch_is_a_hard_error():

@@ -1,5 +1,5 @@
 #!/bin/bash
-# evidence session of a round (tag r05 / r06): full GPU suite, smoke, the default bench line, kernel trace + separate PMC passes of the
+# evidence session of a round (tag r05 / r06): full GPU suite, smoke, the full bench line (bench.py --full), kernel trace + separate PMC passes of the
 # inference command (raw rocpd databases KEPT under gpurun_out/), stall / instruction-mix / exact fabric-byte counters,
 # batch sweep
 TAG=${1:-r05}
@@ -7,8 +7,8 @@ OUT=$PWD/gpurun_out; REPO=$PWD; mkdir -p $OUT
 timeout 1800 python -m pytest tests -m gpu -q -s -p no:cacheprovider > $OUT/pytest_gpu_$TAG.log 2>&1
 echo "pytest exit $?"; grep -E "passed|failed" $OUT/pytest_gpu_$TAG.log | tail -2
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-timeout 900 python bench.py > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; echo "bench exit $?"
-BENCH="$REPO/bench.py --no-cpu-baseline --no-f32 --no-f16x1 --no-train --no-extra"
+timeout 900 python bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; echo "bench exit $?"
+BENCH="$REPO/bench.py --full --no-cpu-baseline --no-f32 --no-f16x1 --no-train --no-extra"
 cd /tmp && export TMPDIR=/tmp
 # the headline replays a hipGraph with TWO half-batch branches (round 6); its trace is kept separately, and every per-kernel
 # pass below runs the one-stream form (CMGAN_BRANCHES=1) so that a launch is the full 32-clip launch bench.py's live table

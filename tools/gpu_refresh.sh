@@ -1,11 +1,11 @@
 #!/bin/bash
-# quick refresh after a late change of an inference source: parity of the TSCNet path, bench line, kernel trace + the three
+# quick refresh after a late change of an inference source: parity of the TSCNet path, full bench line, kernel trace + the three
 # PMC passes behind profiles/<tag>_x3_{kernel_trace_stats,pmc,hbm_traffic}
 TAG=${1:-r05}
 OUT=$PWD/gpurun_out; REPO=$PWD; mkdir -p $OUT
 python -m pytest tests/test_gpu_parity.py -x -q -k "tscnet or config2 or references_own or enhance or stream_encoder or shard" 2>&1 | tail -3
-timeout 900 python bench.py > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; echo "bench exit $?"
-BENCH="$REPO/bench.py --no-cpu-baseline --no-f32 --no-f16x1 --no-train --no-extra"
+timeout 900 python bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; echo "bench exit $?"
+BENCH="$REPO/bench.py --full --no-cpu-baseline --no-f32 --no-f16x1 --no-train --no-extra"
 cd /tmp && export TMPDIR=/tmp
 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_$TAG -o trace -- python $BENCH --steps 3 --warmup 1 > $OUT/prof_$TAG.log 2>&1; echo "trace $?"
 i=0

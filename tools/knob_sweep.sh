@@ -6,7 +6,7 @@ OUT=gpurun_out; mkdir -p $OUT
 run() {
   local combo="$1" tag="$2"
   ( if [ "$combo" != "-" ]; then for kv in $(echo "$combo" | tr ',' ' '); do export "$kv"; done; fi
-    timeout 300 python bench.py --no-cpu-baseline --no-f32 --no-f16x1 --no-train --no-extra --steps 10 --warmup 3 > $OUT/knob_$tag.json 2>$OUT/knob_$tag.err )
+    timeout 300 python bench.py --full --no-cpu-baseline --no-f32 --no-f16x1 --no-train --no-extra --steps 10 --warmup 3 > $OUT/knob_$tag.json 2>$OUT/knob_$tag.err )
   python - "$combo" "$OUT/knob_$tag.json" <<'PY'
 import json, sys
 try:

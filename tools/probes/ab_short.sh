@@ -4,7 +4,7 @@ CMGAN_HIP_LIB=$V timeout 120 python -m pytest tests/test_gpu_parity.py -m gpu -q
 for round in 1 2; do
   for v in default ffnpf8 ; do
     if [ "$v" = default ]; then unset CMGAN_HIP_LIB; else export CMGAN_HIP_LIB=$V; fi
-    timeout 120 python bench.py --no-cpu-baseline --no-f32 --no-train --steps 10 --warmup 3 > $OUT/ab_${v}_$round.json 2>/dev/null
+    timeout 120 python bench.py --full --no-cpu-baseline --no-f32 --no-train --steps 10 --warmup 3 > $OUT/ab_${v}_$round.json 2>/dev/null
     python - "$v" "$round" "$OUT/ab_${v}_$round.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[3]))
