@@ -121,6 +121,23 @@ extern "C" int cmgan_create(cmgan_handle** out, const cmgan_config* cfg) {
         delete h;
         return CMGAN_E_HIP;
     }
+    // the dense DFT kernels stage a block's frames / spectra in dynamic LDS whose size grows with the config: refuse what
+    // cannot launch here rather than at the first stft / istft call
+    int lds_max = 0;
+    e = hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device);
+    if (e != hipSuccess) {
+        fail(nullptr, CMGAN_E_HIP, "hipDeviceGetAttribute(MaxSharedMemoryPerBlock): %s", hipGetErrorString(e));
+        delete h;
+        return CMGAN_E_HIP;
+    }
+    const size_t lds_fwd = stft_dense_lds_bytes(cfg->n_fft, cfg->hop), lds_inv = istft_dense_lds_bytes(cfg->num_features);
+    if (lds_fwd > (size_t)lds_max || lds_inv > (size_t)lds_max) {
+        fail(nullptr, CMGAN_E_UNSUPPORTED,
+             "n_fft=%d hop=%d: the dense STFT / ISTFT kernels need %zu / %zu bytes of LDS per block, the device has %d",
+             cfg->n_fft, cfg->hop, lds_fwd, lds_inv, lds_max);
+        delete h;
+        return CMGAN_E_UNSUPPORTED;
+    }
     // ---- window + forward / inverse DFT matrices (host fp64 -> fp32, fragment-major) ----
     const int N = cfg->n_fft, F = cfg->num_features, FB = (F + 15) / 16;
     const double PI2 = 6.283185307179586476925286766559;

@@ -82,6 +82,10 @@ void launch_stft_compress(LaunchCtx, const SpectralTables&, const float* wav, co
                           int B, int L, int T, float* spec);
 void launch_uncompress_istft(LaunchCtx, const SpectralTables&, const float* re, const float* im,
                              const float* scale, int B, int T, float* frames_ws, float* wav_out);
+// dynamic LDS of the dense DFT kernels (stft_compress_kernel, uncompress_irfft_kernel) for a config: cmgan_create rejects
+// configs for which either exceeds the device's per-block limit
+inline size_t stft_dense_lds_bytes(int n_fft, int hop) { return (size_t)(15 * hop + n_fft) * sizeof(float); }
+inline size_t istft_dense_lds_bytes(int F) { return (size_t)16 * (2 * ((F + 15) / 16) * 16 + 4) * sizeof(float); }
 // stft_fft.hip: n_fft 400 / hop 100 as real FFTs (16 x 25 factorisation on the VALU); window = SpectralTables::window
 void launch_stft_fft400(LaunchCtx, const float* wav, const float* scale, const float* window, int B, int L, int T, float* spec);
 void launch_istft_fft400(LaunchCtx, const float* re, const float* im, const float* scale, const float* window, int B, int T,

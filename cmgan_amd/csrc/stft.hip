@@ -303,7 +303,7 @@ void launch_stft_compress(LaunchCtx ctx, const SpectralTables& tb, const float* 
         return;
     }
     dim3 grid((T + 15) / 16, B);
-    const size_t shm = (size_t)(15 * tb.hop + tb.n_fft) * sizeof(float);
+    const size_t shm = stft_dense_lds_bytes(tb.n_fft, tb.hop);
     LAUNCH(ctx, "stft_compress",
            (stft_compress_kernel<<<grid, 256, shm, ctx.stream>>>(tb, wav, scale, L, T, spec)));
 }
@@ -556,7 +556,7 @@ void launch_uncompress_istft(LaunchCtx ctx, const SpectralTables& tb, const floa
                (irfft_fold_x3_kernel<400><<<grid64, 256, 0, ctx.stream>>>(tb, re, im, T, frames_ws)));
     } else {
         dim3 grid((T + 15) / 16, B);
-        const size_t shm = (size_t)16 * (2 * tb.FB * 16 + 4) * sizeof(float);
+        const size_t shm = istft_dense_lds_bytes(tb.F);
         LAUNCH(ctx, "uncompress_irfft",
                (uncompress_irfft_kernel<<<grid, 256, shm, ctx.stream>>>(tb, re, im, T, frames_ws)));
     }

@@ -49,8 +49,13 @@ typedef struct cmgan_handle cmgan_handle;
  * heads=4, dim_head=16, conv kernel 31             src/models/generator.py:75-90
  * max_pos_emb=512                                  src/models/conformer.py:76      */
 typedef struct cmgan_config {
-    int32_t n_fft;         /* 400 (16 kHz) or 1200 (48 kHz); multiple of 16, even  */
-    int32_t hop;           /* 100 / 300; must divide n_fft                          */
+    int32_t n_fft;         /* 400 (16 kHz) or 1200 (48 kHz); multiple of 16.  Also
+                            * bounded by the device's LDS per block: cmgan_create
+                            * returns CMGAN_E_UNSUPPORTED when the dense DFT kernels
+                            * would need more than it, (15 hop + n_fft) x 4 B forward
+                            * or 16 (32 ceil(F / 16) + 4) x 4 B inverse; at the
+                            * MI355X's 160 KiB that is n_fft <= 2512                */
+    int32_t hop;           /* 100 / 300; multiple of 4, must divide n_fft           */
     int32_t num_features;  /* F = n_fft/2 + 1                                       */
     int32_t num_channel;   /* 64 (the only value the kernels are specialised for)   */
     int32_t num_tscb;      /* 4                                                     */
