@@ -174,6 +174,11 @@ SIGNATURES = {
     "cmgan_stream_tscb": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "cmgan_stream_decoder": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_size_t, c_void_p]),
+    "cmgan_stream_sums_doubles": (c_size_t, [c_void_p, c_int]),
+    "cmgan_stream_encoder_running": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_size_t, c_void_p]),
+    "cmgan_stream_decoder_running": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "cmgan_selftest_mfma": (c_int, [c_void_p, POINTER(c_float)]),
     "cmgan_selftest_mfma_x3": (c_int, [c_void_p, POINTER(c_float)]),
     "cmgan_metrics_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),

@@ -748,10 +748,19 @@ static bool dense_weights(cmgan_handle* h, int grp, DenseW& d) {
 // normalises it on load as before and also stores its split-fp16 image (imgs[i], i < 3); layers i + 1 .. 3 read that
 // image instead of the raw slot - same values to the bit, without the per-re-read normalise / PReLU / split.
 typedef void (*Conv3xFn)(LaunchCtx, const ConvArgs&, const void*, int, int, int);
+// Running-statistics mode (cmgan_stream_*_running): what the norm of instance j needs besides its raw input
+struct RunningNorms {
+    double* sums;              // the stream's sums blob (cmgan_stream_sums_doubles): norm j at j * B * 64 * 3
+    double* part;              // fp64 scratch (the workspace's conv-partials region, unread in this mode)
+    size_t part_doubles;
+    int hist;                  // frames [0, hist) of the call were counted by an earlier step
+    double* norm(int j, int B) const { return sums + (size_t)j * B * 64 * 3; }
+};
 static void run_dense_block(LaunchCtx ctx, bool x3, const DenseW& d, const float* x0, const float* x0_scale,
                             const float* x0_shift, const float* x0_alpha, float* const slots[4], float* partials,
                             float* const nsc[4], float* const nsh[4], int B, int T, int F, float* const* imgs = nullptr,
-                            Conv3xFn conv3x = launch_conv3_x3, bool frozen = false) {
+                            Conv3xFn conv3x = launch_conv3_x3, bool frozen = false,
+                            const RunningNorms* run = nullptr, int j0 = 0) {
     const int nt = x3 ? conv3x_ntiles(T, F, 64) : conv3_ntiles(T, F);
     for (int i = 0; i < 4; ++i) {
         ConvArgs a{};
@@ -771,7 +780,11 @@ static void run_dense_block(LaunchCtx ctx, bool x3, const DenseW& d, const float
         a.T = T; a.F = F; a.dil = 1 << i; a.mode = 0; a.ntiles = nt;
         if (x3) conv3x(ctx, a, d.w16[i], B, 2, 64);
         else launch_conv3(ctx, a, B, 2, 64);
-        if (!frozen) launch_in_finalize(ctx, partials, B, nt, 64, 0, (double)T * F, d.gb[i], nsc[i], nsh[i]);
+        if (run)
+            launch_in_running(ctx, slots[i], B, T, F, run->hist, run->part, run->part_doubles, run->norm(j0 + i, B),
+                              d.gb[i], nsc[i], nsh[i]);
+        else if (!frozen)
+            launch_in_finalize(ctx, partials, B, nt, 64, 0, (double)T * F, d.gb[i], nsc[i], nsh[i]);
     }
 }
 
@@ -780,17 +793,23 @@ static void run_dense_block(LaunchCtx ctx, bool x3, const DenseW& d, const float
 //             the statistics of the tensor in hand: the in_finalize / mask_stats launches are skipped.  With frozen
 //             statistics the encoder and the decoders are exactly time-causal (receptive field 15 frames back,
 //             generator.py:16-20, 39-47): frame t of their output depends on frames t - 15 .. t of their input only.
-//   stats_out the blob of THIS call's own statistics is copied here after the run (calibration)
+//   stats_out the blob of THIS call's own statistics is copied here after the run (calibration); a call without the
+//             encoder phase copies only the decoders' part (norms 6..15), one without the decoders only the encoder's (0..5)
+//   sums      running statistics (cmgan_stream_*_running): every InstanceNorm adds its input over frames [hist, T) to
+//             the carried fp64 sums and normalises all T frames with the statistics of everything counted so far
 //   phases    which third(s) of TSCNet.forward run: encoder (spec -> x_io), TSCBs (x_io in place), decoders
 //             (x_io + spec -> out_re / out_im); x_io = channels-last [B, T, F', 64], the layout the three share
 enum { PH_ENC = 1, PH_TSCB = 2, PH_DEC = 4, PH_ALL = 7 };
 struct TscnetOpts {
     const float* frozen = nullptr;
     float* stats_out = nullptr;
+    double* sums = nullptr;
+    int hist = 0;
     int phases = PH_ALL;
     float* x_io = nullptr;
 };
 static size_t stats_floats(int B) { return (size_t)16 * 2 * B * 64 + (size_t)B * 2; }
+static size_t sums_doubles(int B) { return ((size_t)15 * 64 + 1) * 3 * B; }
 
 static int tscnet_impl(cmgan_handle* h, const float* spec, int B, int T, float* out_re, float* out_im,
                        const cmgan_taps* taps, void* ws, size_t ws_bytes, void* stream, bool reset_prof,
@@ -800,6 +819,8 @@ static int tscnet_impl(cmgan_handle* h, const float* spec, int B, int T, float* 
         (opt.phases != PH_ALL && !opt.x_io))
         return fail(h, CMGAN_E_BADARG, "tscnet_forward: bad argument");
     const bool frozen = opt.frozen != nullptr;
+    if (opt.sums && (frozen || opt.hist < 0 || opt.hist >= T))
+        return fail(h, CMGAN_E_BADARG, "tscnet_forward: bad argument");
     // a time-axis sequence is T rows F2 rows apart: the split-f16 conv-module kernel addresses them with 32-bit byte
     // offsets (conformer_x3_addressable, conformer_x3.hip: 83 k frames per clip at F = 201); the fp32 kernels have no limit
     if (h->cfg.mfma_mode != CMGAN_MFMA_F32 && (long)(T - 1) * ((h->cfg.num_features + 1) / 2) * 512 + 512 >= (1l << 32))
@@ -861,21 +882,30 @@ static int tscnet_impl(cmgan_handle* h, const float* spec, int B, int T, float* 
         HIPCHK(h, hipMemcpyAsync(f + p.ns, opt.frozen, ns_floats * sizeof(float), hipMemcpyDeviceToDevice, hs));
         HIPCHK(h, hipMemcpyAsync(f + p.mstat, opt.frozen + ns_floats, (size_t)B * 2 * sizeof(float), hipMemcpyDeviceToDevice, hs));
     }
-    // (frozen statistics: the convs still write their partial sums, nobody reduces them)
-    auto finalize = [&](int ntiles, int cstride, int fold2, double count, const float* gb, float* sc_, float* sh_) {
-        if (!frozen) launch_in_finalize(ctx, partials, B, ntiles, cstride, fold2, count, gb, sc_, sh_);
+    // (frozen or running statistics: the convs still write their partial sums, nobody reduces them)
+    RunningNorms rn{opt.sums, (double*)partials, (p.ns - p.partials) / 2, opt.hist};
+    const RunningNorms* run = opt.sums ? &rn : nullptr;
+    // norm j's statistics: `raw` = its input [B, T * pf, 64] (running mode reads it again; fold2 = the pixel-shuffled
+    // layout, whose 2F' positions per frame already fold channel c + 64 onto c)
+    auto finalize = [&](int j, int ntiles, int cstride, int fold2, double count, const float* gb, const float* raw,
+                        int pf) {
+        if (run)
+            launch_in_running(ctx, raw, B, T, pf, rn.hist, rn.part, rn.part_doubles, rn.norm(j, B), gb, nsc(j), nsh(j));
+        else if (!frozen)
+            launch_in_finalize(ctx, partials, B, ntiles, cstride, fold2, count, gb, nsc(j), nsh(j));
     };
 
     // ---- dense encoder (generator.py:65-69) --------------------------------------------
     if (ph_enc) {
     launch_conv_in(ctx, spec, c1w, f + p.e[0], partials, B, (int)P);
-    finalize(conv_in_ntiles((int)P), 64, 0, (double)P, c1gb, nsc(0), nsh(0));
+    finalize(0, conv_in_ntiles((int)P), 64, 0, (double)P, c1gb, f + p.e[0], F);
     {
         float* slots[4] = {f + p.e[1], f + p.e[2], f + p.e[3], f + p.e[4]};
         float* sc[4] = {nsc(1), nsc(2), nsc(3), nsc(4)};
         float* sh[4] = {nsh(1), nsh(2), nsh(3), nsh(4)};
         float* imgs[3] = {f + p.img[0], f + p.img[1], f + p.img[2]};
-        run_dense_block(ctx, x3, dbe, f + p.e[0], nsc(0), nsh(0), c1pr, slots, partials, sc, sh, B, T, F, x3 ? imgs : nullptr, conv3x, frozen);
+        run_dense_block(ctx, x3, dbe, f + p.e[0], nsc(0), nsh(0), c1pr, slots, partials, sc, sh, B, T, F, x3 ? imgs : nullptr, conv3x, frozen,
+                        run, 1);
     }
     {   // conv_2: (1,3) stride (1,2) pad (0,1) == stride-1 conv keeping the even columns
         ConvArgs a{};
@@ -884,7 +914,7 @@ static int tscnet_impl(cmgan_handle* h, const float* spec, int B, int T, float* 
         a.T = T; a.F = F; a.dil = 1; a.mode = 1; a.ntiles = x3 ? conv3x_ntiles(T, F, 64) : conv3_ntiles(T, F);
         if (x3) conv3x(ctx, a, c2w16, B, 1, 64);
         else launch_conv3(ctx, a, B, 1, 64);
-        finalize(a.ntiles, 64, 0, (double)P2, c2gb, nsc(5), nsh(5));
+        finalize(5, a.ntiles, 64, 0, (double)P2, c2gb, f + p.xb, F2);
         launch_in_apply(ctx, f + p.xb, nsc(5), nsh(5), c2pr, f + p.xa, B, P2);
     }
     if (taps && taps->encoder_dev) launch_cl_to_nchw(ctx, f + p.xa, taps->encoder_dev, B, P2);
@@ -910,7 +940,12 @@ static int tscnet_impl(cmgan_handle* h, const float* spec, int B, int T, float* 
     }
 
     if (opt.x_io && !ph_dec) HIPCHK(h, hipMemcpyAsync(opt.x_io, f + p.xa, x_bytes, hipMemcpyDeviceToDevice, hs));
-    if (!ph_dec) return check_launch(h, "tscnet_forward");
+    const size_t enc_floats = (size_t)6 * 2 * B * 64;      // norms 0..5 of the blob: the encoder's
+    if (!ph_dec) {
+        if (opt.stats_out && ph_enc)
+            HIPCHK(h, hipMemcpyAsync(opt.stats_out, f + p.ns, enc_floats * sizeof(float), hipMemcpyDeviceToDevice, hs));
+        return check_launch(h, "tscnet_forward");
+    }
 
     // ---- decoders (generator.py:133-139, 151-156) ------------------------------------
     float* dslots[4] = {f + p.e[1], f + p.e[2], f + p.e[3], f + p.e[4]};
@@ -922,7 +957,8 @@ static int tscnet_impl(cmgan_handle* h, const float* spec, int B, int T, float* 
         float* sc[4] = {nsc(j0), nsc(j0 + 1), nsc(j0 + 2), nsc(j0 + 3)};
         float* sh[4] = {nsh(j0), nsh(j0 + 1), nsh(j0 + 2), nsh(j0 + 3)};
         float* imgs[3] = {f + p.img[0], f + p.img[1], f + p.img[2]};
-        run_dense_block(ctx, x3, d, f + p.xa, nullptr, nullptr, nullptr, dslots, partials, sc, sh, B, T, F2, x3 ? imgs : nullptr, conv3x, frozen);
+        run_dense_block(ctx, x3, d, f + p.xa, nullptr, nullptr, nullptr, dslots, partials, sc, sh, B, T, F2, x3 ? imgs : nullptr, conv3x, frozen,
+                        run, j0);
         ConvArgs a{};
         a.in[0] = dslots[3]; a.nscale[0] = sc[3]; a.nshift[0] = sh[3]; a.nalpha[0] = d.prelu[3];
         a.nslots = 1; a.w = dec == 0 ? mk_spw : cx_spw; a.bias = dec == 0 ? mk_spb : cx_spb;
@@ -933,15 +969,21 @@ static int tscnet_impl(cmgan_handle* h, const float* spec, int B, int T, float* 
         if (dec == 0) {
             launch_tail_proj(ctx, sp, nullptr, nullptr, nullptr, mk_tail, f + p.dm, B, (long)T * W2);
         } else {
-            finalize(nt2, 128, 1, (double)T * W2, cx_gb, nsc(14), nsh(14));
+            finalize(14, nt2, 128, 1, (double)T * W2, cx_gb, sp, W2);
             launch_tail_proj(ctx, sp, nsc(14), nsh(14), cx_pr, cx_tail, f + p.dc, B, (long)T * W2);
         }
     }
-    if (!frozen) launch_mask_stats(ctx, f + p.dm, mk_sca, B, T, F, f + p.mstat);
+    if (run)
+        launch_mask_running(ctx, f + p.dm, mk_sca, B, T, F, rn.hist, rn.part, rn.part_doubles, rn.norm(15, B),
+                            f + p.mstat);
+    else if (!frozen)
+        launch_mask_stats(ctx, f + p.dm, mk_sca, B, T, F, f + p.mstat);
     launch_final_combine(ctx, spec, f + p.dm, f + p.dc, f + p.mstat, mk_sca, mk_pout, cx_bias, B, T, F, out_re,
                          out_im, taps ? taps->mask_dev : nullptr, taps ? taps->complex_dev : nullptr);
     if (opt.stats_out) {
-        HIPCHK(h, hipMemcpyAsync(opt.stats_out, f + p.ns, ns_floats * sizeof(float), hipMemcpyDeviceToDevice, hs));
+        const size_t s0 = ph_enc ? 0 : enc_floats;
+        HIPCHK(h, hipMemcpyAsync(opt.stats_out + s0, f + p.ns + s0, (ns_floats - s0) * sizeof(float),
+                                 hipMemcpyDeviceToDevice, hs));
         HIPCHK(h, hipMemcpyAsync(opt.stats_out + ns_floats, f + p.mstat, (size_t)B * 2 * sizeof(float), hipMemcpyDeviceToDevice, hs));
     }
     return check_launch(h, "tscnet_forward");
@@ -996,6 +1038,30 @@ extern "C" int cmgan_stream_decoder(cmgan_handle* h, const float* x, const float
     if (!frozen_stats || !x) return fail(h, CMGAN_E_BADARG, "cmgan_stream_decoder: bad argument");
     TscnetOpts o;
     o.frozen = frozen_stats; o.phases = PH_DEC; o.x_io = const_cast<float*>(x);
+    return tscnet_impl(h, spec, B, T, out_re, out_im, nullptr, ws, ws_bytes, stream, false, o);
+}
+
+// ---- running statistics (include/cmgan_hip.h, "Streaming") ----
+extern "C" size_t cmgan_stream_sums_doubles(const cmgan_handle* h, int B) { return h && B > 0 ? sums_doubles(B) : 0; }
+
+extern "C" int cmgan_stream_encoder_running(cmgan_handle* h, const float* spec, int B, int T, int hist, double* sums_io,
+                                            float* stats_out, float* x_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!h) return CMGAN_E_BADARG;
+    if (!spec || !sums_io || !x_out || B <= 0 || T <= 0 || hist < 0 || hist >= T)
+        return fail(h, CMGAN_E_BADARG, "cmgan_stream_encoder_running: bad argument");
+    TscnetOpts o;
+    o.sums = sums_io; o.hist = hist; o.stats_out = stats_out; o.phases = PH_ENC; o.x_io = x_out;
+    return tscnet_impl(h, spec, B, T, nullptr, nullptr, nullptr, ws, ws_bytes, stream, false, o);
+}
+
+extern "C" int cmgan_stream_decoder_running(cmgan_handle* h, const float* x, const float* spec, int B, int T, int hist,
+                                            double* sums_io, float* stats_out, float* out_re, float* out_im, void* ws,
+                                            size_t ws_bytes, void* stream) {
+    if (!h) return CMGAN_E_BADARG;
+    if (!x || !spec || !sums_io || !out_re || !out_im || B <= 0 || T <= 0 || hist < 0 || hist >= T)
+        return fail(h, CMGAN_E_BADARG, "cmgan_stream_decoder_running: bad argument");
+    TscnetOpts o;
+    o.sums = sums_io; o.hist = hist; o.stats_out = stats_out; o.phases = PH_DEC; o.x_io = const_cast<float*>(x);
     return tscnet_impl(h, spec, B, T, out_re, out_im, nullptr, ws, ws_bytes, stream, false, o);
 }
 

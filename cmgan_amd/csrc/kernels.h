@@ -137,6 +137,15 @@ void launch_final_combine(LaunchCtx, const float* spec, const float* dm, const f
                           int B, int T, int F, float* out_re, float* out_im, float* tap_mask, float* tap_cplx);
 void launch_cl_to_nchw(LaunchCtx, const float* in, float* out, int B, long P);
 
+// ----------------------------- in_running.hip -----------------------------------
+// running InstanceNorm statistics of a carried-state stream: frames [hist, T) of x [B, T*PF, 64] (or of the mask head's
+// values, from dm) added to the fp64 sums [B][C][3] = {n, sum x, sum x^2}, then the pair the next consumer reads;
+// part: fp64 scratch of part_doubles
+void launch_in_running(LaunchCtx, const float* x, int B, int T, int PF, int hist, double* part, size_t part_doubles,
+                       double* sums, const float* gb, float* nscale, float* nshift);
+void launch_mask_running(LaunchCtx, const float* dm, const float* scalars, int B, int T, int F, int hist,
+                         double* part, size_t part_doubles, double* sums, float* mstat);
+
 // ----------------------------- conformer.hip ------------------------------------
 struct ConfWeights {
     const float *ff1_w1, *ff1_b1, *ff1_w2, *ff1_b2;

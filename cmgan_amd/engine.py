@@ -131,7 +131,7 @@ class Engine:
         self._mws: Optional[torch.Tensor] = None          # workspace of metrics()
         self._graphs: dict = {}          # enhance_graphed: input shape -> (graph, in, out, token)
         self._row_graphs: dict = {}      # streaming.enhance_windows: row shape -> (graph, in, out, token)
-        self._stream_slots: dict = {}    # streaming.StreamState(graph=True): (B, W, Ca, La) -> state buffers + step graphs
+        self._stream_slots: dict = {}    # streaming.StreamState(graph=True): (B, W, Ca, La, stats mode) -> state + step graphs
         self.weights_loaded = False
 
     def __del__(self):
@@ -375,6 +375,68 @@ class Engine:
         check(self._h, self.lib.cmgan_stream_decoder(self._h, x.data_ptr(), spec.data_ptr(), B, T, self._stats_arg(stats, B),
                                                      real.data_ptr(), imag.data_ptr(), ws.data_ptr(), ws.numel(),
                                                      self._stream()))
+        return real, imag
+
+    # ---- running-statistics forms (include/cmgan_hip.h, "Streaming": running statistics) ----
+    def stream_sums_doubles(self, B: int) -> int:
+        return int(self.lib.cmgan_stream_sums_doubles(self._h, B))
+
+    def _sums_arg(self, sums: torch.Tensor, B: int) -> int:
+        if (not isinstance(sums, torch.Tensor) or sums.device != self.device or sums.dtype != torch.float64
+                or not sums.is_contiguous() or sums.numel() != self.stream_sums_doubles(B)):
+            raise ValueError(f"sums must be a contiguous float64 tensor on {self.device} of stream_sums_doubles({B}) = "
+                             f"{self.stream_sums_doubles(B)} elements")
+        return sums.data_ptr()
+
+    def _stats_out_arg(self, stats_out: Optional[torch.Tensor], B: int):
+        if stats_out is None:
+            return None
+        if (stats_out.device != self.device or stats_out.dtype != torch.float32 or not stats_out.is_contiguous()
+                or stats_out.numel() != self.stats_floats(B)):
+            raise ValueError(f"stats_out must be a contiguous float32 tensor on {self.device} of stats_floats({B}) elements")
+        return stats_out.data_ptr()
+
+    @_on_device
+    def stream_encoder_running(self, spec: torch.Tensor, hist: int, sums: torch.Tensor, out: Optional[torch.Tensor] = None,
+                               ws: Optional[torch.Tensor] = None, stats_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """stream_encoder under RUNNING statistics: spec [B,2,T,F] whose first `hist` frames were counted by an earlier
+        step -> x [B,T,F',64].  `sums` (float64, stream_sums_doubles(B)) is updated in place (norms 0..5);
+        `stats_out` (float32, stats_floats(B)) receives the encoder's part of the statistics blob this call used."""
+        self._need_weights()
+        spec = self._in(spec, "spec")
+        B, two, T, F = spec.shape
+        if two != 2 or F != self.F:
+            raise ValueError(f"expected [B,2,T,{self.F}], got {tuple(spec.shape)}")
+        ws = self._own_ws(ws, B, T)
+        want = (B, T, (F + 1) // 2, 64)
+        if out is None:
+            out = torch.empty(want, dtype=torch.float32, device=spec.device)
+        elif not out.is_contiguous() or tuple(out.shape) != want:
+            raise ValueError(f"out must be a contiguous [B,T,F',64] = {want} tensor, got {tuple(out.shape)}")
+        check(self._h, self.lib.cmgan_stream_encoder_running(self._h, spec.data_ptr(), B, T, int(hist),
+                                                             self._sums_arg(sums, B), self._stats_out_arg(stats_out, B),
+                                                             self._in(out, "out").data_ptr(), ws.data_ptr(), ws.numel(),
+                                                             self._stream()))
+        return out
+
+    @_on_device
+    def stream_decoder_running(self, x: torch.Tensor, spec: torch.Tensor, hist: int, sums: torch.Tensor,
+                               ws: Optional[torch.Tensor] = None, stats_out: Optional[torch.Tensor] = None):
+        """stream_decoder under RUNNING statistics: x [B,T,F',64], spec [B,2,T,F], the first `hist` frames counted by an
+        earlier step -> (est_real, est_imag) [B,1,T,F].  `sums` is updated in place (norms 6..15); `stats_out` receives
+        the decoders' part of the statistics blob this call used."""
+        self._need_weights()
+        x, spec = self._in(x, "x"), self._in(spec, "spec")
+        B, T, F2, C = x.shape
+        if tuple(spec.shape) != (B, 2, T, self.F) or C != 64 or F2 != (self.F + 1) // 2:
+            raise ValueError(f"expected x [B,T,{(self.F + 1) // 2},64] and spec [B,2,T,{self.F}]")
+        ws = self._own_ws(ws, B, T)
+        real = torch.empty(B, 1, T, self.F, dtype=torch.float32, device=x.device)
+        imag = torch.empty_like(real)
+        check(self._h, self.lib.cmgan_stream_decoder_running(self._h, x.data_ptr(), spec.data_ptr(), B, T, int(hist),
+                                                             self._sums_arg(sums, B), self._stats_out_arg(stats_out, B),
+                                                             real.data_ptr(), imag.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                             self._stream()))
         return real, imag
 
     @_on_device

@@ -114,7 +114,15 @@ def _enhance_rows(model: TSCNet, rows: torch.Tensor, graph: bool) -> torch.Tenso
 #
 # STFT / ISTFT are frame-local (a frame sees 400 samples, a sample 4 frames) and run over the clip's frames before /
 # after the steps; the steps are what is captured into hipGraphs (one per step shape: first, steady, last).
+#
+# stats_mode="running" (opt-in; CPU restatement: tests/stream_running_model.py) needs no calibration blob: every
+# InstanceNorm carries fp64 sums (n, sum x, sum x^2) of its input over the frames the stream has seen.  A step adds its
+# NEW frames (the encoder's [e0, e1), the decoders' kept ones - never the history in front again) and normalises all
+# frames of the call with the cumulative statistics, so every frame is still computed once and the statistics converge
+# towards the whole-clip ones the reference uses.  The encoder's and the decoders' sums are disjoint parts of one blob
+# (include/cmgan_hip.h, "Streaming"): the pipelined form runs them side by side.
 HIST_FRAMES = 15
+STATS_MODES = ("frozen", "running")
 
 
 class StreamCursor:
@@ -183,6 +191,8 @@ class _StreamSlot:
         self.E = torch.empty(B, Ca + La + n_max, F2, 64, device=dev)
         self.D = torch.empty(B, HIST_FRAMES + n_max, F2, 64, device=dev)
         self.stats = torch.empty(eng.stats_floats(B), device=dev)
+        self.sums = torch.zeros(eng.stream_sums_doubles(B), dtype=torch.float64, device=dev)   # running mode
+        self.n_enc_sums = 6 * B * 64 * 3                     # sums[:n_enc_sums]: the encoder's norms, the rest the decoders'
         self.graphs: dict = {}                               # step signature -> (graph, spec_in, out_real, out_imag, token); LRU
         self.owner = None                                    # weakref of the StreamState using the buffers
         # pipelined form (StreamState.step_pipelined): three stages on three streams - encoder of step k + 2 | TSCBs of step
@@ -208,15 +218,24 @@ class _StreamSlot:
 
 
 class StreamState:
-    """Carried state of one stream (or B streams in lock-step): the statistics blob, the encoder-output cache, the
-    decoder's input history and the spectrogram frames they belong to.  `step(spec_frames)` is frame-level.
+    """Carried state of one stream (or B streams in lock-step): the statistics blob (stats_mode="frozen") or the running
+    sums (stats_mode="running", `stats` None), the encoder-output cache, the decoder's input history and the spectrogram
+    frames they belong to.  `step(spec_frames)` is frame-level.
     graph=True: the state lives in an Engine-owned _StreamSlot and every step is ONE hipGraph replay."""
 
-    def __init__(self, model: TSCNet, stats: torch.Tensor, B: int, window: int, context: int, lookahead: int,
-                 graph: bool = True):
+    def __init__(self, model: TSCNet, stats: torch.Tensor | None, B: int, window: int, context: int, lookahead: int,
+                 graph: bool = True, stats_mode: str = "frozen"):
         if window <= 0 or context < 0 or lookahead < 0:
             raise ValueError("window must be positive, context / lookahead non-negative (frames)")
+        if stats_mode not in STATS_MODES:
+            raise ValueError(f"stats_mode must be one of {STATS_MODES}, got {stats_mode!r}")
+        self.running = stats_mode == "running"
+        if self.running and stats is not None:
+            raise ValueError("stats_mode='running' keeps its own statistics: pass stats=None")
+        if not self.running and stats is None:
+            raise ValueError("stats_mode='frozen' needs a statistics blob (Engine.tscnet_forward_stats)")
         self.model, self.eng, self.stats, self.B = model, model.engine, stats, B
+        self.stats_mode = stats_mode
         self.W, self.Ca, self.La, self.graph = window, context, lookahead, graph
         self.F, self.F2 = self.eng.F, (self.eng.F + 1) // 2
         dev = self.eng.device
@@ -225,9 +244,15 @@ class StreamState:
         self.pipeline_stages = 3 if os.environ.get("CMGAN_STREAM_STAGES", "2") == "3" else 2
         if graph:
             self.slot = self._claim_slot()
-            self.slot.stats.copy_(self.eng._in(stats, "stats"))
-            self.stats = self.slot.stats                               # (what the graphs' kernel arguments point at)
+            if self.running:
+                self.slot.sums.zero_()                                 # a new stream has seen nothing
+            else:
+                self.slot.stats.copy_(self.eng._in(stats, "stats"))
+                self.stats = self.slot.stats                           # (what the graphs' kernel arguments point at)
+            self.sums = self.slot.sums
         else:
+            self.sums = (torch.zeros(self.eng.stream_sums_doubles(B), dtype=torch.float64, device=dev)
+                         if self.running else None)
             self.enc = torch.empty(B, 0, self.F2, 64, device=dev)          # cached encoder outputs
             self.spec_tail = torch.empty(B, 2, 0, self.F, device=dev)       # spec frames [spec_lo, ...) still needed
             self.dec_hist = None             # kept TSCB outputs of the last HIST_FRAMES frames before k W
@@ -238,27 +263,39 @@ class StreamState:
     def _claim_slot(self) -> _StreamSlot:
         import weakref
         slots = self.eng._stream_slots
-        key = (self.B, self.W, self.Ca, self.La)
+        key = (self.B, self.W, self.Ca, self.La, self.stats_mode)     # (the step graphs differ by mode)
         slot = slots.get(key)
         if slot is not None and slot.owner is not None and slot.owner() is not None and slot.owner() is not self:
-            slot = _StreamSlot(self.eng, *key)                         # another live stream holds the cached one: a private slot
+            slot = _StreamSlot(self.eng, *key[:4])                     # another live stream holds the cached one: a private slot
         elif slot is None:
-            slot = _StreamSlot(self.eng, *key)
+            slot = _StreamSlot(self.eng, *key[:4])
             while len(slots) >= 4:                                     # a handful of configurations per engine, oldest out
                 slots.pop(next(iter(slots)))
             slots[key] = slot
         slot.owner = weakref.ref(self)
         return slot
 
+    # ---- the encoder / decoder calls of the stream's statistics mode (hist = history frames in front) ----
+    def _encoder(self, spec, hist, stats, sums, ws=None):
+        if self.running:
+            return self.eng.stream_encoder_running(spec, hist, sums, ws=ws)
+        return self.eng.stream_encoder(spec, stats, ws=ws)
+
+    def _decoder(self, x, spec, hist, stats, sums, ws=None):
+        if self.running:
+            return self.eng.stream_decoder_running(x, spec, hist, sums, ws=ws)
+        return self.eng.stream_decoder(x, spec, stats, ws=ws)
+
     # ---- one step on explicit tensors (eager form) ----
     def _run(self, spec_enc, enc_ctx, dec_hist, spec_dec, n_new_enc, keep_lo, n_keep):
         eng = self.eng
-        x_new = eng.stream_encoder(spec_enc, self.stats)[:, spec_enc.size(2) - n_new_enc:]      # drop the history outputs
+        h_enc = spec_enc.size(2) - n_new_enc
+        x_new = self._encoder(spec_enc, h_enc, self.stats, self.sums)[:, h_enc:]      # drop the history outputs
         x = torch.cat([enc_ctx, x_new], dim=1).contiguous()
         eng.stream_tscb(x)
         kept = x[:, keep_lo:keep_lo + n_keep]
         xin = kept if dec_hist is None else torch.cat([dec_hist, kept], dim=1)
-        real, imag = eng.stream_decoder(xin.contiguous(), spec_dec, self.stats)
+        real, imag = self._decoder(xin.contiguous(), spec_dec, xin.size(1) - n_keep, self.stats, self.sums)
         return x_new, kept, real[:, :, xin.size(1) - n_keep:], imag[:, :, xin.size(1) - n_keep:]
 
     # ---- one step as ONE graph replay over the slot's state buffers ----
@@ -268,13 +305,13 @@ class StreamState:
         n_tail, h_enc, n_new, n_ctx, keep_lo, n_keep, h_dec, dec_lo, spec_drop, enc_drop, h_dec_next, last = sig
         eng, S, E, D = self.eng, sl.S, sl.E, sl.D
         S[:, :, n_tail:n_tail + n_new].copy_(spec_in)
-        enc = eng.stream_encoder(S[:, :, n_tail - h_enc:n_tail + n_new].contiguous(), sl.stats)
+        enc = self._encoder(S[:, :, n_tail - h_enc:n_tail + n_new].contiguous(), h_enc, sl.stats, sl.sums)
         E[:, n_ctx:n_ctx + n_new].copy_(enc[:, h_enc:])                # the history outputs are dropped
         x = E[:, :n_ctx + n_new].clone()                               # the TSCBs work in place: the cache keeps the encoder's
         eng.stream_tscb(x)
         D[:, h_dec:h_dec + n_keep].copy_(x[:, keep_lo:keep_lo + n_keep])
-        real, imag = eng.stream_decoder(D[:, :h_dec + n_keep].contiguous(),
-                                        S[:, :, dec_lo:dec_lo + h_dec + n_keep].contiguous(), sl.stats)
+        real, imag = self._decoder(D[:, :h_dec + n_keep].contiguous(),
+                                   S[:, :, dec_lo:dec_lo + h_dec + n_keep].contiguous(), h_dec, sl.stats, sl.sums)
         if not last:                                                   # carry: what the next step's three stages look back at
             for buf, dim, lo, hi in ((S, 2, spec_drop, n_tail + n_new), (E, 1, enc_drop, n_ctx + n_new),
                                      (D, 1, h_dec + n_keep - h_dec_next, h_dec + n_keep)):
@@ -292,7 +329,7 @@ class StreamState:
         if ent is None:
             spec_in = spec_new.contiguous().clone()
             # warm-up outside capture on COPIES of the state (a step updates it): allocator pools, workspace growth
-            saved = (sl.S.clone(), sl.E.clone(), sl.D.clone())
+            saved = (sl.S.clone(), sl.E.clone(), sl.D.clone(), sl.sums.clone())
             side = torch.cuda.Stream(device=eng.device)
             side.wait_stream(torch.cuda.current_stream(eng.device))
             with torch.cuda.stream(side):
@@ -300,12 +337,12 @@ class StreamState:
             torch.cuda.current_stream(eng.device).wait_stream(side)
             torch.cuda.synchronize(eng.device)
             token = eng._ws_token()                                    # (the warm-up may have grown the workspace)
-            for dst, src in zip((sl.S, sl.E, sl.D), saved):
+            for dst, src in zip((sl.S, sl.E, sl.D, sl.sums), saved):
                 dst.copy_(src)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 out_r, out_i = self._graph_body(sl, spec_in, sig)
-            for dst, src in zip((sl.S, sl.E, sl.D), saved):            # (capture does not execute, but keep the rule simple)
+            for dst, src in zip((sl.S, sl.E, sl.D, sl.sums), saved):            # (capture does not execute, but keep the rule simple)
                 dst.copy_(src)
             del saved
             ent = (g, spec_in, out_r, out_i, token)
@@ -324,7 +361,7 @@ class StreamState:
         n_tail, h_enc, n_new, dec_lo, n_dec, spec_drop, last, par = sig
         S = sl.S
         S[:, :, n_tail:n_tail + n_new].copy_(spec_in)
-        enc = self.eng.stream_encoder(S[:, :, n_tail - h_enc:n_tail + n_new].contiguous(), sl.stats, ws=sl.ws_enc)
+        enc = self._encoder(S[:, :, n_tail - h_enc:n_tail + n_new].contiguous(), h_enc, sl.stats, sl.sums, ws=sl.ws_enc)
         sl.ENC[par][:, :n_new].copy_(enc[:, h_enc:])                   # the history outputs are dropped
         sl.SD[par][:, :, :n_dec].copy_(S[:, :, dec_lo:dec_lo + n_dec])
         if not last and spec_drop > 0:
@@ -347,8 +384,8 @@ class StreamState:
 
     def _dec_body(self, sl: _StreamSlot, par, h_dec, n_keep):
         """Stage 3: both decoders on [history | kept frames]."""
-        real, imag = self.eng.stream_decoder(sl.D2[par][:, :h_dec + n_keep].contiguous(),
-                                             sl.SD[par][:, :, :h_dec + n_keep].contiguous(), sl.stats, ws=sl.ws_dec)
+        real, imag = self._decoder(sl.D2[par][:, :h_dec + n_keep].contiguous(),
+                                   sl.SD[par][:, :, :h_dec + n_keep].contiguous(), h_dec, sl.stats, sl.sums, ws=sl.ws_dec)
         return real[:, :, h_dec:], imag[:, :, h_dec:]
 
     def _captured(self, sl: _StreamSlot, key, body, stream, restore=()):
@@ -424,7 +461,8 @@ class StreamState:
             es.wait_stream(cur)                                        # (spec_new was produced on the caller's stream)
         after(es, ev["mid"][par], ev["dec"][par])
         fsig = (p["n_tail"], p["h_enc"], n_new, p["dec_lo"], h_dec + n_keep, p["spec_drop"], last, par)
-        ent = self._captured(sl, ("front",) + fsig, lambda: self._front_body(sl, spec_in, fsig), es, restore=(sl.S,))
+        ent = self._captured(sl, ("front",) + fsig, lambda: self._front_body(sl, spec_in, fsig), es,
+                             restore=(sl.S, sl.sums[:sl.n_enc_sums]))
         with torch.cuda.stream(es):
             spec_in.copy_(spec_new)
             ent[0].replay()
@@ -437,7 +475,8 @@ class StreamState:
         ev["mid"][par] = mark(cur)
         # ---- stage 3 on the decoder stream ----
         after(ds, ev["mid"][par], ev["front"][par])
-        ent = self._captured(sl, ("dec", par, h_dec, n_keep), lambda: self._dec_body(sl, par, h_dec, n_keep), ds)
+        ent = self._captured(sl, ("dec", par, h_dec, n_keep), lambda: self._dec_body(sl, par, h_dec, n_keep), ds,
+                             restore=(sl.sums[sl.n_enc_sums:],))
         with torch.cuda.stream(ds):
             ent[0].replay()
             r, i = ent[1]
@@ -504,21 +543,26 @@ class StreamState:
 @torch.no_grad()
 def enhance_stream(model: TSCNet, noisy: torch.Tensor, window: int = 400, context: int = 40, lookahead: int = 40,
                    stats: torch.Tensor | None = None, calib_frames: int | None = None, graph: bool = True,
-                   pipeline: bool | None = None) -> torch.Tensor:
+                   pipeline: bool | None = None, stats_mode: str = "frozen") -> torch.Tensor:
     """noisy: float32 [1, L] on the GPU -> enhanced [L'] (L' = hop * (T - 1), T = L // hop + 1, like one reference row).
     window / context / lookahead are in FRAMES.  `stats`: a frozen statistics blob (Engine.tscnet_forward_stats); by
-    default the clip's first `calib_frames` (default window + lookahead) frames calibrate it."""
+    default the clip's first `calib_frames` (default window + lookahead) frames calibrate it.  stats_mode="running":
+    no blob and no calibration - every InstanceNorm uses the statistics of all frames the stream has seen so far."""
     if noisy.dim() != 2 or noisy.size(0) != 1:
         raise ValueError("expected a mono track shaped [1, L]")
+    if stats_mode not in STATS_MODES:
+        raise ValueError(f"stats_mode must be one of {STATS_MODES}, got {stats_mode!r}")
+    if stats_mode == "running" and (stats is not None or calib_frames is not None):
+        raise ValueError("stats_mode='running' takes neither stats nor calib_frames")
     eng = model.engine
     noisy = noisy.to(dtype=torch.float32).contiguous()
     c = eng.rms_scale(noisy)                                   # file-level scale, as evaluation.py:21
     spec = eng.stft_compress(noisy, c)                         # [1,2,T,F]: frame-local, see the contract above
     T = spec.size(2)
-    if stats is None:
+    if stats is None and stats_mode == "frozen":
         n = min(T, calib_frames if calib_frames is not None else window + lookahead)
         stats = eng.tscnet_forward_stats(spec[:, :, :n].contiguous())[2]
-    st = StreamState(model, stats, 1, window, context, lookahead, graph)
+    st = StreamState(model, stats, 1, window, context, lookahead, graph, stats_mode=stats_mode)
     real = torch.empty(1, 1, T, eng.F, device=noisy.device)
     imag = torch.empty_like(real)
     k, fed = 0, 0
@@ -548,17 +592,18 @@ class StreamingEnhancer:
     frames + 3 frames.  `scale` = the RMS normalisation factor c (evaluation.py:21-23): a live stream cannot know its
     file-level RMS, so it is a parameter (e.g. from the calibration stretch); the output is divided by it again.
     The result equals `enhance_stream` on the whole signal with the same statistics and scale to rounding (1.5e-6: the
-    split-f16 transforms scale each 64-frame tile by its own power of two, and the blocks tile the frames differently)."""
+    split-f16 transforms scale each 64-frame tile by its own power of two, and the blocks tile the frames differently).
+    stats_mode="running" needs no `stats` (a live caller has no clip to calibrate on): see StreamState."""
 
-    def __init__(self, model: TSCNet, stats: torch.Tensor, window: int = 400, context: int = 40, lookahead: int = 40,
-                 scale: float | torch.Tensor = 1.0, graph: bool = True):
+    def __init__(self, model: TSCNet, stats: torch.Tensor | None = None, window: int = 400, context: int = 40,
+                 lookahead: int = 40, scale: float | torch.Tensor = 1.0, graph: bool = True, stats_mode: str = "frozen"):
         self.eng = model.engine
         self.hop, self.n_fft = self.eng.cfg.hop, self.eng.cfg.n_fft
         if self.n_fft != 4 * self.hop:
             raise ValueError("StreamingEnhancer assumes n_fft = 4 hop (400 / 100, 1200 / 300)")
         dev = self.eng.device
         self.c = torch.as_tensor(scale, dtype=torch.float32, device=dev).reshape(1)
-        self.state = StreamState(model, stats, 1, window, context, lookahead, graph)
+        self.state = StreamState(model, stats, 1, window, context, lookahead, graph, stats_mode=stats_mode)
         self.W, self.La = window, lookahead
         self.samples = torch.empty(0, device=dev)      # received samples from index `s_lo` on
         self.s_lo = 0

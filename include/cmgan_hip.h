@@ -512,6 +512,33 @@ int cmgan_stream_decoder(cmgan_handle* h, const float* x_dev, const float* spec_
                          const float* frozen_stats_dev, float* out_real_dev, float* out_imag_dev,
                          void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Running statistics (opt-in; the frozen blob above stays the default).  A running stream needs no calibration: each
+ * row carries, for each of the 15 64-channel InstanceNorms and the mask head's one-channel norm, three fp64 numbers per
+ * channel - n, sum x, sum x^2 - where x is that norm's INPUT (the conv output, bias included).  A call on T frames whose
+ * first `hist` (0 <= hist < T) are history does, for every norm in network order:
+ *   1. add the norm input over frames [hist, T), all frequency bins, to the carried sums (history is not counted again);
+ *   2. mean = sum x / n, var = max(sum x^2 / n - mean^2, 0) (in_finalize's arithmetic), eps 1e-5 and the affine
+ *      weights give the (scale, shift) pair; the sub-pixel norm folds channels c and c + 64 like the frozen path;
+ *   3. normalise ALL T frames of the call, history included, with that pair.
+ * Frames of earlier calls are not recomputed.  With hist = 0 on fresh (zero) sums the call is the reference arithmetic
+ * on its frames, to fp64 summation order.  The sums are reduced in a fixed order (no atomics): replays of a captured
+ * call give the same bits as eager calls.
+ *   cmgan_stream_sums_doubles(h, B)  doubles of one sums blob, [norm j < 15][B][64][3] then the mask head's [B][3], in
+ *                                    that order (n, sum x, sum x^2); 0 for a null h or B <= 0.  Zero it to start a stream.
+ *   cmgan_stream_encoder_running     cmgan_stream_encoder with running statistics: updates norms 0..5 of sums_io
+ *   cmgan_stream_decoder_running     cmgan_stream_decoder with running statistics: updates norms 6..15 of sums_io
+ * The two touch disjoint parts of one blob, so the encoder of step k + 1 may run beside the decoders of step k.
+ * `stats_out` (may be NULL) receives the statistics blob (cmgan_stats_floats layout) the call used: the encoder writes
+ * its part (norms 0..5), the decoder the rest.  A null or out-of-range argument returns CMGAN_E_BADARG before anything
+ * is enqueued.  Workspace: cmgan_workspace_bytes(h, B, T) of the call's own T.                                         */
+size_t cmgan_stream_sums_doubles(const cmgan_handle* h, int B);
+int cmgan_stream_encoder_running(cmgan_handle* h, const float* spec_dev, int B, int T, int hist, double* sums_io_dev,
+                                 float* stats_out_dev, float* x_out_dev, void* workspace_dev, size_t workspace_bytes,
+                                 void* stream);
+int cmgan_stream_decoder_running(cmgan_handle* h, const float* x_dev, const float* spec_dev, int B, int T, int hist,
+                                 double* sums_io_dev, float* stats_out_dev, float* out_real_dev, float* out_imag_dev,
+                                 void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Self-test of the MFMA fragment conventions every kernel relies on: computes
  * D = A(16xK) * B(Kx16) with the f32 16x16x4 MFMA and the library's fragment
  * packing; returns max |D - reference| through *max_err_host (synchronises).   */
