@@ -185,6 +185,12 @@ SIGNATURES = {
     "cmgan_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_double, c_void_p, c_void_p,
                               c_void_p, c_size_t, c_void_p]),
     "cmgan_metrics_table": (c_int, [c_int, c_int, c_void_p, c_size_t]),
+    "cmgan_resample_geometry": (c_int, [c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "cmgan_resample_out_len": (c_longlong, [c_int, c_int, c_longlong]),
+    "cmgan_resample_table": (c_int, [c_int, c_int, c_void_p, c_size_t]),
+    "cmgan_resample_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "cmgan_resample": (c_int, [c_void_p, c_void_p, c_int, c_int, c_longlong, c_longlong, c_int, c_int, c_longlong, c_int,
+                               c_void_p, c_longlong, c_void_p, c_size_t, c_void_p]),
     "cmgan_set_profiling": (c_int, [c_void_p, c_int]),
     "cmgan_profile_read": (c_int, [c_void_p, POINTER(KernelTime), c_int]),
 }

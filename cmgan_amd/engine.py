@@ -129,6 +129,7 @@ class Engine:
         self._cws: Optional[torch.Tensor] = None
         self._bws: Optional[torch.Tensor] = None          # workspace of the two-branch form (enhance_graphed(branches=2))
         self._mws: Optional[torch.Tensor] = None          # workspace of metrics()
+        self._rws: dict = {}             # resample(): (fs_in, fs_out) -> workspace (the pair's tap table)
         self._graphs: dict = {}          # enhance_graphed: input shape -> (graph, in, out, token)
         self._row_graphs: dict = {}      # streaming.enhance_windows: row shape -> (graph, in, out, token)
         self._stream_slots: dict = {}    # streaming.StreamState(graph=True): (B, W, Ca, La, stats mode) -> state + step graphs
@@ -655,6 +656,54 @@ class Engine:
             return out
         return out, FrameScores(frames[:, 0, :nfw], frames[:, 1, :nfl], frames[:, 2, :nfw])
 
+    # ---- sample-rate conversion ----------------------------------------------------
+    def _resample_ws(self, fs_in: int, fs_out: int) -> torch.Tensor:
+        ws = self._rws.get((fs_in, fs_out))
+        if ws is None:
+            need = int(self.lib.cmgan_resample_workspace_bytes(self._h, fs_in, fs_out))
+            if need == 0:
+                from .resample import geometry
+                geometry(fs_in, fs_out)                       # raises CmganError with the library's message
+            # one allocation per rate pair, kept: a captured graph's kernel arguments point into it
+            ws = self._rws[(fs_in, fs_out)] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return ws
+
+    @_on_device
+    def resample_chunk(self, buf: torch.Tensor, pos_in: int, fs_in: int, fs_out: int, n0: int, n_out: int,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Outputs [n0, n0 + n_out) of the resampled signal whose samples [pos_in, pos_in + n) `buf` [B, n] holds (samples
+        it does not hold count as zero) -> [B, n_out].  The chunk form of resample(): same kernel, same bits."""
+        buf = self._in(buf, "buf")
+        if buf.dim() != 2:
+            raise ValueError(f"expected [B, n], got {tuple(buf.shape)}")
+        fs_in, fs_out = int(fs_in), int(fs_out)
+        B, n_buf = buf.shape
+        ws = self._resample_ws(fs_in, fs_out)
+        if out is None:
+            out = torch.empty(B, n_out, dtype=torch.float32, device=self.device)
+        elif (out.device != self.device or out.dtype != torch.float32 or not out.is_contiguous()
+                or tuple(out.shape) != (B, n_out)):
+            raise ValueError(f"out must be a contiguous float32 [{B}, {n_out}] tensor on {self.device}")
+        if B == 0 or n_out == 0:
+            return out
+        if n_buf == 0:                                        # no sample at all: every output is a sum of zeros
+            return out.zero_()
+        check(self._h, self.lib.cmgan_resample(self._h, buf.data_ptr(), B, n_buf, n_buf, int(pos_in), fs_in, fs_out,
+                                               int(n0), int(n_out), out.data_ptr(), n_out, ws.data_ptr(), ws.numel(),
+                                               self._stream()))
+        return out
+
+    def resample(self, wav: torch.Tensor, fs_in: int, fs_out: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """wav [B, L] (or [L]) at fs_in -> [B, ceil(L up / down)] at fs_out on the GPU (cmgan_resample): the arithmetic
+        of scipy.signal.resample_poly(wav, up, down) in float64, rounded to float32 once.  Supported: rate pairs whose
+        reduced max(up, down) <= 640.  Needs no weights, does not synchronise and is graph-capturable after one call."""
+        from .resample import out_len
+        squeeze = isinstance(wav, torch.Tensor) and wav.dim() == 1
+        if squeeze:
+            wav = wav[None]
+        y = self.resample_chunk(wav, 0, fs_in, fs_out, 0, out_len(fs_in, fs_out, wav.size(-1)), out=out)
+        return y[0] if squeeze else y
+
     # ---- diagnostics ---------------------------------------------------------------
     @_on_device
     def selftest_mfma(self) -> float:
@@ -675,6 +724,7 @@ class Engine:
         self._row_graphs.clear()
         self._stream_slots.clear()
         self._ws = self._bws = self._cws = self._mws = None
+        self._rws.clear()
 
     def set_profiling(self, on: bool):
         check(self._h, self.lib.cmgan_set_profiling(self._h, 1 if on else 0))

@@ -27,11 +27,22 @@ def chunk_rows(padded_len: int, cut_len: int) -> int:
 
 @torch.no_grad()
 def enhance_one_track(model: TSCNet, noisy: torch.Tensor, cut_len: int = 16000 * 16, n_fft: int = 400,
-                      hop: int = 100) -> torch.Tensor:
-    """noisy: float32 [1, L] in [-1, 1] on the GPU -> enhanced [L] on the GPU."""
+                      hop: int = 100, sample_rate: int | None = None, model_rate: int = 16000) -> torch.Tensor:
+    """noisy: float32 [1, L] in [-1, 1] on the GPU -> enhanced [L] on the GPU.
+
+    sample_rate: the track's rate when it is not the model's (`model_rate`: 16000, or 48000 with the 48 kHz model).  The
+    track is then resampled to model_rate on the device (Engine.resample = scipy.signal.resample_poly's arithmetic),
+    enhanced exactly as below - RMS scale, wrap-padding and chunking all apply to the model-rate signal - and resampled
+    back and cut to the input's length (shorter only where the model-rate path itself returns fewer samples than it got:
+    hop 300 on a length that is no multiple of it).  None (or model_rate itself) is the reference's path."""
     if noisy.dim() != 2 or noisy.size(0) != 1:
         raise ValueError("expected a mono track shaped [1, L] (torchaudio.load layout)")
     eng = model.engine
+    if sample_rate is not None and int(sample_rate) != int(model_rate):
+        x = eng.resample(noisy.to(device=eng.device, dtype=torch.float32), sample_rate, model_rate)
+        est = enhance_one_track(model, x, cut_len, n_fft, hop)
+        # ceil(ceil(L u / d) d / u) >= L: the round trip never comes back short
+        return eng.resample(est[None, :], model_rate, sample_rate)[0, :noisy.size(-1)]
     if (eng.cfg.n_fft, eng.cfg.hop) != (n_fft, hop):
         raise ValueError("model was built for a different n_fft / hop")
     noisy = noisy.to(dtype=torch.float32).contiguous()
@@ -80,9 +91,37 @@ def _read_wav(path: str):
     return data, sr
 
 
+def _save_track(path: str, sr: int, est_host: np.ndarray, subtype: str):
+    from scipy.io import wavfile
+    if subtype == "PCM_16":     # libsndfile's float -> int16 conversion: scale by 2^15, round, clip
+        wavfile.write(path, sr, np.clip(np.rint(est_host * 32768.0), -32768, 32767).astype(np.int16))
+    else:
+        wavfile.write(path, sr, est_host.astype(np.float32))
+
+
+def _score_resampled(model, name, noisy, sr, clean_dir, model_rate, n_fft, hop, fn, saved_dir, subtype) -> torch.Tensor:
+    """One file of evaluation(resample=True): enhance at the model's rate, save at the file's, score at 16 kHz.  Returns
+    the six scores as a float64 [6] device tensor."""
+    eng = model.engine
+    dev = torch.device(eng.device)
+    est = enhance_one_track(model, torch.from_numpy(noisy).to(dev, torch.float32)[None, :], model_rate * 16, n_fft, hop,
+                            sample_rate=sr, model_rate=model_rate)
+    if saved_dir is not None:
+        _save_track(os.path.join(saved_dir, name), sr, est.cpu().numpy().astype(np.float64), subtype)
+    clean, sr_c = _read_wav(os.path.join(clean_dir, name))
+    clean16 = eng.resample(torch.from_numpy(clean).to(dev, torch.float32)[None, :], sr_c, 16000)
+    est16 = eng.resample(est[None, :], sr, 16000)
+    mos = None
+    if fn is not None:
+        mos = float(fn(16000, clean16[0].cpu().numpy().astype(np.float64), est16[0].cpu().numpy().astype(np.float64)))
+    s = eng.metrics(clean16, est16, 16000, pesq_mos=mos)
+    return torch.stack(tuple(s[:6]), dim=1)[0]
+
+
 @torch.no_grad()
 def evaluation(model, noisy_dir: str, clean_dir: str, save_tracks: bool = False, saved_dir: str | None = None,
-               pesq_fn=None, verbose: bool = True, subtype: str = "PCM_16", allow_missing_pesq: bool = False):
+               pesq_fn=None, verbose: bool = True, subtype: str = "PCM_16", allow_missing_pesq: bool = False,
+               resample: bool = False, model_rate: int = 16000):
     """Enhance every .wav of `noisy_dir`, score it against the file of the same name in `clean_dir`, and
     return the six averages in the reference's order (pesq, csig, cbak, covl, ssnr, stoi).
 
@@ -93,7 +132,13 @@ def evaluation(model, noisy_dir: str, clean_dir: str, save_tracks: bool = False,
     the four PESQ-dependent averages are NaN and a warning says so.  Saved tracks are 16-bit PCM like the
     reference's `sf.write(path, est, sr)` default (`subtype="FLOAT"` keeps float32 samples instead).  Each track is scored
 on the GPU (`model.engine.metrics`, float64 arithmetic on the float32 device samples); the enhanced track is copied to
-the host only when it is saved or `pesq_fn` needs it."""
+the host only when it is saved or `pesq_fn` needs it.
+
+    resample=False keeps the reference's rule: a file that is not 16 kHz raises (evaluation.py:19).  resample=True takes
+    noisy files at any supported rate: each is enhanced through enhance_one_track(sample_rate=its rate,
+    model_rate=model_rate) - model_rate=48000 with the 48 kHz model - and saved at its own rate and length; the estimate
+    and the clean file are then brought to 16 kHz on the device (Engine.resample) and scored there, since the metric
+    kernels, like the reference's tool, know 16 and 8 kHz only."""
     from . import metrics
     n_fft = 400
     if isinstance(model, (str, os.PathLike)):
@@ -116,15 +161,20 @@ the host only when it is saved or `pesq_fn` needs it."""
     if not names:
         raise ValueError(f"no .wav files in {noisy_dir}")
     eng = model.engine
+    n_fft, hop = int(eng.cfg.n_fft), int(eng.cfg.hop)
     dev = torch.device(eng.device)
     fn = pesq_fn if pesq_fn is not None else metrics._default_pesq()
     total = torch.zeros(6, dtype=torch.float64, device=dev)       # per-track scores summed on the device, in order
     for name in names:
         noisy, sr = _read_wav(os.path.join(noisy_dir, name))
+        if resample:
+            total += _score_resampled(model, name, noisy, sr, clean_dir, model_rate, n_fft, hop, fn,
+                                      saved_dir if save_tracks else None, subtype)
+            continue
         if sr != 16000:
             raise ValueError(f"{name}: expected 16 kHz audio, got {sr}")           # evaluation.py:19
         est = enhance_one_track(model, torch.from_numpy(noisy).to(dev, torch.float32)[None, :],
-                                16000 * 16, n_fft, n_fft // 4)
+                                16000 * 16, n_fft, hop)
         est_host = est.cpu().numpy().astype(np.float64) if (save_tracks or fn is not None) else None
         if save_tracks:
             from scipy.io import wavfile

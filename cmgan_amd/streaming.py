@@ -593,11 +593,24 @@ class StreamingEnhancer:
     file-level RMS, so it is a parameter (e.g. from the calibration stretch); the output is divided by it again.
     The result equals `enhance_stream` on the whole signal with the same statistics and scale to rounding (1.5e-6: the
     split-f16 transforms scale each 64-frame tile by its own power of two, and the blocks tile the frames differently).
-    stats_mode="running" needs no `stats` (a live caller has no clip to calibrate on): see StreamState."""
+    stats_mode="running" needs no `stats` (a live caller has no clip to calibrate on): see StreamState.
+
+    sample_rate: the rate of the pushed audio when it is not the model's (`model_rate`: 16000, or 48000 with the 48 kHz
+    model).  A cmgan_amd.resample.Resampler then sits in front of the stream and another behind it, so samples go in and
+    come out at sample_rate without leaving the device.  At flush() the model-rate signal is zero-padded to the next
+    multiple of hop (the stream must end on one) and the total output is trimmed to the number of samples pushed, which
+    may then be any number.  None (or model_rate itself): no resampler, the class as described above."""
 
     def __init__(self, model: TSCNet, stats: torch.Tensor | None = None, window: int = 400, context: int = 40,
-                 lookahead: int = 40, scale: float | torch.Tensor = 1.0, graph: bool = True, stats_mode: str = "frozen"):
+                 lookahead: int = 40, scale: float | torch.Tensor = 1.0, graph: bool = True, stats_mode: str = "frozen",
+                 sample_rate: int | None = None, model_rate: int = 16000):
         self.eng = model.engine
+        self.rs_in = self.rs_out = None
+        if sample_rate is not None and int(sample_rate) != int(model_rate):
+            from .resample import Resampler
+            self.rs_in = Resampler(self.eng, sample_rate, model_rate)
+            self.rs_out = Resampler(self.eng, model_rate, sample_rate)
+            self.n_ext_in = self.n_ext_out = 0         # samples pushed / emitted at sample_rate
         self.hop, self.n_fft = self.eng.cfg.hop, self.eng.cfg.n_fft
         if self.n_fft != 4 * self.hop:
             raise ValueError("StreamingEnhancer assumes n_fft = 4 hop (400 / 100, 1200 / 300)")
@@ -683,6 +696,15 @@ class StreamingEnhancer:
         """samples: float32 GPU tensor, any shape (flattened) -> the enhanced samples that became final (maybe none)."""
         if self.closed:
             raise RuntimeError("stream already flushed")
+        if self.rs_in is None:
+            return self._push_model(samples)
+        x = samples.reshape(1, -1)
+        self.n_ext_in += x.size(1)
+        y = self.rs_out.push(self._push_model(self.rs_in.push(x))[None, :])[0]
+        self.n_ext_out += y.numel()
+        return y
+
+    def _push_model(self, samples: torch.Tensor) -> torch.Tensor:
         x = samples.reshape(-1).to(device=self.eng.device, dtype=torch.float32)
         self.samples = torch.cat([self.samples, x])
         self.n_in += x.numel()
@@ -695,6 +717,19 @@ class StreamingEnhancer:
         """End of the stream (its length must be a multiple of hop, like one reference row): the remaining samples."""
         if self.closed:
             return torch.empty(0, device=self.eng.device)
+        if self.rs_in is None:
+            return self._flush_model()
+        head = self._push_model(self.rs_in.flush())
+        pad = -self.n_in % self.hop                          # the model-rate stream must end on a multiple of hop
+        if pad:
+            head = torch.cat([head, self._push_model(torch.zeros(pad, device=self.eng.device))])
+        tail = self._flush_model()
+        y = torch.cat([self.rs_out.push(torch.cat([head, tail])[None, :]), self.rs_out.flush()], dim=1)[0]
+        y = y[:self.n_ext_in - self.n_ext_out]               # (the round trip and the padding never come back short)
+        self.n_ext_out += y.numel()
+        return y
+
+    def _flush_model(self) -> torch.Tensor:
         if self.n_in % self.hop or self.n_in <= self.n_fft // 2:
             raise ValueError("a stream must end on a multiple of hop and be longer than n_fft / 2")
         self.closed = True

@@ -569,6 +569,38 @@ int cmgan_metrics(cmgan_handle* h, const float* clean_dev, const float* enh_dev,
  * count; otherwise writes it (cap >= count) and returns it.  Negative CMGAN_E_* on error.                          */
 int cmgan_metrics_table(int fs, int which, double* out_host, size_t cap);
 
+/* ---- Sample-rate conversion (the reference asserts sr == 16000, src/evaluation.py:19, and leaves it to the user) ------
+ * Rational-rate polyphase FIR resampling of a float32 batch: the arithmetic of scipy.signal.resample_poly(x, up, down)
+ * with its default window ('kaiser', 5.0) and padtype='constant'.  With g = gcd(fs_in, fs_out), up = fs_out / g,
+ * down = fs_in / g, m = max(up, down), half_len = 10 m:
+ *   taps        h = firwin(2 half_len + 1, 1 / m, window=('kaiser', 5.0)) * up in float64, with
+ *               pre = down - half_len % down zeros in front (n_taps counts them)
+ *   pre_remove  (half_len + pre) / down
+ *   length      N = ceil(L up / down)
+ *   output      y[n] = sum_i x[i] h[(n + pre_remove) down - i up], 0 <= n < N, over the i whose tap index lies in
+ *               [0, n_taps), with x[i] = 0 outside [0, L)
+ * Products and sums are float64, the taps of one output are added in ascending tap index, and the sum is rounded to
+ * float32 once.  Supported: positive rates whose reduced max(up, down) <= 640 (a table of at most 13 441 doubles), else
+ * CMGAN_E_UNSUPPORTED.  fs_in == fs_out is a copy.
+ * cmgan_resample_geometry / _out_len are host arithmetic (no handle, no GPU; out_len returns a negative code on error);
+ * cmgan_resample_table exports the taps (same C++ code as the table kernel; tap-major, pre-pad included) with the
+ * calling convention of cmgan_metrics_table.
+ * cmgan_resample serves whole signals and chunks: it writes outputs [n0_out, n0_out + n_out) of every row to
+ * y_dev[b * ld_out + (n - n0_out)], reading a buffer x_dev[b * ld_in + q] that holds samples [pos_in, pos_in + n_buf) of
+ * the signal; samples outside the buffer count as zero.  A whole signal is pos_in = n0_out = 0, n_buf = L, n_out = N.
+ * A zero sample leaves the float64 sum unchanged, so a chunked call whose buffer holds every sample its outputs reach -
+ * inputs ceil(((n0_out + pre_remove) down - (n_taps - 1)) / up) .. floor((n0_out + n_out - 1 + pre_remove) down / up),
+ * those inside the signal - gives the SAME BITS as the whole-signal call.  The caller keeps n0_out + n_out <= N.
+ * Workspace: cmgan_resample_workspace_bytes (h may be NULL; 0 for an unsupported pair), 256-byte aligned; it receives
+ * the phase-major tap table, rebuilt by every call.  No synchronisation, no allocation, no atomics; graph-capturable. */
+int cmgan_resample_geometry(int fs_in, int fs_out, int* up, int* down, int* n_taps, int* pre_remove);
+long long cmgan_resample_out_len(int fs_in, int fs_out, long long n_in);
+int cmgan_resample_table(int fs_in, int fs_out, double* out_host, size_t cap);
+size_t cmgan_resample_workspace_bytes(const cmgan_handle* h, int fs_in, int fs_out);
+int cmgan_resample(cmgan_handle* h, const float* x_dev, int B, int n_buf, long long ld_in, long long pos_in,
+                   int fs_in, int fs_out, long long n0_out, int n_out, float* y_dev, long long ld_out,
+                   void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Names + durations (ms) of the kernels of the most recent forward when
  * profiling is enabled with cmgan_set_profiling(h, 1): HIP events are recorded
  * around every launch on the caller's stream.  cmgan_profile_read synchronises
