@@ -64,6 +64,65 @@ class FrameScores(NamedTuple):
     segsnr: torch.Tensor
 
 
+class MixInfo(NamedTuple):
+    """Engine.mix: float64 [B] device tensors - the noise gain, the peak scale and the powers of speech and noise, so the
+    achieved SNR is 10 log10(Ps / (g^2 Pn)) without reading audio again."""
+    g: torch.Tensor
+    scale: torch.Tensor
+    Ps: torch.Tensor
+    Pn: torch.Tensor
+
+
+MIX_MAX_TAPS = 65536          # longest RIR of cmgan_mix
+
+
+def check_mix_args(device, clean, noise_bank, noise_start, noise_len, noise_off, snr_db, rir_bank=None, rir_index=None,
+                   rir_len=None, peak: float = 0.99, early: int = -1):
+    """Argument rules of Engine.mix (shapes, dtypes, devices and host scalars; pure host code).  Returns (B, L, R, Kmax)."""
+    def need(t, name, dtype, shape_txt, ok):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: expected a torch.Tensor, got {type(t).__name__}")
+        if t.dtype != dtype:
+            raise TypeError(f"{name}: expected {str(dtype).replace('torch.', '')}, got {str(t.dtype).replace('torch.', '')}")
+        if t.device != device:
+            raise RuntimeError(f"{name}: tensor is on {t.device} but this Engine is bound to {device}")
+        if not ok(t):
+            raise ValueError(f"{name}: expected {shape_txt}, got {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: must be contiguous")
+
+    need(clean, "clean", torch.float32, "[B, L] with B, L >= 1", lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) >= 1)
+    B, L = clean.shape
+    if B > 65535:
+        raise ValueError(f"clean: at most 65535 rows, got {B}")
+    need(noise_bank, "noise_bank", torch.float32, "a flat bank of >= 1 samples", lambda t: t.dim() == 1 and t.numel() >= 1)
+    row = lambda t: tuple(t.shape) == (B,)
+    need(noise_start, "noise_start", torch.int64, f"[{B}]", row)
+    need(noise_len, "noise_len", torch.int64, f"[{B}]", row)
+    need(noise_off, "noise_off", torch.int64, f"[{B}]", row)
+    need(snr_db, "snr_db", torch.float32, f"[{B}]", row)
+    R, Kmax = 0, 0
+    if rir_bank is None:
+        if rir_index is not None or rir_len is not None:
+            raise ValueError("rir_index / rir_len given without a rir_bank")
+    else:
+        need(rir_bank, "rir_bank", torch.float32, "[R, Kmax] with R, Kmax >= 1",
+             lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) >= 1)
+        R, Kmax = rir_bank.shape
+        if Kmax > MIX_MAX_TAPS:
+            raise ValueError(f"rir_bank: RIRs of up to {MIX_MAX_TAPS} taps are supported, got Kmax = {Kmax}")
+        if rir_index is None or rir_len is None:
+            raise ValueError("a rir_bank needs rir_index and rir_len")
+        need(rir_index, "rir_index", torch.int32, f"[{B}]", row)
+        need(rir_len, "rir_len", torch.int32, f"[{B}]", row)
+    peak = float(peak)
+    if not (peak > 0.0 and peak < float("inf")):
+        raise ValueError(f"peak must be positive and finite, got {peak}")
+    if int(early) != early or early < -1:
+        raise ValueError(f"early must be -1 (dry target) or a sample count >= 0, got {early}")
+    return B, L, R, Kmax
+
+
 def metric_frames(L: int, fs: int):
     """(WSS / segSNR frames, LLR frames) of an L-sample signal: the two counts of cmgan_amd.metrics."""
     win = int(np.round(30 * fs / 1000))
@@ -130,6 +189,7 @@ class Engine:
         self._bws: Optional[torch.Tensor] = None          # workspace of the two-branch form (enhance_graphed(branches=2))
         self._mws: Optional[torch.Tensor] = None          # workspace of metrics()
         self._rws: dict = {}             # resample(): (fs_in, fs_out) -> workspace (the pair's tap table)
+        self._xws: Optional[torch.Tensor] = None          # workspace of mix()
         self._graphs: dict = {}          # enhance_graphed: input shape -> (graph, in, out, token)
         self._row_graphs: dict = {}      # streaming.enhance_windows: row shape -> (graph, in, out, token)
         self._stream_slots: dict = {}    # streaming.StreamState(graph=True): (B, W, Ca, La, stats mode) -> state + step graphs
@@ -704,6 +764,40 @@ class Engine:
         y = self.resample_chunk(wav, 0, fs_in, fs_out, 0, out_len(fs_in, fs_out, wav.size(-1)), out=out)
         return y[0] if squeeze else y
 
+    # ---- dynamic mixing ------------------------------------------------------------
+    @_on_device
+    def mix(self, clean: torch.Tensor, noise_bank: torch.Tensor, noise_start: torch.Tensor, noise_len: torch.Tensor,
+            noise_off: torch.Tensor, snr_db: torch.Tensor, rir_bank: Optional[torch.Tensor] = None,
+            rir_index: Optional[torch.Tensor] = None, rir_len: Optional[torch.Tensor] = None, peak: float = 0.99,
+            early: int = -1):
+        """Noisy (and reverberant) training pairs from clean speech on the GPU (cmgan_mix, include/cmgan_hip.h).
+
+        clean float32 [B, L]; noise_bank flat float32 with int64 [B] noise_start / noise_len / noise_off (row b loops
+        over bank[start : start + len] from offset off); snr_db float32 [B]; optionally rir_bank float32 [R, Kmax]
+        (zero-padded rows) with int32 [B] rir_index / rir_len.  All on this Engine's device; the per-row tensors are read
+        by the kernels only.  `early`: samples of early reflections kept in the target, -1 for the dry clip.
+        Returns (noisy [B, L], target [B, L], MixInfo of float64 [B]).  Float64 arithmetic, one rounding to float32;
+        bit-reproducible, row-independent, no synchronisation, graph-capturable after one call at the shape."""
+        B, L, R, Kmax = check_mix_args(self.device, clean, noise_bank, noise_start, noise_len, noise_off, snr_db, rir_bank,
+                                       rir_index, rir_len, peak, early)
+        need = int(self.lib.cmgan_mix_workspace_bytes(self._h, B, L, max(Kmax, 1)))
+        if need == 0:
+            raise ValueError(f"[{B}, {L}] with {Kmax} taps is outside what cmgan_mix supports")
+        if self._xws is None or self._xws.numel() < need:
+            self._xws = None
+            self._xws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        noisy = torch.empty(B, L, dtype=torch.float32, device=self.device)
+        target = torch.empty(B, L, dtype=torch.float32, device=self.device)
+        info = torch.empty(4, B, dtype=torch.float64, device=self.device)
+        rir = rir_bank is not None
+        check(self._h, self.lib.cmgan_mix(
+            self._h, clean.data_ptr(), B, L, L, noise_bank.data_ptr(), noise_bank.numel(), noise_start.data_ptr(),
+            noise_len.data_ptr(), noise_off.data_ptr(), rir_bank.data_ptr() if rir else None, R, Kmax,
+            rir_index.data_ptr() if rir else None, rir_len.data_ptr() if rir else None, snr_db.data_ptr(), float(peak),
+            int(early), noisy.data_ptr(), target.data_ptr(), L, info[0].data_ptr(), info[1].data_ptr(),
+            info[2].data_ptr(), info[3].data_ptr(), self._xws.data_ptr(), self._xws.numel(), self._stream()))
+        return noisy, target, MixInfo(info[0], info[1], info[2], info[3])
+
     # ---- diagnostics ---------------------------------------------------------------
     @_on_device
     def selftest_mfma(self) -> float:
@@ -723,7 +817,7 @@ class Engine:
         self._graphs.clear()
         self._row_graphs.clear()
         self._stream_slots.clear()
-        self._ws = self._bws = self._cws = self._mws = None
+        self._ws = self._bws = self._cws = self._mws = self._xws = None
         self._rws.clear()
 
     def set_profiling(self, on: bool):

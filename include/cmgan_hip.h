@@ -39,7 +39,7 @@ extern "C" {
 #define CMGAN_E_WORKSPACE   -5   /* workspace too small or misaligned              */
 #define CMGAN_E_HIP         -6   /* a HIP runtime call failed (see last_error)     */
 
-#define CMGAN_ABI_VERSION 6
+#define CMGAN_ABI_VERSION 7
 
 typedef struct cmgan_handle cmgan_handle;
 
@@ -600,6 +600,49 @@ size_t cmgan_resample_workspace_bytes(const cmgan_handle* h, int fs_in, int fs_o
 int cmgan_resample(cmgan_handle* h, const float* x_dev, int B, int n_buf, long long ld_in, long long pos_in,
                    int fs_in, int fs_out, long long n0_out, int n_out, float* y_dev, long long ld_out,
                    void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- Dynamic mixing (the reference replays pairs mixed beforehand: src/data/dataloader.py:13-50 reads clean/x.wav and
+ * noisy/x.wav; its --cut_len help names "denoise and dereverberation") ------------------------------------------------
+ * Turns B rows of clean speech, clean_dev[b * ld + i], 0 <= i < L, into a (noisy, target) training pair per row.  Every
+ * per-row draw is read from DEVICE memory by the kernels, never by the host:
+ *   noise   a flat float32 bank of bank_len samples; row b uses the segment noise_start[b] .. + noise_len[b] from
+ *           offset noise_off[b] (int64 [B] each)
+ *   RIR     optional: a float32 bank [R, Kmax], rows zero-padded, with rir_index[b] and rir_len[b] (int32 [B]);
+ *           rir_bank_dev == NULL means no reverberation (R, Kmax, rir_index_dev, rir_len_dev are then ignored)
+ *   snr_db  float32 [B], the requested speech-to-noise ratio
+ *   peak    host float, the peak limit;  early  host int, the samples of early reflections kept in the target, -1 for a
+ *           dry target
+ * With h = rir[rir_index[b], 0:K], K = rir_len[b] (without a bank h = [1]):
+ *   direct path  d = the FIRST index at which |h| is largest (without a bank d = 0)
+ *   speech       speech[i] = sum_{k = 0 .. K-1} h[k] clean[b, i + d - k], 0 <= i < L, with clean = 0 outside [0, L):
+ *                the direct-path delay is removed, so speech stays aligned with the dry clip
+ *   target       early == -1: target = clean, a copy of its bits.  Otherwise the same sum over the taps k <= d + early:
+ *                early >= K gives the reverberant speech itself, early = 0 everything up to and including the direct path
+ *   noise        n[i] = bank[noise_start[b] + (noise_off[b] + i) mod noise_len[b]]: a short item wraps as often as needed
+ *   gain         Ps = mean(speech^2), Pn = mean(n^2), g = sqrt(Ps / (Pn 10^(snr_db[b] / 10))); g = 0 when Ps == 0 or Pn == 0
+ *   mix          v = speech + g n, m = max_i |v[i]|, s = peak / m if m > peak, else exactly 1
+ *   outputs      noisy_dev[b * ld_out + i] = f32(v[i] s), target_dev[b * ld_out + i] = f32(target[i] s); with s == 1 and
+ *                early == -1 the target is bit-identical to clean.  g_dev, scale_dev (= s), ps_dev, pn_dev: float64 [B]
+ * Every product and sum is float64 and every output sample is rounded to float32 exactly once.  Ps, Pn and m are two-stage
+ * reductions in a fixed order that depends on L alone (one partial per tile of cmgan_mix_tile() samples, then the
+ * partials in ascending order): no atomics, the same bits from run to run, and row b's outputs depend neither on B nor on
+ * the other rows.  Both sums of the target variant come from one pass over the same loads.
+ * Supported: 1 <= B <= 65535, 1 <= L <= 2^31 - 1 - cmgan_mix_tile(), 1 <= Kmax <= 65536 (K may exceed L), else
+ * CMGAN_E_BADARG / CMGAN_E_UNSUPPORTED before any launch.  Every argument is checked before the handle is, and the message
+ * of a call with h == NULL is read with cmgan_last_error(NULL).  Table entries cannot be checked by the host without a
+ * synchronisation, so the kernels never follow one outside its bank: a noise segment that is empty or leaves
+ * [0, bank_len) counts as silence, rir_index is clamped to [0, R) and rir_len to [1, Kmax]; noise_off may be any int64.
+ * Workspace: cmgan_mix_workspace_bytes (h may be NULL; 0 for an unsupported shape; non-decreasing in B, L and Kmax),
+ * 256-byte aligned; it holds the float64 speech and target rows between the launches.  Six launches (five without a
+ * bank), no synchronisation, no allocation; graph-capturable, and a replay reads the tables' current contents.          */
+int cmgan_mix_tile(void);
+size_t cmgan_mix_workspace_bytes(const cmgan_handle* h, int B, int L, int Kmax);
+int cmgan_mix(cmgan_handle* h, const float* clean_dev, int B, int L, long long ld, const float* noise_bank_dev,
+              long long bank_len, const long long* noise_start_dev, const long long* noise_len_dev,
+              const long long* noise_off_dev, const float* rir_bank_dev, int R, int Kmax, const int* rir_index_dev,
+              const int* rir_len_dev, const float* snr_db_dev, float peak, int early, float* noisy_dev,
+              float* target_dev, long long ld_out, double* g_dev, double* scale_dev, double* ps_dev, double* pn_dev,
+              void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* Names + durations (ms) of the kernels of the most recent forward when
  * profiling is enabled with cmgan_set_profiling(h, 1): HIP events are recorded
