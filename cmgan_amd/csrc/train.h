@@ -135,6 +135,47 @@ __device__ __forceinline__ void ln_tile_colsums(f32x4 (&a)[4], f32x4 (&b)[4], in
         }
     }
 }
+// ------------------------------- train_x3.hip ------------------------------------
+// the split-f16 kernels of the slices above, launched from train.hip's launch_* sequences
+void ffn_x3_pack(LaunchCtx, const FfnTrainParams& p, float* img);
+void ffn_x3_forward(LaunchCtx, const float* x, long M, const FfnTrainParams& p, const float* img, const unsigned char* m1,
+                    const unsigned char* m2, float ms, const float* res, float* y);
+int ffn_x3_backward_fused(LaunchCtx, const float* x, const float* dy, long M, const FfnTrainParams& p, const float* img,
+                          const unsigned char* m1, const unsigned char* m2, float ms, const float* dres, float* dx,
+                          float* o_dh, float* o_g1, float* o_dxn, float* dhmax, float* o_dzc, float* o_dhc, float* part_w2,
+                          float* part_w1);
+void ffn_x3_backward(LaunchCtx, const float* x, const float* dy, long M, const FfnTrainParams& p, const float* img,
+                     const unsigned char* m1, const unsigned char* m2, float ms, const float* dres, float* dx, float* o_dz,
+                     float* o_d1, float* o_dh, float* o_xn, float* o_g1, float* o_dxn, float* dhmax, float* o_dzc, float* o_dhc);
+void launch_wgrad_partial64_x3(LaunchCtx, const char* label, const float* P, const float* Q, long M, int R, int C,
+                               float* partial, int nsplit, float* colp);
+void launch_db_conv_wgrad_x3(LaunchCtx, const float* dz, const float* a, int B, int T, int F, int dil, int nsplit,
+                             float* partial, float* colp);
+void cm_x3_pack(LaunchCtx, const ConvModTrainParams& p, float* img_w1, float* img_w1t);
+void cm_x3_pw1glu(LaunchCtx, const float* x, long M, const float* img_w1, const ConvModTrainParams& p, float* u);
+void cm_x3_bwd2(LaunchCtx, const float* x, const float* du, long M, const float* img_w1, const float* img_w1t,
+                const ConvModTrainParams& p, const float* dres, float* dx, float* dag, float* xn_out, float* g1c, float* dxc);
+void cm_x3_pack_pw2(LaunchCtx, const ConvModTrainParams& p, float* img_w2, float* img_w2t);
+void cm_x3_bn_swish_pw2(LaunchCtx, const float* d, long M, const float* scale, const float* shift, const float* img_w2,
+                        const float* b2, const float* res, float* y);
+int cm_x3_bwd2_fused(LaunchCtx, const float* x, const float* du, long M, const float* img_w1t, const ConvModTrainParams& p,
+                     const float* dres, float* dx, float* dag, float* o_g1, float* o_dxn, float* o_dhc, float* dhmax,
+                     float* part_w1);
+int cm_x3_bwd1_fused(LaunchCtx, const float* dy, const float* d, long M, const float* mean, const float* rstd,
+                     const float* scale, const float* shift, const float* w2raw, float* ddn, float* g2c, float* ddnc, float* dyc,
+                     float* part_w2);
+void cm_x3_bwd1(LaunchCtx, const float* dy, const float* d, long M, const float* mean, const float* rstd, const float* scale,
+                const float* shift, const float* img_w2t, float* ddn, float* s_out, float* g2c, float* ddnc, float* dyc);
+void at_x3_pack(LaunchCtx, const float* wraw, float* img_w, float* img_wt);
+void at_x3_qkv(LaunchCtx, const float* x, long M, const float* img_w, const float* ln_w, const float* ln_b, float* qkv,
+               int as_image, float qscale);
+void at_x3_qkv_bwd(LaunchCtx, const float* x, const float* dqkv, long M, const float* img_wt, const float* ln_w,
+                   const float* ln_b, const float* dres, float* dx, float* xn_out, float* g1c, float* dxc);
+// row-conv geometry (train.hip "Row conv"); Fo = output positions per row (before the pixel shuffle)
+struct RcGeom { int B, T, Fi, Fo, KW, SF, PL; };
+void launch_rc_wgrad_x3(LaunchCtx, int ng, const float* dz, const float* in, const RcGeom& gm, int nsplit, float* partial,
+                        float* colp);
+bool launch_rc_dgrad_x3(LaunchCtx, int ng, const float* dz, const float* wraw, const RcGeom& gm, float* din);
 // ------------------------------- disc.hip ----------------------------------------
 // the metric discriminator Discriminator(ndf=16) (src/models/discriminator.py:29-64) on RAW parameters
 struct DiscParams {

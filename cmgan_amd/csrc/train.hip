@@ -106,9 +106,9 @@ void launch_loss_terms(LaunchCtx ctx, const float* est_real, const float* est_im
 // with autograd on the oracle.
 // The residual add of ConformerBlock.forward (conformer.py:217) stays with the caller (dx_total = dy + dx).
 //
-// Same per-token transposed MFMA chain as the inference kernels (out^T = W x^T on v_mfma_f32_16x16x4_f32, a wave owns
-// 16 tokens, C-fragments of one layer are the B-fragments of the next), on RAW parameters: the four A-operand images
-// (W1, W2, W2^T, W1^T, fragment-major) are re-packed on the device at every call because an optimiser step changes them.
+// Same per-token transposed MFMA chain as the inference kernels (out^T = W x^T, C-fragments of one layer are the
+// B-fragments of the next) on split-f16 products (the kernels are in train_x3.hip), on RAW parameters: the four A-operand
+// images (W1, W2, W2^T, W1^T) are re-packed on the device at every call because an optimiser step changes them.
 // Backward recomputes LN / W1 / Swish from x instead of saving the [M,256] hidden activations of the forward
 // (1 GB at B = 32): on this machine the extra 64x256 GEMM is cheaper than the HBM round trip.
 //   dz = 0.5 m2 dy              dW2 = dz^T d1     db2 = colsum dz
@@ -119,7 +119,7 @@ void launch_loss_terms(LaunchCtx ctx, const float* est_real, const float* est_im
 // second kernel adds in a fixed order - deterministic, no atomics.
 // =====================================================================================
 // row-major W [R, K] (leading dimension ldw; transpose = 1: the image of W^T) -> fragment-major image [R/16][K/16][64][4]
-// (common.hip.h); the four images of one module in ONE launch (blockIdx.y = image): a training step re-packs 128 images
+// (common.hip.h); the images of one module in ONE launch (blockIdx.y = image)
 struct PackJob { const float* w; int R, K, ldw, transpose; float* out; };
 struct PackJobs { PackJob j[4]; };
 __global__ void pack_fm4_kernel(PackJobs jobs) {
@@ -131,7 +131,7 @@ __global__ void pack_fm4_kernel(PackJobs jobs) {
     const int row = 16 * rb + (lane & 15), col = 16 * kb + 4 * (lane >> 4) + r;
     q.out[i] = q.transpose ? q.w[(long)col * q.ldw + row] : q.w[(long)row * q.ldw + col];
 }
-static void launch_pack4(LaunchCtx ctx, const char* label, const PackJobs& jobs, int njobs = 4) {
+static void launch_pack4(LaunchCtx ctx, const char* label, const PackJobs& jobs, int njobs) {
     int most = 0;
     for (int k = 0; k < njobs; ++k) most = jobs.j[k].R * jobs.j[k].K > most ? jobs.j[k].R * jobs.j[k].K : most;
     LAUNCH(ctx, label, (pack_fm4_kernel<<<dim3((most + 255) / 256, njobs), 256, 0, ctx.stream>>>(jobs)));
@@ -139,17 +139,6 @@ static void launch_pack4(LaunchCtx ctx, const char* label, const PackJobs& jobs,
 
 // Dropout keep-masks are BYTES (non-zero = keep; the kept values are scaled by `ms` = 1 / (1 - p)): a quarter of the
 // traffic of float masks - per conformer block and token 704 mask values are read in the forward and again in the backward
-__device__ __forceinline__ unsigned mask_word(const unsigned char* __restrict__ m, long idx) {   // idx % 4 == 0
-    return *reinterpret_cast<const unsigned*>(m + idx);
-}
-__device__ __forceinline__ f32x4 mask4w(unsigned v, float ms) {
-    f32x4 r;
-    r[0] = (v & 0x000000ffu) ? ms : 0.f;
-    r[1] = (v & 0x0000ff00u) ? ms : 0.f;
-    r[2] = (v & 0x00ff0000u) ? ms : 0.f;
-    r[3] = (v & 0xff000000u) ? ms : 0.f;
-    return r;
-}
 __device__ __forceinline__ f32x4 mask4(const unsigned char* __restrict__ m, long idx, float ms) {
     const unsigned v = *reinterpret_cast<const unsigned*>(m + idx);          // idx is a multiple of 4
     f32x4 r;
@@ -160,307 +149,13 @@ __device__ __forceinline__ f32x4 mask4(const unsigned char* __restrict__ m, long
     return r;
 }
 
-struct FfnTrainImg {
-    const float *w1, *w2, *w2t, *w1t;     // fm [16][4], [4][16], [16][4], [4][16]
-    const float *gamma, *beta, *b1, *b2;
-};
-
-__device__ __forceinline__ bool ffn_load_norm(const float* __restrict__ x, long M, long t0, int c, int g,
-                                              const FfnTrainImg& w, f32x4 (&xh)[4], f32x4 (&xn)[1][4], float& rstd,
-                                              long& row) {
-    const long t = t0 + c;
-    const bool ok = t < M;
-    row = ok ? t : M - 1;
-    f32x4 xv[4];
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) xv[kb] = ldg4(x + row * 64 + 16 * kb + 4 * g);
-    float mean;
-    ln_stats(xv, mean, rstd);
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-        xh[kb] = (xv[kb] - splat4(mean)) * splat4(rstd);
-        xn[0][kb] = xh[kb] * ldg4(w.gamma + 16 * kb + 4 * g) + ldg4(w.beta + 16 * kb + 4 * g);
-    }
-    return ok;
-}
-
-// four weight fragments = the A operands of 16 MFMAs.  rows: fragments [blk][0..3] of an image whose k-blocks are
-// contiguous (W1 [16][4], W2^T [16][4]); cols: fragments [0..3][blk] of an image with 16 k-blocks per row (W2, W1^T [4][16])
-struct FfnFrag { f32x4 a[4]; };
-__device__ __forceinline__ FfnFrag ffn_frag_rows(const float* __restrict__ img, int blk, int lane) {
-    FfnFrag f;
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) f.a[kb] = ldg4(img + ((long)blk * 4 + kb) * 256 + lane * 4);
-    __builtin_amdgcn_sched_barrier(0);    // keep the loads HERE: the scheduler otherwise sinks them next to their use
-    return f;
-}
-__device__ __forceinline__ FfnFrag ffn_frag_cols(const float* __restrict__ img, int blk, int lane) {
-    FfnFrag f;
-#pragma unroll
-    for (int ob = 0; ob < 4; ++ob) f.a[ob] = ldg4(img + ((long)ob * 16 + blk) * 256 + lane * 4);
-    __builtin_amdgcn_sched_barrier(0);
-    return f;
-}
-// acc + sum_kb frag[kb] x xf[kb]: one output block of a per-token linear layer (lin_acc<4, 1> on prefetched fragments)
-__device__ __forceinline__ f32x4 ffn_frag_mma(const FfnFrag& f, const f32x4 (&xf)[4], f32x4 acc) {
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc = mfma16(f.a[kb][r], xf[kb][r], acc);
-    return acc;
-}
-
-__global__ __launch_bounds__(256) void ffn_train_fwd_kernel(const float* __restrict__ x, long M, FfnTrainImg w,
-                                                            const unsigned char* __restrict__ m1,
-                                                            const unsigned char* __restrict__ m2, float ms,
-                                                            const float* __restrict__ res, float* __restrict__ y) {
-    const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
-    const long t0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16;
-    if (t0 >= M) return;
-    f32x4 xh[4], xn[1][4];
-    float rstd;
-    long row;
-    const bool ok = ffn_load_norm(x, M, t0, c, g, w, xh, xn, rstd, row);
-    f32x4 acc[4];
-#pragma unroll
-    for (int ob = 0; ob < 4; ++ob) acc[ob] = ldg4(w.b2 + 16 * ob + 4 * g);
-    // the weight fragments of the NEXT 16 MFMAs are fetched while the current 16 run (as written by the compiler, every
-    // group of 4 MFMAs waited for its own fragment: the kernel ran at L1 latency, not at the matrix rate)
-    // (loads retire in order: the small mask / bias loads of a block are issued BEFORE the fragment loads that are
-    // still in flight when they are needed)
-    unsigned mw = m1 ? mask_word(m1, row * 256 + 4 * g) : 0u;
-    f32x4 b1v = ldg4(w.b1 + 4 * g);
-    FfnFrag g1 = ffn_frag_rows(w.w1, 0, lane), g2;
-    for (int hb = 0; hb < 16; ++hb) {
-        g2 = ffn_frag_cols(w.w2, hb, lane);
-        const f32x4 h = ffn_frag_mma(g1, xn[0], b1v);
-        const f32x4 mk = m1 ? mask4w(mw, ms) : splat4(1.f);
-        const int hn = hb < 15 ? hb + 1 : 15;
-        if (m1) mw = mask_word(m1, row * 256 + 16 * hn + 4 * g);
-        b1v = ldg4(w.b1 + 16 * hn + 4 * g);
-        g1 = ffn_frag_rows(w.w1, hn, lane);
-        f32x4 s;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) s[r] = swishf(h[r]) * mk[r];
-#pragma unroll
-        for (int ob = 0; ob < 4; ++ob) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[ob] = mfma16(g2.a[ob][r], s[r], acc[ob]);
-        }
-    }
-    if (ok) {
-#pragma unroll
-        for (int ob = 0; ob < 4; ++ob) {
-            f32x4 v = acc[ob] * splat4(0.5f);
-            if (m2) v = v * mask4(m2, row * 64 + 16 * ob + 4 * g, ms);
-            if (res) v = v + ldg4(res + row * 64 + 16 * ob + 4 * g);      // the block's residual add, fused
-            stg4(y + row * 64 + 16 * ob + 4 * g, v);
-        }
-    }
-}
-
 struct FfnBwdBufs {
     float *dz, *d1, *dh, *xn, *g1, *dxn;      // [M,64] [M,256] [M,256] [M,64] [M,64] [M,64]
 };
 
-__global__ __launch_bounds__(256) void ffn_train_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy,
-                                                            long M, FfnTrainImg w, const unsigned char* __restrict__ m1,
-                                                            const unsigned char* __restrict__ m2, float ms,
-                                                            const float* __restrict__ dres, float* __restrict__ dx,
-                                                            FfnBwdBufs o) {
-    const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
-    const long t0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16;
-    if (t0 >= M) return;
-    f32x4 xh[4], xn[1][4];
-    float rstd;
-    long row;
-    const bool ok = ffn_load_norm(x, M, t0, c, g, w, xh, xn, rstd, row);
-    f32x4 dz[1][4];
-#pragma unroll
-    for (int ob = 0; ob < 4; ++ob) {
-        f32x4 v = ldg4(dy + row * 64 + 16 * ob + 4 * g) * splat4(0.5f);
-        if (m2) v = v * mask4(m2, row * 64 + 16 * ob + 4 * g, ms);
-        if (!ok) v = splat4(0.f);                       // padding tokens of the last block contribute nothing
-        dz[0][ob] = v;
-        if (ok) {
-            stg4(o.dz + row * 64 + 16 * ob + 4 * g, v);
-            stg4(o.xn + row * 64 + 16 * ob + 4 * g, xn[0][ob]);
-        }
-    }
-    f32x4 dxn[4];
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) dxn[kb] = splat4(0.f);
-    // three groups of 16 MFMAs per hidden block (W1 recompute, W2^T, W1^T); the next group's fragments are in flight
-    // while one runs
-    unsigned mw = m1 ? mask_word(m1, row * 256 + 4 * g) : 0u;
-    f32x4 b1v = ldg4(w.b1 + 4 * g);
-    FfnFrag g1 = ffn_frag_rows(w.w1, 0, lane), g2, g3;
-    for (int hb = 0; hb < 16; ++hb) {
-        g2 = ffn_frag_rows(w.w2t, hb, lane);
-        const f32x4 h = ffn_frag_mma(g1, xn[0], b1v);
-        g3 = ffn_frag_cols(w.w1t, hb, lane);
-        const f32x4 dd1 = ffn_frag_mma(g2, dz[0], splat4(0.f));
-        const f32x4 mk = m1 ? mask4w(mw, ms) : splat4(1.f);
-        const int hn = hb < 15 ? hb + 1 : 15;
-        if (m1) mw = mask_word(m1, row * 256 + 16 * hn + 4 * g);
-        b1v = ldg4(w.b1 + 16 * hn + 4 * g);
-        g1 = ffn_frag_rows(w.w1, hn, lane);
-        f32x4 d1v, dhv;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float hv = h[r], sg = sigmoidf_fast(hv);
-            d1v[r] = hv * sg * mk[r];
-            dhv[r] = dd1[r] * mk[r] * (sg * (1.f + hv * (1.f - sg)));
-        }
-        if (ok) {
-            stg4(o.d1 + row * 256 + 16 * hb + 4 * g, d1v);
-            stg4(o.dh + row * 256 + 16 * hb + 4 * g, dhv);
-        }
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dxn[kb] = mfma16(g3.a[kb][r], dhv[r], dxn[kb]);
-        }
-    }
-    // LayerNorm backward (per token: the 64 channels live in the 4 lanes c, c+16, c+32, c+48)
-    f32x4 dxh[4];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-        dxh[kb] = dxn[kb] * ldg4(w.gamma + 16 * kb + 4 * g);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            s1 += dxh[kb][r];
-            s2 = fmaf(dxh[kb][r], xh[kb][r], s2);
-        }
-    }
-    const float mu1 = red_g_sum(s1) * (1.0f / 64.0f), mu2 = red_g_sum(s2) * (1.0f / 64.0f);
-    if (ok) {
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb) {
-            f32x4 dv = (dxh[kb] - splat4(mu1) - xh[kb] * splat4(mu2)) * splat4(rstd);
-            if (dres) dv = dv + ldg4(dres + row * 64 + 16 * kb + 4 * g);   // + the gradient of the residual path
-            stg4(dx + row * 64 + 16 * kb + 4 * g, dv);
-        }
-    }
-    f32x4 ca[4], cb[4];
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-        ca[kb] = ok ? dxn[kb] * xh[kb] : splat4(0.f);
-        cb[kb] = ok ? dxn[kb] : splat4(0.f);
-    }
-    ln_tile_colsums(ca, cb, c, g, t0 >> 4, o.g1, o.dxn);
-}
-
-// out_partial[s][i][j] = sum over the s-th token range of P[m][i] * Q[m][j]   (P [M,R], Q [M,C], row-major), a 64 x 64
-// output tile per block (all four 16-row blocks of a 64-row band): a first version with 16 x 64 tiles
-// re-read Q once per row block and P once per column block - 664 MB of L2 / HBM reads for the 166 MB of
-// operands of one FeedForward weight gradient, which is what bounded it (83 us at 8 TB/s of cache traffic).  Here a
-// wave-step loads 16 + 16 operand dwords for 64 MFMAs; the four waves' tiles are combined through 32 KB of LDS in a
-// fixed order.  Grid (R / 64, C / 64, WG_SPLIT).
 #define WG_SPLIT 256                  // largest split (sizes the slab buffers); a launch uses wg_split(tiles) <= WG_SPLIT
-__global__ __launch_bounds__(256) void wgrad_partial64_kernel(const float* __restrict__ P, const float* __restrict__ Q,
-                                                              long M, int R, int C, float* __restrict__ partial) {
-    __shared__ float red[2][64 * 64];
-    const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int ic = blockIdx.x, jc = blockIdx.y, s = blockIdx.z;
-    const int nsplit = gridDim.z;
-    const long full = M / 16, per = (full + nsplit - 1) / nsplit;            // full 16-row steps, dealt to the splits
-    const long st0 = (long)s * per, st1 = st0 + per < full ? st0 + per : full;
-    f32x4 acc[4][4];                                  // [ib][jb]
-#pragma unroll
-    for (int ib = 0; ib < 4; ++ib)
-#pragma unroll
-        for (int jb = 0; jb < 4; ++jb) acc[ib][jb] = splat4(0.f);
-    // two steps per trip: the 32 operand dwords of the other step are in flight while the 64 MFMAs of one run (a wave
-    // that waited for its own loads before every step spent more time on HBM / L2 latency than on products)
-    unsigned oa[4], ob[4];                            // lane offsets of row 4g + r inside a step (P: + 16 ib, Q: + 16 jb)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        oa[r] = (unsigned)((4 * g + r) * R + 64 * ic + c);
-        ob[r] = (unsigned)((4 * g + r) * C + 64 * jc + c);
-    }
-    auto load = [&](long st, f32x4 (&a)[4], f32x4 (&b)[4]) {       // [ib][r], [jb][r]; a full step (16 rows < M)
-        const float* __restrict__ Pp = P + st * 16 * R;             // uniform
-        const float* __restrict__ Qp = Q + st * 16 * C;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float* __restrict__ pa = Pp + oa[r];              // + 16 ib / + 16 jb are instruction immediates
-            const float* __restrict__ qa = Qp + ob[r];
-#pragma unroll
-            for (int ib = 0; ib < 4; ++ib) a[ib][r] = pa[16 * ib];
-#pragma unroll
-            for (int jb = 0; jb < 4; ++jb) b[jb][r] = qa[16 * jb];
-        }
-    };
-    auto mma = [&](const f32x4 (&a)[4], const f32x4 (&b)[4]) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int ib = 0; ib < 4; ++ib)
-#pragma unroll
-                for (int jb = 0; jb < 4; ++jb) acc[ib][jb] = mfma16(a[ib][r], b[jb][r], acc[ib][jb]);
-    };
-    f32x4 a0[4], b0[4], a1[4], b1[4];
-    long st = st0 + wv;
-    if (st < st1) load(st, a0, b0);
-    while (st < st1) {
-        const long sn = st + 4;
-        if (sn < st1) load(sn, a1, b1);
-        mma(a0, b0);
-        st = sn + 4;
-        if (st < st1) load(st, a0, b0);
-        if (sn < st1) mma(a1, b1);
-    }
-    if ((M & 15) && s == nsplit - 1 && wv == 0) {   // the one ragged step of the tensor: rows past M contribute zeros
-        const float* __restrict__ Pp = P + full * 16 * R;
-        const float* __restrict__ Qp = Q + full * 16 * C;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const bool ok = full * 16 + 4 * g + r < M;
-#pragma unroll
-            for (int ib = 0; ib < 4; ++ib) a0[ib][r] = ok ? Pp[oa[r] + 16 * ib] : 0.f;
-#pragma unroll
-            for (int jb = 0; jb < 4; ++jb) b0[jb][r] = ok ? Qp[ob[r] + 16 * jb] : 0.f;
-        }
-        mma(a0, b0);
-    }
-    // (wave 2 + wave 0), (wave 3 + wave 1), then (wave 1 + wave 0): element (row 16 ib + 4 g + r, col 16 jb + c)
-    auto put = [&](float* dst) {
-#pragma unroll
-        for (int ib = 0; ib < 4; ++ib)
-#pragma unroll
-            for (int jb = 0; jb < 4; ++jb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) dst[(16 * ib + 4 * g + r) * 64 + 16 * jb + c] = acc[ib][jb][r];
-    };
-    auto add = [&](const float* src) {
-#pragma unroll
-        for (int ib = 0; ib < 4; ++ib)
-#pragma unroll
-            for (int jb = 0; jb < 4; ++jb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[ib][jb][r] += src[(16 * ib + 4 * g + r) * 64 + 16 * jb + c];
-    };
-    if (wv >= 2) put(red[wv - 2]);
-    __syncthreads();
-    if (wv < 2) add(red[wv]);
-    __syncthreads();
-    if (wv == 1) put(red[0]);
-    __syncthreads();
-    if (wv == 0) {
-        add(red[0]);
-#pragma unroll
-        for (int ib = 0; ib < 4; ++ib)
-#pragma unroll
-            for (int jb = 0; jb < 4; ++jb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    partial[((long)s * R + 64 * ic + 16 * ib + 4 * g + r) * C + 64 * jc + 16 * jb + c] = acc[ib][jb][r];
-    }
-}
-// the kernel holds two steps of operands next to its 64 x 64 accumulators: 184 registers, two waves per SIMD.  The
-// split is chosen so that one launch is at most those 2048 waves (tiles x split x 4), i.e. a single round
+// token ranges of one weight-gradient launch (a 64 x 64 output tile per 4-wave block, grid (R / 64, C / 64, split)): at
+// most 2048 waves (tiles x split x 4)
 static int wg_split(int tiles) { return tiles >= 3 ? 128 : 256; }
 
 // column sums of X [M,C] over NB fixed row ranges -> partial [NB][C]; four independent accumulators per thread keep
@@ -587,77 +282,22 @@ static void colsum_batch(LaunchCtx ctx, const char* label, const ColsumJobs& job
     LAUNCH(ctx, label, (colsum_multi_reduce_kernel<<<dim3(4, njobs), 1024, 0, ctx.stream>>>(jobs, cpart)));
 }
 
-#ifndef TRAIN_X3
-#define TRAIN_X3 1          // 1: FeedForward forward / backward and the token-contraction weight gradients on split-f16
-#endif                      //    products (train_x3.hip); 0: the fp32-MFMA kernels of this file
-// train_x3.hip
-void ffn_x3_pack(LaunchCtx, const FfnTrainParams& p, float* img);
-void ffn_x3_forward(LaunchCtx, const float* x, long M, const FfnTrainParams& p, const float* img, const unsigned char* m1,
-                    const unsigned char* m2, float ms, const float* res, float* y);
-int ffn_x3_backward_fused(LaunchCtx, const float* x, const float* dy, long M, const FfnTrainParams& p, const float* img,
-                          const unsigned char* m1, const unsigned char* m2, float ms, const float* dres, float* dx,
-                          float* o_dh, float* o_g1, float* o_dxn, float* dhmax, float* o_dzc, float* o_dhc, float* part_w2,
-                          float* part_w1);
-void ffn_x3_backward(LaunchCtx, const float* x, const float* dy, long M, const FfnTrainParams& p, const float* img,
-                     const unsigned char* m1, const unsigned char* m2, float ms, const float* dres, float* dx, float* o_dz,
-                     float* o_d1, float* o_dh, float* o_xn, float* o_g1, float* o_dxn, float* dhmax, float* o_dzc, float* o_dhc);
-void launch_wgrad_partial64_x3(LaunchCtx, const char* label, const float* P, const float* Q, long M, int R, int C,
-                               float* partial, int nsplit, float* colp);
-void launch_db_conv_wgrad_x3(LaunchCtx, const float* dz, const float* a, int B, int T, int F, int dil, int nsplit,
-                             float* partial, float* colp);
-void cm_x3_pack(LaunchCtx, const ConvModTrainParams& p, float* img_w1, float* img_w1t);
-void cm_x3_pw1glu(LaunchCtx, const float* x, long M, const float* img_w1, const ConvModTrainParams& p, float* u);
-void cm_x3_bwd2(LaunchCtx, const float* x, const float* du, long M, const float* img_w1, const float* img_w1t,
-                const ConvModTrainParams& p, const float* dres, float* dx, float* dag, float* xn_out, float* g1c, float* dxc);
-void cm_x3_pack_pw2(LaunchCtx, const ConvModTrainParams& p, float* img_w2, float* img_w2t);
-void cm_x3_bn_swish_pw2(LaunchCtx, const float* d, long M, const float* scale, const float* shift, const float* img_w2,
-                        const float* b2, const float* res, float* y);
-int cm_x3_bwd2_fused(LaunchCtx, const float* x, const float* du, long M, const float* img_w1t, const ConvModTrainParams& p,
-                     const float* dres, float* dx, float* dag, float* o_g1, float* o_dxn, float* o_dhc, float* dhmax,
-                     float* part_w1);
-int cm_x3_bwd1_fused(LaunchCtx, const float* dy, const float* d, long M, const float* mean, const float* rstd,
-                     const float* scale, const float* shift, const float* w2raw, float* ddn, float* g2c, float* ddnc, float* dyc,
-                     float* part_w2);
-void cm_x3_bwd1(LaunchCtx, const float* dy, const float* d, long M, const float* mean, const float* rstd, const float* scale,
-                const float* shift, const float* img_w2t, float* ddn, float* s_out, float* g2c, float* ddnc, float* dyc);
-void at_x3_pack(LaunchCtx, const float* wraw, float* img_w, float* img_wt);
-void at_x3_qkv(LaunchCtx, const float* x, long M, const float* img_w, const float* ln_w, const float* ln_b, float* qkv,
-               int as_image, float qscale);
-void at_x3_qkv_bwd(LaunchCtx, const float* x, const float* dqkv, long M, const float* img_wt, const float* ln_w,
-                   const float* ln_b, const float* dres, float* dx, float* xn_out, float* g1c, float* dxc);
-// the token-contraction weight gradient in either mode: grid (R / 64, C / 64, nsplit)
-// colp / colsum_out (split-f16 build only): also the column sums of P -> colsum_out[R], through [nsplit][R] partials at colp
+// the token-contraction weight gradient: grid (R / 64, C / 64, nsplit)
+// colp / colsum_out (optional): also the column sums of P -> colsum_out[R], through [nsplit][R] partials at colp
 static void wgrad_partial64(LaunchCtx ctx, const char* label, const float* P, const float* Q, long M, int R, int C,
                             float* partial, int nsplit, float* colp = nullptr, float* colsum_out = nullptr,
                             const char* reduce_label = nullptr) {
-#if TRAIN_X3
     launch_wgrad_partial64_x3(ctx, label, P, Q, M, R, C, partial, nsplit, colp);
     if (colp) LAUNCH(ctx, reduce_label, (reduce_partials_kernel<<<4, 1024, 0, ctx.stream>>>(colp, nsplit, R, colsum_out)));
-#else
-    (void)colp; (void)colsum_out; (void)reduce_label;
-    LAUNCH(ctx, label, (wgrad_partial64_kernel<<<dim3(R / 64, C / 64, nsplit), 256, 0, ctx.stream>>>(P, Q, M, R, C, partial)));
-#endif
-}
-
-// pack = false: the images the forward of the SAME parameters left in the workspace are reused (backward passes)
-static FfnTrainImg ffn_pack_images(LaunchCtx ctx, const FfnTrainParams& p, float* img, bool pack = true) {
-    hipStream_t s = ctx.stream;
-    float *w1 = img, *w2 = img + 16384, *w2t = img + 2 * 16384, *w1t = img + 3 * 16384;
-    if (!pack) return FfnTrainImg{w1, w2, w2t, w1t, p.gamma, p.beta, p.b1, p.b2};
-    launch_pack4(ctx, "ffn_train_pack", PackJobs{{{p.w1, 256, 64, 64, 0, w1},       // rows = hidden
-                                                  {p.w2, 64, 256, 256, 0, w2},      // rows = out
-                                                  {p.w2, 256, 64, 256, 1, w2t},     // rows = hidden
-                                                  {p.w1, 64, 256, 64, 1, w1t}}});   // rows = in
-    return FfnTrainImg{w1, w2, w2t, w1t, p.gamma, p.beta, p.b1, p.b2};
 }
 
 // The fused backward (train_x3.hip, the default) keeps dh [M,256] and per-tile partial rows only: its workspace is COMPACT -
 // 270 floats per token instead of the 768 of dz | d1 | dh | xn | g1 | dxn (3.2 GB -> 1.1 GB per FeedForward at 32 clips,
-// sixteen of them in the generator).  Compact <=> this build, CMGAN_FFN_BWD_FUSED != 0 and a dh tensor under 2 GB; a call the
+// sixteen of them in the generator).  Compact <=> CMGAN_FFN_BWD_FUSED != 0 and a dh tensor under 2 GB; a call the
 // fused kernel cannot take then (one keep-mask without the other) is an ERROR, not a fallback into buffers that are not there.
 static bool ffn_ws_compact(long M) {
     static const bool k_fused = env_knob("CMGAN_FFN_BWD_FUSED", 1, 0, 1) != 0;
-    return TRAIN_X3 && k_fused && M * 1024 < (1l << 31);
+    return k_fused && M * 1024 < (1l << 31);
 }
 size_t ffn_train_ws_floats(long M) {
     const size_t tiles = (size_t)((M + 31) / 32);
@@ -667,22 +307,15 @@ size_t ffn_train_ws_floats(long M) {
 
 void launch_ffn_train_forward(LaunchCtx ctx, const float* x, long M, const FfnTrainParams& p, const unsigned char* m1,
                               const unsigned char* m2, float ms, const float* res, float* y, float* ws) {
-#if TRAIN_X3
     ffn_x3_pack(ctx, p, ws);
     ffn_x3_forward(ctx, x, M, p, ws, m1, m2, ms, res, y);
-#else
-    const FfnTrainImg w = ffn_pack_images(ctx, p, ws);
-    const unsigned grid = (unsigned)((M + 63) / 64);
-    LAUNCH(ctx, "ffn_train_fwd", (ffn_train_fwd_kernel<<<grid, 256, 0, ctx.stream>>>(x, M, w, m1, m2, ms, res, y)));
-#endif
 }
 
 bool launch_ffn_train_backward(LaunchCtx ctx, const float* x, const float* dy, long M, const FfnTrainParams& p,
                                const unsigned char* m1, const unsigned char* m2, float ms, const float* dres, float* dx,
                                const FfnTrainParams& grad, float* ws) {
     hipStream_t s = ctx.stream;
-    const FfnTrainImg w = ffn_pack_images(ctx, p, ws, false);
-    float* act = ws + 4 * 16384;
+    float* act = ws + 4 * 16384;                                  // behind the forward's four images (same parameters)
     const bool compact = ffn_ws_compact(M);
     const long xrows = (M + 31) / 32;
     // compact: dh | g1 rows | dz sums | dxn rows | dh sums (ffn_train_ws_floats); else dz | d1 | dh | xn | g1 | dxn
@@ -690,8 +323,6 @@ bool launch_ffn_train_backward(LaunchCtx ctx, const float* x, const float* dy, l
                            : FfnBwdBufs{act, act + M * 64, act + M * 320, act + M * 576, act + M * 640, act + M * 704};
     float* part = act + (compact ? M * 256 + xrows * 448 : M * 768);      // [SPLIT][16384] x 2, then colsum slabs
     float* cpart = part + (size_t)WG_SPLIT * 16384 * 2;
-#if TRAIN_X3
-    (void)w;
     // per-tile partial sums for the four column sums: [tiles][64] dgamma | dz (db2) in the g1 region, [tiles][64] dbeta |
     // [tiles][256] dh (db1) in the dxn region (the full [M,64] g1 / dxn tensors of round 2 are no longer written)
     float *dzc = o.g1 + xrows * 64, *dhc = o.dxn + xrows * 64;   // dzc: [2 tiles][64] (fused form: [tiles][64])
@@ -705,11 +336,6 @@ bool launch_ffn_train_backward(LaunchCtx ctx, const float* x, const float* dy, l
         ffn_x3_backward(ctx, x, dy, M, p, ws, m1, m2, ms, dres, dx, o.dz, o.d1, o.dh, o.xn, o.g1, o.dxn,
                         cpart,                                    // per-tile |dh| maxima: the column-sum slabs are free until colsum_batch
                         dzc, dhc);
-#else
-    const int fused_slabs = 0;
-    const unsigned grid = (unsigned)((M + 63) / 64);
-    LAUNCH(ctx, "ffn_train_bwd", (ffn_train_bwd_kernel<<<grid, 256, 0, s>>>(x, dy, M, w, m1, m2, ms, dres, dx, o)));
-#endif
     // dW2 [64,256] = dz^T d1 ; dW1 [256,64] = dh^T xn
     if (!fused_slabs) {
         wgrad_partial64(ctx, "ffn_train_wgrad", o.dz, o.d1, M, 64, 256, part, wg_split(4));
@@ -719,15 +345,9 @@ bool launch_ffn_train_backward(LaunchCtx ctx, const float* x, const float* dy, l
     LAUNCH(ctx, "ffn_train_reduce", (reduce_partials_kernel<<<256, 1024, 0, s>>>(part, nslab, 16384, grad.w2)));
     LAUNCH(ctx, "ffn_train_reduce", (reduce_partials_kernel<<<256, 1024, 0, s>>>(part + (size_t)WG_SPLIT * 16384, nslab, 16384,
                                                                                  grad.w1)));
-    // o.g1 / o.dxn hold per-tile partial sums (ln_tile_colsums): one row per 32-token tile (x3) / 16-token tile (fp32)
-    const long trows = TRAIN_X3 ? (M + 31) / 32 : (M + 15) / 16;
-#if TRAIN_X3
+    // o.g1 / o.dxn hold per-tile partial sums (ln_tile_colsums): one row per 32-token tile
     const ColsumJobs jobs{{dhc, dzc, o.g1, o.dxn}, {grad.b1, grad.b2, grad.gamma, grad.beta}, {256, 64, 64, 64},
-                          {trows, fused_slabs ? trows : 2 * trows, trows, trows}};      // dz sums: per 16-token block (per tile: fused)
-#else
-    const ColsumJobs jobs{{o.dh, o.dz, o.g1, o.dxn}, {grad.b1, grad.b2, grad.gamma, grad.beta}, {256, 64, 64, 64},
-                          {0, 0, trows, trows}};
-#endif
+                          {xrows, fused_slabs ? xrows : 2 * xrows, xrows, xrows}};      // dz sums: per 16-token block (per tile: fused)
     colsum_batch(ctx, "ffn_train_reduce", jobs, 4, M, cpart);
     return true;
 }
@@ -801,13 +421,13 @@ void launch_adamw(LaunchCtx ctx, float* p, const float* g, float* m, float* v, l
 // Training-mode ConformerConvModule (second backward slice of SURVEY.md N2; conformer.py:151-176):
 //   LayerNorm -> Conv1d(64,256,1) -> GLU -> DepthWiseConv1d(k=31, 'same') -> BatchNorm1d(128, BATCH statistics)
 //   -> Swish -> Conv1d(128,64,1)            (its Dropout has p = conv_dropout = 0)
-// on contiguous sequences x [N, L, 64] (token m = n L + l).  The pointwise stages are the per-token fp32-MFMA chain of
-// the FeedForward slice; the depthwise conv (and its data-gradient, the same kernel with flipped taps) is a 16-output
-// sliding window per thread; BatchNorm statistics and every parameter gradient are fixed-order two-pass reductions.
+// on contiguous sequences x [N, L, 64] (token m = n L + l).  The pointwise stages are the per-token split-f16 chain of
+// the FeedForward slice (train_x3.hip); the depthwise conv (and its data-gradient, the same kernel with flipped taps) is a
+// 16-output sliding window per thread; BatchNorm statistics and every parameter gradient are fixed-order two-pass reductions.
 // The forward leaves u (GLU output), d (depthwise output) and the batch statistics in the workspace for the backward.
 // =====================================================================================
 struct CmImg {
-    const float *w1, *w1t, *w2, *w2t;       // fm: pw1 [16][4], pw1^T [4][16], pw2 [4][8], pw2^T [8][4]
+    const float *w1, *w1t, *w2, *w2t;       // split-f16 images (train_x3.hip): pw1, pw1^T in 64 KB slots, pw2, pw2^T in 32 KB slots
 };
 struct CmStats { float *mean, *rstd, *scale, *shift; };   // [128] each: batch mean, 1/sqrt(var+eps), gamma rstd, beta - mean gamma rstd
 
@@ -828,34 +448,6 @@ __device__ __forceinline__ bool cm_load_norm(const float* __restrict__ x, long M
         xn[0][kb] = xh[kb] * ldg4(gamma + 16 * kb + 4 * g) + ldg4(beta + 16 * kb + 4 * g);
     }
     return ok;
-}
-
-// LN -> pointwise 64 -> 256 -> GLU:  u [M,128]
-__global__ __launch_bounds__(256) void cm_pw1glu_kernel(const float* __restrict__ x, long M, const float* __restrict__ w1fm,
-                                                        ConvModTrainParams p, float* __restrict__ u) {
-    const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
-    const long t0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16;
-    if (t0 >= M) return;
-    f32x4 xh[4], xn[1][4];
-    float rstd;
-    long row;
-    const bool ok = cm_load_norm(x, M, t0, c, g, p.ln_w, p.ln_b, xh, xn, rstd, row);
-    // value half, then gate half of an output block; the other half's weight fragments are in flight meanwhile
-    f32x4 ba = ldg4(p.pw1_b + 4 * g), bg = ldg4(p.pw1_b + 128 + 4 * g);
-    FfnFrag fa = ffn_frag_rows(w1fm, 0, lane), fg;
-    for (int ob = 0; ob < 8; ++ob) {
-        fg = ffn_frag_rows(w1fm, ob + 8, lane);
-        const f32x4 a = ffn_frag_mma(fa, xn[0], ba);
-        const int on = ob < 7 ? ob + 1 : 7;
-        ba = ldg4(p.pw1_b + 16 * on + 4 * g);
-        fa = ffn_frag_rows(w1fm, on, lane);
-        const f32x4 gt = ffn_frag_mma(fg, xn[0], bg);
-        bg = ldg4(p.pw1_b + 128 + 16 * on + 4 * g);
-        f32x4 r;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) r[e] = a[e] * sigmoidf_fast(gt[e]);
-        if (ok) stg4(u + row * 128 + 16 * ob + 4 * g, r);
-    }
 }
 
 // Staging of one 32-position tile of a [N, L, 128] tensor for the depthwise kernels: the 62 rows l0 - 15 .. l0 + 46
@@ -995,90 +587,6 @@ __global__ void cm_bn_finalize_kernel(const double* __restrict__ part, double co
     }
 }
 
-// BatchNorm apply -> Swish -> pointwise 128 -> 64 + bias
-__global__ __launch_bounds__(256) void cm_bn_swish_pw2_kernel(const float* __restrict__ d, long M, CmStats st,
-                                                              const float* __restrict__ w2fm,
-                                                              const float* __restrict__ b2, const float* __restrict__ res,
-                                                              float* __restrict__ y) {
-    const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
-    const long t0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16;
-    if (t0 >= M) return;
-    const long t = t0 + c;
-    const bool ok = t < M;
-    const long row = ok ? t : M - 1;
-    f32x4 s[1][8];
-#pragma unroll
-    for (int kb = 0; kb < 8; ++kb) {
-        const f32x4 dn = ldg4(d + row * 128 + 16 * kb + 4 * g) * ldg4(st.scale + 16 * kb + 4 * g) +
-                         ldg4(st.shift + 16 * kb + 4 * g);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s[0][kb][e] = swishf(dn[e]);
-    }
-#pragma unroll
-    for (int ob = 0; ob < 4; ++ob) {
-        f32x4 acc[1] = {ldg4(b2 + 16 * ob + 4 * g)};
-        lin_acc<8, 1>(w2fm + (long)ob * 8 * 256 + lane * 4, s, acc);
-        if (res) acc[0] = acc[0] + ldg4(res + row * 64 + 16 * ob + 4 * g);
-        if (ok) stg4(y + row * 64 + 16 * ob + 4 * g, acc[0]);
-    }
-}
-
-// backward, part 1 (per token): ds = pw2^T dy, through Swish; writes ddn = dL/d(bn output), s (for dW_pw2) and the
-// per-tile column sums the three reductions of this stage are finished from (ln_tile_colsums' scheme): rows of
-// [tiles][128] for g2 = ddn * dhat (BatchNorm dgamma) and ddn (dbeta), [tiles][64] for dy (the pointwise bias)
-__global__ __launch_bounds__(256) void cm_bwd1_kernel(const float* __restrict__ dy, const float* __restrict__ d, long M,
-                                                      CmStats st, const float* __restrict__ w2tfm,
-                                                      float* __restrict__ ddn, float* __restrict__ s_out,
-                                                      float* __restrict__ g2c, float* __restrict__ ddnc,
-                                                      float* __restrict__ dyc) {
-    const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
-    const long t0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16;
-    if (t0 >= M) return;
-    const long t = t0 + c;
-    const bool ok = t < M;
-    const long row = ok ? t : M - 1;
-    f32x4 dyf[1][4];
-#pragma unroll
-    for (int ob = 0; ob < 4; ++ob) dyf[0][ob] = ldg4(dy + row * 64 + 16 * ob + 4 * g);
-    const long tile = t0 >> 4;
-#pragma unroll
-    for (int ob = 0; ob < 4; ++ob) {
-        f32x4 v = ok ? dyf[0][ob] : splat4(0.f);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = red_c_sum(v[r]);
-        if (c == 0) stg4(dyc + tile * 64 + 16 * ob + 4 * g, v);
-    }
-#pragma unroll 2
-    for (int hb = 0; hb < 8; ++hb) {
-        f32x4 ds[1] = {splat4(0.f)};
-        lin_acc<4, 1>(w2tfm + (long)hb * 4 * 256 + lane * 4, dyf, ds);
-        const f32x4 dv = ldg4(d + row * 128 + 16 * hb + 4 * g);
-        const f32x4 dhat = (dv - ldg4(st.mean + 16 * hb + 4 * g)) * ldg4(st.rstd + 16 * hb + 4 * g);
-        const f32x4 dn = dv * ldg4(st.scale + 16 * hb + 4 * g) + ldg4(st.shift + 16 * hb + 4 * g);
-        f32x4 o_ddn, o_s;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float sg = sigmoidf_fast(dn[e]);
-            o_s[e] = dn[e] * sg;
-            o_ddn[e] = ds[0][e] * (sg * (1.f + dn[e] * (1.f - sg)));
-        }
-        if (ok) {
-            stg4(ddn + row * 128 + 16 * hb + 4 * g, o_ddn);
-            stg4(s_out + row * 128 + 16 * hb + 4 * g, o_s);
-        }
-        f32x4 ca = ok ? o_ddn * dhat : splat4(0.f), cb = ok ? o_ddn : splat4(0.f);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            ca[r] = red_c_sum(ca[r]);
-            cb[r] = red_c_sum(cb[r]);
-        }
-        if (c == 0) {
-            stg4(g2c + tile * 128 + 16 * hb + 4 * g, ca);
-            stg4(ddnc + tile * 128 + 16 * hb + 4 * g, cb);
-        }
-    }
-}
-
 // BatchNorm backward (batch statistics): dd = gamma rstd (ddn - mean(ddn) - dhat mean(ddn dhat)), in place on ddn
 // bpart (optional): [gridDim.x][128] per-block sums of dd - the depthwise BIAS gradient's partials - for free in this HBM-bound
 // pass: a thread's channel is fixed (the stride is a multiple of 128), two threads per channel are combined through LDS.
@@ -1173,104 +681,20 @@ __global__ __launch_bounds__(256) void cm_dw_wgrad_kernel(const float* __restric
     }
 }
 
-// backward, part 2 (per token): GLU backward with a, g recomputed from x, dxn = pw1^T [da; dg], LayerNorm backward
-__global__ __launch_bounds__(256) void cm_bwd2_kernel(const float* __restrict__ x, const float* __restrict__ du, long M,
-                                                      const float* __restrict__ w1fm, const float* __restrict__ w1tfm,
-                                                      ConvModTrainParams p, const float* __restrict__ dres,
-                                                      float* __restrict__ dx, float* __restrict__ dag,
-                                                      float* __restrict__ xn_out, float* __restrict__ g1,
-                                                      float* __restrict__ dxn_out) {
-    const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
-    const long t0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16;
-    if (t0 >= M) return;
-    f32x4 xh[4], xn[1][4];
-    float rstd;
-    long row;
-    const bool ok = cm_load_norm(x, M, t0, c, g, p.ln_w, p.ln_b, xh, xn, rstd, row);
-    f32x4 dxn[4];
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) dxn[kb] = splat4(0.f);
-    // four groups of 16 MFMAs per output block (value, gate, and their two transposed products); the fragments of a
-    // group are fetched while the previous groups run
-    f32x4 ba = ldg4(p.pw1_b + 4 * g), bg = ldg4(p.pw1_b + 128 + 4 * g), dun = ldg4(du + row * 128 + 4 * g);
-    FfnFrag fa = ffn_frag_rows(w1fm, 0, lane), fg, ta, tg;
-    for (int ob = 0; ob < 8; ++ob) {
-        fg = ffn_frag_rows(w1fm, ob + 8, lane);
-        const f32x4 a = ffn_frag_mma(fa, xn[0], ba);
-        ta = ffn_frag_cols(w1tfm, ob, lane);
-        const f32x4 gt = ffn_frag_mma(fg, xn[0], bg);
-        tg = ffn_frag_cols(w1tfm, ob + 8, lane);
-        f32x4 duv = dun;
-        if (!ok) duv = splat4(0.f);
-        const int on = ob < 7 ? ob + 1 : 7;
-        ba = ldg4(p.pw1_b + 16 * on + 4 * g);
-        bg = ldg4(p.pw1_b + 128 + 16 * on + 4 * g);
-        dun = ldg4(du + row * 128 + 16 * on + 4 * g);
-        f32x4 da, dg;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float sg = sigmoidf_fast(gt[e]);
-            da[e] = duv[e] * sg;
-            dg[e] = duv[e] * a[e] * sg * (1.f - sg);
-        }
-        if (ok) {
-            stg4(dag + row * 256 + 16 * ob + 4 * g, da);
-            stg4(dag + row * 256 + 128 + 16 * ob + 4 * g, dg);
-        }
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dxn[kb] = mfma16(ta.a[kb][r], da[r], dxn[kb]);
-        fa = ffn_frag_rows(w1fm, on, lane);
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dxn[kb] = mfma16(tg.a[kb][r], dg[r], dxn[kb]);
-    }
-    f32x4 dxh[4];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-        dxh[kb] = dxn[kb] * ldg4(p.ln_w + 16 * kb + 4 * g);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            s1 += dxh[kb][r];
-            s2 = fmaf(dxh[kb][r], xh[kb][r], s2);
-        }
-    }
-    const float mu1 = red_g_sum(s1) * (1.0f / 64.0f), mu2 = red_g_sum(s2) * (1.0f / 64.0f);
-    if (ok) {
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb) {
-            f32x4 dv = (dxh[kb] - splat4(mu1) - xh[kb] * splat4(mu2)) * splat4(rstd);
-            if (dres) dv = dv + ldg4(dres + row * 64 + 16 * kb + 4 * g);
-            stg4(dx + row * 64 + 16 * kb + 4 * g, dv);
-            stg4(xn_out + row * 64 + 16 * kb + 4 * g, xn[0][kb]);
-        }
-    }
-    f32x4 ca[4], cb[4];
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-        ca[kb] = ok ? dxn[kb] * xh[kb] : splat4(0.f);
-        cb[kb] = ok ? dxn[kb] : splat4(0.f);
-    }
-    ln_tile_colsums(ca, cb, c, g, t0 >> 4, g1, dxn_out);            // [tiles][64] slabs: dgamma / dbeta partial sums
-}
-
 // tiles per block of the depthwise kernels: at most `cap` blocks (three 48 KB blocks fit a CU: 768 per round)
 #define CM_DW_BLOCKS 1536
 static int cm_dw_tpb(long ntile, int cap) { return (int)((ntile + cap - 1) / cap); }
 
 // The fused backward parts (train_x3.hip, the default) never write s = Swish(BN(d)) [M,128] (part 1) nor xn [M,64] (part 2): the
-// workspace leaves them out.  Compact <=> this build, the part's knob != 0 and a tensor size its 32-bit offsets cover; a call
+// workspace leaves them out.  Compact <=> the part's knob != 0 and a tensor size its 32-bit offsets cover; a call
 // the fused part cannot take then is an ERROR, not a fallback into buffers that are not there.
 static bool cm_ws_compact1(long M) {
     static const bool k = env_knob("CMGAN_CM_BWD1_FUSED", 1, 0, 1) != 0;
-    return TRAIN_X3 && k && M * 512 < (1l << 31);
+    return k && M * 512 < (1l << 31);
 }
 static bool cm_ws_compact2(long M) {
     static const bool k = env_knob("CMGAN_CM_BWD2_FUSED", 1, 0, 1) != 0;
-    return TRAIN_X3 && k && M * 1024 < (1l << 31);
+    return k && M * 1024 < (1l << 31);
 }
 // workspace layout (floats): images | u | d | stats (4 x 128) | bwd buffers | partials
 struct CmPlan {
@@ -1300,17 +724,11 @@ static CmPlan cm_plan(int N, int L) {
 size_t convmod_train_ws_floats(int N, int L) { return cm_plan(N, L).total; }
 
 static CmImg cm_pack_images(LaunchCtx ctx, const ConvModTrainParams& p, float* img, bool pack = true) {
-    hipStream_t s = ctx.stream;
     float *w1 = img, *w1t = img + 16384, *w2 = img + 32768, *w2t = img + 32768 + 8192;
     if (!pack) return CmImg{w1, w1t, w2, w2t};
-#if TRAIN_X3
     // every per-token stage of the module runs on split products: split-f16 images in the four slots
     cm_x3_pack(ctx, p, w1, w1t);
     cm_x3_pack_pw2(ctx, p, w2, w2t);
-#else
-    launch_pack4(ctx, "convmod_train_pack", PackJobs{{{p.pw1_w, 256, 64, 64, 0, w1}, {p.pw1_w, 64, 256, 64, 1, w1t},
-                                                      {p.pw2_w, 64, 128, 128, 0, w2}, {p.pw2_w, 128, 64, 128, 1, w2t}}});
-#endif
     return CmImg{w1, w1t, w2, w2t};
 }
 
@@ -1321,13 +739,8 @@ void launch_convmod_train_forward(LaunchCtx ctx, const float* x, int N, int L, c
     const long M = (long)N * L;
     const CmImg im = cm_pack_images(ctx, p, ws + pl.img);
     const CmStats st{ws + pl.st, ws + pl.st + 128, ws + pl.st + 256, ws + pl.st + 384};
-    const unsigned grid = (unsigned)((M + 63) / 64);
     const dim3 dgrid(N, (L + 31) / 32);
-#if TRAIN_X3
     cm_x3_pw1glu(ctx, x, M, im.w1, p, ws + pl.u);
-#else
-    LAUNCH(ctx, "convmod_train_fwd", (cm_pw1glu_kernel<<<grid, 256, 0, s>>>(x, M, im.w1, p, ws + pl.u)));
-#endif
     const long ntile = (long)dgrid.x * dgrid.y;
     const int tpb = cm_dw_tpb(ntile, CM_DW_BLOCKS), dblocks = (int)((ntile + tpb - 1) / tpb);
     LAUNCH(ctx, "convmod_train_fwd", (cm_depthwise_kernel<<<dblocks, 256, 0, s>>>(ws + pl.u, p.dw_w, p.dw_b, 0, L, (int)dgrid.y, ntile,
@@ -1336,11 +749,7 @@ void launch_convmod_train_forward(LaunchCtx ctx, const float* x, int N, int L, c
     LAUNCH(ctx, "convmod_train_fwd", (cm_bn_reduce_kernel<<<CM_BN_RED, 256, 0, s>>>(ws + pl.bnpart, (long)dblocks, bnred)));
     LAUNCH(ctx, "convmod_train_fwd", (cm_bn_finalize_kernel<<<1, 128, 0, s>>>(bnred, (double)M, p.bn_w, p.bn_b, st,
                                                                               running_mean, running_var)));
-#if TRAIN_X3
     cm_x3_bn_swish_pw2(ctx, ws + pl.d, M, st.scale, st.shift, im.w2, p.pw2_b, res, y);
-#else
-    LAUNCH(ctx, "convmod_train_fwd", (cm_bn_swish_pw2_kernel<<<grid, 256, 0, s>>>(ws + pl.d, M, st, im.w2, p.pw2_b, res, y)));
-#endif
 }
 
 bool launch_convmod_train_backward(LaunchCtx ctx, const float* x, const float* dy, int N, int L,
@@ -1351,14 +760,12 @@ bool launch_convmod_train_backward(LaunchCtx ctx, const float* x, const float* d
     const long M = (long)N * L;
     const CmImg im = cm_pack_images(ctx, p, ws + pl.img, false);   // the forward's images (same parameters)
     const CmStats st{ws + pl.st, ws + pl.st + 128, ws + pl.st + 256, ws + pl.st + 384};
-    const unsigned grid = (unsigned)((M + 63) / 64);
     const dim3 dgrid(N, (L + 31) / 32);
     const long nblk = (long)dgrid.x * dgrid.y;
     float* cpart = ws + pl.cpart;
     long trows = (M + 15) / 16;                                   // per-tile partial sums inside the g2 region [M,128]
     float *g2c = ws + pl.g2, *ddnc = g2c + trows * 128, *dyc = ddnc + trows * 128;
     int ns_pw2 = 0;                                               // > 0: dW_pw2's slabs already written (fused part 1)
-#if TRAIN_X3
     // default: part 1 with the pointwise-2 weight gradient contracted on the chip (train_x3.hip; s never leaves it; its
     // partial-sum rows are per 32-token tile); CMGAN_CM_BWD1_FUSED=0: A/B
     static const bool k_fused1 = env_knob("CMGAN_CM_BWD1_FUSED", 1, 0, 1) != 0;
@@ -1368,10 +775,6 @@ bool launch_convmod_train_backward(LaunchCtx ctx, const float* x, const float* d
     if (ns_pw2) trows = (M + 31) / 32;
     else if (cm_ws_compact1(M)) return false;                     // (the device refused the fused kernel's LDS)
     else cm_x3_bwd1(ctx, dy, ws + pl.d, M, st.mean, st.rstd, st.scale, st.shift, im.w2t, ws + pl.ddn, ws + pl.s, g2c, ddnc, dyc);
-#else
-    LAUNCH(ctx, "convmod_train_bwd", (cm_bwd1_kernel<<<grid, 256, 0, s>>>(dy, ws + pl.d, M, st, im.w2t, ws + pl.ddn,
-                                                                          ws + pl.s, g2c, ddnc, dyc)));
-#endif
     // pointwise-2 gradients: dW_pw2 [64,128] = dy^T s, db_pw2 = colsum dy
     if (!ns_pw2) {
         wgrad_partial64(ctx, "convmod_train_wgrad", dy, ws + pl.s, M, 64, 128, ws + pl.wpart, wg_split(2));
@@ -1400,7 +803,6 @@ bool launch_convmod_train_backward(LaunchCtx ctx, const float* x, const float* d
         LAUNCH(ctx, "convmod_train_bwd", (cm_depthwise_kernel<<<dblocks, 256, 0, s>>>(dd, p.dw_w, nullptr, 1, L, (int)dgrid.y, nblk, tpb,
                                                                                       ws + pl.du, nullptr)));
     }
-#if TRAIN_X3
     // default: part 2 split like the FeedForward's backward - LN / GLU backward / [da ; dg] + dW_pw1 on the chip, then the
     // FeedForward's own part B on pw1's image (train_x3.hip); CMGAN_CM_BWD2_FUSED=0: A/B
     static const bool k_fused2 = env_knob("CMGAN_CM_BWD2_FUSED", 1, 0, 1) != 0;
@@ -1417,31 +819,16 @@ bool launch_convmod_train_backward(LaunchCtx ctx, const float* x, const float* d
     }
     if (cm_ws_compact2(M)) return false;
     cm_x3_bwd2(ctx, x, ws + pl.du, M, im.w1, im.w1t, p, dres, dx, ws + pl.dag, ws + pl.xn, ws + pl.g1, ws + pl.dxn);
-#else
-    LAUNCH(ctx, "convmod_train_bwd", (cm_bwd2_kernel<<<grid, 256, 0, s>>>(x, ws + pl.du, M, im.w1, im.w1t, p, dres, dx,
-                                                                          ws + pl.dag, ws + pl.xn, ws + pl.g1,
-                                                                          ws + pl.dxn)));
-#endif
     // pointwise-1 and LayerNorm gradients
-#if TRAIN_X3
     // db_pw1 = colsum [da ; dg] comes out of the weight-gradient kernel, which holds every element of dag anyway (the column-sum
     // pass re-read the [M,256] tensor); its [split][256] partials use the fourth job's region of cpart
     wgrad_partial64(ctx, "convmod_train_wgrad", ws + pl.dag, ws + pl.xn, M, 256, 64, ws + pl.wpart, wg_split(4),
                     cpart + (size_t)3 * FFN_COLSUM_BLOCKS * 256, grad.pw1_b, "convmod_train_reduce");
-#else
-    wgrad_partial64(ctx, "convmod_train_wgrad", ws + pl.dag, ws + pl.xn, M, 256, 64, ws + pl.wpart, wg_split(4));
-#endif
     LAUNCH(ctx, "convmod_train_reduce", (reduce_partials_kernel<<<256, 1024, 0, s>>>(ws + pl.wpart, wg_split(4), 16384,
                                                                                    grad.pw1_w)));
-#if TRAIN_X3
     const ColsumJobs jobs{{ws + pl.g1, ws + pl.dxn}, {grad.ln_w, grad.ln_b}, {64, 64},
                           {(M + 15) / 16, (M + 15) / 16}};                        // g1 / dxn: per-tile partial sums
     colsum_batch(ctx, "convmod_train_reduce", jobs, 2, M, cpart);
-#else
-    const ColsumJobs jobs{{ws + pl.dag, ws + pl.g1, ws + pl.dxn}, {grad.pw1_b, grad.ln_w, grad.ln_b}, {256, 64, 64},
-                          {0, (M + 15) / 16, (M + 15) / 16}};                     // g1 / dxn: per-tile partial sums
-    colsum_batch(ctx, "convmod_train_reduce", jobs, 3, M, cpart);
-#endif
     return true;
 }
 
@@ -1449,17 +836,14 @@ bool launch_convmod_train_backward(LaunchCtx ctx, const float* x, const float* d
 // Training-mode PreNorm(Attention) (third backward slice of SURVEY.md N2; conformer.py:54-72, 75-133):
 //   LayerNorm -> to_q / to_kv (no bias) -> per head softmax((q k^T + q E[clamp(i - j)]^T) / 4) v -> to_out + bias
 //   -> Dropout (keep-mask on the [M,64] output)
-// on contiguous sequences x [N, L, 64], L <= AT_MAX_L.  The projections are the per-token fp32-MFMA chain; the
-// attention core runs on the fp32 matrix pipe, one wave per (sequence, head, 16-row block) task (see below), each
-// backward core recomputing the probabilities from q, k, E and the saved row log-sum-exp, so no task ever accumulates
+// on contiguous sequences x [N, L, 64], L <= AT_MAX_L.  The projections are the per-token split-f16 chain
+// (train_x3.hip); the attention core runs on split-f16 products too, one wave per (sequence, head, 16-row block) task
+// (see below), each backward core recomputing the probabilities from q, k, E and the saved row log-sum-exp, so no task ever accumulates
 // into another task's output and every sum has a fixed order.
 // =====================================================================================
 #define AT_MAX_L 4096                 // a workspace-size bound only: the cores have no length-dependent resource
 
-#ifndef AT_X3
-#define AT_X3 1             // 1: the attention cores on split-f16 products fed from PRE-SPLIT operand images (below);
-#endif                      // 0: exact fp32 products (v_mfma_f32_16x16x4_f32), operands straight from the fp32 tensors
-// AT_X3 operand images.  Every tensor the cores read (q | k | v, dO, the relative-position window) is stored split into
+// Operand images.  Every tensor the cores read (q | k | v, dO, the relative-position window) is stored split into
 // fp16 hi / lo halves by its PRODUCER: the 4 bytes of element i hold (hi_i, lo_i), so that a core's operand is its
 // load plus four v_perm_b32 (at_row_a) instead of a 6-VALU split per float4 and product (round 3's first split-f16
 // form split inside the cores, which took back what the matrix pipe gave - VALU and MFMA issue add up on this
@@ -1468,9 +852,9 @@ bool launch_convmod_train_backward(LaunchCtx ctx, const float* x, const float* d
 // doubled the bytes a (sequence, head) keeps in L2, which cost far more (at_bwd_fused_kernel).
 // q is stored PRE-SCALED by dim_head^-0.5 log2(e) (the factor every score product applies; dk and dE, which contract
 // with q, are multiplied by ln 2 instead of 0.25 at the end); dO is stored pre-scaled by the exact power of two of
-// at_scale.  fp32 build: both "images" are the fp32 tensor itself.
+// at_scale.
 struct AtBufs {
-    float *qkv;      // [M,192]  q | k | v  (features 16 h + d inside each 64): fp32, or the (hi, lo) image
+    float *qkv;      // [M,192]  q | k | v  (features 16 h + d inside each 64), as the (hi, lo) image
     float *qkvp;     //          = qkv (a second interleaving lived here)
     float *o;        // [M,64]   softmax(.) v, heads concatenated
     float *lse;      // [N,4,L]  row log-sum-exp of the scaled scores
@@ -1490,49 +874,15 @@ __device__ __forceinline__ f32x4 at_img4(const f32x4& v) {
     return __builtin_bit_cast(f32x4, __builtin_shufflevector(h, l, 0, 4, 1, 5, 2, 6, 3, 7));
 }
 
-// fp32 build: the projection as is.  AT_X3: both operand images, the q part (output blocks 0 .. 3) pre-scaled
-__device__ __forceinline__ void at_store_qkv(float* __restrict__ qkv, float* __restrict__ qkvp, long off, f32x4 v, bool is_q,
-                                             bool ok) {
-#if AT_X3
-    (void)qkvp;
-    if (is_q) v = v * splat4(AT_QSCALE);
-    if (ok) stg4(qkv + off, at_img4(v));
-#else
-    (void)qkvp; (void)is_q;
-    if (ok) stg4(qkv + off, v);
-#endif
-}
-// LN -> [to_q ; to_kv] (A image [12][4]) -> qkv
-__global__ __launch_bounds__(256) void at_qkv_kernel(const float* __restrict__ x, long M, const float* __restrict__ wfm,
-                                                     const float* __restrict__ ln_w, const float* __restrict__ ln_b,
-                                                     float* __restrict__ qkv, float* __restrict__ qkvp) {
-    const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
-    const long t0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16;
-    if (t0 >= M) return;
-    f32x4 xh[4], xn[1][4];
-    float rstd;
-    long row;
-    const bool ok = cm_load_norm(x, M, t0, c, g, ln_w, ln_b, xh, xn, rstd, row);
-    FfnFrag f0 = ffn_frag_rows(wfm, 0, lane), f1;     // the next output block's fragments in flight
-    for (int ob = 0; ob < 12; ob += 2) {
-        f1 = ffn_frag_rows(wfm, ob + 1, lane);
-        const f32x4 q0 = ffn_frag_mma(f0, xn[0], splat4(0.f));
-        at_store_qkv(qkv, qkvp, row * 192 + 16 * ob + 4 * g, q0, ob < 4, ok);
-        f0 = ffn_frag_rows(wfm, ob + 2 < 12 ? ob + 2 : 11, lane);
-        const f32x4 q1 = ffn_frag_mma(f1, xn[0], splat4(0.f));
-        at_store_qkv(qkv, qkvp, row * 192 + 16 * (ob + 1) + 4 * g, q1, ob + 1 < 4, ok);
-    }
-}
-
 // ---------------------------------------------------------------------------------
-// Attention cores on the fp32 matrix pipe (v_mfma_f32_16x16x4_f32), one WAVE per task, no block barriers:
+// Attention cores, one WAVE per task, no block barriers:
 //   forward  task (n, h, query block)  : S^T = K q^T, E q^T -> skew -> online softmax down the key blocks -> o^T += V^T P^T
 //   dq       task (n, h, query block)  : recompute P^T, dS^T;  dq += dS K + unskew(dS) E_band
 //   dk / dv  task (n, h, key block)    : recompute P, dS;      dk += dS^T q, dv += P^T dO
 //   dE       task (n, h, tile diagonal): recompute dS;         dE_band += unskew(dS)^T q   (all tiles of a diagonal
 //                                        share their 31 distances, so the band stays in registers)
-// A 16 x 16 tile of (query, key) pairs costs 4 MFMAs for q.k, 8 for the relative-position term (the 31 distances of
-// the tile, as q . E_band^T) and 4 for dO.v; the band result is turned into the tile ("skew": R[i][j] =
+// A 16 x 16 tile of (query, key) pairs costs one product (at_mma) for q.k, two for the relative-position term (the 31
+// distances of the tile, as q . E_band^T) and one for dO.v; the band result is turned into the tile ("skew": R[i][j] =
 // QE[i][15 + i - j]) through a wave-private LDS patch, and dS goes back the same way for the two E-side products.
 // Operand fragments (common.hip.h convention, lane = (g, c)):
 //   "A-type" XA[s] = X[row0 + c][4g + s]   one float4 per lane: at_dot(XA, YA)[r] = sum_d X[4g + r][d] Y[c][d]
@@ -1561,11 +911,10 @@ __device__ __forceinline__ bool at_task(long ntask, int nb, AtTask& t) {
 }
 // ---- operand types of the cores ------------------------------------------------------------------------------------
 // at_mma(a, b, acc) = acc + sum over the 16 contraction indices (g, s) of a(lane (i, g))[s] * b(lane (j, g))[s].
-// fp32 build: operands are the lanes' float4s, four v_mfma_f32_16x16x4_f32 steps.  AT_X3: the A side is the lane's
-// [hi(4) | lo(4)] along the 32-wide contraction of v_mfma_f32_16x16x32_f16, the B side [hi | hi], then [lo | lo]: two
-// MFMAs give all four split terms.  Loaded operands arrive in these forms from the images (at_lda / at_row_a, no VALU
-// but register shuffles); operands computed in the core (probabilities, dS, unskewed bands) are split by at_a / at_b.
-#if AT_X3
+// The A side is the lane's [hi(4) | lo(4)] along the 32-wide contraction of v_mfma_f32_16x16x32_f16, the B side
+// [hi | hi], then [lo | lo]: two MFMAs give all four split terms.  Loaded operands arrive in these forms from the images
+// (at_lda / at_row_a, no VALU but register shuffles); operands computed in the core (probabilities, dS, unskewed bands)
+// are split by at_a / at_b.
 typedef f16x8 AtA;
 struct AtB { f16x8 hh, ll; };
 __device__ __forceinline__ AtA at_a(const f32x4& x) {
@@ -1593,38 +942,15 @@ __device__ __forceinline__ f32x4 at_mma(const AtA& a, const AtB& b, f32x4 acc) {
     return mfma32l(a, b.ll, acc);
 }
 #define AT_QBACK 0.6931471805599453f      // dk, dE contract with the PRE-SCALED q: 0.25 = (0.25 log2 e) ln 2
-#else
-typedef f32x4 AtA;
-typedef f32x4 AtB;
-__device__ __forceinline__ AtA at_a(const f32x4& x) { return x; }
-__device__ __forceinline__ AtB at_b_of(const AtA& a) { return a; }
-__device__ __forceinline__ AtB at_b(const f32x4& x) { return x; }
-__device__ __forceinline__ AtA at_lda(const float* __restrict__ p) { return ldg4(p); }
-__device__ __forceinline__ AtA at_row_a(const f32x4& raw) { return raw; }
-__device__ __forceinline__ f32x4 at_mma(const AtA& a, const AtB& b, f32x4 acc) {
-#pragma unroll
-    for (int s = 0; s < 4; ++s) acc = mfma16(a[s], b[s], acc);
-    return acc;
-}
-#define AT_QBACK 0.25f
-#endif
 __device__ __forceinline__ AtB at_row_b(const f32x4& raw) { return at_b_of(at_row_a(raw)); }
 __device__ __forceinline__ f32x4 at_dot(const AtA& a, const AtB& b) { return at_mma(a, b, splat4(0.f)); }
-// the q fragment of a score product (A-type rows of the q image / tensor): fp32 build applies the score scale here
+// the q fragment of a score product (A-type rows of the q image, which is stored with the score scale applied)
 __device__ __forceinline__ AtA at_ldq(const float* __restrict__ p) {
-#if AT_X3
     return at_lda(p);
-#else
-    return ldg4(p) * splat4(AT_QSCALE);
-#endif
 }
-// a q fragment that did not come through at_ldq (fp32 build: the score scale is still to be applied)
+// a q fragment that did not come through at_ldq (nothing to do: the image already carries the score scale)
 __device__ __forceinline__ AtA at_qfix(const AtA& q) {
-#if AT_X3
     return q;
-#else
-    return q * splat4(AT_QSCALE);
-#endif
 }
 // loads as uniform base + 32-bit per-lane BYTE offset: the global_load "saddr" form (no 64-bit VALU address arithmetic)
 __device__ __forceinline__ f32x4 at_ld4b(const float* __restrict__ base, unsigned boff) {
@@ -1636,16 +962,14 @@ __device__ __forceinline__ float at_ld1b(const float* __restrict__ base, unsigne
 // exact power-of-two scale of the backward cores' gradient operands (dO and D = rowsum(dO o)): s brings the largest
 // |dO| of the whole tensor (*amax: per-block maxima of at_out_bwd_kernel reduced by at_amax_kernel - order-independent)
 // to [1, 2); the dO images are stored scaled, D is scaled on load, and every output of a core - linear in dO - is
-// multiplied by inv = 1 / s at the end.  fp32 build: 1, 1.
+// multiplied by inv = 1 / s at the end.
 __device__ __forceinline__ void at_scale(const float* __restrict__ amax, float& s, float& inv) {
     s = 1.0f; inv = 1.0f;
-#if AT_X3
     const unsigned e = (__float_as_uint(amax[0]) >> 23) & 0xffu;
     if (e > 0u && e < 254u) {
         s = __uint_as_float((254u - e) << 23);
         inv = __uint_as_float(e << 23);
     }
-#endif
 }
 // lane offsets (floats) of the fragments of the 16 rows that start at row R0 of a sequence of L rows, relative to row
 // R0: rows past the end read row L - 1 (finite; masked or never stored).  Full blocks use the affine forms
@@ -1667,13 +991,8 @@ __global__ void at_window_kernel(const float* __restrict__ rel, int W, int max_p
     int dist = (q >> 2) - W;
     dist = dist < -max_pos ? -max_pos : (dist > max_pos ? max_pos : dist);
     const f32x4 v = ldg4(rel + (long)(dist + max_pos) * 16 + (q & 3) * 4);
-#if AT_X3
     (void)ewinp;
     stg4(ewin + 4 * q, at_img4(v));
-#else
-    (void)ewinp;
-    stg4(ewin + 4 * q, v);
-#endif
 }
 // band^T [32 distances][16 queries] (two accumulators) -> R^T[key 4g + r][query c] = band[15 + c - (4g + r)][c]
 __device__ __forceinline__ f32x4 at_skew_t(float* buf, const f32x4& eq0, const f32x4& eq1, int c, int g) {
@@ -1842,7 +1161,6 @@ __global__ __launch_bounds__(256) void at_out_bwd_kernel(const float* __restrict
             mx = fmaxf(fmaxf(mx, fmaxf(fabsf(acc[0][0]), fabsf(acc[0][1]))), fmaxf(fabsf(acc[0][2]), fabsf(acc[0][3])));
         }
     }
-#if AT_X3
     // the wave's largest |dO|, one slot per 16-token tile (at_amax_kernel reduces them): the exact power-of-two scale of
     // the split-f16 cores (at_scale).  (One atomicMax per wave on a single word cost ~70 us per launch.)
     mx = red_g_max(mx);
@@ -1851,11 +1169,7 @@ __global__ __launch_bounds__(256) void at_out_bwd_kernel(const float* __restrict
     mx = fmaxf(mx, dpp_perm<0x141>(mx));
     mx = fmaxf(mx, dpp_perm<0x140>(mx));
     if (lane == 0) maxslot[t0 >> 4] = mx;
-#else
-    (void)mx; (void)maxslot;
-#endif
 }
-#if AT_X3
 // out[0] = max of n non-negative floats (one block; max is order-independent)
 __global__ __launch_bounds__(1024) void at_amax_kernel(const float* __restrict__ slots, long n, float* __restrict__ out) {
     __shared__ float red[16];
@@ -1883,7 +1197,6 @@ __global__ __launch_bounds__(256) void at_dO_split_kernel(float* __restrict__ dO
         stg4(dO + 4 * i, at_img4(ldg4(dO + 4 * i) * splat4(gs)));
     }
 }
-#endif
 
 // p_ij and ds_ij of one (query i, key j) pair; scores are recomputed, never stored.  q is the RAW query row (the
 // 16^-0.5 scale is applied to the score), so that rows can come straight from wave-uniform scalar loads.
@@ -2509,76 +1822,6 @@ __global__ void at_de_scatter_kernel(const float* __restrict__ slabs, int L, int
 }
 
 
-// backward of the projections: dxn = [to_q ; to_kv]^T dqkv (A image [4][12]), LayerNorm backward
-__global__ __launch_bounds__(256) void at_qkv_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dqkv, long M,
-                                                         const float* __restrict__ wtfm, const float* __restrict__ ln_w,
-                                                         const float* __restrict__ ln_b, const float* __restrict__ dres,
-                                                         float* __restrict__ dx, float* __restrict__ xn_out,
-                                                         float* __restrict__ g1, float* __restrict__ dxn_out) {
-    const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
-    const long t0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16;
-    if (t0 >= M) return;
-    f32x4 xh[4], xn[1][4];
-    float rstd;
-    long row;
-    const bool ok = cm_load_norm(x, M, t0, c, g, ln_w, ln_b, xh, xn, rstd, row);
-    f32x4 df[1][12];
-#pragma unroll
-    for (int kb = 0; kb < 12; ++kb) {
-        df[0][kb] = ldg4(dqkv + row * 192 + 16 * kb + 4 * g);
-        if (!ok) df[0][kb] = splat4(0.f);
-    }
-    f32x4 dxn[4];
-    // 12 groups of 4 fragments (image [4 row blocks][12 k-blocks] = group index rb * 3 + third); next group in flight
-    {
-        FfnFrag f0 = ffn_frag_rows(wtfm, 0, lane), f1;
-#pragma unroll
-        for (int rb = 0; rb < 4; ++rb) {
-            f32x4 acc = splat4(0.f);
-#pragma unroll
-            for (int t = 0; t < 3; ++t) {
-                const int gi = rb * 3 + t;
-                FfnFrag& cur = (gi & 1) ? f1 : f0;
-                FfnFrag& nxt = (gi & 1) ? f0 : f1;
-                nxt = ffn_frag_rows(wtfm, gi + 1 < 12 ? gi + 1 : 11, lane);
-#pragma unroll
-                for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) acc = mfma16(cur.a[kb][r], df[0][4 * t + kb][r], acc);
-            }
-            dxn[rb] = acc;
-        }
-    }
-    f32x4 dxh[4];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-        dxh[kb] = dxn[kb] * ldg4(ln_w + 16 * kb + 4 * g);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            s1 += dxh[kb][r];
-            s2 = fmaf(dxh[kb][r], xh[kb][r], s2);
-        }
-    }
-    const float mu1 = red_g_sum(s1) * (1.0f / 64.0f), mu2 = red_g_sum(s2) * (1.0f / 64.0f);
-    if (ok) {
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb) {
-            f32x4 dv = (dxh[kb] - splat4(mu1) - xh[kb] * splat4(mu2)) * splat4(rstd);
-            if (dres) dv = dv + ldg4(dres + row * 64 + 16 * kb + 4 * g);
-            stg4(dx + row * 64 + 16 * kb + 4 * g, dv);
-            stg4(xn_out + row * 64 + 16 * kb + 4 * g, xn[0][kb]);
-        }
-    }
-    f32x4 ca[4], cb[4];
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-        ca[kb] = ok ? dxn[kb] * xh[kb] : splat4(0.f);
-        cb[kb] = ok ? dxn[kb] : splat4(0.f);
-    }
-    ln_tile_colsums(ca, cb, c, g, t0 >> 4, g1, dxn_out);            // [tiles][64] slabs: dgamma / dbeta partial sums
-}
-
 // dynamic LDS above the 64 KB default needs an explicit opt-in per kernel
 static int at_blocks(int L) { return (L + 15) / 16; }
 static int at_window(int L) { return 16 * at_blocks(L) + 16; }      // half-width W of the relative-position window
@@ -2594,7 +1837,7 @@ static AtPlan at_plan(int N, int L) {
     p.ewin = take((size_t)(2 * at_window(L) + 1) * 16);
     p.qkv = take(M * 192); p.o = take(M * 64); p.lse = take((size_t)N * 4 * L);
     p.dout = take(M * 64); p.dO = take(M * 64); p.D = take(M * 4); p.dqkv = take(M * 192);
-    p.ewinp = p.ewin; p.qkvp = p.qkv; p.dOp = p.dO;             // one image per tensor (or the fp32 tensor itself)
+    p.ewinp = p.ewin; p.qkvp = p.qkv; p.dOp = p.dO;             // one image per tensor
     p.xn = take(M * 64); p.g1 = take((M + 15) / 16 * 64); p.dxn = take((M + 15) / 16 * 64);      // g1 / dxn: per-tile partial rows
     const size_t slabs = (size_t)(2 * at_blocks(L) - 1) * 512;       // dE band slabs [2 nb - 1][32][16]
     p.depart = take((size_t)N * 4 * slabs);
@@ -2617,15 +1860,9 @@ static void at_pack_images(LaunchCtx ctx, const AttnTrainParams& p, float* ws, c
         hipMemcpyAsync(ws + pl.raw + 4096, p.wkv, 8192 * sizeof(float), hipMemcpyDeviceToDevice, s);    // rows 64..191
         raw = ws + pl.raw;
     }
-#if TRAIN_X3
     at_x3_pack(ctx, raw, ws + pl.wqkv, ws + pl.wqkvt);              // the projections run on split products
     launch_pack4(ctx, "attn_train_pack", PackJobs{{{p.wo, 64, 64, 64, 0, ws + pl.wo}, {p.wo, 64, 64, 64, 1, ws + pl.wot},
                                                    {}, {}}}, 2);
-#else
-    launch_pack4(ctx, "attn_train_pack", PackJobs{{{raw, 192, 64, 64, 0, ws + pl.wqkv},
-                                                   {raw, 64, 192, 64, 1, ws + pl.wqkvt},
-                                                   {p.wo, 64, 64, 64, 0, ws + pl.wo}, {p.wo, 64, 64, 64, 1, ws + pl.wot}}});
-#endif
 }
 
 void launch_attn_train_forward(LaunchCtx ctx, const float* x, int N, int L, const AttnTrainParams& p, int max_pos,
@@ -2636,11 +1873,7 @@ void launch_attn_train_forward(LaunchCtx ctx, const float* x, int N, int L, cons
     at_pack_images(ctx, p, ws, pl);
     const AtBufs b{ws + pl.qkv, ws + pl.qkvp, ws + pl.o, ws + pl.lse};
     const unsigned grid = (unsigned)((M + 63) / 64);
-#if TRAIN_X3
-    at_x3_qkv(ctx, x, M, ws + pl.wqkv, p.ln_w, p.ln_b, b.qkv, AT_X3, AT_QSCALE);
-#else
-    LAUNCH(ctx, "attn_train_fwd", (at_qkv_kernel<<<grid, 256, 0, s>>>(x, M, ws + pl.wqkv, p.ln_w, p.ln_b, b.qkv, b.qkvp)));
-#endif
+    at_x3_qkv(ctx, x, M, ws + pl.wqkv, p.ln_w, p.ln_b, b.qkv, 1, AT_QSCALE);
     const int nb = at_blocks(L);
     const long ntask = (long)N * 4 * nb;
     const int W = at_window(L);
@@ -2663,19 +1896,13 @@ void launch_attn_train_backward(LaunchCtx ctx, const float* x, const float* dy, 
                                                           // are idle until the end of this function)
     LAUNCH(ctx, "attn_train_bwd", (at_out_bwd_kernel<<<grid, 256, 0, s>>>(dy, mask, ms, b.o, M, ws + pl.wot, ws + pl.dout,
                                                                           ws + pl.dO, ws + pl.D, cpart + 64)));
-#if AT_X3
     LAUNCH(ctx, "attn_train_bwd", (at_amax_kernel<<<1, 1024, 0, s>>>(cpart + 64, (M + 15) / 16, cpart)));
     LAUNCH(ctx, "attn_train_bwd", (at_dO_split_kernel<<<2048, 256, 0, s>>>(ws + pl.dO, ws + pl.dOp, cpart, M * 16)));
-#endif
     // to_out gradients: dWo [64,64] = dout^T O, dbo = colsum dout
-#if TRAIN_X3
     // (cpart holds the per-block |dO| maxima in its first rows until at_amax_kernel / at_dO_split_kernel above have run; the
     // column-sum partials of dout go to the fourth job's region, which colsum_batch below - three jobs at most - never uses)
     wgrad_partial64(ctx, "attn_train_wgrad", ws + pl.dout, b.o, M, 64, 64, ws + pl.wpart, wg_split(1),
                     cpart + (size_t)3 * FFN_COLSUM_BLOCKS * 256, grad.bo, "attn_train_reduce");
-#else
-    wgrad_partial64(ctx, "attn_train_wgrad", ws + pl.dout, b.o, M, 64, 64, ws + pl.wpart, wg_split(1));
-#endif
     LAUNCH(ctx, "attn_train_reduce", (reduce_partials_kernel<<<64, 1024, 0, s>>>(ws + pl.wpart, wg_split(1), 4096,
                                                                                 grad.wo)));
     // attention core: dq (query blocks), dk / dv (key blocks), dE (tile diagonals)
@@ -2720,12 +1947,7 @@ void launch_attn_train_backward(LaunchCtx ctx, const float* x, const float* dy, 
     LAUNCH(ctx, "attn_train_reduce", (at_de_scatter_kernel<<<(rel_elems + 255) / 256, 256, 0, s>>>(ws + pl.dewin, L, nb, max_pos,
                                                                                                   grad.rel)));
     // projections + LayerNorm
-#if TRAIN_X3
     at_x3_qkv_bwd(ctx, x, ws + pl.dqkv, M, ws + pl.wqkvt, p.ln_w, p.ln_b, dres, dx, ws + pl.xn, ws + pl.g1, ws + pl.dxn);
-#else
-    LAUNCH(ctx, "attn_train_bwd", (at_qkv_bwd_kernel<<<grid, 256, 0, s>>>(x, ws + pl.dqkv, M, ws + pl.wqkvt, p.ln_w, p.ln_b,
-                                                                          dres, dx, ws + pl.xn, ws + pl.g1, ws + pl.dxn)));
-#endif
     wgrad_partial64(ctx, "attn_train_wgrad", ws + pl.dqkv, ws + pl.xn, M, 192, 64, ws + pl.wpart, wg_split(3));
     // [192,64] = [dW_q ; dW_kv]: straight into the gradient tensors when they are adjacent (views of one flat bucket), else split
     const bool adjacent = grad.wkv == grad.wq + 4096;
@@ -2735,15 +1957,9 @@ void launch_attn_train_backward(LaunchCtx ctx, const float* x, const float* dy, 
         hipMemcpyAsync(grad.wq, ws + pl.raw, 4096 * sizeof(float), hipMemcpyDeviceToDevice, s);
         hipMemcpyAsync(grad.wkv, ws + pl.raw + 4096, 8192 * sizeof(float), hipMemcpyDeviceToDevice, s);
     }
-#if TRAIN_X3
     const ColsumJobs jobs{{ws + pl.g1, ws + pl.dxn}, {grad.ln_w, grad.ln_b}, {64, 64},
                           {(M + 15) / 16, (M + 15) / 16}};                        // g1 / dxn: per-tile partial sums (dbo: above)
     colsum_batch(ctx, "attn_train_reduce", jobs, 2, M, cpart);
-#else
-    const ColsumJobs jobs{{ws + pl.dout, ws + pl.g1, ws + pl.dxn}, {grad.bo, grad.ln_w, grad.ln_b}, {64, 64, 64},
-                          {0, (M + 15) / 16, (M + 15) / 16}};                     // g1 / dxn: per-tile partial sums
-    colsum_batch(ctx, "attn_train_reduce", jobs, 3, M, cpart);
-#endif
 }
 
 // ---------------------------------------------------------------------------------
@@ -3371,7 +2587,6 @@ __global__ void db_pack_layer_kernel(const float* __restrict__ w, int i, float* 
     (tr ? imgT : img)[(long)st * 4096 + e] = v;
 }
 
-#if TRAIN_X3
 // The forward convolution of the training step IS the inference kernel (conv3x_kernel<2, 64>, conv_x3.hip: 256-position
 // tiles staged through LDS, split-f16 products): the training plane layout, the causal time taps and the raw output
 // are the same; only the operand image has to be rebuilt from the raw weight after every optimiser step.
@@ -3447,18 +2662,16 @@ __global__ __launch_bounds__(256) void db_dgrad_setup_kernel(float* __restrict__
     if (threadIdx.x < 64) { sc[128 + threadIdx.x] = 1.0f; sc[192 + threadIdx.x] = 0.0f; }
     for (int i = threadIdx.x; i < B * 64; i += 256) { sc[256 + i] = s; sc[256 + B * 64 + i] = 0.0f; }
 }
-#endif
 
 // the inference conv kernel steps its staging rows by 64 per load and assumes a plane row (F + 1 positions with the
 // virtual zero column) is at least that long: true for every model size (F = 201 / 101 / 601 / 301); tiny test planes
 // take the per-position fp32 kernel
-static bool db_x3_forward(int F) { return TRAIN_X3 && F + 1 >= 64; }
+static bool db_x3_forward(int F) { return F + 1 >= 64; }
 
 static void db_pack_images(LaunchCtx ctx, const DenseTrainParams& p, float* ws, const DbPlan& pl, int F, bool pack = true) {
     if (!pack) return;
     for (int i = 0; i < 4; ++i) {
         const long off = (long)db_img_index(i, 0) * 4096;
-#if TRAIN_X3
         if (db_x3_forward(F)) {
             // forward and data-gradient operand images in split-f16 form (exactly the space of the fp32 ones)
             const int nthr = 2 * (i + 1) * 6 * 4 * 64;
@@ -3469,7 +2682,6 @@ static void db_pack_images(LaunchCtx ctx, const DenseTrainParams& p, float* ws, 
             (void)off;
             continue;
         }
-#endif
         LAUNCH(ctx, "dense_train_pack", (db_pack_layer_kernel<<<dim3(16, 6 * (i + 1), 2), 256, 0, ctx.stream>>>(
                                             p.conv_w[i], i, ws + pl.img + off, ws + pl.imgT + off)));
     }
@@ -3497,7 +2709,6 @@ void launch_dense_train_forward(LaunchCtx ctx, const float* x, int B, int T, int
         float* a = i == 3 ? y : ws + pl.a + (size_t)i * M * 64;
         const int dil = 1 << i;
         bool tile_stats = false;
-#if TRAIN_X3
         if (db_x3_forward(F)) {
             ConvArgs ca{};                                  // slots arrive normalised + activated (or raw: slot 0): identity on load
             for (int sl = 0; sl <= i; ++sl) ca.in[sl] = in.p[sl];
@@ -3508,9 +2719,7 @@ void launch_dense_train_forward(LaunchCtx ctx, const float* x, int B, int T, int
             ca.T = T; ca.F = F; ca.dil = dil; ca.mode = 0; ca.ntiles = conv3x_ntiles(T, F, 64);
             launch_conv3_x3(ctx, ca, reinterpret_cast<const _Float16*>(ws + pl.img) + db_x3_img_off(i), B, 2, 64);
             tile_stats = true;
-        } else
-#endif
-        {
+        } else {
             const float* wimg = ws + pl.img + (long)db_img_index(i, 0) * 4096;
             switch (i) {
                 case 0: db_launch_conv<1>(ctx, in, wimg, p.conv_b[i], B, T, F, dil, z); break;
@@ -3569,13 +2778,11 @@ void launch_dense_train_backward(LaunchCtx ctx, const float* x, const float* dy,
                                                                                     ws + pl.m1, ws + pl.m2,
                                                                                     x3d ? sc + 256 + (size_t)2 * B * 64 : nullptr)));
         const int dil = 1 << i, Cin = 64 * (i + 1);
-#if TRAIN_X3
         if (x3d) LAUNCH(ctx, "dense_train_bwd", (db_dgrad_setup_kernel<<<1, 256, 0, st>>>(sc, B)));
-#endif
         for (int s = 0; s <= i; ++s) {
             // the split-f16 kernel addresses a plane with 32-bit byte offsets: planes of 4 GB and more (16.7 M positions,
             // 250 clips of the encoder's shape) take the fp32 kernel
-            if (TRAIN_X3 && (long)M * 256 < (1L << 32)) {
+            if ((long)M * 256 < (1L << 32)) {
                 // (the conv-bias gradient of layer i = colsum of its dz rides on the first of its weight-gradient launches)
                 launch_db_conv_wgrad_x3(ctx, g, aslot(s), B, T, F, dil, DB_WG_SPLIT, ws + pl.wpart, s == 0 ? cpart : nullptr);
                 if (s == 0)
@@ -3586,7 +2793,6 @@ void launch_dense_train_backward(LaunchCtx ctx, const float* x, const float* dy,
                                                      g, aslot(s), B, T, F, dil, ws + pl.wpart)));
             LAUNCH(ctx, "dense_train_reduce", (db_wgrad_scatter_kernel<<<6 * 64, 256, 0, st>>>(ws + pl.wpart, Cin, 64 * (i - s),
                                                                                                grad.conv_w[i])));
-#if TRAIN_X3
             if (x3d) {
                 ConvArgs ca{};                              // dz scaled by an exact power of two on load, ga(s) += result / scale
                 ca.in[0] = g; ca.nscale[0] = sc + 256; ca.nshift[0] = sc + 256 + (size_t)B * 64; ca.nalpha[0] = sc + 128;
@@ -3598,13 +2804,12 @@ void launch_dense_train_backward(LaunchCtx ctx, const float* x, const float* dy,
                 launch_conv3_x3_dgrad(ctx, ca, reinterpret_cast<const _Float16*>(ws + pl.imgT) + db_x3_dgrad_off(i, s), B);
                 continue;
             }
-#endif
             LAUNCH(ctx, "dense_train_bwd", (db_conv_dgrad_kernel<<<(unsigned)((M + 63) / 64), 256, 0, st>>>(
                                                g, ws + pl.imgT + (long)db_img_index(i, s) * 4096, B, T, F, dil, ga(s))));
         }
     }
     // the four conv-bias gradients (column sums of the layers' dz planes, which stay untouched once written) in one batch
-    if (!(TRAIN_X3 && (long)M * 256 < (1L << 32))) {              // (split-f16 build: done inside the weight-gradient launches)
+    if ((long)M * 256 >= (1L << 32)) {                            // (else: done inside the weight-gradient launches)
         const ColsumJobs jobs{{ga(1), ga(2), ga(3), ga(4)}, {grad.conv_b[0], grad.conv_b[1], grad.conv_b[2], grad.conv_b[3]},
                               {64, 64, 64, 64}};
         colsum_batch(ctx, "dense_train_reduce", jobs, 4, M, cpart);
@@ -3619,21 +2824,11 @@ void launch_dense_train_backward(LaunchCtx ctx, const float* x, const float* dy,
 // channels are written pixel-shuffled, channel 64 r + c of position f -> channel c of position 2 f + r of a plane
 // that is twice as wide (SPConvTranspose2d, generator.py:102-119) - the shuffle is an index map, never a copy.
 // =====================================================================================
-struct RcGeom { int B, T, Fi, Fo, KW, SF, PL; };      // Fo = output positions per row (before the pixel shuffle)
 #define RC_WG_SPLIT 256               // position ranges of the split-f16 weight gradient (sizes the slab buffers; >= FFN_WGRAD_SPLIT)
-void launch_rc_wgrad_x3(LaunchCtx, int ng, const float* dz, const float* in, const int* gm7, int nsplit, float* partial,
-                        float* colp);
-bool launch_rc_dgrad_x3(LaunchCtx, int ng, const float* dz, const float* wraw, const int* gm7, float* din);
-// the data gradient on split products (train_x3.hip) when the build and the geometry allow; CMGAN_RC_DGRAD_X3=0: A/B
+// the data gradient on split products (train_x3.hip) when the geometry allows; CMGAN_RC_DGRAD_X3=0: A/B
 static bool rc_dgrad_x3(LaunchCtx ctx, int ng, const float* dz, const float* wraw, const RcGeom& gm, float* din) {
-#if TRAIN_X3
     static const bool k_on = env_knob("CMGAN_RC_DGRAD_X3", 1, 0, 1) != 0;
-    const int gm7[7] = {gm.B, gm.T, gm.Fi, gm.Fo, gm.KW, gm.SF, gm.PL};
-    return k_on && launch_rc_dgrad_x3(ctx, ng, dz, wraw, gm7, din);
-#else
-    (void)ctx; (void)ng; (void)dz; (void)wraw; (void)gm; (void)din;
-    return false;
-#endif
+    return k_on && launch_rc_dgrad_x3(ctx, ng, dz, wraw, gm, din);
 }
 
 template <int NG>
@@ -3881,7 +3076,6 @@ static void in_prelu_backward(LaunchCtx ctx, const float* z, float* g, int B, in
     LAUNCH(ctx, "in_prelu_train", (db_in_bwd_kernel<<<2048, 256, 0, st>>>(g, z, (long)B * P * 64, P, mean, rstd, gamma, m1, m2)));
 }
 
-#if TRAIN_X3
 // The forward 1 x 3 convolutions of the training step (the encoder's stride-2 conv, the decoders' sub-pixel conv) ARE the
 // inference kernels (conv3x_kernel<1, 64> mode 1 / <1, 128> mode 2, conv_x3.hip), as the dense blocks' convs are: same
 // planes, same zero padding, raw output; only the operand image is rebuilt from the raw weight [Co, 64, 1, 3] every step.
@@ -3911,12 +3105,10 @@ static bool rc_x3_forward(const RcGeom& gm, int NG) {
     return k_on && gm.KW == 3 && gm.PL == 1 && gm.Fi + 1 >= 64 &&
            ((NG == 2 && gm.SF == 1 && gm.Fo == gm.Fi) || (NG == 1 && gm.SF == 2 && gm.Fo == (gm.Fi - 1) / 2 + 1));
 }
-#endif
 // img: the fp32 fragment image of rc_pack_kernel; the split-f16 path rebuilds it in place (same size) from the raw weight
 template <int NG>
 static void rc_forward(LaunchCtx ctx, const float* in, float* img, const float* wraw, const float* bias, const RcGeom& gm,
                        float* z) {
-#if TRAIN_X3
     if (rc_x3_forward(gm, NG)) {
         const int nthr = 2 * 3 * 4 * NG * 64;
         LAUNCH(ctx, "rowconv_train", (rc_pack_x3_kernel<<<(nthr + 255) / 256, 256, 0, ctx.stream>>>(
@@ -3930,13 +3122,11 @@ static void rc_forward(LaunchCtx ctx, const float* in, float* img, const float* 
         launch_conv3_x3(ctx, ca, img, gm.B, 1, 64 * NG);
         return;
     }
-#endif
-    (void)wraw;
     const long Mo = (long)gm.B * gm.T * gm.Fo;
     LAUNCH(ctx, "rowconv_train", (rc_fwd_kernel<NG><<<(unsigned)((Mo + 63) / 64), 256, 0, ctx.stream>>>(in, img, bias, gm, z)));
 }
 // db / cpart (optional): the bias gradient from the weight-gradient kernel ([RC_WG_SPLIT][64 NG] partials at cpart); returns
-// false if the caller still has to compute it (fp32 build / planes of 4 GB)
+// false if the caller still has to compute it (CMGAN_RC_WGRAD_X3=0 / planes of 4 GB)
 template <int NG>
 static bool rc_backward(LaunchCtx ctx, const float* dz, const float* in, const float* imgT, const RcGeom& gm, float* din,
                         float* dW, float* wpart, float* db = nullptr, float* cpart = nullptr) {
@@ -3945,21 +3135,16 @@ static bool rc_backward(LaunchCtx ctx, const float* dz, const float* in, const f
     const long Mi = (long)gm.B * gm.T * gm.Fi;
     const int nw = gm.KW * 64 * NG * 64;
     const long rows = (long)gm.B * gm.T * (gm.Fi > NG * gm.Fo ? gm.Fi : NG * gm.Fo);
-#if TRAIN_X3
     static const bool k_wx3 = env_knob("CMGAN_RC_WGRAD_X3", 1, 0, 1) != 0;
     if (k_wx3 && rows * 256 < (1l << 32)) {           // split products (train_x3.hip), RC_WG_SPLIT position ranges
-        const int gm7[7] = {gm.B, gm.T, gm.Fi, gm.Fo, gm.KW, gm.SF, gm.PL};
-        launch_rc_wgrad_x3(ctx, NG, dz, in, gm7, RC_WG_SPLIT, wpart, db ? cpart : nullptr);
+        launch_rc_wgrad_x3(ctx, NG, dz, in, gm, RC_WG_SPLIT, wpart, db ? cpart : nullptr);
         LAUNCH(ctx, "rowconv_train", (rc_wgrad_scatter_kernel<<<(nw + 63) / 64, 256, 0, st>>>(wpart, RC_WG_SPLIT, 64 * NG,
                                                                                                 gm.KW, dW)));
         if (db) {
             LAUNCH(ctx, "rowconv_train", (reduce_partials_kernel<<<4, 1024, 0, st>>>(cpart, RC_WG_SPLIT, 64 * NG, db)));
             db_done = true;
         }
-    } else
-#endif
-    {
-        (void)rows;
+    } else {
         LAUNCH(ctx, "rowconv_train", (rc_wgrad_kernel<NG><<<dim3(4 * NG, gm.KW, FFN_WGRAD_SPLIT), 256, 0, st>>>(
                                          dz, in, gm, FFN_WGRAD_SPLIT, wpart)));
         LAUNCH(ctx, "rowconv_train", (rc_wgrad_scatter_kernel<<<(nw + 63) / 64, 256, 0, st>>>(wpart, FFN_WGRAD_SPLIT, 64 * NG,

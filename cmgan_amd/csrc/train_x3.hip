@@ -1,14 +1,14 @@
 // train_x3.hip - the training-mode FeedForward and the token-contraction weight gradient on the f16 matrix pipe with
 // 3-term split products (common.hip.h "x3": hi.hi + hi.lo + lo.hi on v_mfma_f32_16x16x32_f16, fp32 accumulation, ~2^-21
 // per product) instead of v_mfma_f32_16x16x4_f32, which runs at 1/16 of that pipe's rate.  Same mathematics, same
-// C ABI, same workspace layout as the fp32 kernels of train.hip (kept there; -DTRAIN_X3=0 selects them).
+// C ABI, same workspace layout as the fp32 kernels train.hip used to carry.  Entry points: train.h.
 //
 //   forward    y = res + 0.5 m2 (W2 (m1 Swish(W1 LN(x) + b1)) + b2)          conformer.py:54-72,136-148,211
 //   backward   dz = 0.5 m2 dy;  dd1 = W2^T dz;  dh = m1 dd1 Swish'(h);  dxn = W1^T dh;  LayerNorm backward
 //   wgrad      dW[i][j] = sum_m P[m][i] Q[m][j]  (token contraction, split-K partial slabs)
 //
 // Structure follows the inference kernel ffn_x3_kernel (conformer_x3.hip): persistent 768-thread blocks with the
-// weight images resident in LDS (the fp32 training kernels streamed 8 KB of weight fragments per token from L1 / L2),
+// weight images resident in LDS (the earlier fp32 kernels streamed 8 KB of weight fragments per token from L1 / L2),
 // two 16-token blocks per wave, the per-token chain in registers.  The backward is two kernels because its three
 // weight images (W1, W2^T, W1^T: 192 KB) do not fit one CU's LDS: A holds W1 and W2^T (h recompute, dd1, d1 / dh
 // stores), B holds W1^T (dxn, LayerNorm backward); dh [M,256] is written by A anyway (the W1 gradient contracts it).
@@ -736,10 +736,11 @@ __global__ __launch_bounds__(512) void ffn_train_bwd_aw_x3_kernel(const float* _
 
 // ---------------------------------------------------------------------------------
 // out_partial[s][i][j] = sum over the s-th token range of P[m][i] Q[m][j]  (P [M,R], Q [M,C] row-major fp32): the
-// token-contraction weight gradient of wgrad_partial64_kernel (train.hip) with split products.  A wave-step is 32
+// token-contraction weight gradient (train.hip wgrad_partial64) with split products.  A wave-step is 32
 // tokens: lane (c, g) feeds slot e of the contraction with token 8 g + e, i.e. eight dwords of one column of P
 // (resp. Q) per 16-wide block, split to fp16 hi / lo in registers; 16 output tiles x 3 products = 48 MFMAs per step
-// instead of 128 fp32 ones.  Same 64 x 64 tile per block, same fixed-order LDS combine, same slab layout.
+// instead of the 128 of exact fp32 products.  A 64 x 64 tile per block (all four 16-row blocks of a 64-row band), the
+// four waves' tiles combined through LDS in a fixed order, slabs [split][R][C].
 // ---------------------------------------------------------------------------------
 // colp (optional): the column sums of P - a bias gradient - as [split][R] partials for free: the blocks with jc = 0 hold
 // every P element of their range in registers anyway (the separate column-sum pass re-read P: 1 GB for the conv module's
@@ -1103,11 +1104,10 @@ void launch_db_conv_wgrad_x3(LaunchCtx ctx, const float* dz, const float* a, int
 // lane's eight positions from ONE 32-bit division plus carries (the fp32 kernel: a 64-bit division per position), dz at
 // the running exact power-of-two scale.  NG = 2: dz is the pixel-shuffled plane, channel group r of position m at row 2 m + r.
 // ---------------------------------------------------------------------------------
-struct RcGeomX3 { int B, T, Fi, Fo, KW, SF, PL; };    // = RcGeom (train.hip)
 // colp (optional): the bias gradient - column sums of dz - as [split][64 NG] partials from the kw = 0 blocks, which hold every
 // dz element of their range in registers (the separate pass re-read the whole gradient plane).
 template <int NG>
-__global__ __launch_bounds__(256) void rc_wgrad_x3_kernel(const float* __restrict__ dz, const float* __restrict__ in, RcGeomX3 gm,
+__global__ __launch_bounds__(256) void rc_wgrad_x3_kernel(const float* __restrict__ dz, const float* __restrict__ in, RcGeom gm,
                                                           int nsplit, float* __restrict__ partial, float* __restrict__ colp) {
     __shared__ float red[2][64 * 64];
     __shared__ float cs_l[4][64];
@@ -1237,7 +1237,7 @@ __global__ __launch_bounds__(256) void rc_wgrad_x3_kernel(const float* __restric
 // the block's largest magnitude (dz is a gradient), split, and contracted with 12 NG x 3 MFMAs per output block.
 // ---------------------------------------------------------------------------------
 template <int NG>
-__global__ __launch_bounds__(512) void rc_dgrad_x3_kernel(const float* __restrict__ dz, const float* __restrict__ wraw, RcGeomX3 gm,
+__global__ __launch_bounds__(512) void rc_dgrad_x3_kernel(const float* __restrict__ dz, const float* __restrict__ wraw, RcGeom gm,
                                                           float* __restrict__ din, int ntiles) {
     constexpr int M32 = 2 * NG;                                   // k32 blocks of the contraction (64 NG output channels)
     extern __shared__ __attribute__((aligned(16))) _Float16 rd_w[];             // [kw 3][ob 4][M32][hi | lo][64][8]
@@ -1308,8 +1308,7 @@ __global__ __launch_bounds__(512) void rc_dgrad_x3_kernel(const float* __restric
     }
 }
 // returns false when the geometry is not one this kernel covers (the caller takes the fp32 kernel)
-bool launch_rc_dgrad_x3(LaunchCtx ctx, int ng, const float* dz, const float* wraw, const int* gm7, float* din) {
-    const RcGeomX3 gm{gm7[0], gm7[1], gm7[2], gm7[3], gm7[4], gm7[5], gm7[6]};
+bool launch_rc_dgrad_x3(LaunchCtx ctx, int ng, const float* dz, const float* wraw, const RcGeom& gm, float* din) {
     if (gm.KW != 3 || (gm.SF != 1 && gm.SF != 2)) return false;
     const long Mi = (long)gm.B * gm.T * gm.Fi;
     if (Mi * 256 >= (1l << 32) || (long)gm.B * gm.T * gm.Fo * ng * 256 >= (1l << 32)) return false;
@@ -1339,10 +1338,9 @@ bool launch_rc_dgrad_x3(LaunchCtx ctx, int ng, const float* dz, const float* wra
     return true;
 }
 
-// gm7: the seven ints of RcGeom.  The plane offsets are 32-bit: the caller checks rows * 256 < 2^32
-void launch_rc_wgrad_x3(LaunchCtx ctx, int ng, const float* dz, const float* in, const int* gm7, int nsplit, float* partial,
+// The plane offsets are 32-bit: the caller checks rows * 256 < 2^32
+void launch_rc_wgrad_x3(LaunchCtx ctx, int ng, const float* dz, const float* in, const RcGeom& gm, int nsplit, float* partial,
                         float* colp) {
-    const RcGeomX3 gm{gm7[0], gm7[1], gm7[2], gm7[3], gm7[4], gm7[5], gm7[6]};
     if (ng == 1)
         LAUNCH(ctx, "rowconv_train", (rc_wgrad_x3_kernel<1><<<dim3(1, gm.KW, nsplit), 256, 0, ctx.stream>>>(dz, in, gm, nsplit, partial,
                                                                                                             colp)));
@@ -1352,7 +1350,7 @@ void launch_rc_wgrad_x3(LaunchCtx ctx, int ng, const float* dz, const float* in,
 }
 
 // ---------------------------------------------------------------------------------
-// host side (called from train.hip's launch_ffn_train_* when TRAIN_X3 is on)
+// host side (called from train.hip's launch_ffn_train_*)
 // ---------------------------------------------------------------------------------
 static int tx_grid(int ntiles, int waves) {
     const int want = (ntiles + waves - 1) / waves;
@@ -1436,9 +1434,9 @@ void launch_wgrad_partial64_x3(LaunchCtx ctx, const char* label, const float* P,
 }
 
 // ---------------------------------------------------------------------------------
-// Conv module, per-token stages on split products (the fp32 kernels cm_pw1glu_kernel / cm_bwd2_kernel of train.hip ran
+// Conv module, per-token stages on split products (on exact fp32 products LN -> pw1 -> GLU and its backward took
 // 256 / 512 v_mfma_f32_16x16x4_f32 per 16-token tile with L2-streamed weight fragments: 35-40 % matrix-pipe busy, the
-// largest fp32 items left in the step).  Same structure as the FeedForward kernels above: persistent blocks, weight
+// largest fp32 items of the step at the time).  Same structure as the FeedForward kernels above: persistent blocks, weight
 // images resident in LDS, the per-token chain in registers.
 //   forward    u = a * sigmoid(gt),  [a ; gt] = W1 LN(x) + b1               conformer.py:161-164 (LayerNorm, pw conv, GLU)
 //   backward   da = du sigmoid(gt),  dg = du a sigmoid'(gt)  (a, gt recomputed);  dxn = W1^T [da ; dg];  LayerNorm backward
@@ -1657,7 +1655,8 @@ __global__ __launch_bounds__(512) void cm_bn_swish_pw2_x3_kernel(const float* __
 }
 
 // backward, part 1: ds = pw2^T dy (dy scaled by the block's exact power of two), through Swish; ddn, s and the per-block
-// partial sums of g2 = ddn dhat, ddn and dy (see cm_bwd1_kernel).  LDS: pw2^T image [8][2] = 32 KB.
+// partial sums the stage's three reductions are finished from: rows of [tiles][128] for g2 = ddn dhat (BatchNorm dgamma)
+// and ddn (dbeta), [tiles][64] for dy (the pointwise bias).  LDS: pw2^T image [8][2] = 32 KB.
 __global__ __launch_bounds__(512) void cm_bwd1_x3_kernel(const float* __restrict__ dy, const float* __restrict__ d, long M,
                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
                                                          const float* __restrict__ scale, const float* __restrict__ shift,
@@ -1729,7 +1728,7 @@ __global__ __launch_bounds__(512) void cm_bwd1_x3_kernel(const float* __restrict
 }
 
 // LN -> [to_q ; to_kv] (image [12][2] = 48 KB) -> q | k | v.  as_image: the attention cores' (hi, lo) operand image with
-// the q part (output blocks 0 .. 3) pre-scaled by qscale (train.hip, AT_X3); else the fp32 projection.
+// the q part (output blocks 0 .. 3) pre-scaled by qscale (train.hip, Operand images); else the fp32 projection.
 __global__ __launch_bounds__(512) void at_qkv_x3_kernel(const float* __restrict__ x, long M, const _Float16* __restrict__ wi,
                                                         const float* __restrict__ ln_w, const float* __restrict__ ln_b,
                                                         float* __restrict__ qkv, int as_image, float qscale, int ntiles) {

@@ -234,8 +234,8 @@ def test_three_adamw_steps_of_the_feed_forward_branch_match_torch():
         # Adam divides every gradient element by its own running magnitude, so an absolute gradient error of 1e-6 of the
         # tensor's maximum (the split-f16 products: 2^-21 each) becomes a RELATIVE update error of 1e-3 on an element
         # whose gradient is a thousand times below that maximum: 3 steps x lr 5e-4 x 1e-3 = 1.5e-6 absolute, i.e. 1e-5
-        # of the largest parameter (the fp32-MFMA build, -DTRAIN_X3=0, sits at 1e-6 here).  The second bar - the update
-        # itself is resolved to 2 % - is unchanged.
+        # of the largest parameter (exact fp32 products, the form these kernels had before, sat at 1e-6 here).  The second
+        # bar - the update itself is resolved to 2 % - is unchanged.
         assert _report(f"param {k} after 3 AdamW steps", rel_err(ffm.params[k], leaf["ff1." + k].detach())) < 5e-5, k
         # the update itself (3 x lr = 1.5e-3 per element at most) is resolved, not just the unchanged bulk
         moved = (leaf["ff1." + k].detach() - csd["ff1." + k]).abs().max()
