@@ -68,6 +68,7 @@ _KEYS = ("fn.norm.weight", "fn.norm.bias", "fn.fn.net.0.weight", "fn.fn.net.0.bi
          "fn.fn.net.3.weight", "fn.fn.net.3.bias")
 _FIELDS = ("ln_weight", "ln_bias", "w1", "b1", "w2", "b2")
 _SHAPES = ((64,), (64,), (256, 64), (256,), (64, 256), (64,))
+_FFN_TABLE = tuple(zip(_KEYS, _FIELDS))
 
 
 def dropout_mask(shape, p: float, device, generator: Optional[torch.Generator] = None) -> Optional[torch.Tensor]:
@@ -141,15 +142,86 @@ def _buckets(shapes: Dict[str, tuple], state, views, device):
     return pb, gb, pb.views, gb.views
 
 
+def _substate(state, prefix: str):
+    """The entries of `state` under `prefix.`, keys relative to it (a sub-module's slice of a state dict)."""
+    n = len(prefix) + 1
+    return {k[n:]: v for k, v in state.items() if k.startswith(prefix + ".")}
+
+
 def _subviews(views, prefix: str):
     """The (params, grads) view dictionaries of the sub-module `prefix`, keys relative to it."""
-    n = len(prefix) + 1
-    params, grads = views
-    return ({k[n:]: v for k, v in params.items() if k.startswith(prefix + ".")},
-            {k[n:]: v for k, v in grads.items() if k.startswith(prefix + ".")})
+    return _substate(views[0], prefix), _substate(views[1], prefix)
 
 
-class FeedForwardTrain:
+def _engine(engine: Optional[Engine], device) -> Engine:
+    return engine if engine is not None else Engine(device=device)
+
+
+def _launch(eng, name: str, *args) -> None:
+    """One native call `name(handle, *args, stream)` with the engine's device current (what `_on_device` does for the
+    Engine's own methods: the launch goes to eng's device whatever device the caller has current), checked.  A tensor
+    goes as its device pointer - an optional tensor that is None as a null pointer -, a parameter struct by reference,
+    everything else as it is."""
+    args = [a.data_ptr() if isinstance(a, torch.Tensor) else ctypes.byref(a) if isinstance(a, ctypes.Structure) else a
+            for a in args]
+    with torch.cuda.device(eng.device):
+        check(eng._h, getattr(eng.lib, name)(eng._h, *args, eng._stream()))
+
+
+def _add(eng, a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """a + b as one launch, into `out` (which may be `a`) or a new tensor."""
+    out = torch.empty_like(a) if out is None else out
+    _launch(eng, "cmgan_add", a, b, out, a.numel())
+    return out
+
+
+def _grown(ws: Optional[torch.Tensor], need: int, device) -> torch.Tensor:
+    """The grow-only byte workspace: `ws` when it holds `need` bytes, else a new allocation of that size."""
+    return ws if ws is not None and ws.numel() >= need else torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def _fill(s, table, tensors, prefix: str = ""):
+    """Point the fields of the ctypes parameter struct `s` at `tensors`: `table` is (key, field) pairs, a field either
+    a name or (name of a pointer array, index); `prefix` goes in front of every key.  Fields the table does not name
+    stay as they are (null in a new struct)."""
+    for key, field in table:
+        ptr = tensors[prefix + key].data_ptr()
+        if isinstance(field, tuple):
+            getattr(s, field[0])[field[1]] = ptr
+        else:
+            setattr(s, field, ptr)
+    return s
+
+
+class _TrainModule:
+    """Common plumbing of the *Train wrappers: the engine, parameters and gradients in two flat buckets (own ones
+    loaded from `state`, or `views` = (params, grads) dicts of tensors that are views of a parent's buckets), a
+    grow-only workspace and the data-parallel gradient mean."""
+
+    def __init__(self, shapes: Dict[str, tuple], state, engine: Optional[Engine], device, views=None):
+        self.engine = _engine(engine, device)
+        # parameters and gradients live in two flat buckets (views per tensor): one collective, one optimiser launch
+        self.param_bucket, self.grad_bucket, self.params, self.grads = _buckets(shapes, state, views, self.engine.device)
+        self._ws: Optional[torch.Tensor] = None
+        self._shape = None
+
+    @property
+    def _keep_scale(self) -> float:
+        """What the kernels multiply the values a Dropout(self.p) keeps by."""
+        return 1.0 / (1.0 - self.p) if self.p > 0.0 else 1.0
+
+    def _grow(self, need: int) -> torch.Tensor:
+        self._ws = _grown(self._ws, need, self.engine.device)
+        return self._ws
+
+    def allreduce_gradients(self) -> torch.Tensor:
+        """Mean of the gradients over the data-parallel ranks: ONE all-reduce (RCCL) over the flat bucket."""
+        if self.grad_bucket is None:
+            raise RuntimeError("this module's gradients are views of its parent's bucket: all-reduce the parent")
+        return allreduce_mean(self.grad_bucket.flat)
+
+
+class FeedForwardTrain(_TrainModule):
     """ff1 / ff2 branch of one ConformerBlock in train mode on the HIP kernels.
 
     `state` holds the branch's six tensors under the reference's key names relative to `ff1.` / `ff2.`
@@ -160,27 +232,11 @@ class FeedForwardTrain:
     def __init__(self, state: Optional[Dict[str, torch.Tensor]] = None, dropout: float = 0.2,
                  engine: Optional[Engine] = None, device=None, views=None):
         """`views` = (params, grads): dicts of tensors that are views of a larger FlatBucket (ConformerBlockTrain)."""
-        self.engine = engine if engine is not None else Engine(device=device)
+        super().__init__(self.SHAPES, state, engine, device, views)
         self.p = float(dropout)
-        # parameters and gradients live in two flat buckets (views per tensor): one collective, one optimiser launch
-        self.param_bucket, self.grad_bucket, self.params, self.grads = _buckets(self.SHAPES, state, views,
-                                                                                self.engine.device)
-        self._ws: Optional[torch.Tensor] = None
-
-    def _struct(self, tensors: Dict[str, torch.Tensor]) -> FfnParams:
-        s = FfnParams()
-        for key, field in zip(_KEYS, _FIELDS):
-            setattr(s, field, tensors[key].data_ptr())
-        return s
 
     def _workspace(self, M: int) -> torch.Tensor:
-        need = self.engine.lib.cmgan_ffn_train_workspace_bytes(self.engine._h, M)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.engine.device)
-        return self._ws
-
-    def _scale(self) -> float:
-        return 1.0 / (1.0 - self.p) if self.p > 0.0 else 1.0
+        return self._grow(self.engine.lib.cmgan_ffn_train_workspace_bytes(self.engine._h, M))
 
     def masks(self, M: int, generator: Optional[torch.Generator] = None):
         """Fresh keep-masks for the two Dropout layers (conformer.py:142,144)."""
@@ -200,12 +256,8 @@ class FeedForwardTrain:
         m2 = _keep_mask(mask2, (M, 64), self.p, eng.device, "mask2")
         y = torch.empty_like(x2)
         ws = self._workspace(M)
-        p = self._struct(self.params)
-        with torch.cuda.device(eng.device):
-            check(eng._h, eng.lib.cmgan_ffn_train_forward(
-                eng._h, x2.data_ptr(), M, ctypes.byref(p), m1.data_ptr() if m1 is not None else None,
-                m2.data_ptr() if m2 is not None else None, self._scale(), r, y.data_ptr(), ws.data_ptr(), ws.numel(),
-                eng._stream()))
+        _launch(eng, "cmgan_ffn_train_forward", x2, M, _fill(FfnParams(), _FFN_TABLE, self.params), m1, m2,
+                self._keep_scale, r, y, ws, ws.numel())
         return y.reshape(shape)
 
     def backward(self, x: torch.Tensor, dy: torch.Tensor, mask1: Optional[torch.Tensor] = None,
@@ -222,19 +274,9 @@ class FeedForwardTrain:
         m2 = _keep_mask(mask2, (M, 64), self.p, eng.device, "mask2")
         dx = torch.empty_like(x2)
         ws = self._workspace(M)
-        p, g = self._struct(self.params), self._struct(self.grads)
-        with torch.cuda.device(eng.device):
-            check(eng._h, eng.lib.cmgan_ffn_train_backward(
-                eng._h, x2.data_ptr(), dy2.data_ptr(), M, ctypes.byref(p), m1.data_ptr() if m1 is not None else None,
-                m2.data_ptr() if m2 is not None else None, self._scale(), r, dx.data_ptr(), ctypes.byref(g),
-                ws.data_ptr(), ws.numel(), eng._stream()))
+        _launch(eng, "cmgan_ffn_train_backward", x2, dy2, M, _fill(FfnParams(), _FFN_TABLE, self.params), m1, m2,
+                self._keep_scale, r, dx, _fill(FfnParams(), _FFN_TABLE, self.grads), ws, ws.numel())
         return dx.reshape(shape), self.grads
-
-    def allreduce_gradients(self) -> torch.Tensor:
-        """Mean of the six gradients over the data-parallel ranks: ONE all-reduce (RCCL) over the flat bucket."""
-        if self.grad_bucket is None:
-            raise RuntimeError("this module's gradients are views of its parent's bucket: all-reduce the parent")
-        return allreduce_mean(self.grad_bucket.flat)
 
 
 def step_lr(epoch: int, init_lr: float = 5e-4, decay_epoch: int = 30, gamma: float = 0.5) -> float:
@@ -274,11 +316,8 @@ class AdamW:
         if lr is not None:
             self.set_lr(lr)
         p, g = eng._in(self.params.flat, "params"), eng._in(self.grads.flat, "grads")
-        with torch.cuda.device(eng.device):
-            check(eng._h, eng.lib.cmgan_adamw_step_dev(eng._h, p.data_ptr(), g.data_ptr(), self.exp_avg.data_ptr(),
-                                                       self.exp_avg_sq.data_ptr(), self.params.numel,
-                                                       self.state.data_ptr(), float(self.betas[0]), float(self.betas[1]),
-                                                       float(self.eps), float(self.weight_decay), eng._stream()))
+        _launch(eng, "cmgan_adamw_step_dev", p, g, self.exp_avg, self.exp_avg_sq, self.params.numel, self.state,
+                float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay))
 
 
 @torch.no_grad()
@@ -317,9 +356,10 @@ _CM_KEYS = ("net.0.weight", "net.0.bias", "net.2.weight", "net.2.bias", "net.4.c
 _CM_FIELDS = ("ln_weight", "ln_bias", "pw1_weight", "pw1_bias", "dw_weight", "dw_bias", "bn_weight", "bn_bias",
               "pw2_weight", "pw2_bias")
 _CM_SHAPES = ((64,), (64,), (256, 64, 1), (256,), (128, 1, 31), (128,), (128,), (128,), (64, 128, 1), (64,))
+_CM_TABLE = tuple(zip(_CM_KEYS, _CM_FIELDS))
 
 
-class ConvModuleTrain:
+class ConvModuleTrain(_TrainModule):
     """`conv` branch of one ConformerBlock in train mode on the HIP kernels (csrc/train.hip).
 
     `state` holds the module's tensors under the reference's key names relative to `conv.` (`net.0.weight`,
@@ -329,26 +369,14 @@ class ConvModuleTrain:
     SHAPES = dict(zip(_CM_KEYS, _CM_SHAPES))
 
     def __init__(self, state: Dict[str, torch.Tensor], engine: Optional[Engine] = None, device=None, views=None):
-        self.engine = engine if engine is not None else Engine(device=device)
+        super().__init__(self.SHAPES, state, engine, device, views)
         dev = self.engine.device
-        self.param_bucket, self.grad_bucket, self.params, self.grads = _buckets(self.SHAPES, state, views, dev)
         self.running_mean = state["net.5.running_mean"].detach().to(dev, torch.float32).clone()
         self.running_var = state["net.5.running_var"].detach().to(dev, torch.float32).clone()
         self.num_batches_tracked = int(state.get("net.5.num_batches_tracked", 0))
-        self._ws: Optional[torch.Tensor] = None
-        self._shape = None
-
-    def _struct(self, tensors) -> ConvModParams:
-        s = ConvModParams()
-        for key, field in zip(_CM_KEYS, _CM_FIELDS):
-            setattr(s, field, tensors[key].data_ptr())
-        return s
 
     def _workspace(self, N: int, L: int) -> torch.Tensor:
-        need = self.engine.lib.cmgan_convmod_train_workspace_bytes(self.engine._h, N, L)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.engine.device)
-        return self._ws
+        return self._grow(self.engine.lib.cmgan_convmod_train_workspace_bytes(self.engine._h, N, L))
 
     def forward(self, x: torch.Tensor, update_running_stats: bool = True,
                 residual: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -361,12 +389,9 @@ class ConvModuleTrain:
             raise ValueError("conformer dim must be 64")
         ws = self._workspace(N, L)
         y = torch.empty_like(x)
-        p = self._struct(self.params)
-        rm = self.running_mean.data_ptr() if update_running_stats else None
-        rv = self.running_var.data_ptr() if update_running_stats else None
-        with torch.cuda.device(eng.device):
-            check(eng._h, eng.lib.cmgan_convmod_train_forward(eng._h, x.data_ptr(), N, L, ctypes.byref(p), rm, rv,
-                                                              r, y.data_ptr(), ws.data_ptr(), ws.numel(), eng._stream()))
+        rm, rv = (self.running_mean, self.running_var) if update_running_stats else (None, None)
+        _launch(eng, "cmgan_convmod_train_forward", x, N, L, _fill(ConvModParams(), _CM_TABLE, self.params), rm, rv, r, y,
+                ws, ws.numel())
         self._shape = (N, L)
         if update_running_stats:
             self.num_batches_tracked += 1
@@ -384,23 +409,18 @@ class ConvModuleTrain:
             raise RuntimeError("backward() needs the forward() of the same [N, L, 64] input first")
         ws = self._workspace(N, L)
         dx = torch.empty_like(x)
-        p, g = self._struct(self.params), self._struct(self.grads)
-        with torch.cuda.device(eng.device):
-            check(eng._h, eng.lib.cmgan_convmod_train_backward(eng._h, x.data_ptr(), dy.data_ptr(), N, L, ctypes.byref(p),
-                                                               r, dx.data_ptr(), ctypes.byref(g), ws.data_ptr(),
-                                                               ws.numel(), eng._stream()))
+        _launch(eng, "cmgan_convmod_train_backward", x, dy, N, L, _fill(ConvModParams(), _CM_TABLE, self.params), r, dx,
+                _fill(ConvModParams(), _CM_TABLE, self.grads), ws, ws.numel())
         return dx, self.grads
-
-    def allreduce_gradients(self) -> torch.Tensor:
-        return allreduce_mean(self.grad_bucket.flat)
 
 
 _AT_KEYS = ("norm.weight", "norm.bias", "fn.to_q.weight", "fn.to_kv.weight", "fn.to_out.weight", "fn.to_out.bias",
             "fn.rel_pos_emb.weight")
 _AT_FIELDS = ("ln_weight", "ln_bias", "to_q_weight", "to_kv_weight", "to_out_weight", "to_out_bias", "rel_pos_emb")
+_AT_TABLE = tuple(zip(_AT_KEYS, _AT_FIELDS))
 
 
-class AttentionTrain:
+class AttentionTrain(_TrainModule):
     """`attn` branch (PreNorm + Attention) of one ConformerBlock in train mode on the HIP kernels (csrc/train.hip).
     `state` holds the branch's tensors under the reference's key names relative to `attn.`.  Sequences of up to 4096
     positions; `backward` must follow the `forward` of the same x (it reads q|k|v, O and the row log-sum-exp)."""
@@ -413,26 +433,15 @@ class AttentionTrain:
 
     def __init__(self, state: Optional[Dict[str, torch.Tensor]] = None, dropout: float = 0.2,
                  engine: Optional[Engine] = None, device=None, views=None):
-        self.engine = engine if engine is not None else Engine(device=device)
+        eng = _engine(engine, device)
+        super().__init__(self.shapes(eng.cfg.max_pos_emb), state, eng, device, views)
         self.p = float(dropout)
-        self.param_bucket, self.grad_bucket, self.params, self.grads = _buckets(
-            self.shapes(self.engine.cfg.max_pos_emb), state, views, self.engine.device)
-        self._ws: Optional[torch.Tensor] = None
-        self._shape = None
-
-    def _struct(self, tensors) -> AttnParams:
-        s = AttnParams()
-        for key, field in zip(_AT_KEYS, _AT_FIELDS):
-            setattr(s, field, tensors[key].data_ptr())
-        return s
 
     def _workspace(self, N: int, L: int) -> torch.Tensor:
         need = self.engine.lib.cmgan_attn_train_workspace_bytes(self.engine._h, N, L)
         if need == 0:
             raise ValueError(f"unsupported attention shape N={N}, L={L} (L <= 4096)")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.engine.device)
-        return self._ws
+        return self._grow(need)
 
     def mask(self, N: int, L: int, generator: Optional[torch.Generator] = None):
         return dropout_mask((N, L, 64), self.p, self.engine.device, generator)
@@ -448,12 +457,8 @@ class AttentionTrain:
         m = _keep_mask(mask, (N, L, 64), self.p, eng.device, "mask")
         ws = self._workspace(N, L)
         y = torch.empty_like(x)
-        p = self._struct(self.params)
-        scale = 1.0 / (1.0 - self.p) if self.p > 0.0 else 1.0
-        with torch.cuda.device(eng.device):
-            check(eng._h, eng.lib.cmgan_attn_train_forward(eng._h, x.data_ptr(), N, L, ctypes.byref(p),
-                                                           m.data_ptr() if m is not None else None, scale, r,
-                                                           y.data_ptr(), ws.data_ptr(), ws.numel(), eng._stream()))
+        _launch(eng, "cmgan_attn_train_forward", x, N, L, _fill(AttnParams(), _AT_TABLE, self.params), m,
+                self._keep_scale, r, y, ws, ws.numel())
         self._shape = (N, L)
         return y
 
@@ -468,20 +473,12 @@ class AttentionTrain:
         m = _keep_mask(mask, (N, L, 64), self.p, eng.device, "mask")
         ws = self._workspace(N, L)
         dx = torch.empty_like(x)
-        p, g = self._struct(self.params), self._struct(self.grads)
-        scale = 1.0 / (1.0 - self.p) if self.p > 0.0 else 1.0
-        with torch.cuda.device(eng.device):
-            check(eng._h, eng.lib.cmgan_attn_train_backward(eng._h, x.data_ptr(), dy.data_ptr(), N, L, ctypes.byref(p),
-                                                            m.data_ptr() if m is not None else None, scale, r,
-                                                            dx.data_ptr(), ctypes.byref(g), ws.data_ptr(), ws.numel(),
-                                                            eng._stream()))
+        _launch(eng, "cmgan_attn_train_backward", x, dy, N, L, _fill(AttnParams(), _AT_TABLE, self.params), m,
+                self._keep_scale, r, dx, _fill(AttnParams(), _AT_TABLE, self.grads), ws, ws.numel())
         return dx, self.grads
 
-    def allreduce_gradients(self) -> torch.Tensor:
-        return allreduce_mean(self.grad_bucket.flat)
 
-
-class ConformerBlockTrain:
+class ConformerBlockTrain(_TrainModule):
     """`models.conformer.ConformerBlock(dim=64, dim_head=16, heads=4, conv_kernel_size=31, attn_dropout, ff_dropout)`
     in TRAIN mode on the HIP kernels:  x -> ff1(x)+x -> attn(.)+. -> conv(.)+. -> ff2(.)+. -> post_norm
     (conformer.py:216-222).  Dropout layers are explicit keep-masks (`masks()` draws them), BatchNorm1d runs on batch
@@ -490,18 +487,14 @@ class ConformerBlockTrain:
 
     def __init__(self, state: Dict[str, torch.Tensor], attn_dropout: float = 0.2, ff_dropout: float = 0.2,
                  engine: Optional[Engine] = None, device=None, views=None):
-        self.engine = eng = engine if engine is not None else Engine(device=device)
-        self.param_bucket, self.grad_bucket, self.params, self.grads = _buckets(
-            self.shapes(eng.cfg.max_pos_emb), state, views, eng.device)
-
+        eng = _engine(engine, device)
+        super().__init__(self.shapes(eng.cfg.max_pos_emb), state, eng, device, views)     # _ws: the post_norm backward's
         views = lambda prefix: _subviews((self.params, self.grads), prefix)
         self.ff1 = FeedForwardTrain(dropout=ff_dropout, engine=eng, views=views("ff1"))
         self.attn = AttentionTrain(dropout=attn_dropout, engine=eng, views=views("attn"))
-        self.conv = ConvModuleTrain({k[5:]: v for k, v in state.items() if k.startswith("conv.")}, engine=eng,
-                                    views=views("conv"))
+        self.conv = ConvModuleTrain(_substate(state, "conv"), engine=eng, views=views("conv"))
         self.ff2 = FeedForwardTrain(dropout=ff_dropout, engine=eng, views=views("ff2"))
         self._saved = None
-        self._lnws: Optional[torch.Tensor] = None
 
     @staticmethod
     def shapes(max_pos_emb: int = 512) -> Dict[str, tuple]:
@@ -516,12 +509,6 @@ class ConformerBlockTrain:
         b1, b2 = self.ff2.masks(N * L, generator)
         return {"ff1_1": a1, "ff1_2": a2, "attn": at, "ff2_1": b1, "ff2_2": b2}
 
-    def _add(self, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-        eng = self.engine
-        out = torch.empty_like(a)
-        check(eng._h, eng.lib.cmgan_add(eng._h, a.data_ptr(), b.data_ptr(), out.data_ptr(), a.numel(), eng._stream()))
-        return out
-
     def forward(self, x: torch.Tensor, masks: Optional[Dict[str, Optional[torch.Tensor]]] = None,
                 residual: Optional[torch.Tensor] = None) -> torch.Tensor:
         """ConformerBlock(x) [+ residual, fused into the post_norm store: the `+ x` of generator.py:95,97]."""
@@ -535,10 +522,8 @@ class ConformerBlockTrain:
             x3 = self.conv.forward(x2, residual=x2)                                      # last kernel
             x4 = self.ff2.forward(x3, m.get("ff2_1"), m.get("ff2_2"), residual=x3)
             y = torch.empty_like(x4)
-            check(eng._h, eng.lib.cmgan_layernorm_train_forward(eng._h, x4.data_ptr(), x4.numel() // 64,
-                                                                self.params["post_norm.weight"].data_ptr(),
-                                                                self.params["post_norm.bias"].data_ptr(), r,
-                                                                y.data_ptr(), eng._stream()))
+            _launch(eng, "cmgan_layernorm_train_forward", x4, x4.numel() // 64, self.params["post_norm.weight"],
+                    self.params["post_norm.bias"], r, y)
         self._saved = (x0, x1, x2, x3, x4, m)
         return y
 
@@ -550,25 +535,17 @@ class ConformerBlockTrain:
         x0, x1, x2, x3, x4, m = self._saved
         dy = eng._in(dy, "dy")
         M = x4.numel() // 64
-        need = eng.lib.cmgan_layernorm_train_workspace_bytes(eng._h, M)
-        if self._lnws is None or self._lnws.numel() < need:
-            self._lnws = torch.empty(need, dtype=torch.uint8, device=eng.device)
+        ws = self._grow(eng.lib.cmgan_layernorm_train_workspace_bytes(eng._h, M))
         with torch.cuda.device(eng.device):
             d4 = torch.empty_like(x4)
-            check(eng._h, eng.lib.cmgan_layernorm_train_backward(
-                eng._h, x4.data_ptr(), dy.data_ptr(), M, self.params["post_norm.weight"].data_ptr(),
-                self.params["post_norm.bias"].data_ptr(), d4.data_ptr(), self.grads["post_norm.weight"].data_ptr(),
-                self.grads["post_norm.bias"].data_ptr(), self._lnws.data_ptr(), self._lnws.numel(), eng._stream()))
+            _launch(eng, "cmgan_layernorm_train_backward", x4, dy, M, self.params["post_norm.weight"],
+                    self.params["post_norm.bias"], d4, self.grads["post_norm.weight"], self.grads["post_norm.bias"], ws,
+                    ws.numel())
             d3 = self.ff2.backward(x3, d4, m.get("ff2_1"), m.get("ff2_2"), dresidual=d4)[0]
             d2 = self.conv.backward(x2, d3, dresidual=d3)[0]
             d1 = self.attn.backward(x1, d2, m.get("attn"), dresidual=d2)[0]
             d0 = self.ff1.backward(x0, d1, m.get("ff1_1"), m.get("ff1_2"), dresidual=d1)[0]
         return d0, self.grads
-
-    def allreduce_gradients(self) -> torch.Tensor:
-        if self.grad_bucket is None:
-            raise RuntimeError("this module's gradients are views of its parent's bucket: all-reduce the parent")
-        return allreduce_mean(self.grad_bucket.flat)
 
 
 class TSCBTrain:
@@ -578,11 +555,10 @@ class TSCBTrain:
     `freq_conformer.*`)."""
 
     def __init__(self, state: Dict[str, torch.Tensor], engine: Optional[Engine] = None, device=None, views=None):
-        self.engine = eng = engine if engine is not None else Engine(device=device)
-        sub = lambda p: {k[len(p) + 1:]: v for k, v in state.items() if k.startswith(p + ".")}
+        self.engine = eng = _engine(engine, device)
         vw = lambda p: None if views is None else _subviews(views, p)
-        self.time = ConformerBlockTrain(sub("time_conformer"), engine=eng, views=vw("time_conformer"))
-        self.freq = ConformerBlockTrain(sub("freq_conformer"), engine=eng, views=vw("freq_conformer"))
+        self.time = ConformerBlockTrain(_substate(state, "time_conformer"), engine=eng, views=vw("time_conformer"))
+        self.freq = ConformerBlockTrain(_substate(state, "freq_conformer"), engine=eng, views=vw("freq_conformer"))
         self._shape = None
 
     @staticmethod
@@ -597,8 +573,7 @@ class TSCBTrain:
         """[B, A, C, 64] -> [B, C, A, 64] of x (+ add, same layout as x: a residual riding on the flip)."""
         eng = self.engine
         out = torch.empty(B, C, A, 64, dtype=torch.float32, device=x.device)
-        check(eng._h, eng.lib.cmgan_swap_axes(eng._h, x.data_ptr(), add.data_ptr() if add is not None else None,
-                                              out.data_ptr(), B, A, C, eng._stream()))
+        _launch(eng, "cmgan_swap_axes", x, add, out, B, A, C)
         return out
 
     def forward(self, x: torch.Tensor, masks_time=None, masks_freq=None) -> torch.Tensor:
@@ -627,7 +602,17 @@ class TSCBTrain:
             return self._swap(self.time.backward(dxt2)[0], B, F2, T, add=dxt2)
 
 
-class DenseBlockTrain:
+_DENSE_TABLE = tuple((f"{m}{i + 1}.{w}", (f"{m}_{w}", i)) for i in range(4)
+                     for m, w in (("conv", "weight"), ("conv", "bias"), ("norm", "weight"), ("norm", "bias"),
+                                  ("prelu", "weight")))
+
+
+def _dense_struct(tensors, prefix: str = "") -> DenseParams:
+    """The pointers of one DilatedDenseNet, its keys under `prefix` (the encoder's and the decoders' sub-struct)."""
+    return _fill(DenseParams(), _DENSE_TABLE, tensors, prefix)
+
+
+class DenseBlockTrain(_TrainModule):
     """`models.generator.DilatedDenseNet(depth=4, in_channels=64)` (generator.py:6-47) in train mode on the HIP kernels.
     Activations are channels-last `[B, T, F, 64]`.  `state` = the block's tensors under the reference's key names
     (`conv1.weight` ... `prelu4.weight`), e.g. the `dense_encoder.dilated_dense.` slice of the generator state_dict."""
@@ -639,27 +624,10 @@ class DenseBlockTrain:
 
     def __init__(self, state: Optional[Dict[str, torch.Tensor]] = None, engine: Optional[Engine] = None, device=None,
                  views=None):
-        self.engine = engine if engine is not None else Engine(device=device)
-        self.param_bucket, self.grad_bucket, self.params, self.grads = _buckets(self.SHAPES, state, views,
-                                                                                self.engine.device)
-        self._ws: Optional[torch.Tensor] = None
-        self._shape = None
-
-    def _struct(self, tensors) -> DenseParams:
-        s = DenseParams()
-        for i in range(4):
-            s.conv_weight[i] = tensors[f"conv{i + 1}.weight"].data_ptr()
-            s.conv_bias[i] = tensors[f"conv{i + 1}.bias"].data_ptr()
-            s.norm_weight[i] = tensors[f"norm{i + 1}.weight"].data_ptr()
-            s.norm_bias[i] = tensors[f"norm{i + 1}.bias"].data_ptr()
-            s.prelu_weight[i] = tensors[f"prelu{i + 1}.weight"].data_ptr()
-        return s
+        super().__init__(self.SHAPES, state, engine, device, views)
 
     def _workspace(self, B: int, T: int, F: int) -> torch.Tensor:
-        need = self.engine.lib.cmgan_dense_train_workspace_bytes(self.engine._h, B, T, F)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.engine.device)
-        return self._ws
+        return self._grow(self.engine.lib.cmgan_dense_train_workspace_bytes(self.engine._h, B, T, F))
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         eng = self.engine
@@ -669,10 +637,7 @@ class DenseBlockTrain:
             raise ValueError("expected channels-last [B, T, F, 64]")
         ws = self._workspace(B, T, F)
         y = torch.empty_like(x)
-        p = self._struct(self.params)
-        with torch.cuda.device(eng.device):
-            check(eng._h, eng.lib.cmgan_dense_train_forward(eng._h, x.data_ptr(), B, T, F, ctypes.byref(p), y.data_ptr(),
-                                                            ws.data_ptr(), ws.numel(), eng._stream()))
+        _launch(eng, "cmgan_dense_train_forward", x, B, T, F, _dense_struct(self.params), y, ws, ws.numel())
         self._shape = (B, T, F)
         return y
 
@@ -684,51 +649,23 @@ class DenseBlockTrain:
             raise RuntimeError("backward() needs the forward() of the same [B, T, F, 64] input first")
         ws = self._workspace(B, T, F)
         dx = torch.empty_like(x)
-        p, g = self._struct(self.params), self._struct(self.grads)
-        with torch.cuda.device(eng.device):
-            check(eng._h, eng.lib.cmgan_dense_train_backward(eng._h, x.data_ptr(), dy.data_ptr(), B, T, F, ctypes.byref(p),
-                                                             dx.data_ptr(), ctypes.byref(g), ws.data_ptr(), ws.numel(),
-                                                             eng._stream()))
+        _launch(eng, "cmgan_dense_train_backward", x, dy, B, T, F, _dense_struct(self.params), dx,
+                _dense_struct(self.grads), ws, ws.numel())
         return dx, self.grads
 
-    def allreduce_gradients(self) -> torch.Tensor:
-        if self.grad_bucket is None:
-            raise RuntimeError("this module's gradients are views of its parent's bucket: all-reduce the parent")
-        return allreduce_mean(self.grad_bucket.flat)
+
+_ENC_TABLE = tuple((f"conv_{i}.{j}.{w}", f"{m}{i}_{w}") for i in (1, 2)
+                   for j, m, w in ((0, "conv", "weight"), (0, "conv", "bias"), (1, "norm", "weight"),
+                                   (1, "norm", "bias"), (2, "prelu", "weight")))
 
 
-def _dense_struct(tensors, prefix: str) -> DenseParams:
-    s = DenseParams()
-    for i in range(4):
-        s.conv_weight[i] = tensors[f"{prefix}conv{i + 1}.weight"].data_ptr()
-        s.conv_bias[i] = tensors[f"{prefix}conv{i + 1}.bias"].data_ptr()
-        s.norm_weight[i] = tensors[f"{prefix}norm{i + 1}.weight"].data_ptr()
-        s.norm_bias[i] = tensors[f"{prefix}norm{i + 1}.bias"].data_ptr()
-        s.prelu_weight[i] = tensors[f"{prefix}prelu{i + 1}.weight"].data_ptr()
+def _encoder_struct(t) -> EncoderParams:
+    s = _fill(EncoderParams(), _ENC_TABLE, t)
+    s.dense = _dense_struct(t, "dilated_dense.")
     return s
 
 
-class _WsModule:
-    """Common plumbing of the encoder / decoder wrappers: buckets (own or views) and a grow-only workspace."""
-
-    def __init__(self, shapes, state, engine, device, views):
-        self.engine = engine if engine is not None else Engine(device=device)
-        self.param_bucket, self.grad_bucket, self.params, self.grads = _buckets(shapes, state, views, self.engine.device)
-        self._ws: Optional[torch.Tensor] = None
-        self._shape = None
-
-    def _grow(self, need: int) -> torch.Tensor:
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.engine.device)
-        return self._ws
-
-    def allreduce_gradients(self) -> torch.Tensor:
-        if self.grad_bucket is None:
-            raise RuntimeError("this module's gradients are views of its parent's bucket: all-reduce the parent")
-        return allreduce_mean(self.grad_bucket.flat)
-
-
-class DenseEncoderTrain(_WsModule):
+class DenseEncoderTrain(_TrainModule):
     """`models.generator.DenseEncoder(in_channel=3, channels=64)` (generator.py:50-69) in train mode on the HIP
     kernels.  Input `[B, T, F, 3]` channels-last (|spec|, re, im), output `[B, T, F', 64]`, F' = (F - 1) // 2 + 1.
     `state`: the `dense_encoder.` slice of the generator state_dict.  The input carries no gradient."""
@@ -742,17 +679,6 @@ class DenseEncoderTrain(_WsModule):
     def __init__(self, state=None, engine: Optional[Engine] = None, device=None, views=None):
         super().__init__(self.SHAPES, state, engine, device, views)
 
-    def _struct(self, t) -> EncoderParams:
-        s = EncoderParams()
-        for i, pre in ((1, "conv_1"), (2, "conv_2")):
-            setattr(s, f"conv{i}_weight", t[pre + ".0.weight"].data_ptr())
-            setattr(s, f"conv{i}_bias", t[pre + ".0.bias"].data_ptr())
-            setattr(s, f"norm{i}_weight", t[pre + ".1.weight"].data_ptr())
-            setattr(s, f"norm{i}_bias", t[pre + ".1.bias"].data_ptr())
-            setattr(s, f"prelu{i}_weight", t[pre + ".2.weight"].data_ptr())
-        s.dense = _dense_struct(t, "dilated_dense.")
-        return s
-
     def forward(self, xin: torch.Tensor) -> torch.Tensor:
         eng = self.engine
         xin = eng._in(xin, "xin")
@@ -761,10 +687,7 @@ class DenseEncoderTrain(_WsModule):
             raise ValueError("expected channels-last [B, T, F, 3]")
         ws = self._grow(eng.lib.cmgan_encoder_train_workspace_bytes(eng._h, B, T, F))
         y = torch.empty(B, T, (F - 1) // 2 + 1, 64, dtype=torch.float32, device=eng.device)
-        p = self._struct(self.params)
-        with torch.cuda.device(eng.device):
-            check(eng._h, eng.lib.cmgan_encoder_train_forward(eng._h, xin.data_ptr(), B, T, F, ctypes.byref(p), y.data_ptr(),
-                                                              ws.data_ptr(), ws.numel(), eng._stream()))
+        _launch(eng, "cmgan_encoder_train_forward", xin, B, T, F, _encoder_struct(self.params), y, ws, ws.numel())
         self._shape = (B, T, F)
         self._xin = xin
         return y
@@ -777,15 +700,27 @@ class DenseEncoderTrain(_WsModule):
         dy = eng._in(dy, "dy")
         if tuple(dy.shape) != (B, T, (F - 1) // 2 + 1, 64):
             raise ValueError("dy does not match the forward() output")
-        p, g = self._struct(self.params), self._struct(self.grads)
-        with torch.cuda.device(eng.device):
-            check(eng._h, eng.lib.cmgan_encoder_train_backward(eng._h, self._xin.data_ptr(), dy.data_ptr(), B, T, F,
-                                                               ctypes.byref(p), ctypes.byref(g), self._ws.data_ptr(),
-                                                               self._ws.numel(), eng._stream()))
+        _launch(eng, "cmgan_encoder_train_backward", self._xin, dy, B, T, F, _encoder_struct(self.params),
+                _encoder_struct(self.grads), self._ws, self._ws.numel())
         return self.grads
 
 
-class DecoderTrain(_WsModule):
+_DEC_COMMON = (("sub_pixel.conv.weight", "sub_pixel_weight"), ("sub_pixel.conv.bias", "sub_pixel_bias"),
+               ("norm.weight", "norm_weight"), ("norm.bias", "norm_bias"), ("prelu.weight", "prelu_weight"))
+# the complex decoder has no final conv and no output PReLU: final_* and prelu_out_weight stay null
+_DEC_TABLES = {"mask": _DEC_COMMON + (("conv_1.weight", "conv_weight"), ("conv_1.bias", "conv_bias"),
+                                      ("final_conv.weight", "final_weight"), ("final_conv.bias", "final_bias"),
+                                      ("prelu_out.weight", "prelu_out_weight")),
+               "complex": _DEC_COMMON + (("conv.weight", "conv_weight"), ("conv.bias", "conv_bias"))}
+
+
+def _decoder_struct(t, kind: str) -> DecoderParams:
+    s = _fill(DecoderParams(), _DEC_TABLES[kind], t)
+    s.dense = _dense_struct(t, "dense_block.")
+    return s
+
+
+class DecoderTrain(_TrainModule):
     """`MaskDecoder(num_features)` (kind "mask", generator.py:121-138) or `ComplexDecoder()` (kind "complex",
     generator.py:141-156) in train mode on the HIP kernels.  Input `[B, T, F', 64]` channels-last; output `[B, T, F]`
     (mask) or `[B, T, F, 2]` (complex), F = 2 F' - 1.  `state`: the `mask_decoder.` / `complex_decoder.` slice."""
@@ -809,24 +744,10 @@ class DecoderTrain(_WsModule):
                  device=None, views=None):
         if kind not in self.KINDS:
             raise ValueError("kind must be 'mask' or 'complex'")
-        eng = engine if engine is not None else Engine(device=device)
+        eng = _engine(engine, device)
         self.kind = kind
         self.num_features = int(num_features if num_features is not None else eng.cfg.num_features)
         super().__init__(self.shapes(kind, self.num_features), state, eng, device, views)
-
-    def _struct(self, t) -> DecoderParams:
-        s = DecoderParams()
-        s.dense = _dense_struct(t, "dense_block.")
-        s.sub_pixel_weight = t["sub_pixel.conv.weight"].data_ptr()
-        s.sub_pixel_bias = t["sub_pixel.conv.bias"].data_ptr()
-        conv = "conv_1" if self.kind == "mask" else "conv"
-        s.conv_weight, s.conv_bias = t[conv + ".weight"].data_ptr(), t[conv + ".bias"].data_ptr()
-        s.norm_weight, s.norm_bias = t["norm.weight"].data_ptr(), t["norm.bias"].data_ptr()
-        s.prelu_weight = t["prelu.weight"].data_ptr()
-        if self.kind == "mask":
-            s.final_weight, s.final_bias = t["final_conv.weight"].data_ptr(), t["final_conv.bias"].data_ptr()
-            s.prelu_out_weight = t["prelu_out.weight"].data_ptr()
-        return s
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         eng = self.engine
@@ -839,11 +760,8 @@ class DecoderTrain(_WsModule):
             raise ValueError(f"2 F' - 1 = {F} does not match num_features = {self.num_features} (prelu_out)")
         ws = self._grow(eng.lib.cmgan_decoder_train_workspace_bytes(eng._h, B, T, Fe))
         out = torch.empty((B, T, F) if self.kind == "mask" else (B, T, F, 2), dtype=torch.float32, device=eng.device)
-        p = self._struct(self.params)
-        with torch.cuda.device(eng.device):
-            check(eng._h, eng.lib.cmgan_decoder_train_forward(eng._h, self.KINDS[self.kind], x.data_ptr(), B, T, Fe,
-                                                              ctypes.byref(p), out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                              eng._stream()))
+        _launch(eng, "cmgan_decoder_train_forward", self.KINDS[self.kind], x, B, T, Fe,
+                _decoder_struct(self.params, self.kind), out, ws, ws.numel())
         self._shape = (B, T, Fe)
         self._x = x
         return out
@@ -858,16 +776,13 @@ class DecoderTrain(_WsModule):
         if tuple(dout.shape) != ((B, T, F) if self.kind == "mask" else (B, T, F, 2)):
             raise ValueError("dout does not match the forward() output")
         dx = torch.empty_like(self._x)
-        p, g = self._struct(self.params), self._struct(self.grads)
-        with torch.cuda.device(eng.device):
-            check(eng._h, eng.lib.cmgan_decoder_train_backward(eng._h, self.KINDS[self.kind], self._x.data_ptr(),
-                                                               dout.data_ptr(), B, T, Fe, ctypes.byref(p), dx.data_ptr(),
-                                                               ctypes.byref(g), self._ws.data_ptr(), self._ws.numel(),
-                                                               eng._stream()))
+        _launch(eng, "cmgan_decoder_train_backward", self.KINDS[self.kind], self._x, dout, B, T, Fe,
+                _decoder_struct(self.params, self.kind), dx, _decoder_struct(self.grads, self.kind), self._ws,
+                self._ws.numel())
         return dx, self.grads
 
 
-class GeneratorTrain:
+class GeneratorTrain(_TrainModule):
     """`models.generator.TSCNet(num_channel=64, num_features)` (generator.py:159-201) in TRAIN mode on the HIP kernels.
 
     `state` is the reference generator state_dict.  Every learnable tensor (`named_parameters()` of the reference
@@ -879,7 +794,7 @@ class GeneratorTrain:
     BLOCKS = ("TSCB_1", "TSCB_2", "TSCB_3", "TSCB_4")
 
     def __init__(self, state: Dict[str, torch.Tensor], engine: Optional[Engine] = None, device=None):
-        self.engine = eng = engine if engine is not None else Engine(device=device)
+        eng = _engine(engine, device)
         F = eng.cfg.num_features
         shapes: Dict[str, tuple] = {}
         shapes.update({f"dense_encoder.{k}": v for k, v in DenseEncoderTrain.SHAPES.items()})
@@ -887,11 +802,10 @@ class GeneratorTrain:
             shapes.update({f"{b}.{k}": v for k, v in TSCBTrain.shapes(eng.cfg.max_pos_emb).items()})
         shapes.update({f"mask_decoder.{k}": v for k, v in DecoderTrain.shapes("mask", F).items()})
         shapes.update({f"complex_decoder.{k}": v for k, v in DecoderTrain.shapes("complex", F).items()})
-        self.param_bucket, self.grad_bucket, self.params, self.grads = _buckets(shapes, state, None, eng.device)
+        super().__init__(shapes, state, eng, device)
         views = (self.params, self.grads)
-        sub = lambda p: {k[len(p) + 1:]: v for k, v in state.items() if k.startswith(p + ".")}
         self.dense_encoder = DenseEncoderTrain(engine=eng, views=_subviews(views, "dense_encoder"))
-        self.blocks = [TSCBTrain(sub(b), engine=eng, views=_subviews(views, b)) for b in self.BLOCKS]
+        self.blocks = [TSCBTrain(_substate(state, b), engine=eng, views=_subviews(views, b)) for b in self.BLOCKS]
         self.mask_decoder = DecoderTrain("mask", engine=eng, views=_subviews(views, "mask_decoder"))
         self.complex_decoder = DecoderTrain("complex", engine=eng, views=_subviews(views, "complex_decoder"))
         self._saved = None
@@ -907,9 +821,7 @@ class GeneratorTrain:
         state = self.mask_rng_state(generator)
         n16 = (nbytes + 15) // 16 * 16
         buf = torch.empty(n16, dtype=torch.uint8, device=eng.device)
-        with torch.cuda.device(eng.device):              # (like every other native call: the launch goes to eng's device)
-            check(eng._h, eng.lib.cmgan_dropout_masks(eng._h, buf.data_ptr(), n16, 1.0 - p, state.data_ptr(),
-                                                      eng._stream()))
+        _launch(eng, "cmgan_dropout_masks", buf, n16, 1.0 - p, state)
         return buf[:nbytes]
 
     def mask_rng_state(self, generator: Optional[torch.Generator] = None) -> torch.Tensor:
@@ -974,7 +886,7 @@ class GeneratorTrain:
             raise ValueError(f"expected [B, 2, T, {eng.cfg.num_features}]")
         with torch.cuda.device(eng.device):
             xin = torch.empty(B, T, F, 3, dtype=torch.float32, device=eng.device)
-            check(eng._h, eng.lib.cmgan_tscnet_prologue(eng._h, spec.data_ptr(), B, T, xin.data_ptr(), eng._stream()))
+            _launch(eng, "cmgan_tscnet_prologue", spec, B, T, xin)
             x = self.dense_encoder.forward(xin)                                     # generator.py:181
             for i, blk in enumerate(self.blocks):                                   # :182-185
                 mt, mf = masks[i] if masks is not None else (None, None)
@@ -983,9 +895,7 @@ class GeneratorTrain:
             cplx = self.complex_decoder.forward(x)                                  # :190
             est_real = torch.empty(B, 1, T, F, dtype=torch.float32, device=eng.device)
             est_imag = torch.empty_like(est_real)
-            check(eng._h, eng.lib.cmgan_tscnet_epilogue_forward(eng._h, spec.data_ptr(), mask.data_ptr(), cplx.data_ptr(),
-                                                                B, T, est_real.data_ptr(), est_imag.data_ptr(),
-                                                                eng._stream()))    # :188-199
+            _launch(eng, "cmgan_tscnet_epilogue_forward", spec, mask, cplx, B, T, est_real, est_imag)    # :188-199
         self._saved = (spec, B, T, F)
         return est_real, est_imag
 
@@ -1001,12 +911,10 @@ class GeneratorTrain:
         with torch.cuda.device(eng.device):
             dmask = torch.empty(B, T, F, dtype=torch.float32, device=eng.device)
             dcplx = torch.empty(B, T, F, 2, dtype=torch.float32, device=eng.device)
-            check(eng._h, eng.lib.cmgan_tscnet_epilogue_backward(eng._h, spec.data_ptr(), d_real.data_ptr(),
-                                                                 d_imag.data_ptr(), B, T, dmask.data_ptr(),
-                                                                 dcplx.data_ptr(), eng._stream()))
+            _launch(eng, "cmgan_tscnet_epilogue_backward", spec, d_real, d_imag, B, T, dmask, dcplx)
             dx_m, _ = self.mask_decoder.backward(dmask)
             dx_c, _ = self.complex_decoder.backward(dcplx)
-            dx = self.blocks[0].time._add(dx_m, dx_c)
+            dx = _add(eng, dx_m, dx_c)
             for blk in reversed(self.blocks):
                 dx = blk.backward(dx)
             self.dense_encoder.backward(dx)
@@ -1022,9 +930,6 @@ class GeneratorTrain:
                 out[f"{name}.{ax}.conv.net.5.num_batches_tracked"] = torch.tensor(
                     conf.conv.num_batches_tracked, dtype=torch.int64)
         return out
-
-    def allreduce_gradients(self) -> torch.Tensor:
-        return allreduce_mean(self.grad_bucket.flat)
 
 
 def generator_train_step(gen: GeneratorTrain, optimizer: "AdamW", clean: torch.Tensor, noisy: torch.Tensor,
@@ -1051,11 +956,8 @@ def generator_train_step(gen: GeneratorTrain, optimizer: "AdamW", clean: torch.T
     clean_cut = clean[:, :La].contiguous()                      # train.py:187: the time term sees the RAW clean batch
     loss, terms = generator_loss_terms(eng, est_real, est_imag, clean_spec, est_audio, clean_cut, loss_weights)
     d_real, d_imag = torch.empty_like(est_real), torch.empty_like(est_imag)
-    with torch.cuda.device(eng.device):
-        check(eng._h, eng.lib.cmgan_loss_backward(eng._h, est_real.data_ptr(), est_imag.data_ptr(), clean_spec.data_ptr(),
-                                                  B, T, est_audio.data_ptr(), clean_cut.data_ptr(),
-                                                  float(loss_weights[0]), float(loss_weights[1]), float(loss_weights[2]),
-                                                  d_real.data_ptr(), d_imag.data_ptr(), eng._stream()))
+    _launch(eng, "cmgan_loss_backward", est_real, est_imag, clean_spec, B, T, est_audio, clean_cut, float(loss_weights[0]),
+            float(loss_weights[1]), float(loss_weights[2]), d_real, d_imag)
     gen.backward(d_real, d_imag)                                # train.py:190 (loss.backward())
     if update:                                                  # False: stop after the backward (GraphedTrainStep)
         gen.allreduce_gradients()                               # DDP's gradient mean, one collective
@@ -1064,9 +966,24 @@ def generator_train_step(gen: GeneratorTrain, optimizer: "AdamW", clean: torch.T
 
 
 _DISC_CH = (2, 16, 32, 64, 128)
+_DISC_TABLE = (tuple(kf for i in range(4) for kf in ((f"layers.{3 * i}.weight_orig", ("conv_weight_orig", i)),
+                                                     (f"layers.{3 * i + 1}.weight", ("norm_weight", i)),
+                                                     (f"layers.{3 * i + 1}.bias", ("norm_bias", i)),
+                                                     (f"layers.{3 * i + 2}.weight", ("prelu_weight", i))))
+               + (("layers.14.weight_orig", "fc1_weight_orig"), ("layers.14.bias", "fc1_bias"),
+                  ("layers.16.weight", "prelu5_weight"), ("layers.17.weight_orig", "fc2_weight_orig"),
+                  ("layers.17.bias", "fc2_bias"), ("layers.18.slope", "slope")))
+# the power-iteration vectors: buffers, so a gradient struct leaves these fields null
+_DISC_BUFFERS = (tuple((f"layers.{3 * i}.weight_{s}", (f"conv_{s}", i)) for i in range(4) for s in "uv")
+                 + tuple((f"layers.{l}.weight_{s}", f"fc{n}_{s}") for n, l in ((1, 14), (2, 17)) for s in "uv"))
 
 
-class DiscriminatorTrain:
+def _disc_struct(t, buffers=None) -> DiscParams:
+    s = _fill(DiscParams(), _DISC_TABLE, t)
+    return s if buffers is None else _fill(s, _DISC_BUFFERS, buffers)
+
+
+class DiscriminatorTrain(_TrainModule):
     """`models.discriminator.Discriminator(ndf=16)` (discriminator.py:29-64) on the HIP kernels of csrc/disc.hip.
 
     `state` is the module's state_dict (34 entries: `layers.N.weight_orig / weight_u / weight_v` of the six spectral
@@ -1091,35 +1008,16 @@ class DiscriminatorTrain:
 
     def __init__(self, state: Dict[str, torch.Tensor], engine: Optional[Engine] = None, device=None, dropout: float = 0.3,
                  slots: int = 2):
-        self.engine = eng = engine if engine is not None else Engine(device=device)
+        super().__init__(self.shapes(), state, engine, device)
+        eng = self.engine
         self.dropout = float(dropout)
-        self.param_bucket, self.grad_bucket, self.params, self.grads = _buckets(self.shapes(), state, None, eng.device)
         self._scratch = FlatBucket(self.shapes(), eng.device)          # second graph's gradients before accumulation
         self.buffers = {}
         for p in self._SN:
             for s in ("weight_u", "weight_v"):
                 self.buffers[f"{p}.{s}"] = state[f"{p}.{s}"].detach().to(eng.device, torch.float32).clone().contiguous()
-        self._ws = [None] * slots
+        self._ws = [None] * slots                                      # one workspace per slot, None until its first forward
         self._saved = [None] * slots
-
-    def _struct(self, t, with_buffers: bool = True) -> DiscParams:
-        s = DiscParams()
-        for i in range(4):
-            s.conv_weight_orig[i] = t[f"layers.{3 * i}.weight_orig"].data_ptr()
-            s.norm_weight[i] = t[f"layers.{3 * i + 1}.weight"].data_ptr()
-            s.norm_bias[i] = t[f"layers.{3 * i + 1}.bias"].data_ptr()
-            s.prelu_weight[i] = t[f"layers.{3 * i + 2}.weight"].data_ptr()
-            if with_buffers:
-                s.conv_u[i] = self.buffers[f"layers.{3 * i}.weight_u"].data_ptr()
-                s.conv_v[i] = self.buffers[f"layers.{3 * i}.weight_v"].data_ptr()
-        s.fc1_weight_orig, s.fc1_bias = t["layers.14.weight_orig"].data_ptr(), t["layers.14.bias"].data_ptr()
-        s.prelu5_weight = t["layers.16.weight"].data_ptr()
-        s.fc2_weight_orig, s.fc2_bias = t["layers.17.weight_orig"].data_ptr(), t["layers.17.bias"].data_ptr()
-        s.slope = t["layers.18.slope"].data_ptr()
-        if with_buffers:
-            s.fc1_u, s.fc1_v = self.buffers["layers.14.weight_u"].data_ptr(), self.buffers["layers.14.weight_v"].data_ptr()
-            s.fc2_u, s.fc2_v = self.buffers["layers.17.weight_u"].data_ptr(), self.buffers["layers.17.weight_v"].data_ptr()
-        return s
 
     def mask(self, B: int, generator: Optional[torch.Generator] = None) -> Optional[torch.Tensor]:
         """Float keep-mask [B, 64] (0 or 1 / 0.7) of the Dropout(0.3): 256 bytes per clip, not worth a byte form."""
@@ -1133,10 +1031,9 @@ class DiscriminatorTrain:
         clean_spec = eng._in(clean_spec, "clean_spec")
         B, _, T, F = clean_spec.shape
         xy = torch.empty(B, T, F, 2, dtype=torch.float32, device=eng.device)
-        er = eng._in(est_real, "est_real").data_ptr() if est_real is not None else None
-        ei = eng._in(est_imag, "est_imag").data_ptr() if est_imag is not None else None
-        with torch.cuda.device(eng.device):
-            check(eng._h, eng.lib.cmgan_mag_pair(eng._h, clean_spec.data_ptr(), er, ei, B, T, xy.data_ptr(), eng._stream()))
+        er = eng._in(est_real, "est_real") if est_real is not None else None
+        ei = eng._in(est_imag, "est_imag") if est_imag is not None else None
+        _launch(eng, "cmgan_mag_pair", clean_spec, er, ei, B, T, xy)
         return xy
 
     def forward(self, xy: torch.Tensor, mask: Optional[torch.Tensor] = None, train: bool = True, slot: int = 0) -> torch.Tensor:
@@ -1148,18 +1045,13 @@ class DiscriminatorTrain:
         need = eng.lib.cmgan_disc_workspace_bytes(eng._h, B, T)
         if need == 0:
             raise ValueError("the discriminator needs T >= 16 frames and F >= 16 bins")
-        if self._ws[slot] is None or self._ws[slot].numel() < need:
-            self._ws[slot] = torch.empty(need, dtype=torch.uint8, device=eng.device)
-        ws = self._ws[slot]
+        ws = self._ws[slot] = _grown(self._ws[slot], need, eng.device)
         score = torch.empty(B, dtype=torch.float32, device=eng.device)
         mask = eng._in(mask, "mask") if mask is not None else None        # float32, contiguous; kept for the backward
         if mask is not None and tuple(mask.shape) != (B, 64):
             raise ValueError(f"mask must be [B, 64] = [{B}, 64]")
-        mp = mask.data_ptr() if mask is not None else None
-        p = self._struct(self.params)
-        with torch.cuda.device(eng.device):
-            check(eng._h, eng.lib.cmgan_disc_forward(eng._h, xy.data_ptr(), B, T, ctypes.byref(p), mp, 1 if train else 0,
-                                                     score.data_ptr(), ws.data_ptr(), ws.numel(), eng._stream()))
+        _launch(eng, "cmgan_disc_forward", xy, B, T, _disc_struct(self.params, self.buffers), mask, 1 if train else 0,
+                score, ws, ws.numel())
         self._saved[slot] = (xy, mask, B, T)
         return score
 
@@ -1174,16 +1066,11 @@ class DiscriminatorTrain:
         dscore = eng._in(dscore, "dscore")
         dxy = torch.empty_like(xy) if need_input_grad else None
         target = self._scratch.views if accumulate else self.grads
-        p, g = self._struct(self.params), self._struct(target, with_buffers=False)
-        mp = mask.data_ptr() if mask is not None else None
         ws = self._ws[slot]
-        with torch.cuda.device(eng.device):
-            check(eng._h, eng.lib.cmgan_disc_backward(eng._h, xy.data_ptr(), dscore.data_ptr(), B, T, ctypes.byref(p), mp,
-                                                      dxy.data_ptr() if dxy is not None else None, ctypes.byref(g),
-                                                      ws.data_ptr(), ws.numel(), eng._stream()))
-            if accumulate:
-                gf, sf = self.grad_bucket.flat, self._scratch.flat
-                check(eng._h, eng.lib.cmgan_add(eng._h, gf.data_ptr(), sf.data_ptr(), gf.data_ptr(), gf.numel(), eng._stream()))
+        _launch(eng, "cmgan_disc_backward", xy, dscore, B, T, _disc_struct(self.params, self.buffers), mask, dxy,
+                _disc_struct(target), ws, ws.numel())
+        if accumulate:
+            _add(eng, self.grad_bucket.flat, self._scratch.flat, out=self.grad_bucket.flat)
         return dxy
 
     def score_mse(self, score: torch.Tensor, target: Optional[torch.Tensor] = None, scale: float = 1.0):
@@ -1192,19 +1079,14 @@ class DiscriminatorTrain:
         B = score.numel()
         loss = torch.empty(1, dtype=torch.float32, device=eng.device)
         dscore = torch.empty(B, dtype=torch.float32, device=eng.device)
-        tp = eng._in(target, "target").data_ptr() if target is not None else None
-        with torch.cuda.device(eng.device):
-            check(eng._h, eng.lib.cmgan_score_mse(eng._h, score.data_ptr(), tp, B, float(scale), loss.data_ptr(),
-                                                  dscore.data_ptr(), eng._stream()))
+        target = eng._in(target, "target") if target is not None else None
+        _launch(eng, "cmgan_score_mse", score, target, B, float(scale), loss, dscore)
         return loss[0], dscore
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         out = {k: v.detach().clone() for k, v in self.params.items()}
         out.update({k: v.clone() for k, v in self.buffers.items()})
         return out
-
-    def allreduce_gradients(self) -> torch.Tensor:
-        return allreduce_mean(self.grad_bucket.flat)
 
 
 def _adversarial_generator_half(gen: GeneratorTrain, disc: DiscriminatorTrain, clean: torch.Tensor, noisy: torch.Tensor,
@@ -1235,14 +1117,10 @@ def _adversarial_generator_half(gen: GeneratorTrain, disc: DiscriminatorTrain, c
     gan, dscore = disc.score_mse(score, None, scale=float(loss_weights[3]))    # train.py:129-131
     loss = base + float(loss_weights[3]) * gan
     d_real, d_imag = torch.empty_like(est_real), torch.empty_like(est_imag)
-    with torch.cuda.device(eng.device):
-        check(eng._h, eng.lib.cmgan_loss_backward(eng._h, est_real.data_ptr(), est_imag.data_ptr(), clean_spec.data_ptr(),
-                                                  B, T, est_audio.data_ptr(), clean_cut.data_ptr(),
-                                                  float(loss_weights[0]), float(loss_weights[1]), float(loss_weights[2]),
-                                                  d_real.data_ptr(), d_imag.data_ptr(), eng._stream()))
-        dxy = disc.backward(dscore, slot=0, need_input_grad=True)
-        check(eng._h, eng.lib.cmgan_mag_pair_backward(eng._h, est_real.data_ptr(), est_imag.data_ptr(), dxy.data_ptr(), B, T,
-                                                      1.0, d_real.data_ptr(), d_imag.data_ptr(), eng._stream()))
+    _launch(eng, "cmgan_loss_backward", est_real, est_imag, clean_spec, B, T, est_audio, clean_cut, float(loss_weights[0]),
+            float(loss_weights[1]), float(loss_weights[2]), d_real, d_imag)
+    dxy = disc.backward(dscore, slot=0, need_input_grad=True)
+    _launch(eng, "cmgan_mag_pair_backward", est_real, est_imag, dxy, B, T, 1.0, d_real, d_imag)
     gen.backward(d_real, d_imag)                                              # train.py:190
     ctx = dict(xy=xy, clean_spec=clean_spec, est_audio=est_audio, clean_cut=clean_cut, disc_masks=disc_masks)
     return loss, terms, gan, ctx
