@@ -123,6 +123,58 @@ def check_mix_args(device, clean, noise_bank, noise_start, noise_len, noise_off,
     return B, L, R, Kmax
 
 
+RIR_MAX_TAPS = 65536          # longest response of cmgan_rir (= MIX_MAX_TAPS: its output is a bank of cmgan_mix)
+RIR_MAX_IMAGES = 255          # largest image index per axis
+RIR_MAX_TW = 64               # largest half-width of the fractional-delay filter
+
+
+def check_rir_args(device, rooms, n_taps, K, n_images, fs=16000, c: float = 343.0, tw: int = 40, out=None):
+    """Argument rules of Engine.rir (shapes, dtypes, devices and host scalars; pure host code).  Returns (R, K, (Nx, Ny, Nz))."""
+    def need(t, name, dtype, shape_txt, ok):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: expected a torch.Tensor, got {type(t).__name__}")
+        if t.dtype != dtype:
+            raise TypeError(f"{name}: expected {str(dtype).replace('torch.', '')}, got {str(t.dtype).replace('torch.', '')}")
+        if t.device != device:
+            raise RuntimeError(f"{name}: tensor is on {t.device} but this Engine is bound to {device}")
+        if not ok(t):
+            raise ValueError(f"{name}: expected {shape_txt}, got {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: must be contiguous")
+
+    need(rooms, "rooms", torch.float64, "[R, 15] with R >= 1", lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) == 15)
+    R = rooms.size(0)
+    if R > 65535:
+        raise ValueError(f"rooms: at most 65535 rows, got {R}")
+    need(n_taps, "n_taps", torch.int32, f"[{R}]", lambda t: tuple(t.shape) == (R,))
+    if int(K) != K or not 1 <= K <= RIR_MAX_TAPS:
+        raise ValueError(f"K must be a tap count in [1, {RIR_MAX_TAPS}], got {K}")
+    try:
+        N = tuple(n_images)
+    except TypeError:
+        N = ()
+    if len(N) != 3 or any(int(n) != n or not 0 <= n <= RIR_MAX_IMAGES for n in N):
+        raise ValueError(f"n_images must be (Nx, Ny, Nz) with 0 <= N <= {RIR_MAX_IMAGES}, got {n_images}")
+    N = tuple(int(n) for n in N)
+    if 8 * (2 * N[0] + 1) * (2 * N[1] + 1) * (2 * N[2] + 1) >= 2 ** 31:
+        raise ValueError(f"n_images: 8 (2Nx+1)(2Ny+1)(2Nz+1) must stay below 2^31, got {N}")
+    if int(fs) != fs or fs < 1:
+        raise ValueError(f"fs must be a positive sample rate, got {fs}")
+    c = float(c)
+    if not (c > 0.0 and c < float("inf")):
+        raise ValueError(f"c must be positive and finite, got {c}")
+    if int(tw) != tw or not 1 <= tw <= RIR_MAX_TW:
+        raise ValueError(f"tw must be a half-width in [1, {RIR_MAX_TW}] samples, got {tw}")
+    if out is not None:
+        try:
+            rir, length = out
+        except (TypeError, ValueError):
+            raise ValueError("out must be a pair (rir float32 [R, K], length int32 [R])") from None
+        need(rir, "out[0]", torch.float32, f"[{R}, {int(K)}]", lambda t: tuple(t.shape) == (R, int(K)))
+        need(length, "out[1]", torch.int32, f"[{R}]", lambda t: tuple(t.shape) == (R,))
+    return R, int(K), N
+
+
 def metric_frames(L: int, fs: int):
     """(WSS / segSNR frames, LLR frames) of an L-sample signal: the two counts of cmgan_amd.metrics."""
     win = int(np.round(30 * fs / 1000))
@@ -190,6 +242,7 @@ class Engine:
         self._mws: Optional[torch.Tensor] = None          # workspace of metrics()
         self._rws: dict = {}             # resample(): (fs_in, fs_out) -> workspace (the pair's tap table)
         self._xws: Optional[torch.Tensor] = None          # workspace of mix()
+        self._iws: Optional[torch.Tensor] = None          # workspace of rir()
         self._graphs: dict = {}          # enhance_graphed: input shape -> (graph, in, out, token)
         self._row_graphs: dict = {}      # streaming.enhance_windows: row shape -> (graph, in, out, token)
         self._stream_slots: dict = {}    # streaming.StreamState(graph=True): (B, W, Ca, La, stats mode) -> state + step graphs
@@ -798,6 +851,36 @@ class Engine:
             info[2].data_ptr(), info[3].data_ptr(), self._xws.data_ptr(), self._xws.numel(), self._stream()))
         return noisy, target, MixInfo(info[0], info[1], info[2], info[3])
 
+    # ---- room impulse responses ----------------------------------------------------
+    @_on_device
+    def rir(self, rooms: torch.Tensor, n_taps: torch.Tensor, K: int, n_images, fs: int = 16000, c: float = 343.0,
+            tw: int = 40, out=None):
+        """Room impulse responses of shoe-box rooms by the image-source method (cmgan_rir, include/cmgan_hip.h).
+
+        rooms float64 [R, 15] (size Lx Ly Lz in metres, source, receiver, reflection coefficients bx0 bx1 by0 by1 bz0
+        bz1) and n_taps int32 [R], both on this Engine's device and read by the kernels only; K taps per row of the
+        result; n_images = (Nx, Ny, Nz), the image index range per axis; fs in Hz, c the speed of sound in m/s, tw the
+        half-width of the windowed-sinc fractional-delay filter in samples.  `out` = (float32 [R, K], int32 [R]) is
+        written in place.  Returns (rir float32 [R, K], length int32 [R]): exactly the `rir_bank` / `rir_len` source of
+        Engine.mix.  Row r holds clamp(n_taps[r], 1, K) taps and zeros after them; an invalid row (a non-finite entry, a
+        size <= 0, a coefficient outside [0, 1]) is zeros with length 1.  Float64 arithmetic, one rounding to float32;
+        bit-reproducible, row-independent, no synchronisation, graph-capturable after one call at the shape."""
+        R, K, N = check_rir_args(self.device, rooms, n_taps, K, n_images, fs, c, tw, out)
+        need = int(self.lib.cmgan_rir_workspace_bytes(self._h, R, K, int(tw)))
+        if need == 0:
+            raise ValueError(f"[{R}, {K}] with tw = {tw} is outside what cmgan_rir supports")
+        if self._iws is None or self._iws.numel() < need:
+            self._iws = None
+            self._iws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        if out is None:
+            out = (torch.empty(R, K, dtype=torch.float32, device=self.device),
+                   torch.empty(R, dtype=torch.int32, device=self.device))
+        rir, length = out
+        check(self._h, self.lib.cmgan_rir(self._h, rooms.data_ptr(), n_taps.data_ptr(), R, K, int(fs), float(c), int(tw),
+                                          N[0], N[1], N[2], rir.data_ptr(), K, length.data_ptr(), self._iws.data_ptr(),
+                                          self._iws.numel(), self._stream()))
+        return rir, length
+
     # ---- diagnostics ---------------------------------------------------------------
     @_on_device
     def selftest_mfma(self) -> float:
@@ -817,7 +900,7 @@ class Engine:
         self._graphs.clear()
         self._row_graphs.clear()
         self._stream_slots.clear()
-        self._ws = self._bws = self._cws = self._mws = self._xws = None
+        self._ws = self._bws = self._cws = self._mws = self._xws = self._iws = None
         self._rws.clear()
 
     def set_profiling(self, on: bool):

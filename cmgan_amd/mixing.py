@@ -9,12 +9,17 @@ takes - with `clean` the training target (the dry clip, or the clip with its ear
     noise = NoiseBank.from_dir("noise/", 16000, engine)
     rirs = RirBank.from_dir("rirs/", 16000, engine)
     mixer = DynamicMixer(engine, noise, rirs, snr_db=(0, 20), early_ms=50)
+    # without recorded responses: simulate shoe-box rooms on the device (Engine.rir / cmgan_rir, image-source method),
+    # either a fixed bank       rirs = RirBank.simulate(engine, RoomSampler(), 256)
+    # or a fresh room per row of every batch
+    mixer = DynamicMixer(engine, noise, rooms=RoomSampler(rt60=(0.2, 0.8)), snr_db=(0, 20), early_ms=50)
     clean = torch.utils.data.DataLoader(clean_only("data/train", 32000), batch_size=32, pin_memory=True, drop_last=True)
     Trainer(train_ds=MixingLoader(clean, mixer), ...)
 """
 from __future__ import annotations
 
 import collections
+import math
 import os
 import random
 from typing import NamedTuple, Optional, Sequence
@@ -25,7 +30,11 @@ import torch.utils.data
 
 from .data import _natural_key, fit_length, read_wav
 
-__all__ = ["NoiseBank", "RirBank", "DynamicMixer", "MixingLoader", "CleanDataset", "clean_only", "Draw", "tile"]
+__all__ = ["NoiseBank", "RirBank", "RoomSampler", "sabine_beta", "DynamicMixer", "MixingLoader", "CleanDataset",
+           "clean_only", "Draw", "tile"]
+
+SPEED_OF_SOUND = 343.0        # m/s, the default `c` of Engine.rir
+RIR_TW = 40                   # the default half-width of its fractional-delay filter, in samples
 
 
 def tile() -> int:
@@ -90,11 +99,72 @@ class NoiseBank:
         return cls.from_arrays(_read_dir(path, sample_rate, engine), device=engine.device)
 
 
-class RirBank:
-    """Room impulse responses as one float32 [R, Kmax] device allocation, rows zero-padded, plus `length` (int32 [R])."""
+def sabine_beta(rt60, dims) -> torch.Tensor:
+    """The reflection coefficient that gives a shoe-box room of size `dims` ([..., 3], metres) the reverberation time
+    `rt60` ([...], seconds) by Sabine's formula: alpha = 0.161 V / (S rt60) clamped to [0, 1], beta = sqrt(1 - alpha), the
+    same for all six walls.  Plain tensor arithmetic on the device of its arguments; returns a tensor of rt60's shape."""
+    dims = dims if isinstance(dims, torch.Tensor) else torch.as_tensor(dims, dtype=torch.float64)
+    rt60 = rt60 if isinstance(rt60, torch.Tensor) else torch.as_tensor(rt60, dtype=dims.dtype, device=dims.device)
+    lx, ly, lz = dims[..., 0], dims[..., 1], dims[..., 2]
+    volume = lx * ly * lz
+    surface = 2.0 * (lx * ly + ly * lz + lx * lz)
+    alpha = (0.161 * volume / (surface * rt60)).clamp(0.0, 1.0)
+    return torch.sqrt(1.0 - alpha)
 
-    def __init__(self, data: torch.Tensor, length: torch.Tensor):
-        self.data, self.length = data, length
+
+class RoomSampler:
+    """Random shoe-box rooms for Engine.rir: `draw(R, K, fs)` -> `(rooms float64 [R, 15], n_taps int32 [R])`.
+
+    Per row: the size uniform per axis between `dims` = (low, high) (metres), source and receiver uniform and independent
+    in the room shrunk by `margin` on every side, rt60 uniform in `rt60` = (low, high) seconds; the six reflection
+    coefficients are `sabine_beta(rt60, size)` and n_taps = min(K, ceil(rt60 fs)).  Everything is drawn from `generator`
+    (None: the device's default one) on the device with tensor arithmetic: no host synchronisation."""
+
+    def __init__(self, dims=((3.0, 3.0, 2.5), (10.0, 8.0, 4.0)), rt60=(0.2, 0.8), margin: float = 0.5,
+                 generator: Optional[torch.Generator] = None):
+        try:
+            lo, hi = (tuple(float(v) for v in d) for d in dims)
+        except (TypeError, ValueError):
+            raise ValueError(f"dims must be ((Lx, Ly, Lz) low, (Lx, Ly, Lz) high), got {dims}") from None
+        if len(lo) != 3 or len(hi) != 3 or not all(0.0 < a <= b < math.inf for a, b in zip(lo, hi)):
+            raise ValueError(f"dims must be ((Lx, Ly, Lz) low, (Lx, Ly, Lz) high) with 0 < low <= high, got {dims}")
+        t_lo, t_hi = float(rt60[0]), float(rt60[1])
+        if not 0.0 < t_lo <= t_hi < math.inf:
+            raise ValueError(f"rt60 must be (low, high) with 0 < low <= high, got {rt60}")
+        margin = float(margin)
+        if not 0.0 <= margin < 0.5 * min(lo):
+            raise ValueError(f"margin must lie in [0, {0.5 * min(lo)}): half the smallest room size of {dims}, got {margin}")
+        self.lo, self.hi, self.rt60, self.margin, self.generator = lo, hi, (t_lo, t_hi), margin, generator
+
+    def n_images(self, K: int, fs: int, c: float = SPEED_OF_SOUND, tw: int = RIR_TW):
+        """(Nx, Ny, Nz) that leaves out no image of a K-tap response in any room this sampler draws: host arithmetic on
+        the LOWER size bound, ceil((K + tw) c / fs / (2 Lmin_axis)) + 1."""
+        return tuple(int(math.ceil((K + tw) * c / fs / (2.0 * l))) + 1 for l in self.lo)
+
+    def draw(self, R: int, K: int, fs: int, device=None):
+        gen = self.generator
+        device = torch.device(device) if device is not None else (gen.device if gen is not None else torch.device("cpu"))
+        u = torch.rand(R, 10, dtype=torch.float64, generator=gen, device=device)
+        lo = torch.tensor(self.lo, dtype=torch.float64).to(device, non_blocking=True)
+        hi = torch.tensor(self.hi, dtype=torch.float64).to(device, non_blocking=True)
+        size = lo + (hi - lo) * u[:, 0:3]
+        inner = size - 2.0 * self.margin
+        source = self.margin + inner * u[:, 3:6]
+        receiver = self.margin + inner * u[:, 6:9]
+        rt = self.rt60[0] + (self.rt60[1] - self.rt60[0]) * u[:, 9]
+        beta = sabine_beta(rt, size)
+        rooms = torch.cat([size, source, receiver, beta[:, None].expand(R, 6)], dim=1).contiguous()
+        n_taps = torch.ceil(rt * fs).clamp(1, K).to(torch.int32)
+        return rooms, n_taps
+
+
+class RirBank:
+    """Room impulse responses as one float32 [R, Kmax] device allocation, rows zero-padded, plus `length` (int32 [R]).
+    Recorded responses come from `from_dir` / `from_arrays`; `simulate` makes the bank on the device from random shoe-box
+    rooms (Engine.rir, the image-source method) and keeps their table as `rooms` (float64 [R, 15], else None)."""
+
+    def __init__(self, data: torch.Tensor, length: torch.Tensor, rooms: Optional[torch.Tensor] = None):
+        self.data, self.length, self.rooms = data, length, rooms
 
     def __len__(self) -> int:
         return self.data.size(0)
@@ -117,6 +187,14 @@ class RirBank:
     def from_dir(cls, path: str, sample_rate: int, engine) -> "RirBank":
         return cls.from_arrays(_read_dir(path, sample_rate, engine), device=engine.device)
 
+    @classmethod
+    def simulate(cls, engine, sampler: RoomSampler, R: int, seconds: float = 0.5, sample_rate: int = 16000) -> "RirBank":
+        """R rooms drawn by `sampler`, each simulated for up to `seconds` (a row's own length is its rt60, if shorter)."""
+        K = int(round(seconds * sample_rate))
+        rooms, n_taps = sampler.draw(R, K, sample_rate, device=engine.device)
+        data, length = engine.rir(rooms, n_taps, K, sampler.n_images(K, sample_rate), fs=sample_rate)
+        return cls(data, length, rooms)
+
     def with_identity(self) -> "RirBank":
         """The bank with a one-tap identity response appended as its last row (rows that get no reverberation)."""
         row = torch.zeros(1, self.data.size(1), dtype=torch.float32, device=self.device)
@@ -133,6 +211,7 @@ class Draw(NamedTuple):
     snr_db: torch.Tensor
     rir_index: Optional[torch.Tensor]
     rir_len: Optional[torch.Tensor]
+    rooms: Optional[torch.Tensor] = None      # DynamicMixer(rooms=...): the float64 [B, 15] room table of the batch
 
 
 class DynamicMixer:
@@ -143,11 +222,18 @@ class DynamicMixer:
     (lo, hi) dB and, with a `rir_bank`, a RIR (uniform; with probability 1 - p_reverb the row gets the one-tap identity
     appended to the bank instead).  `early_ms`: the target keeps that much of the RIR after its direct path (the usual
     dereverberation target); None makes the dry clip the target.  Nothing here synchronises with the host; the draws of
-    the last call stay readable as `mixer.last_draw`."""
+    the last call stay readable as `mixer.last_draw`.
+
+    `rooms` (a RoomSampler, instead of a `rir_bank`) gives every row of every call a room of its own: B rooms are drawn
+    and simulated for `rir_seconds` by Engine.rir into one persistent [B (+ 1), K] allocation, row b uses response b
+    (rir_index = arange(B)), and with p_reverb < 1 the dry rows use the identity appended as row B.  The room draws come
+    from the sampler's own generator, after the mixer's; the bank of the last call stays readable as `mixer.last_bank`
+    (the next call overwrites it in place)."""
 
     def __init__(self, engine, noise_bank: NoiseBank, rir_bank: Optional[RirBank] = None, snr_db=(0.0, 20.0),
                  early_ms: Optional[float] = 50.0, p_reverb: float = 1.0, peak: float = 0.99,
-                 generator: Optional[torch.Generator] = None, sample_rate: int = 16000):
+                 generator: Optional[torch.Generator] = None, sample_rate: int = 16000,
+                 rooms: Optional[RoomSampler] = None, rir_seconds: float = 0.5):
         lo, hi = float(snr_db[0]), float(snr_db[1])
         if not lo <= hi:
             raise ValueError(f"snr_db must be (low, high) with low <= high, got {snr_db}")
@@ -164,6 +250,18 @@ class DynamicMixer:
         self.rir_bank = rir_bank.with_identity() if rir_bank is not None and p_reverb < 1.0 else rir_bank
         self.early = -1 if early_ms is None else int(round(early_ms * sample_rate / 1000.0))
         self.last_draw: Optional[Draw] = None
+        self.rooms, self.sample_rate = rooms, int(sample_rate)
+        self.rir_taps, self.n_images, self.last_bank = 0, None, None
+        if rooms is not None:
+            if rir_bank is not None:
+                raise ValueError("give either a rir_bank or rooms, not both")
+            self.rir_taps = int(round(rir_seconds * sample_rate))
+            if not 1 <= self.rir_taps <= 65536:
+                raise ValueError(f"rir_seconds must give 1 .. 65536 taps, got {rir_seconds} s at {sample_rate} Hz")
+            self.n_images = rooms.n_images(self.rir_taps, self.sample_rate)
+            if max(self.n_images) > 255:
+                raise ValueError(f"responses of {rir_seconds} s in rooms as small as {rooms.lo} need image ranges "
+                                 f"{self.n_images}; up to 255 are supported")
 
     def draw(self, B: int) -> Draw:
         dev, gen, nb = self.engine.device, self.generator, self.noise_bank
@@ -181,11 +279,34 @@ class DynamicMixer:
                 idx = torch.where(wet, idx, torch.full_like(idx, self.n_rirs))
             rlen = self.rir_bank.length[idx].contiguous()
             idx = idx.to(torch.int32)
-        return Draw(start.contiguous(), length.contiguous(), off, snr, idx, rlen)
+        table = None
+        if self.rooms is not None:
+            table, rlen = self.rooms.draw(B, self.rir_taps, self.sample_rate, device=dev)
+            idx = torch.arange(B, dtype=torch.int32, device=dev)
+            if self.p_reverb < 1.0:
+                wet = torch.rand(B, dtype=torch.float32, generator=gen, device=dev) < self.p_reverb
+                idx = torch.where(wet, idx, torch.full_like(idx, B))
+                rlen = torch.where(wet, rlen, torch.ones_like(rlen))
+        return Draw(start.contiguous(), length.contiguous(), off, snr, idx, rlen, table)
+
+    def _simulate(self, d: Draw) -> RirBank:
+        """The batch's responses, simulated into the persistent allocation (made anew only when B changes)."""
+        B, K = d.rooms.size(0), self.rir_taps
+        rows = B + (1 if self.p_reverb < 1.0 else 0)
+        if self.last_bank is None or self.last_bank.data.size(0) != rows:
+            data = torch.zeros(rows, K, dtype=torch.float32, device=self.engine.device)
+            length = torch.ones(rows, dtype=torch.int32, device=self.engine.device)
+            if rows > B:
+                data[B, 0] = 1.0                                  # the identity of the dry rows
+            self.last_bank = RirBank(data, length)
+        sim = self.last_bank
+        # rir_len is the sampler's n_taps, or 1 for a dry row (whose response is then one tap that no row uses)
+        self.engine.rir(d.rooms, d.rir_len, K, self.n_images, fs=self.sample_rate, out=(sim.data[:B], sim.length[:B]))
+        return sim
 
     def __call__(self, clean: torch.Tensor):
         d = self.last_draw = self.draw(clean.size(0))
-        rir = self.rir_bank
+        rir = self.rir_bank if self.rooms is None else self._simulate(d)
         noisy, target, info = self.engine.mix(clean, self.noise_bank.data, d.noise_start, d.noise_len, d.noise_off,
                                               d.snr_db, rir.data if rir is not None else None, d.rir_index, d.rir_len,
                                               peak=self.peak, early=self.early if rir is not None else -1)

@@ -39,7 +39,7 @@ extern "C" {
 #define CMGAN_E_WORKSPACE   -5   /* workspace too small or misaligned              */
 #define CMGAN_E_HIP         -6   /* a HIP runtime call failed (see last_error)     */
 
-#define CMGAN_ABI_VERSION 7
+#define CMGAN_ABI_VERSION 8
 
 typedef struct cmgan_handle cmgan_handle;
 
@@ -643,6 +643,44 @@ int cmgan_mix(cmgan_handle* h, const float* clean_dev, int B, int L, long long l
               const int* rir_len_dev, const float* snr_db_dev, float peak, int early, float* noisy_dev,
               float* target_dev, long long ld_out, double* g_dev, double* scale_dev, double* ps_dev, double* pn_dev,
               void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- Room impulse responses (the reference ships no impulse responses and no simulator; its --cut_len help names
+ * "denoise and dereverberation", src/data/dataloader.py:13-50 replays pairs mixed beforehand) --------------------------
+ * Simulates R shoe-box rooms by the image-source method (Allen & Berkley 1979) with Peterson's Hann-windowed sinc for the
+ * fractional delays, into the float32 [R, K] bank + int32 [R] lengths that cmgan_mix takes as rir_bank_dev / rir_len.
+ * Per-row inputs are read from DEVICE memory by the kernels, never by the host:
+ *   rooms_dev   float64 [R, 15]: room size Lx Ly Lz (m), source sx sy sz, receiver mx my mz, reflection coefficients
+ *               bx0 bx1 by0 by1 bz0 bz1 (wall at 0 and wall at L, per axis)
+ *   n_taps_dev  int32 [R], the length of row r's response
+ * Host arguments: fs (Hz), c (speed of sound, m/s), tw (half-width of the fractional-delay filter in samples),
+ * Nx Ny Nz (image index range per axis), K (taps per row of the bank), ld (floats between rows, >= K).
+ * For row r, with k_r = clamp(n_taps[r], 1, K), the sum runs over n = (nx, ny, nz), |n_axis| <= N_axis, and over
+ * p = (px, py, pz) in {0, 1}^3:
+ *   offset   per axis (1 - 2 p) s + 2 n L - m;  d = its Euclidean length;  tau = d fs / c
+ *   a        prod_axis b_axis0^|n - p| b_axis1^|n| / (4 pi max(d, CMGAN_RIR_DMIN))                      (0^0 = 1)
+ *   taps     h[k] = sum_images a w(k - tau) sinc(k - tau), 0 <= k < k_r, with w(t) = (1 + cos(pi t / tw)) / 2 for
+ *            |t| < tw, else 0, and sinc(t) = sin(pi t) / (pi t), sinc(0) = 1; images with tau - tw >= K add nothing
+ *   outputs  rir_dev[r * ld + k] = f32(h[k]) for k < k_r and exactly 0.0f for k_r <= k < K;  len_dev[r] = k_r
+ * Not modelled: a high-pass filter, air absorption, directivity.  All arithmetic is float64 and each tap is rounded to
+ * float32 exactly once.  A block owns cmgan_rir_tile() consecutive taps of one row and adds the images that reach them in
+ * one fixed enumeration order (nx, ny, p, nz ascending), staged cmgan_rir_list_capacity() at a time in an on-chip list by
+ * an order-preserving compaction: no atomics, the same bits from run to run, row r's bits depend neither on R nor on the
+ * other rows, and an N larger than the response needs changes no bit.
+ * Table entries cannot be checked by the host without a synchronisation: a row with a non-finite entry, a room size <= 0
+ * or a coefficient outside [0, 1] is written as all zeros with len = 1, n_taps is clamped to [1, K], and no entry is ever
+ * turned into an address.  Checked before any launch and before the handle is looked at (the message of a call with
+ * h == NULL is read with cmgan_last_error(NULL)): null or misaligned pointers, 1 <= R <= 65535, 1 <= K <= 65536, ld >= K,
+ * fs > 0, c > 0 and finite, 1 <= tw <= 64, 0 <= N_axis <= 255 and 8 (2Nx+1)(2Ny+1)(2Nz+1) < 2^31; otherwise
+ * CMGAN_E_BADARG / CMGAN_E_UNSUPPORTED.  Workspace: cmgan_rir_workspace_bytes (h may be NULL; 0 when unsupported;
+ * non-decreasing in R, K and tw), 256-byte aligned; it holds each row's verdict and the powers of its coefficients between
+ * the two launches.  No synchronisation, no allocation; graph-capturable, and a replay reads the tables' current contents. */
+#define CMGAN_RIR_DMIN 0.01   /* metres: the distance below which 1 / (4 pi d) stops growing */
+int cmgan_rir_tile(void);
+int cmgan_rir_list_capacity(void);
+size_t cmgan_rir_workspace_bytes(const cmgan_handle* h, int R, int K, int tw);
+int cmgan_rir(cmgan_handle* h, const double* rooms_dev, const int* n_taps_dev, int R, int K, int fs, double c, int tw,
+              int Nx, int Ny, int Nz, float* rir_dev, long long ld, int* len_dev, void* workspace_dev,
+              size_t workspace_bytes, void* stream);
 
 /* Names + durations (ms) of the kernels of the most recent forward when
  * profiling is enabled with cmgan_set_profiling(h, 1): HIP events are recorded
