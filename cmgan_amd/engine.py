@@ -175,6 +175,58 @@ def check_rir_args(device, rooms, n_taps, K, n_images, fs=16000, c: float = 343.
     return R, int(K), N
 
 
+class SpeechLevel(NamedTuple):
+    """Engine.speech_level: float64 [B] device tensors - the mean square of the row, the mean square over the time its
+    talker is active (ITU-T P.56, method B) and their ratio, the fraction of the row that is active."""
+    ms: torch.Tensor
+    active_ms: torch.Tensor
+    activity: torch.Tensor
+
+
+LEVEL_FS = (8000, 192000)     # sample rates of cmgan_speech_level
+LEVEL_TILE = 1024             # its samples per block (= cmgan_speech_level_tile())
+LEVEL_MAX_L = 2 ** 31 - 1 - LEVEL_TILE
+
+
+def level_workspace_bytes(B: int, L: int) -> int:
+    """cmgan_speech_level_workspace_bytes: five float64 [B, tiles] planes, one float64 [B] and one int32 [B, tiles, 16],
+    each rounded up to 256 bytes; 0 for a shape the kernels do not take."""
+    if not (1 <= B <= 65535 and 1 <= L <= LEVEL_MAX_L):
+        return 0
+    up = lambda v: (v + 255) & ~255
+    nt = (L + LEVEL_TILE - 1) // LEVEL_TILE
+    return 5 * up(B * nt * 8) + up(B * 8) + up(B * nt * 16 * 4)
+
+
+def check_level_args(device, wav, lengths=None, fs=16000):
+    """Argument rules of Engine.speech_level (shapes, dtypes, devices and host scalars; pure host code).  Returns (B, L)."""
+    def need(t, name, dtype, shape_txt, ok):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: expected a torch.Tensor, got {type(t).__name__}")
+        if t.dtype != dtype:
+            raise TypeError(f"{name}: expected {str(dtype).replace('torch.', '')}, got {str(t.dtype).replace('torch.', '')}")
+        if t.device != device:
+            raise RuntimeError(f"{name}: tensor is on {t.device} but this Engine is bound to {device}")
+        if not ok(t):
+            raise ValueError(f"{name}: expected {shape_txt}, got {tuple(t.shape)}")
+
+    need(wav, "wav", torch.float32, "[B, L] with B, L >= 1", lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) >= 1)
+    B, L = wav.shape
+    if B > 65535:
+        raise ValueError(f"wav: at most 65535 rows, got {B}")
+    if L > LEVEL_MAX_L:
+        raise ValueError(f"wav: rows of up to {LEVEL_MAX_L} samples are supported, got {L}")
+    if wav.stride(1) != 1 or (B > 1 and wav.stride(0) < L):
+        raise ValueError(f"wav: rows must be contiguous and at least L apart, got strides {tuple(wav.stride())}")
+    if lengths is not None:
+        need(lengths, "lengths", torch.int32, f"[{B}]", lambda t: tuple(t.shape) == (B,))
+        if not lengths.is_contiguous():
+            raise ValueError("lengths: must be contiguous")
+    if isinstance(fs, bool) or int(fs) != fs or not LEVEL_FS[0] <= fs <= LEVEL_FS[1]:
+        raise ValueError(f"fs must be a sample rate in [{LEVEL_FS[0]}, {LEVEL_FS[1]}] Hz, got {fs}")
+    return B, L
+
+
 def metric_frames(L: int, fs: int):
     """(WSS / segSNR frames, LLR frames) of an L-sample signal: the two counts of cmgan_amd.metrics."""
     win = int(np.round(30 * fs / 1000))
@@ -243,6 +295,7 @@ class Engine:
         self._rws: dict = {}             # resample(): (fs_in, fs_out) -> workspace (the pair's tap table)
         self._xws: Optional[torch.Tensor] = None          # workspace of mix()
         self._iws: Optional[torch.Tensor] = None          # workspace of rir()
+        self._lws: Optional[torch.Tensor] = None          # workspace of speech_level()
         self._graphs: dict = {}          # enhance_graphed: input shape -> (graph, in, out, token)
         self._row_graphs: dict = {}      # streaming.enhance_windows: row shape -> (graph, in, out, token)
         self._stream_slots: dict = {}    # streaming.StreamState(graph=True): (B, W, Ca, La, stats mode) -> state + step graphs
@@ -881,6 +934,35 @@ class Engine:
                                           self._iws.numel(), self._stream()))
         return rir, length
 
+    # ---- active speech level -------------------------------------------------------
+    @_on_device
+    def speech_level(self, wav: torch.Tensor, lengths: Optional[torch.Tensor] = None, fs: int = 16000, counts: bool = False):
+        """The active speech level of every row of a batch on the GPU (cmgan_speech_level, include/cmgan_hip.h): the level
+        meter of ITU-T P.56, method B, as its published description gives it - not compared with ITU's own program.
+
+        wav float32 [B, L] (rows contiguous, any row stride >= L); lengths int32 [B] on this Engine's device, read by the
+        kernels only (None: every row has L samples; samples from a row's length on are never read); fs in 8000 .. 192000.
+        Returns SpeechLevel(ms, active_ms, activity) of float64 [B]: the mean square, the mean square over the active time
+        (200 ms hangover included) and their ratio.  All three are 0 where no speech is detected and NaN where the row
+        holds a non-finite sample.  counts=True adds an int64 [B, 16] tensor: the active samples per threshold
+        2^-15 .. 2^-1 and the row's length.  Float64 arithmetic; bit-reproducible, row-independent, no synchronisation,
+        graph-capturable after one call at the shape."""
+        B, L = check_level_args(self.device, wav, lengths, fs)
+        need = int(self.lib.cmgan_speech_level_workspace_bytes(B, L))
+        if need == 0:
+            raise ValueError(f"[{B}, {L}] is outside what cmgan_speech_level supports")
+        if self._lws is None or self._lws.numel() < need:
+            self._lws = None
+            self._lws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        level = torch.empty(B, 3, dtype=torch.float64, device=self.device)
+        cnt = torch.empty(B, 16, dtype=torch.int64, device=self.device) if counts else None
+        check(self._h, self.lib.cmgan_speech_level(
+            self._h, wav.data_ptr(), B, L, wav.stride(0) if B > 1 else L, lengths.data_ptr() if lengths is not None else None,
+            int(fs), level.data_ptr(), cnt.data_ptr() if counts else None, self._lws.data_ptr(), self._lws.numel(),
+            self._stream()))
+        out = SpeechLevel(level[:, 0], level[:, 1], level[:, 2])
+        return (out, cnt) if counts else out
+
     # ---- diagnostics ---------------------------------------------------------------
     @_on_device
     def selftest_mfma(self) -> float:
@@ -900,7 +982,7 @@ class Engine:
         self._graphs.clear()
         self._row_graphs.clear()
         self._stream_slots.clear()
-        self._ws = self._bws = self._cws = self._mws = self._xws = self._iws = None
+        self._ws = self._bws = self._cws = self._mws = self._xws = self._iws = self._lws = None
         self._rws.clear()
 
     def set_profiling(self, on: bool):

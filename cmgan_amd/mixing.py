@@ -212,6 +212,7 @@ class Draw(NamedTuple):
     rir_index: Optional[torch.Tensor]
     rir_len: Optional[torch.Tensor]
     rooms: Optional[torch.Tensor] = None      # DynamicMixer(rooms=...): the float64 [B, 15] room table of the batch
+    level_db: Optional[torch.Tensor] = None   # DynamicMixer(level_db=...): the float64 [B] target active level in dBFS
 
 
 class DynamicMixer:
@@ -228,12 +229,36 @@ class DynamicMixer:
     and simulated for `rir_seconds` by Engine.rir into one persistent [B (+ 1), K] allocation, row b uses response b
     (rir_index = arange(B)), and with p_reverb < 1 the dry rows use the identity appended as row B.  The room draws come
     from the sampler's own generator, after the mixer's; the bank of the last call stays readable as `mixer.last_bank`
-    (the next call overwrites it in place)."""
+    (the next call overwrites it in place).
+
+    Levels (Engine.speech_level / cmgan_speech_level: the active speech level of ITU-T P.56, method B).  Either option
+    below measures the clean batch once per call, on the device; the measurement stays readable as `mixer.last_level`.
+    With both at their defaults nothing is measured, no draw is added and the outputs are what they were without them.
+    `snr_on="active"`: the drawn SNR relates the ACTIVE speech power to the noise power, as speech corpora define it: the
+    mixer passes snr_db - D to Engine.mix, D = -10 log10(activity) where the row's activity is finite and > 0, else 0
+    ("rms", the default: mean(speech^2) over the whole clip, pauses included).  `last_draw.snr_db` stays the drawn value.
+    D is measured on the dry clip; with a RIR the reverberant speech's own activity differs slightly.
+    `level_db=(lo, hi)`: a target active level, uniform in dBFS, is drawn per row (after every other draw) and the clean
+    row is multiplied in float32 by f32(sqrt(10^(level / 10) / active_ms)) before Engine.mix; the factor is 1 where no
+    speech was detected.  This is one measurement and one gain: the thresholds of P.56 are absolute, so measuring the
+    scaled row again gives a slightly different level than the one drawn."""
 
     def __init__(self, engine, noise_bank: NoiseBank, rir_bank: Optional[RirBank] = None, snr_db=(0.0, 20.0),
                  early_ms: Optional[float] = 50.0, p_reverb: float = 1.0, peak: float = 0.99,
                  generator: Optional[torch.Generator] = None, sample_rate: int = 16000,
-                 rooms: Optional[RoomSampler] = None, rir_seconds: float = 0.5):
+                 rooms: Optional[RoomSampler] = None, rir_seconds: float = 0.5, snr_on: str = "rms", level_db=None):
+        if snr_on not in ("rms", "active"):
+            raise ValueError(f"snr_on must be 'rms' or 'active', got {snr_on!r}")
+        if level_db is not None:
+            try:
+                level_db = (float(level_db[0]), float(level_db[1]))
+            except (TypeError, ValueError, IndexError):
+                raise ValueError(f"level_db must be None or (low, high) in dBFS, got {level_db}") from None
+            if not level_db[0] <= level_db[1] < math.inf or level_db[0] == -math.inf:
+                raise ValueError(f"level_db must be (low, high) with finite low <= high, got {level_db}")
+        if (snr_on == "active" or level_db is not None) and not 8000 <= int(sample_rate) <= 192000:
+            raise ValueError(f"the speech level is measured at 8000 .. 192000 Hz, got sample_rate = {sample_rate}")
+        self.snr_on, self.level_db, self.last_level = snr_on, level_db, None
         lo, hi = float(snr_db[0]), float(snr_db[1])
         if not lo <= hi:
             raise ValueError(f"snr_db must be (low, high) with low <= high, got {snr_db}")
@@ -287,7 +312,11 @@ class DynamicMixer:
                 wet = torch.rand(B, dtype=torch.float32, generator=gen, device=dev) < self.p_reverb
                 idx = torch.where(wet, idx, torch.full_like(idx, B))
                 rlen = torch.where(wet, rlen, torch.ones_like(rlen))
-        return Draw(start.contiguous(), length.contiguous(), off, snr, idx, rlen, table)
+        level = None
+        if self.level_db is not None:
+            lo, hi = self.level_db
+            level = lo + (hi - lo) * torch.rand(B, dtype=torch.float64, generator=gen, device=dev)
+        return Draw(start.contiguous(), length.contiguous(), off, snr, idx, rlen, table, level)
 
     def _simulate(self, d: Draw) -> RirBank:
         """The batch's responses, simulated into the persistent allocation (made anew only when B changes)."""
@@ -304,11 +333,30 @@ class DynamicMixer:
         self.engine.rir(d.rooms, d.rir_len, K, self.n_images, fs=self.sample_rate, out=(sim.data[:B], sim.length[:B]))
         return sim
 
+    @staticmethod
+    def level_gain(level, level_db: torch.Tensor) -> torch.Tensor:
+        """The float32 [B] factor that takes rows measured as `level` (a SpeechLevel) to the active level `level_db`
+        (float64 [B], dBFS): f32(sqrt(10^(level_db / 10) / active_ms)), and 1 where active_ms is not finite and > 0."""
+        ok = torch.isfinite(level.active_ms) & (level.active_ms > 0)
+        active = torch.where(ok, level.active_ms, torch.ones_like(level.active_ms))
+        gain = torch.sqrt(torch.pow(10.0, level_db / 10.0) / active)
+        return torch.where(ok, gain, torch.ones_like(gain)).to(torch.float32)
+
     def __call__(self, clean: torch.Tensor):
         d = self.last_draw = self.draw(clean.size(0))
         rir = self.rir_bank if self.rooms is None else self._simulate(d)
+        snr = d.snr_db
+        if self.snr_on == "active" or d.level_db is not None:
+            lv = self.last_level = self.engine.speech_level(clean, fs=self.sample_rate)
+            if self.snr_on == "active":
+                ok = torch.isfinite(lv.activity) & (lv.activity > 0)
+                delta = torch.where(ok, -10.0 * torch.log10(torch.where(ok, lv.activity, torch.ones_like(lv.activity))),
+                                    torch.zeros_like(lv.activity))
+                snr = (d.snr_db.to(torch.float64) - delta).to(torch.float32).contiguous()
+            if d.level_db is not None:
+                clean = (clean * self.level_gain(lv, d.level_db)[:, None]).contiguous()
         noisy, target, info = self.engine.mix(clean, self.noise_bank.data, d.noise_start, d.noise_len, d.noise_off,
-                                              d.snr_db, rir.data if rir is not None else None, d.rir_index, d.rir_len,
+                                              snr, rir.data if rir is not None else None, d.rir_index, d.rir_len,
                                               peak=self.peak, early=self.early if rir is not None else -1)
         return target, noisy, info
 

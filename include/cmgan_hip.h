@@ -39,7 +39,7 @@ extern "C" {
 #define CMGAN_E_WORKSPACE   -5   /* workspace too small or misaligned              */
 #define CMGAN_E_HIP         -6   /* a HIP runtime call failed (see last_error)     */
 
-#define CMGAN_ABI_VERSION 8
+#define CMGAN_ABI_VERSION 9
 
 typedef struct cmgan_handle cmgan_handle;
 
@@ -681,6 +681,42 @@ size_t cmgan_rir_workspace_bytes(const cmgan_handle* h, int R, int K, int tw);
 int cmgan_rir(cmgan_handle* h, const double* rooms_dev, const int* n_taps_dev, int R, int K, int fs, double c, int tw,
               int Nx, int Ny, int Nz, float* rir_dev, long long ld, int* len_dev, void* workspace_dev,
               size_t workspace_bytes, void* stream);
+
+/* ---- Active speech level (the reference has no level handling: src/data/dataloader.py:13-50 replays pairs mixed
+ * beforehand) ---------------------------------------------------------------------------------------------------------
+ * The level meter of ITU-T P.56, method B, as its published description gives it, for B rows x_dev[b * ld + i] of float32
+ * samples.  ITU's own program was not available to compare with: the definition below is the contract, and equality with
+ * that program is neither claimed nor tested.  lengths_dev is int32 [B] in DEVICE memory, read by the kernels only, or NULL
+ * for n = L; n = clamp(lengths[b], 0, L), and samples at i >= n are never read.  fs is a host int.  For row b:
+ *   g   = exp(-1 / (0.03 fs))              I = ceil(0.2 fs)              c_j = 2^(j-15), j = 0..14
+ *   p_i = g p_{i-1} + (1-g) |x_i|,  q_i = g q_{i-1} + (1-g) p_i,          p_{-1} = q_{-1} = 0
+ *   a_j = #{ i < n : q_i' >= c_j for some i' in [i-I, i] }                (activity with a hangover of I samples;
+ *                                                                          a_j is non-increasing in j)
+ *   sq  = sum_{i < n} x_i^2,  ms = sq / n
+ *   J   = #{ j : a_j > 0 };  A_j = 10 log10(sq / a_j),  C_j = 20 log10(c_j),  D_j = A_j - C_j,  M = 15.9
+ *   A*  = A_0                                      if D_0 <= M
+ *       = A_{j-1} + t (A_j - A_{j-1}),  t = (D_{j-1} - M) / (D_{j-1} - D_j)   for the first j in 1..J-1 with D_j <= M
+ *       = A_{J-1}                                  if there is none
+ *   active_ms = 10^(A* / 10),  activity = ms / active_ms
+ *   outputs   level_dev[b * 3 + 0..2] = {ms, active_ms, activity} (float64);  counts_dev (int64 [B][16], may be NULL)
+ *             = {a_0 .. a_14, n}
+ * n == 0, sq == 0 or J == 0: all three outputs are 0.  sq not finite: all three are NaN (and the row's a_j mean nothing).
+ * All arithmetic is float64 on the VALU.  A block owns a tile of cmgan_speech_level_tile() samples: the recurrence is run
+ * per tile from zero state, the tiles' end states are folded in ascending order (a segment of m samples acts on an incoming
+ * state as p' = g^m p + P, q' = g^m q + m (1-g) g^m p + Q), every tile reports the first and last crossing of each threshold,
+ * and a_j is an integer fold over the tiles.  No atomics; every reduction runs in an order that depends on the tile grid
+ * alone, so the same bits come out from run to run, row b's bits depend neither on B nor on the other rows, and a row of
+ * length n gives the same bits at every L >= n.
+ * Checked before any launch and before the handle is looked at (the message of a call with h == NULL is read with
+ * cmgan_last_error(NULL)): null or misaligned pointers (4 bytes for x and lengths, 8 for level and counts), 1 <= B <= 65535,
+ * 1 <= L <= 2^31 - 1 - cmgan_speech_level_tile(), ld >= L, 8000 <= fs <= 192000, a workspace that is null, not 256-byte
+ * aligned or smaller than cmgan_speech_level_workspace_bytes(B, L) (0 for an unsupported shape; non-decreasing in B and L);
+ * each is CMGAN_E_BADARG.  Four launches, no synchronisation, no allocation; graph-capturable, and a replay reads the
+ * current contents of x_dev and lengths_dev.                                                                            */
+int cmgan_speech_level_tile(void);
+size_t cmgan_speech_level_workspace_bytes(int B, int L);
+int cmgan_speech_level(cmgan_handle* h, const float* x_dev, int B, int L, long long ld, const int* lengths_dev, int fs,
+                       double* level_dev, long long* counts_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* Names + durations (ms) of the kernels of the most recent forward when
  * profiling is enabled with cmgan_set_profiling(h, 1): HIP events are recorded
