@@ -16,17 +16,32 @@ from . import _lib
 from ._lib import Config, KernelTime, Taps, check
 
 
-def _f32c(t: torch.Tensor, name: str, device: Optional[torch.device] = None) -> torch.Tensor:
+def tensor_arg(t, name: str, dtype, device, shape_txt: Optional[str] = None, ok=None, contiguous: bool = True, error=None):
+    """The one rule for a tensor argument (pure host code): a torch.Tensor (TypeError) of `dtype` (TypeError) on `device`
+    (RuntimeError) for which `ok(t)` holds (ValueError naming `shape_txt`; None = any shape) and, unless told otherwise,
+    contiguous (ValueError).  `error`: one exception type for every rule, for the arguments that have always raised
+    ValueError whatever was wrong.  Returns t."""
     if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name}: expected a torch.Tensor")
-    if not t.is_cuda:
-        raise RuntimeError(f"{name}: tensor must live on the GPU (cmgan_amd has no CPU path)")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name}: expected float32, got {t.dtype}")
-    if device is not None and t.device != device:
-        raise RuntimeError(f"{name}: tensor is on {t.device} but this Engine is bound to {device} "
-                           "(one handle = one device; build one Engine per GPU)")
-    return t.contiguous()
+        kind, what = TypeError, f"expected a torch.Tensor, got {type(t).__name__}"
+    elif t.dtype != dtype:
+        kind, what = TypeError, f"expected {dtype}, got {t.dtype}".replace("torch.", "")
+    elif t.device != device:
+        kind, what = RuntimeError, f"tensor is on {t.device} but this Engine is bound to {device}"
+    elif ok is not None and not ok(t):
+        kind, what = ValueError, f"expected {shape_txt}, got {tuple(t.shape)}"
+    elif contiguous and not t.is_contiguous():
+        kind, what = ValueError, "must be contiguous"
+    else:
+        return t
+    raise (error or kind)(f"{name}: {what}")
+
+
+def native_call(eng, name: str, *args) -> None:
+    """`name(handle, *args)` of eng.lib, checked.  A tensor goes as its device pointer, a parameter struct by reference,
+    everything else as it is (None: a null pointer)."""
+    args = [a.data_ptr() if isinstance(a, torch.Tensor) else ctypes.byref(a) if isinstance(a, ctypes.Structure) else a
+            for a in args]
+    check(eng._h, getattr(eng.lib, name)(eng._h, *args))
 
 
 def _on_device(fn):
@@ -79,42 +94,32 @@ MIX_MAX_TAPS = 65536          # longest RIR of cmgan_mix
 def check_mix_args(device, clean, noise_bank, noise_start, noise_len, noise_off, snr_db, rir_bank=None, rir_index=None,
                    rir_len=None, peak: float = 0.99, early: int = -1):
     """Argument rules of Engine.mix (shapes, dtypes, devices and host scalars; pure host code).  Returns (B, L, R, Kmax)."""
-    def need(t, name, dtype, shape_txt, ok):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name}: expected a torch.Tensor, got {type(t).__name__}")
-        if t.dtype != dtype:
-            raise TypeError(f"{name}: expected {str(dtype).replace('torch.', '')}, got {str(t.dtype).replace('torch.', '')}")
-        if t.device != device:
-            raise RuntimeError(f"{name}: tensor is on {t.device} but this Engine is bound to {device}")
-        if not ok(t):
-            raise ValueError(f"{name}: expected {shape_txt}, got {tuple(t.shape)}")
-        if not t.is_contiguous():
-            raise ValueError(f"{name}: must be contiguous")
-
-    need(clean, "clean", torch.float32, "[B, L] with B, L >= 1", lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) >= 1)
+    tensor_arg(clean, "clean", torch.float32, device, "[B, L] with B, L >= 1",
+               lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) >= 1)
     B, L = clean.shape
     if B > 65535:
         raise ValueError(f"clean: at most 65535 rows, got {B}")
-    need(noise_bank, "noise_bank", torch.float32, "a flat bank of >= 1 samples", lambda t: t.dim() == 1 and t.numel() >= 1)
+    tensor_arg(noise_bank, "noise_bank", torch.float32, device, "a flat bank of >= 1 samples",
+               lambda t: t.dim() == 1 and t.numel() >= 1)
     row = lambda t: tuple(t.shape) == (B,)
-    need(noise_start, "noise_start", torch.int64, f"[{B}]", row)
-    need(noise_len, "noise_len", torch.int64, f"[{B}]", row)
-    need(noise_off, "noise_off", torch.int64, f"[{B}]", row)
-    need(snr_db, "snr_db", torch.float32, f"[{B}]", row)
+    tensor_arg(noise_start, "noise_start", torch.int64, device, f"[{B}]", row)
+    tensor_arg(noise_len, "noise_len", torch.int64, device, f"[{B}]", row)
+    tensor_arg(noise_off, "noise_off", torch.int64, device, f"[{B}]", row)
+    tensor_arg(snr_db, "snr_db", torch.float32, device, f"[{B}]", row)
     R, Kmax = 0, 0
     if rir_bank is None:
         if rir_index is not None or rir_len is not None:
             raise ValueError("rir_index / rir_len given without a rir_bank")
     else:
-        need(rir_bank, "rir_bank", torch.float32, "[R, Kmax] with R, Kmax >= 1",
+        tensor_arg(rir_bank, "rir_bank", torch.float32, device, "[R, Kmax] with R, Kmax >= 1",
              lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) >= 1)
         R, Kmax = rir_bank.shape
         if Kmax > MIX_MAX_TAPS:
             raise ValueError(f"rir_bank: RIRs of up to {MIX_MAX_TAPS} taps are supported, got Kmax = {Kmax}")
         if rir_index is None or rir_len is None:
             raise ValueError("a rir_bank needs rir_index and rir_len")
-        need(rir_index, "rir_index", torch.int32, f"[{B}]", row)
-        need(rir_len, "rir_len", torch.int32, f"[{B}]", row)
+        tensor_arg(rir_index, "rir_index", torch.int32, device, f"[{B}]", row)
+        tensor_arg(rir_len, "rir_len", torch.int32, device, f"[{B}]", row)
     peak = float(peak)
     if not (peak > 0.0 and peak < float("inf")):
         raise ValueError(f"peak must be positive and finite, got {peak}")
@@ -130,23 +135,12 @@ RIR_MAX_TW = 64               # largest half-width of the fractional-delay filte
 
 def check_rir_args(device, rooms, n_taps, K, n_images, fs=16000, c: float = 343.0, tw: int = 40, out=None):
     """Argument rules of Engine.rir (shapes, dtypes, devices and host scalars; pure host code).  Returns (R, K, (Nx, Ny, Nz))."""
-    def need(t, name, dtype, shape_txt, ok):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name}: expected a torch.Tensor, got {type(t).__name__}")
-        if t.dtype != dtype:
-            raise TypeError(f"{name}: expected {str(dtype).replace('torch.', '')}, got {str(t.dtype).replace('torch.', '')}")
-        if t.device != device:
-            raise RuntimeError(f"{name}: tensor is on {t.device} but this Engine is bound to {device}")
-        if not ok(t):
-            raise ValueError(f"{name}: expected {shape_txt}, got {tuple(t.shape)}")
-        if not t.is_contiguous():
-            raise ValueError(f"{name}: must be contiguous")
-
-    need(rooms, "rooms", torch.float64, "[R, 15] with R >= 1", lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) == 15)
+    tensor_arg(rooms, "rooms", torch.float64, device, "[R, 15] with R >= 1",
+               lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) == 15)
     R = rooms.size(0)
     if R > 65535:
         raise ValueError(f"rooms: at most 65535 rows, got {R}")
-    need(n_taps, "n_taps", torch.int32, f"[{R}]", lambda t: tuple(t.shape) == (R,))
+    tensor_arg(n_taps, "n_taps", torch.int32, device, f"[{R}]", lambda t: tuple(t.shape) == (R,))
     if int(K) != K or not 1 <= K <= RIR_MAX_TAPS:
         raise ValueError(f"K must be a tap count in [1, {RIR_MAX_TAPS}], got {K}")
     try:
@@ -170,8 +164,8 @@ def check_rir_args(device, rooms, n_taps, K, n_images, fs=16000, c: float = 343.
             rir, length = out
         except (TypeError, ValueError):
             raise ValueError("out must be a pair (rir float32 [R, K], length int32 [R])") from None
-        need(rir, "out[0]", torch.float32, f"[{R}, {int(K)}]", lambda t: tuple(t.shape) == (R, int(K)))
-        need(length, "out[1]", torch.int32, f"[{R}]", lambda t: tuple(t.shape) == (R,))
+        tensor_arg(rir, "out[0]", torch.float32, device, f"[{R}, {int(K)}]", lambda t: tuple(t.shape) == (R, int(K)))
+        tensor_arg(length, "out[1]", torch.int32, device, f"[{R}]", lambda t: tuple(t.shape) == (R,))
     return R, int(K), N
 
 
@@ -200,17 +194,8 @@ def level_workspace_bytes(B: int, L: int) -> int:
 
 def check_level_args(device, wav, lengths=None, fs=16000):
     """Argument rules of Engine.speech_level (shapes, dtypes, devices and host scalars; pure host code).  Returns (B, L)."""
-    def need(t, name, dtype, shape_txt, ok):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name}: expected a torch.Tensor, got {type(t).__name__}")
-        if t.dtype != dtype:
-            raise TypeError(f"{name}: expected {str(dtype).replace('torch.', '')}, got {str(t.dtype).replace('torch.', '')}")
-        if t.device != device:
-            raise RuntimeError(f"{name}: tensor is on {t.device} but this Engine is bound to {device}")
-        if not ok(t):
-            raise ValueError(f"{name}: expected {shape_txt}, got {tuple(t.shape)}")
-
-    need(wav, "wav", torch.float32, "[B, L] with B, L >= 1", lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) >= 1)
+    tensor_arg(wav, "wav", torch.float32, device, "[B, L] with B, L >= 1",
+               lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) >= 1, contiguous=False)     # (its own stride rule below)
     B, L = wav.shape
     if B > 65535:
         raise ValueError(f"wav: at most 65535 rows, got {B}")
@@ -219,9 +204,7 @@ def check_level_args(device, wav, lengths=None, fs=16000):
     if wav.stride(1) != 1 or (B > 1 and wav.stride(0) < L):
         raise ValueError(f"wav: rows must be contiguous and at least L apart, got strides {tuple(wav.stride())}")
     if lengths is not None:
-        need(lengths, "lengths", torch.int32, f"[{B}]", lambda t: tuple(t.shape) == (B,))
-        if not lengths.is_contiguous():
-            raise ValueError("lengths: must be contiguous")
+        tensor_arg(lengths, "lengths", torch.int32, device, f"[{B}]", lambda t: tuple(t.shape) == (B,))
     if isinstance(fs, bool) or int(fs) != fs or not LEVEL_FS[0] <= fs <= LEVEL_FS[1]:
         raise ValueError(f"fs must be a sample rate in [{LEVEL_FS[0]}, {LEVEL_FS[1]}] Hz, got {fs}")
     return B, L
@@ -288,14 +271,9 @@ class Engine:
         if rc != 0:
             msg = self.lib.cmgan_last_error(None)
             raise _lib.CmganError(rc, msg.decode() if msg else "?")
-        self._ws: Optional[torch.Tensor] = None
-        self._cws: Optional[torch.Tensor] = None
-        self._bws: Optional[torch.Tensor] = None          # workspace of the two-branch form (enhance_graphed(branches=2))
-        self._mws: Optional[torch.Tensor] = None          # workspace of metrics()
-        self._rws: dict = {}             # resample(): (fs_in, fs_out) -> workspace (the pair's tap table)
-        self._xws: Optional[torch.Tensor] = None          # workspace of mix()
-        self._iws: Optional[torch.Tensor] = None          # workspace of rir()
-        self._lws: Optional[torch.Tensor] = None          # workspace of speech_level()
+        #: grow-only uint8 workspaces by name (_grow): "main", "branched" (enhance_graphed(branches > 1)), "conformer",
+        #: "metrics", "mix", "rir", "level" and ("resample", fs_in, fs_out), the rate pair's tap table
+        self._wss: dict = {}
         self._graphs: dict = {}          # enhance_graphed: input shape -> (graph, in, out, token)
         self._row_graphs: dict = {}      # streaming.enhance_windows: row shape -> (graph, in, out, token)
         self._stream_slots: dict = {}    # streaming.StreamState(graph=True): (B, W, Ca, La, stats mode) -> state + step graphs
@@ -320,47 +298,65 @@ class Engine:
         self._row_graphs.clear()
         self._stream_slots.clear()
         with torch.cuda.device(self.device):
-            check(self._h, self.lib.cmgan_load_weights(self._h, blob.ctypes.data_as(ctypes.c_void_p), blob.nbytes))
+            native_call(self, "cmgan_load_weights", blob.ctypes.data_as(ctypes.c_void_p), blob.nbytes)
         self.weights_loaded = True
 
     def _stream(self) -> int:
         return torch.cuda.current_stream(self.device).cuda_stream
 
     def _in(self, t: torch.Tensor, name: str) -> torch.Tensor:
-        return _f32c(t, name, self.device)
+        return tensor_arg(t, name, torch.float32, self.device, contiguous=False).contiguous()
+
+    def _call(self, name: str, *args) -> None:
+        """One native call `name(handle, *args, stream)` (native_call) on the current stream of the engine's device, with
+        that device current: the launch goes there whatever device the caller has current."""
+        if torch.cuda.current_device() != self.device.index:
+            with torch.cuda.device(self.device):
+                return self._call(name, *args)
+        native_call(self, name, *args, self._stream())
 
     # ---- workspace -----------------------------------------------------------------
     def _ws_token(self):
         """Identity of what a captured graph's kernel arguments point into: the workspace allocation and the
         weight buffers (cmgan_weights_generation).  A graph whose token differs is stale and is re-captured."""
-        ws = self._ws
+        ws = self._wss.get("main")
         return (ws.data_ptr() if ws is not None else 0, ws.numel() if ws is not None else 0,
                 int(self.lib.cmgan_weights_generation(self._h)))
 
+    def _evict_main(self):
+        # graphs captured on the old allocation are stale AND keep it (multi-GB) alive: evict them all
+        self._graphs = {k: v for k, v in self._graphs.items() if k[1] != 1}
+        self._row_graphs.clear()
+        for slot in self._stream_slots.values():
+            slot.graphs.clear()
+            slot.stage_graphs.clear()
+
+    def _evict_branched(self):
+        self._graphs = {k: v for k, v in self._graphs.items() if k[1] == 1}
+
+    #: what a slot's growth evicts first: the captured graphs whose kernel arguments point into its old allocation
+    _EVICT = {"main": _evict_main, "branched": _evict_branched}
+
+    def _grow(self, slot, need: int, bad: Optional[str] = None) -> torch.Tensor:
+        """The grow-only workspace `slot`: its tensor when it holds `need` bytes, else a new one of that size (the old
+        allocation is dropped first, so the peak is not old + new).  need == 0 with a message `bad`: ValueError(bad)."""
+        if need == 0 and bad is not None:
+            raise ValueError(bad)
+        if slot not in self._wss or self._wss[slot].numel() < need:
+            if slot in self._EVICT:
+                self._EVICT[slot](self)
+            self._wss.pop(slot, None)
+            self._wss[slot] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._wss[slot]
+
     def _workspace(self, B: int, T: int) -> torch.Tensor:
-        need = self.lib.cmgan_workspace_bytes(self._h, B, T)
-        if need == 0:
-            raise ValueError(f"bad batch/frames ({B}, {T})")
-        if self._ws is None or self._ws.numel() < need:
-            # graphs captured on the old allocation are stale AND keep it (multi-GB) alive: evict them all
-            self._graphs = {k: v for k, v in self._graphs.items() if k[1] != 1}
-            self._row_graphs.clear()
-            for slot in self._stream_slots.values():
-                slot.graphs.clear()
-                slot.stage_graphs.clear()
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
+        return self._grow("main", self.lib.cmgan_workspace_bytes(self._h, B, T), f"bad batch/frames ({B}, {T})")
 
     def workspace_bytes(self, B: int, T: int) -> int:
         return int(self.lib.cmgan_workspace_bytes(self._h, B, T))
 
     def _conf_workspace(self, N: int, L: int) -> torch.Tensor:
-        need = self.lib.cmgan_conformer_workspace_bytes(self._h, N, L)
-        if self._cws is None or self._cws.numel() < need:
-            self._cws = None
-            self._cws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._cws
+        return self._grow("conformer", self.lib.cmgan_conformer_workspace_bytes(self._h, N, L))
 
     @property
     def F(self) -> int:
@@ -375,39 +371,37 @@ class Engine:
         wav = self._in(wav, "wav")
         B, L = wav.shape
         out = torch.empty(B, dtype=torch.float32, device=wav.device)
-        check(self._h, self.lib.cmgan_rms_scale(self._h, wav.data_ptr(), B, L, out.data_ptr(), self._stream()))
+        self._call("cmgan_rms_scale", wav, B, L, out)
         return out
 
     @_on_device
     def stft_compress(self, wav: torch.Tensor, scale: Optional[torch.Tensor] = None) -> torch.Tensor:
         wav = self._in(wav, "wav")
         B, L = wav.shape
-        sp = self._in(scale, "scale").data_ptr() if scale is not None else None
+        sp = self._in(scale, "scale") if scale is not None else None
         out = torch.empty(B, 2, self.num_frames(L), self.F, dtype=torch.float32, device=wav.device)
-        check(self._h, self.lib.cmgan_stft_compress(self._h, wav.data_ptr(), sp, B, L, out.data_ptr(), self._stream()))
+        self._call("cmgan_stft_compress", wav, sp, B, L, out)
         return out
 
     @_on_device
     def uncompress_istft(self, real: torch.Tensor, imag: torch.Tensor,
                          scale: Optional[torch.Tensor] = None) -> torch.Tensor:
         real, imag = self._in(real, "real"), self._in(imag, "imag")
-        B, _, T, F = real.shape
-        if F != self.F or imag.shape != real.shape:
-            raise ValueError(f"expected 2 x [B,1,T,{self.F}], got {tuple(real.shape)} / {tuple(imag.shape)}")
+        B, T = self._est_shape(real, imag)
         ws = self._workspace(B, T)
-        sp = self._in(scale, "scale").data_ptr() if scale is not None else None
+        sp = self._in(scale, "scale") if scale is not None else None
         out = torch.empty(B, self.cfg.hop * (T - 1), dtype=torch.float32, device=real.device)
-        check(self._h, self.lib.cmgan_uncompress_istft(self._h, real.data_ptr(), imag.data_ptr(), sp, B, T,
-                                                       out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
+        self._call("cmgan_uncompress_istft", real, imag, sp, B, T, out, ws, ws.numel())
         return out
 
     @_on_device
     def power_compress(self, x: torch.Tensor) -> torch.Tensor:
         x = self._in(x, "x")
-        B, F, T, two = x.shape
-        assert two == 2
+        if x.dim() != 4 or x.size(3) != 2:
+            raise ValueError(f"expected [B,F,T,2], got {tuple(x.shape)}")
+        B, F, T, _ = x.shape
         y = torch.empty(B, 2, F, T, dtype=torch.float32, device=x.device)
-        check(self._h, self.lib.cmgan_power_compress(self._h, x.data_ptr(), B, F, T, y.data_ptr(), self._stream()))
+        self._call("cmgan_power_compress", x, B, F, T, y)
         return y
 
     @_on_device
@@ -415,8 +409,7 @@ class Engine:
         real, imag = self._in(real, "real"), self._in(imag, "imag")
         B, one, F, T = real.shape
         y = torch.empty(B, 1, F, T, 2, dtype=torch.float32, device=real.device)
-        check(self._h, self.lib.cmgan_power_uncompress(self._h, real.data_ptr(), imag.data_ptr(), B, F, T,
-                                                       y.data_ptr(), self._stream()))
+        self._call("cmgan_power_uncompress", real, imag, B, F, T, y)
         return y
 
     # ---- model ---------------------------------------------------------------------
@@ -424,21 +417,43 @@ class Engine:
         if not self.weights_loaded:
             raise RuntimeError("no weights loaded: call load_state_dict() first")
 
+    # ---- the model-layout tensors: spectrogram [B,2,T,F], features [B,T,F',64], estimate 2 x [B,1,T,F] ----
+    def _spec_shape(self, x: torch.Tensor):
+        if x.dim() != 4 or x.size(1) != 2 or x.size(3) != self.F:
+            raise ValueError(f"expected [B,2,T,{self.F}], got {tuple(x.shape)}")
+        return x.size(0), x.size(2)
+
+    def _feat_shape(self, x: torch.Tensor):
+        if x.dim() != 4 or x.size(2) != (self.F + 1) // 2 or x.size(3) != 64:
+            raise ValueError(f"expected [B,T,{(self.F + 1) // 2},64], got {tuple(x.shape)}")
+        return x.size(0), x.size(1)
+
+    def _est_shape(self, real: torch.Tensor, imag: torch.Tensor):
+        if real.dim() != 4 or real.size(3) != self.F or imag.shape != real.shape:
+            raise ValueError(f"expected 2 x [B,1,T,{self.F}], got {tuple(real.shape)} / {tuple(imag.shape)}")
+        return real.size(0), real.size(2)
+
+    def _decoder_shape(self, x: torch.Tensor, spec: torch.Tensor):
+        B, T = self._feat_shape(x)
+        if self._spec_shape(spec) != (B, T):
+            raise ValueError(f"x {tuple(x.shape)} and spec {tuple(spec.shape)} differ in batch or frames")
+        return B, T
+
+    def _est_pair(self, B: int, T: int):
+        real = torch.empty(B, 1, T, self.F, dtype=torch.float32, device=self.device)
+        return real, torch.empty_like(real)
+
     @_on_device
     def tscnet_forward(self, x: torch.Tensor, taps: bool = False):
         self._need_weights()
         x = self._in(x, "x")
-        B, two, T, F = x.shape
-        if two != 2 or F != self.F:
-            raise ValueError(f"expected [B,2,T,{self.F}], got {tuple(x.shape)}")
+        B, T = self._spec_shape(x)
         ws = self._workspace(B, T)
-        real = torch.empty(B, 1, T, F, dtype=torch.float32, device=x.device)
-        imag = torch.empty_like(real)
+        real, imag = self._est_pair(B, T)
         if not taps:
-            check(self._h, self.lib.cmgan_tscnet_forward(self._h, x.data_ptr(), B, T, real.data_ptr(),
-                                                         imag.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
+            self._call("cmgan_tscnet_forward", x, B, T, real, imag, ws, ws.numel())
             return real, imag
-        F2 = (F + 1) // 2
+        F, F2 = self.F, (self.F + 1) // 2
         st = {"encoder": torch.empty(B, 64, T, F2, dtype=torch.float32, device=x.device),
               "mask": torch.empty(B, 1, T, F, dtype=torch.float32, device=x.device),
               "complex": torch.empty(B, 2, T, F, dtype=torch.float32, device=x.device)}
@@ -448,9 +463,7 @@ class Engine:
             st[f"tscb{k + 1}"] = torch.empty(B, 64, T, F2, dtype=torch.float32, device=x.device)
             tp.tscb_dev[k] = st[f"tscb{k + 1}"].data_ptr()
         tp.mask_dev, tp.complex_dev = st["mask"].data_ptr(), st["complex"].data_ptr()
-        check(self._h, self.lib.cmgan_tscnet_forward_taps(self._h, x.data_ptr(), B, T, real.data_ptr(),
-                                                          imag.data_ptr(), ctypes.byref(tp), ws.data_ptr(),
-                                                          ws.numel(), self._stream()))
+        self._call("cmgan_tscnet_forward_taps", x, B, T, real, imag, tp, ws, ws.numel())
         return real, imag, st
 
     # ---- frozen-statistics / sliced forms (streaming with carried state; include/cmgan_hip.h, "Streaming") ----
@@ -463,17 +476,11 @@ class Engine:
         reference's arithmetic).  Returns (real, imag, blob of the statistics this call used or None)."""
         self._need_weights()
         x = self._in(x, "x")
-        B, two, T, F = x.shape
-        if two != 2 or F != self.F:
-            raise ValueError(f"expected [B,2,T,{self.F}], got {tuple(x.shape)}")
+        B, T = self._spec_shape(x)
         ws = self._workspace(B, T)
-        real = torch.empty(B, 1, T, F, dtype=torch.float32, device=x.device)
-        imag = torch.empty_like(real)
-        fz = self._stats_arg(frozen, B)
+        real, imag = self._est_pair(B, T)
         out = torch.empty(self.stats_floats(B), dtype=torch.float32, device=x.device) if export else None
-        check(self._h, self.lib.cmgan_tscnet_forward_stats(self._h, x.data_ptr(), B, T, real.data_ptr(), imag.data_ptr(),
-                                                           fz, out.data_ptr() if export else None, ws.data_ptr(),
-                                                           ws.numel(), self._stream()))
+        self._call("cmgan_tscnet_forward_stats", x, B, T, real, imag, self._stats_arg(frozen, B), out, ws, ws.numel())
         return real, imag, out
 
     def _stats_arg(self, stats: Optional[torch.Tensor], B: int):
@@ -482,14 +489,21 @@ class Engine:
         stats = self._in(stats, "stats")
         if stats.numel() != self.stats_floats(B):
             raise ValueError(f"statistics blob has {stats.numel()} floats, a batch of {B} rows needs {self.stats_floats(B)}")
-        return stats.data_ptr()
+        return stats
 
     def _own_ws(self, ws: Optional[torch.Tensor], B: int, T: int) -> torch.Tensor:
         if ws is None:
             return self._workspace(B, T)
-        if not ws.is_cuda or ws.dtype != torch.uint8 or ws.numel() < self.workspace_bytes(B, T):
-            raise ValueError("ws must be a uint8 GPU tensor of at least workspace_bytes(B, T) bytes")
-        return ws
+        need = self.workspace_bytes(B, T)
+        return tensor_arg(ws, "ws", torch.uint8, self.device, f"at least workspace_bytes({B}, {T}) = {need} bytes",
+                          lambda t: t.numel() >= need, error=ValueError)
+
+    def _feat_out(self, out: Optional[torch.Tensor], B: int, T: int) -> torch.Tensor:
+        """The [B,T,F',64] result of the stream encoders: a new tensor, or the caller's (the kernel writes it in place)."""
+        want = (B, T, (self.F + 1) // 2, 64)
+        if out is None:
+            return torch.empty(want, dtype=torch.float32, device=self.device)
+        return tensor_arg(out, "out", torch.float32, self.device, f"[B,T,F',64] = {want}", lambda t: tuple(t.shape) == want)
 
     @_on_device
     def stream_encoder(self, spec: torch.Tensor, stats: torch.Tensor, out: Optional[torch.Tensor] = None,
@@ -498,18 +512,10 @@ class Engine:
         caller's instead of the engine's (lets the call run on another stream beside a step's TSCBs)."""
         self._need_weights()
         spec = self._in(spec, "spec")
-        B, two, T, F = spec.shape
-        if two != 2 or F != self.F:
-            raise ValueError(f"expected [B,2,T,{self.F}], got {tuple(spec.shape)}")
+        B, T = self._spec_shape(spec)
         ws = self._own_ws(ws, B, T)
-        want = (B, T, (F + 1) // 2, 64)
-        if out is None:
-            out = torch.empty(want, dtype=torch.float32, device=spec.device)
-        elif not out.is_contiguous() or tuple(out.shape) != want:
-            raise ValueError(f"out must be a contiguous [B,T,F',64] = {want} tensor (the kernel writes it in place), "
-                             f"got {tuple(out.shape)}{'' if out.is_contiguous() else ' (non-contiguous)'}")
-        check(self._h, self.lib.cmgan_stream_encoder(self._h, spec.data_ptr(), B, T, self._stats_arg(stats, B),
-                                                     self._in(out, "out").data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
+        out = self._feat_out(out, B, T)
+        self._call("cmgan_stream_encoder", spec, B, T, self._stats_arg(stats, B), out, ws, ws.numel())
         return out
 
     @_on_device
@@ -519,11 +525,9 @@ class Engine:
         if not x.is_contiguous():
             raise ValueError("stream_tscb works in place: x must be contiguous")
         x = self._in(x, "x")
-        B, T, F2, C = x.shape
-        if C != 64 or F2 != (self.F + 1) // 2:
-            raise ValueError(f"expected [B,T,{(self.F + 1) // 2},64], got {tuple(x.shape)}")
+        B, T = self._feat_shape(x)
         ws = self._workspace(B, T)
-        check(self._h, self.lib.cmgan_stream_tscb(self._h, x.data_ptr(), B, T, ws.data_ptr(), ws.numel(), self._stream()))
+        self._call("cmgan_stream_tscb", x, B, T, ws, ws.numel())
         return x
 
     @_on_device
@@ -533,35 +537,27 @@ class Engine:
         engine's - what lets a decoder call run on another stream BESIDE the next step's encoder / TSCBs."""
         self._need_weights()
         x, spec = self._in(x, "x"), self._in(spec, "spec")
-        B, T, F2, C = x.shape
-        if tuple(spec.shape) != (B, 2, T, self.F) or C != 64 or F2 != (self.F + 1) // 2:
-            raise ValueError(f"expected x [B,T,{(self.F + 1) // 2},64] and spec [B,2,T,{self.F}]")
+        B, T = self._decoder_shape(x, spec)
         ws = self._own_ws(ws, B, T)
-        real = torch.empty(B, 1, T, self.F, dtype=torch.float32, device=x.device)
-        imag = torch.empty_like(real)
-        check(self._h, self.lib.cmgan_stream_decoder(self._h, x.data_ptr(), spec.data_ptr(), B, T, self._stats_arg(stats, B),
-                                                     real.data_ptr(), imag.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                     self._stream()))
+        real, imag = self._est_pair(B, T)
+        self._call("cmgan_stream_decoder", x, spec, B, T, self._stats_arg(stats, B), real, imag, ws, ws.numel())
         return real, imag
 
     # ---- running-statistics forms (include/cmgan_hip.h, "Streaming": running statistics) ----
     def stream_sums_doubles(self, B: int) -> int:
         return int(self.lib.cmgan_stream_sums_doubles(self._h, B))
 
-    def _sums_arg(self, sums: torch.Tensor, B: int) -> int:
-        if (not isinstance(sums, torch.Tensor) or sums.device != self.device or sums.dtype != torch.float64
-                or not sums.is_contiguous() or sums.numel() != self.stream_sums_doubles(B)):
-            raise ValueError(f"sums must be a contiguous float64 tensor on {self.device} of stream_sums_doubles({B}) = "
-                             f"{self.stream_sums_doubles(B)} elements")
-        return sums.data_ptr()
+    def _sums_arg(self, sums: torch.Tensor, B: int) -> torch.Tensor:
+        n = self.stream_sums_doubles(B)
+        return tensor_arg(sums, "sums", torch.float64, self.device, f"stream_sums_doubles({B}) = {n} elements",
+                          lambda t: t.numel() == n, error=ValueError)
 
-    def _stats_out_arg(self, stats_out: Optional[torch.Tensor], B: int):
+    def _stats_out_arg(self, stats_out: Optional[torch.Tensor], B: int) -> Optional[torch.Tensor]:
         if stats_out is None:
             return None
-        if (stats_out.device != self.device or stats_out.dtype != torch.float32 or not stats_out.is_contiguous()
-                or stats_out.numel() != self.stats_floats(B)):
-            raise ValueError(f"stats_out must be a contiguous float32 tensor on {self.device} of stats_floats({B}) elements")
-        return stats_out.data_ptr()
+        n = self.stats_floats(B)
+        return tensor_arg(stats_out, "stats_out", torch.float32, self.device, f"stats_floats({B}) = {n} elements",
+                          lambda t: t.numel() == n, error=ValueError)
 
     @_on_device
     def stream_encoder_running(self, spec: torch.Tensor, hist: int, sums: torch.Tensor, out: Optional[torch.Tensor] = None,
@@ -571,19 +567,11 @@ class Engine:
         `stats_out` (float32, stats_floats(B)) receives the encoder's part of the statistics blob this call used."""
         self._need_weights()
         spec = self._in(spec, "spec")
-        B, two, T, F = spec.shape
-        if two != 2 or F != self.F:
-            raise ValueError(f"expected [B,2,T,{self.F}], got {tuple(spec.shape)}")
+        B, T = self._spec_shape(spec)
         ws = self._own_ws(ws, B, T)
-        want = (B, T, (F + 1) // 2, 64)
-        if out is None:
-            out = torch.empty(want, dtype=torch.float32, device=spec.device)
-        elif not out.is_contiguous() or tuple(out.shape) != want:
-            raise ValueError(f"out must be a contiguous [B,T,F',64] = {want} tensor, got {tuple(out.shape)}")
-        check(self._h, self.lib.cmgan_stream_encoder_running(self._h, spec.data_ptr(), B, T, int(hist),
-                                                             self._sums_arg(sums, B), self._stats_out_arg(stats_out, B),
-                                                             self._in(out, "out").data_ptr(), ws.data_ptr(), ws.numel(),
-                                                             self._stream()))
+        out = self._feat_out(out, B, T)
+        self._call("cmgan_stream_encoder_running", spec, B, T, int(hist), self._sums_arg(sums, B),
+                   self._stats_out_arg(stats_out, B), out, ws, ws.numel())
         return out
 
     @_on_device
@@ -594,16 +582,11 @@ class Engine:
         the decoders' part of the statistics blob this call used."""
         self._need_weights()
         x, spec = self._in(x, "x"), self._in(spec, "spec")
-        B, T, F2, C = x.shape
-        if tuple(spec.shape) != (B, 2, T, self.F) or C != 64 or F2 != (self.F + 1) // 2:
-            raise ValueError(f"expected x [B,T,{(self.F + 1) // 2},64] and spec [B,2,T,{self.F}]")
+        B, T = self._decoder_shape(x, spec)
         ws = self._own_ws(ws, B, T)
-        real = torch.empty(B, 1, T, self.F, dtype=torch.float32, device=x.device)
-        imag = torch.empty_like(real)
-        check(self._h, self.lib.cmgan_stream_decoder_running(self._h, x.data_ptr(), spec.data_ptr(), B, T, int(hist),
-                                                             self._sums_arg(sums, B), self._stats_out_arg(stats_out, B),
-                                                             real.data_ptr(), imag.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                             self._stream()))
+        real, imag = self._est_pair(B, T)
+        self._call("cmgan_stream_decoder_running", x, spec, B, T, int(hist), self._sums_arg(sums, B),
+                   self._stats_out_arg(stats_out, B), real, imag, ws, ws.numel())
         return real, imag
 
     @_on_device
@@ -618,18 +601,14 @@ class Engine:
         y = torch.empty_like(x)
         tp = torch.empty(4, N, L, 64, dtype=torch.float32, device=x.device) if taps else None
         if mask is None:
-            check(self._h, self.lib.cmgan_conformer_forward(self._h, index, x.data_ptr(), N, L, y.data_ptr(),
-                                                            tp.data_ptr() if taps else None, ws.data_ptr(),
-                                                            ws.numel(), self._stream()))
+            self._call("cmgan_conformer_forward", index, x, N, L, y, tp, ws, ws.numel())
         else:
             if tuple(mask.shape) != (N, L):
                 raise ValueError(f"mask must be [N, L] = [{N}, {L}], got {tuple(mask.shape)}")
             if mask.device != x.device:
                 raise ValueError(f"mask is on {mask.device}, x on {x.device}")
             mk = (mask != 0).to(torch.uint8).contiguous()
-            check(self._h, self.lib.cmgan_conformer_forward_masked(self._h, index, x.data_ptr(), N, L, mk.data_ptr(),
-                                                                   y.data_ptr(), tp.data_ptr() if taps else None,
-                                                                   ws.data_ptr(), ws.numel(), self._stream()))
+            self._call("cmgan_conformer_forward_masked", index, x, N, L, mk, y, tp, ws, ws.numel())
         return (y, tp) if taps else y
 
     @_on_device
@@ -640,8 +619,7 @@ class Engine:
         B, L = wav.shape
         ws = self._workspace(B, self.num_frames(L))
         out = torch.empty_like(wav)
-        check(self._h, self.lib.cmgan_enhance(self._h, wav.data_ptr(), B, L, out.data_ptr(), ws.data_ptr(),
-                                              ws.numel(), self._stream()))
+        self._call("cmgan_enhance", wav, B, L, out, ws, ws.numel())
         return out
 
     # ---- hipGraph replay of the whole pipeline -------------------------------------------
@@ -657,22 +635,15 @@ class Engine:
     def _enhance_call(self, wav, out, B, L, branches: int, offset: int):
         if branches == 1:
             ws = self._workspace(B, self.num_frames(L))
-            check(self._h, self.lib.cmgan_enhance(self._h, wav.data_ptr(), B, L, out.data_ptr(), ws.data_ptr(),
-                                                  ws.numel(), self._stream()))
+            self._call("cmgan_enhance", wav, B, L, out, ws, ws.numel())
         else:
             ws = self._branched_workspace(B, self.num_frames(L), branches)
-            check(self._h, self.lib.cmgan_enhance_branched(self._h, wav.data_ptr(), B, L, out.data_ptr(), ws.data_ptr(),
-                                                           ws.numel(), self._stream(), branches, offset))
+            with torch.cuda.device(self.device):           # (the one entry point whose stream is not its last argument)
+                native_call(self, "cmgan_enhance_branched", wav, B, L, out, ws, ws.numel(), self._stream(), branches, offset)
 
     def _branched_workspace(self, B: int, T: int, branches: int) -> torch.Tensor:
-        need = self.lib.cmgan_workspace_bytes_branched(self._h, B, T, branches)
-        if need == 0:
-            raise ValueError(f"bad batch / frames / branches ({B}, {T}, {branches})")
-        if self._bws is None or self._bws.numel() < need:
-            self._graphs = {k: v for k, v in self._graphs.items() if k[1] == 1}
-            self._bws = None
-            self._bws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._bws
+        return self._grow("branched", self.lib.cmgan_workspace_bytes_branched(self._h, B, T, branches),
+                          f"bad batch / frames / branches ({B}, {T}, {branches})")
 
     def _branch_args(self, B: int, branches: Optional[int], offset: Optional[int]):
         import os
@@ -699,6 +670,35 @@ class Engine:
         return out
 
     @_on_device
+    def _capture(self, body, restore=(), stream=None):
+        """body() captured into a hipGraph -> (graph, what body returned).  THE protocol of every captured graph here:
+        warm-up outside capture on a side stream (allocator pools, workspace growth, first-launch set-up), with the
+        device idle before and after; `restore` - the state a run of the body modifies - is put back after the warm-up
+        and again after the capture.  `stream`: where the graph will be replayed (default: the current stream); it is
+        captured there unless that is the device's default stream, which cannot capture - torch's own capture stream does
+        it then.  The workspace may have grown in here: callers read _ws_token() AFTER this returns."""
+        dev = self.device
+        stream = torch.cuda.current_stream(dev) if stream is None else stream
+        torch.cuda.synchronize(dev)
+        saved = [t.clone() for t in restore]
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(stream)
+        with torch.cuda.stream(side):
+            body()
+        stream.wait_stream(side)
+        torch.cuda.synchronize(dev)
+        for dst, src in zip(restore, saved):
+            dst.copy_(src)
+        torch.cuda.synchronize(dev)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=None if stream == torch.cuda.default_stream(dev) else stream):
+            outs = body()
+        for dst, src in zip(restore, saved):                   # (capture does not execute, but keep the rule simple)
+            dst.copy_(src)
+        torch.cuda.synchronize(dev)
+        return graph, outs
+
+    @_on_device
     def enhance_graphed(self, wav: torch.Tensor, branches: Optional[int] = None, offset: Optional[int] = None) -> torch.Tensor:
         """Same result as enhance(), but the ~250 kernel launches of cmgan_enhance are captured once
         per input shape into a hipGraph (torch.cuda.CUDAGraph on the capture stream) and replayed:
@@ -721,15 +721,7 @@ class Engine:
         if ent is None:
             g_in, g_out = torch.empty_like(wav), torch.empty_like(wav)
             g_in.copy_(wav)
-            side = torch.cuda.Stream(device=self.device)
-            side.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(side):                       # warm-up outside capture
-                self._enhance_call(g_in, g_out, B, L, branches, offset)
-            torch.cuda.current_stream(self.device).wait_stream(side)
-            torch.cuda.synchronize(self.device)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                self._enhance_call(g_in, g_out, B, L, branches, offset)
+            graph, _ = self._capture(lambda: self._enhance_call(g_in, g_out, B, L, branches, offset))
             ent = (graph, g_in, g_out, token)
             self._graphs[key] = ent
         graph, g_in, g_out, _ = ent
@@ -751,23 +743,19 @@ class Engine:
         if any(t is None for t in audio) and not all(t is None for t in audio):
             raise ValueError("the time term needs est_audio and clean_audio together")
         B = T = L = 0
-        ptr = [None] * 5
         if spec[0] is not None:
-            er, ei, cs = (self._in(t, n) for t, n in zip(spec, ("est_real", "est_imag", "clean_spec")))
-            B, _, T, F = er.shape
-            if F != self.F or ei.shape != er.shape or tuple(cs.shape) != (B, 2, T, F):
+            spec = [self._in(t, n) for t, n in zip(spec, ("est_real", "est_imag", "clean_spec"))]
+            B, T = self._est_shape(spec[0], spec[1])
+            if self._spec_shape(spec[2]) != (B, T):
                 raise ValueError(f"expected est [B,1,T,{self.F}] x2 and clean_spec [B,2,T,{self.F}]")
-            ptr[0:3] = [er.data_ptr(), ei.data_ptr(), cs.data_ptr()]
         if audio[0] is not None:
-            ea, ca = self._in(audio[0], "est_audio"), self._in(audio[1], "clean_audio")
+            audio = ea, ca = [self._in(audio[0], "est_audio"), self._in(audio[1], "clean_audio")]
             if ea.shape != ca.shape or ea.dim() != 2 or (B and ea.size(0) != B):
                 raise ValueError("est_audio / clean_audio must both be [B, L]")
             B, L = ea.shape
-            ptr[3:5] = [ea.data_ptr(), ca.data_ptr()]
         if out is None:
             out = torch.empty(4, dtype=torch.float32, device=self.device)
-        check(self._h, self.lib.cmgan_loss_terms(self._h, ptr[0], ptr[1], ptr[2], B, T, ptr[3], ptr[4], L,
-                                                 self._in(out, "out").data_ptr(), self._stream()))
+        self._call("cmgan_loss_terms", *spec, B, T, *audio, L, self._in(out, "out"))
         return out
 
     # ---- objective metrics ---------------------------------------------------------
@@ -800,23 +788,18 @@ class Engine:
             if rc < 0:
                 raise _lib.CmganError(rc, f"unsupported sample rate {fs} (16000 or 8000)")
             raise ValueError(f"[{B}, {L}] at fs={fs} is too short to score (one 30-frame STOI window is needed)")
-        if self._mws is None or self._mws.numel() < need:
-            self._mws = None
-            self._mws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        pesq_ptr = None
+        ws = self._grow("metrics", need)
+        pesq = None
         if pesq_mos is not None:
             if isinstance(pesq_mos, torch.Tensor):
                 pesq = pesq_mos.to(device=self.device, dtype=torch.float64).reshape(-1).expand(B).contiguous()
             else:
                 pesq = torch.full((B,), float(pesq_mos), dtype=torch.float64, device=self.device)
-            pesq_ptr = pesq.data_ptr()
         scores = torch.empty(B, 9, dtype=torch.float64, device=self.device)
         nfw, nfl = metric_frames(L, fs)
         nf = max(nfw, nfl)
         frames = torch.empty(B, 3, nf, dtype=torch.float64, device=self.device) if per_frame else None
-        check(self._h, self.lib.cmgan_metrics(self._h, clean.data_ptr(), enhanced.data_ptr(), B, L, fs, pesq_ptr,
-                                              offset, scores.data_ptr(), frames.data_ptr() if per_frame else None,
-                                              self._mws.data_ptr(), self._mws.numel(), self._stream()))
+        self._call("cmgan_metrics", clean, enhanced, B, L, fs, pesq, offset, scores, frames, ws, ws.numel())
         out = DeviceScores(*scores.unbind(1))
         if not per_frame:
             return out
@@ -824,14 +807,14 @@ class Engine:
 
     # ---- sample-rate conversion ----------------------------------------------------
     def _resample_ws(self, fs_in: int, fs_out: int) -> torch.Tensor:
-        ws = self._rws.get((fs_in, fs_out))
+        ws = self._wss.get(("resample", fs_in, fs_out))
         if ws is None:
             need = int(self.lib.cmgan_resample_workspace_bytes(self._h, fs_in, fs_out))
             if need == 0:
                 from .resample import geometry
                 geometry(fs_in, fs_out)                       # raises CmganError with the library's message
             # one allocation per rate pair, kept: a captured graph's kernel arguments point into it
-            ws = self._rws[(fs_in, fs_out)] = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ws = self._grow(("resample", fs_in, fs_out), need)
         return ws
 
     @_on_device
@@ -847,16 +830,15 @@ class Engine:
         ws = self._resample_ws(fs_in, fs_out)
         if out is None:
             out = torch.empty(B, n_out, dtype=torch.float32, device=self.device)
-        elif (out.device != self.device or out.dtype != torch.float32 or not out.is_contiguous()
-                or tuple(out.shape) != (B, n_out)):
-            raise ValueError(f"out must be a contiguous float32 [{B}, {n_out}] tensor on {self.device}")
+        else:
+            tensor_arg(out, "out", torch.float32, self.device, f"[{B}, {n_out}]", lambda t: tuple(t.shape) == (B, n_out),
+                       error=ValueError)
         if B == 0 or n_out == 0:
             return out
         if n_buf == 0:                                        # no sample at all: every output is a sum of zeros
             return out.zero_()
-        check(self._h, self.lib.cmgan_resample(self._h, buf.data_ptr(), B, n_buf, n_buf, int(pos_in), fs_in, fs_out,
-                                               int(n0), int(n_out), out.data_ptr(), n_out, ws.data_ptr(), ws.numel(),
-                                               self._stream()))
+        self._call("cmgan_resample", buf, B, n_buf, n_buf, int(pos_in), fs_in, fs_out, int(n0), int(n_out), out, n_out, ws,
+                   ws.numel())
         return out
 
     def resample(self, wav: torch.Tensor, fs_in: int, fs_out: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -886,22 +868,14 @@ class Engine:
         bit-reproducible, row-independent, no synchronisation, graph-capturable after one call at the shape."""
         B, L, R, Kmax = check_mix_args(self.device, clean, noise_bank, noise_start, noise_len, noise_off, snr_db, rir_bank,
                                        rir_index, rir_len, peak, early)
-        need = int(self.lib.cmgan_mix_workspace_bytes(self._h, B, L, max(Kmax, 1)))
-        if need == 0:
-            raise ValueError(f"[{B}, {L}] with {Kmax} taps is outside what cmgan_mix supports")
-        if self._xws is None or self._xws.numel() < need:
-            self._xws = None
-            self._xws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._grow("mix", int(self.lib.cmgan_mix_workspace_bytes(self._h, B, L, max(Kmax, 1))),
+                        f"[{B}, {L}] with {Kmax} taps is outside what cmgan_mix supports")
         noisy = torch.empty(B, L, dtype=torch.float32, device=self.device)
         target = torch.empty(B, L, dtype=torch.float32, device=self.device)
         info = torch.empty(4, B, dtype=torch.float64, device=self.device)
-        rir = rir_bank is not None
-        check(self._h, self.lib.cmgan_mix(
-            self._h, clean.data_ptr(), B, L, L, noise_bank.data_ptr(), noise_bank.numel(), noise_start.data_ptr(),
-            noise_len.data_ptr(), noise_off.data_ptr(), rir_bank.data_ptr() if rir else None, R, Kmax,
-            rir_index.data_ptr() if rir else None, rir_len.data_ptr() if rir else None, snr_db.data_ptr(), float(peak),
-            int(early), noisy.data_ptr(), target.data_ptr(), L, info[0].data_ptr(), info[1].data_ptr(),
-            info[2].data_ptr(), info[3].data_ptr(), self._xws.data_ptr(), self._xws.numel(), self._stream()))
+        self._call("cmgan_mix", clean, B, L, L, noise_bank, noise_bank.numel(), noise_start, noise_len, noise_off, rir_bank, R,
+                   Kmax, rir_index, rir_len, snr_db, float(peak), int(early), noisy, target, L, info[0], info[1], info[2],
+                   info[3], ws, ws.numel())
         return noisy, target, MixInfo(info[0], info[1], info[2], info[3])
 
     # ---- room impulse responses ----------------------------------------------------
@@ -919,19 +893,14 @@ class Engine:
         size <= 0, a coefficient outside [0, 1]) is zeros with length 1.  Float64 arithmetic, one rounding to float32;
         bit-reproducible, row-independent, no synchronisation, graph-capturable after one call at the shape."""
         R, K, N = check_rir_args(self.device, rooms, n_taps, K, n_images, fs, c, tw, out)
-        need = int(self.lib.cmgan_rir_workspace_bytes(self._h, R, K, int(tw)))
-        if need == 0:
-            raise ValueError(f"[{R}, {K}] with tw = {tw} is outside what cmgan_rir supports")
-        if self._iws is None or self._iws.numel() < need:
-            self._iws = None
-            self._iws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._grow("rir", int(self.lib.cmgan_rir_workspace_bytes(self._h, R, K, int(tw))),
+                        f"[{R}, {K}] with tw = {tw} is outside what cmgan_rir supports")
         if out is None:
             out = (torch.empty(R, K, dtype=torch.float32, device=self.device),
                    torch.empty(R, dtype=torch.int32, device=self.device))
         rir, length = out
-        check(self._h, self.lib.cmgan_rir(self._h, rooms.data_ptr(), n_taps.data_ptr(), R, K, int(fs), float(c), int(tw),
-                                          N[0], N[1], N[2], rir.data_ptr(), K, length.data_ptr(), self._iws.data_ptr(),
-                                          self._iws.numel(), self._stream()))
+        self._call("cmgan_rir", rooms, n_taps, R, K, int(fs), float(c), int(tw), N[0], N[1], N[2], rir, K, length, ws,
+                   ws.numel())
         return rir, length
 
     # ---- active speech level -------------------------------------------------------
@@ -948,18 +917,12 @@ class Engine:
         2^-15 .. 2^-1 and the row's length.  Float64 arithmetic; bit-reproducible, row-independent, no synchronisation,
         graph-capturable after one call at the shape."""
         B, L = check_level_args(self.device, wav, lengths, fs)
-        need = int(self.lib.cmgan_speech_level_workspace_bytes(B, L))
-        if need == 0:
-            raise ValueError(f"[{B}, {L}] is outside what cmgan_speech_level supports")
-        if self._lws is None or self._lws.numel() < need:
-            self._lws = None
-            self._lws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._grow("level", int(self.lib.cmgan_speech_level_workspace_bytes(B, L)),
+                        f"[{B}, {L}] is outside what cmgan_speech_level supports")
         level = torch.empty(B, 3, dtype=torch.float64, device=self.device)
         cnt = torch.empty(B, 16, dtype=torch.int64, device=self.device) if counts else None
-        check(self._h, self.lib.cmgan_speech_level(
-            self._h, wav.data_ptr(), B, L, wav.stride(0) if B > 1 else L, lengths.data_ptr() if lengths is not None else None,
-            int(fs), level.data_ptr(), cnt.data_ptr() if counts else None, self._lws.data_ptr(), self._lws.numel(),
-            self._stream()))
+        self._call("cmgan_speech_level", wav, B, L, wav.stride(0) if B > 1 else L, lengths, int(fs), level, cnt, ws,
+                   ws.numel())
         out = SpeechLevel(level[:, 0], level[:, 1], level[:, 2])
         return (out, cnt) if counts else out
 
@@ -967,13 +930,13 @@ class Engine:
     @_on_device
     def selftest_mfma(self) -> float:
         err = ctypes.c_float()
-        check(self._h, self.lib.cmgan_selftest_mfma(self._h, ctypes.byref(err)))
+        native_call(self, "cmgan_selftest_mfma", ctypes.byref(err))
         return float(err.value)
 
     @_on_device
     def selftest_mfma_x3(self) -> float:
         err = ctypes.c_float()
-        check(self._h, self.lib.cmgan_selftest_mfma_x3(self._h, ctypes.byref(err)))
+        native_call(self, "cmgan_selftest_mfma_x3", ctypes.byref(err))
         return float(err.value)
 
     def release_workspaces(self):
@@ -982,11 +945,10 @@ class Engine:
         self._graphs.clear()
         self._row_graphs.clear()
         self._stream_slots.clear()
-        self._ws = self._bws = self._cws = self._mws = self._xws = self._iws = self._lws = None
-        self._rws.clear()
+        self._wss.clear()
 
     def set_profiling(self, on: bool):
-        check(self._h, self.lib.cmgan_set_profiling(self._h, 1 if on else 0))
+        native_call(self, "cmgan_set_profiling", 1 if on else 0)
 
     def profile(self):
         """[(kernel name, ms)] of the most recent forward (profiling must be on)."""

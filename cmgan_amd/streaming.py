@@ -62,29 +62,19 @@ def enhance_windows(model: TSCNet, noisy: torch.Tensor, window: int = 40000, con
 def _enhance_rows(model: TSCNet, rows: torch.Tensor, graph: bool) -> torch.Tensor:
     """One reference row pipeline (stft -> compress -> TSCNet -> uncompress -> istft) on already scaled rows."""
     eng = model.engine
+
+    def body(x):
+        return eng.uncompress_istft(*model(eng.stft_compress(x)))
+
     if not graph:
-        spec = eng.stft_compress(rows)
-        real, imag = model(spec)
-        return eng.uncompress_istft(real, imag)
+        return body(rows)
     key = ("rows",) + tuple(rows.shape)
     cache = eng._row_graphs
     ent = cache.get(key)
     if ent is None or ent[3] != eng._ws_token():
         g_in = torch.empty_like(rows)
         g_in.copy_(rows)
-        side = torch.cuda.Stream(device=rows.device)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                           # warm-up outside capture (allocates the workspace)
-            spec = eng.stft_compress(g_in)
-            real, imag = model(spec)
-            eng.uncompress_istft(real, imag)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            spec = eng.stft_compress(g_in)
-            real, imag = model(spec)
-            g_out = eng.uncompress_istft(real, imag)
+        g, g_out = eng._capture(lambda: body(g_in))             # (the warm-up allocates the workspace)
         ent = (g, g_in, g_out, eng._ws_token())
         while len(cache) >= 8:                                  # one entry per (batch, span): a few configurations, oldest out
             cache.pop(next(iter(cache)))
@@ -322,30 +312,14 @@ class StreamState:
 
     def _step_graphed(self, spec_new, sig):
         sl, eng = self.slot, self.eng
-        token = eng._ws_token()
         ent = sl.graphs.pop(sig, None)
-        if ent is not None and ent[4] != token:
+        if ent is not None and ent[4] != eng._ws_token():
             ent = None
         if ent is None:
             spec_in = spec_new.contiguous().clone()
-            # warm-up outside capture on COPIES of the state (a step updates it): allocator pools, workspace growth
-            saved = (sl.S.clone(), sl.E.clone(), sl.D.clone(), sl.sums.clone())
-            side = torch.cuda.Stream(device=eng.device)
-            side.wait_stream(torch.cuda.current_stream(eng.device))
-            with torch.cuda.stream(side):
-                self._graph_body(sl, spec_in, sig)
-            torch.cuda.current_stream(eng.device).wait_stream(side)
-            torch.cuda.synchronize(eng.device)
-            token = eng._ws_token()                                    # (the warm-up may have grown the workspace)
-            for dst, src in zip((sl.S, sl.E, sl.D, sl.sums), saved):
-                dst.copy_(src)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                out_r, out_i = self._graph_body(sl, spec_in, sig)
-            for dst, src in zip((sl.S, sl.E, sl.D, sl.sums), saved):            # (capture does not execute, but keep the rule simple)
-                dst.copy_(src)
-            del saved
-            ent = (g, spec_in, out_r, out_i, token)
+            g, (out_r, out_i) = eng._capture(lambda: self._graph_body(sl, spec_in, sig),      # (a step updates the state)
+                                             restore=(sl.S, sl.E, sl.D, sl.sums))
+            ent = (g, spec_in, out_r, out_i, eng._ws_token())
         sl.graphs[sig] = ent                                           # most recently used last
         while len(sl.graphs) > _StreamSlot.MAX_GRAPHS:
             sl.graphs.pop(next(iter(sl.graphs)))
@@ -389,34 +363,13 @@ class StreamState:
         return real[:, :, h_dec:], imag[:, :, h_dec:]
 
     def _captured(self, sl: _StreamSlot, key, body, stream, restore=()):
-        """LRU-cached hipGraph of one stage (warm-up outside capture; `restore`: state a run of the body modifies)."""
+        """LRU-cached hipGraph of one stage (Engine._capture; `restore`: state a run of the body modifies)."""
         eng = self.eng
-        token = eng._ws_token()
         ent = sl.stage_graphs.pop(key, None)
-        if ent is not None and ent[2] != token:
+        if ent is not None and ent[2] != eng._ws_token():
             ent = None
         if ent is None:
-            torch.cuda.synchronize(eng.device)                         # the other stages are idle while this one is captured
-            saved = [t.clone() for t in restore]
-            side = torch.cuda.Stream(device=eng.device)
-            side.wait_stream(stream)
-            with torch.cuda.stream(side):
-                body()
-            stream.wait_stream(side)
-            torch.cuda.synchronize(eng.device)
-            for dst, src in zip(restore, saved):
-                dst.copy_(src)
-            torch.cuda.synchronize(eng.device)
-            g = torch.cuda.CUDAGraph()
-            # (a graph cannot be captured ON the default stream - the caller's, for the middle stage; torch's own capture
-            # stream does it then; replaying on the default stream is fine)
-            cap = None if stream == torch.cuda.default_stream(eng.device) else stream
-            with torch.cuda.graph(g, stream=cap):
-                outs = body()
-            for dst, src in zip(restore, saved):                       # (capture does not execute, but keep the rule simple)
-                dst.copy_(src)
-            torch.cuda.synchronize(eng.device)
-            ent = (g, outs, eng._ws_token())
+            ent = eng._capture(body, restore, stream) + (eng._ws_token(),)
         sl.stage_graphs[key] = ent                                     # most recently used last
         while len(sl.stage_graphs) > 3 * _StreamSlot.MAX_GRAPHS:
             sl.stage_graphs.pop(next(iter(sl.stage_graphs)))

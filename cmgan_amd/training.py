@@ -51,13 +51,11 @@ draws the dropout masks with torch's generator (plumbing) and passes pointers.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, Optional, Tuple
 
 import torch
 
-from ._lib import (AttnParams, ConvModParams, DecoderParams, DenseParams, DiscParams, EncoderParams, FfnParams,
-                   check)
+from ._lib import (AttnParams, ConvModParams, DecoderParams, DenseParams, DiscParams, EncoderParams, FfnParams)
 from .dist import FlatBucket, all_agree, allreduce_mean, broadcast_from_rank0, get_rank
 from .engine import Engine
 
@@ -157,21 +155,10 @@ def _engine(engine: Optional[Engine], device) -> Engine:
     return engine if engine is not None else Engine(device=device)
 
 
-def _launch(eng, name: str, *args) -> None:
-    """One native call `name(handle, *args, stream)` with the engine's device current (what `_on_device` does for the
-    Engine's own methods: the launch goes to eng's device whatever device the caller has current), checked.  A tensor
-    goes as its device pointer - an optional tensor that is None as a null pointer -, a parameter struct by reference,
-    everything else as it is."""
-    args = [a.data_ptr() if isinstance(a, torch.Tensor) else ctypes.byref(a) if isinstance(a, ctypes.Structure) else a
-            for a in args]
-    with torch.cuda.device(eng.device):
-        check(eng._h, getattr(eng.lib, name)(eng._h, *args, eng._stream()))
-
-
 def _add(eng, a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """a + b as one launch, into `out` (which may be `a`) or a new tensor."""
     out = torch.empty_like(a) if out is None else out
-    _launch(eng, "cmgan_add", a, b, out, a.numel())
+    eng._call("cmgan_add", a, b, out, a.numel())
     return out
 
 
@@ -256,8 +243,8 @@ class FeedForwardTrain(_TrainModule):
         m2 = _keep_mask(mask2, (M, 64), self.p, eng.device, "mask2")
         y = torch.empty_like(x2)
         ws = self._workspace(M)
-        _launch(eng, "cmgan_ffn_train_forward", x2, M, _fill(FfnParams(), _FFN_TABLE, self.params), m1, m2,
-                self._keep_scale, r, y, ws, ws.numel())
+        eng._call("cmgan_ffn_train_forward", x2, M, _fill(FfnParams(), _FFN_TABLE, self.params), m1, m2,
+                  self._keep_scale, r, y, ws, ws.numel())
         return y.reshape(shape)
 
     def backward(self, x: torch.Tensor, dy: torch.Tensor, mask1: Optional[torch.Tensor] = None,
@@ -274,8 +261,8 @@ class FeedForwardTrain(_TrainModule):
         m2 = _keep_mask(mask2, (M, 64), self.p, eng.device, "mask2")
         dx = torch.empty_like(x2)
         ws = self._workspace(M)
-        _launch(eng, "cmgan_ffn_train_backward", x2, dy2, M, _fill(FfnParams(), _FFN_TABLE, self.params), m1, m2,
-                self._keep_scale, r, dx, _fill(FfnParams(), _FFN_TABLE, self.grads), ws, ws.numel())
+        eng._call("cmgan_ffn_train_backward", x2, dy2, M, _fill(FfnParams(), _FFN_TABLE, self.params), m1, m2,
+                  self._keep_scale, r, dx, _fill(FfnParams(), _FFN_TABLE, self.grads), ws, ws.numel())
         return dx.reshape(shape), self.grads
 
 
@@ -316,8 +303,8 @@ class AdamW:
         if lr is not None:
             self.set_lr(lr)
         p, g = eng._in(self.params.flat, "params"), eng._in(self.grads.flat, "grads")
-        _launch(eng, "cmgan_adamw_step_dev", p, g, self.exp_avg, self.exp_avg_sq, self.params.numel, self.state,
-                float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay))
+        eng._call("cmgan_adamw_step_dev", p, g, self.exp_avg, self.exp_avg_sq, self.params.numel, self.state,
+                  float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay))
 
 
 @torch.no_grad()
@@ -390,8 +377,8 @@ class ConvModuleTrain(_TrainModule):
         ws = self._workspace(N, L)
         y = torch.empty_like(x)
         rm, rv = (self.running_mean, self.running_var) if update_running_stats else (None, None)
-        _launch(eng, "cmgan_convmod_train_forward", x, N, L, _fill(ConvModParams(), _CM_TABLE, self.params), rm, rv, r, y,
-                ws, ws.numel())
+        eng._call("cmgan_convmod_train_forward", x, N, L, _fill(ConvModParams(), _CM_TABLE, self.params), rm, rv, r, y,
+                  ws, ws.numel())
         self._shape = (N, L)
         if update_running_stats:
             self.num_batches_tracked += 1
@@ -409,8 +396,8 @@ class ConvModuleTrain(_TrainModule):
             raise RuntimeError("backward() needs the forward() of the same [N, L, 64] input first")
         ws = self._workspace(N, L)
         dx = torch.empty_like(x)
-        _launch(eng, "cmgan_convmod_train_backward", x, dy, N, L, _fill(ConvModParams(), _CM_TABLE, self.params), r, dx,
-                _fill(ConvModParams(), _CM_TABLE, self.grads), ws, ws.numel())
+        eng._call("cmgan_convmod_train_backward", x, dy, N, L, _fill(ConvModParams(), _CM_TABLE, self.params), r, dx,
+                  _fill(ConvModParams(), _CM_TABLE, self.grads), ws, ws.numel())
         return dx, self.grads
 
 
@@ -457,8 +444,8 @@ class AttentionTrain(_TrainModule):
         m = _keep_mask(mask, (N, L, 64), self.p, eng.device, "mask")
         ws = self._workspace(N, L)
         y = torch.empty_like(x)
-        _launch(eng, "cmgan_attn_train_forward", x, N, L, _fill(AttnParams(), _AT_TABLE, self.params), m,
-                self._keep_scale, r, y, ws, ws.numel())
+        eng._call("cmgan_attn_train_forward", x, N, L, _fill(AttnParams(), _AT_TABLE, self.params), m,
+                  self._keep_scale, r, y, ws, ws.numel())
         self._shape = (N, L)
         return y
 
@@ -473,8 +460,8 @@ class AttentionTrain(_TrainModule):
         m = _keep_mask(mask, (N, L, 64), self.p, eng.device, "mask")
         ws = self._workspace(N, L)
         dx = torch.empty_like(x)
-        _launch(eng, "cmgan_attn_train_backward", x, dy, N, L, _fill(AttnParams(), _AT_TABLE, self.params), m,
-                self._keep_scale, r, dx, _fill(AttnParams(), _AT_TABLE, self.grads), ws, ws.numel())
+        eng._call("cmgan_attn_train_backward", x, dy, N, L, _fill(AttnParams(), _AT_TABLE, self.params), m,
+                  self._keep_scale, r, dx, _fill(AttnParams(), _AT_TABLE, self.grads), ws, ws.numel())
         return dx, self.grads
 
 
@@ -522,8 +509,8 @@ class ConformerBlockTrain(_TrainModule):
             x3 = self.conv.forward(x2, residual=x2)                                      # last kernel
             x4 = self.ff2.forward(x3, m.get("ff2_1"), m.get("ff2_2"), residual=x3)
             y = torch.empty_like(x4)
-            _launch(eng, "cmgan_layernorm_train_forward", x4, x4.numel() // 64, self.params["post_norm.weight"],
-                    self.params["post_norm.bias"], r, y)
+            eng._call("cmgan_layernorm_train_forward", x4, x4.numel() // 64, self.params["post_norm.weight"],
+                      self.params["post_norm.bias"], r, y)
         self._saved = (x0, x1, x2, x3, x4, m)
         return y
 
@@ -538,9 +525,9 @@ class ConformerBlockTrain(_TrainModule):
         ws = self._grow(eng.lib.cmgan_layernorm_train_workspace_bytes(eng._h, M))
         with torch.cuda.device(eng.device):
             d4 = torch.empty_like(x4)
-            _launch(eng, "cmgan_layernorm_train_backward", x4, dy, M, self.params["post_norm.weight"],
-                    self.params["post_norm.bias"], d4, self.grads["post_norm.weight"], self.grads["post_norm.bias"], ws,
-                    ws.numel())
+            eng._call("cmgan_layernorm_train_backward", x4, dy, M, self.params["post_norm.weight"],
+                      self.params["post_norm.bias"], d4, self.grads["post_norm.weight"], self.grads["post_norm.bias"], ws,
+                      ws.numel())
             d3 = self.ff2.backward(x3, d4, m.get("ff2_1"), m.get("ff2_2"), dresidual=d4)[0]
             d2 = self.conv.backward(x2, d3, dresidual=d3)[0]
             d1 = self.attn.backward(x1, d2, m.get("attn"), dresidual=d2)[0]
@@ -573,7 +560,7 @@ class TSCBTrain:
         """[B, A, C, 64] -> [B, C, A, 64] of x (+ add, same layout as x: a residual riding on the flip)."""
         eng = self.engine
         out = torch.empty(B, C, A, 64, dtype=torch.float32, device=x.device)
-        _launch(eng, "cmgan_swap_axes", x, add, out, B, A, C)
+        eng._call("cmgan_swap_axes", x, add, out, B, A, C)
         return out
 
     def forward(self, x: torch.Tensor, masks_time=None, masks_freq=None) -> torch.Tensor:
@@ -637,7 +624,7 @@ class DenseBlockTrain(_TrainModule):
             raise ValueError("expected channels-last [B, T, F, 64]")
         ws = self._workspace(B, T, F)
         y = torch.empty_like(x)
-        _launch(eng, "cmgan_dense_train_forward", x, B, T, F, _dense_struct(self.params), y, ws, ws.numel())
+        eng._call("cmgan_dense_train_forward", x, B, T, F, _dense_struct(self.params), y, ws, ws.numel())
         self._shape = (B, T, F)
         return y
 
@@ -649,8 +636,8 @@ class DenseBlockTrain(_TrainModule):
             raise RuntimeError("backward() needs the forward() of the same [B, T, F, 64] input first")
         ws = self._workspace(B, T, F)
         dx = torch.empty_like(x)
-        _launch(eng, "cmgan_dense_train_backward", x, dy, B, T, F, _dense_struct(self.params), dx,
-                _dense_struct(self.grads), ws, ws.numel())
+        eng._call("cmgan_dense_train_backward", x, dy, B, T, F, _dense_struct(self.params), dx,
+                  _dense_struct(self.grads), ws, ws.numel())
         return dx, self.grads
 
 
@@ -687,7 +674,7 @@ class DenseEncoderTrain(_TrainModule):
             raise ValueError("expected channels-last [B, T, F, 3]")
         ws = self._grow(eng.lib.cmgan_encoder_train_workspace_bytes(eng._h, B, T, F))
         y = torch.empty(B, T, (F - 1) // 2 + 1, 64, dtype=torch.float32, device=eng.device)
-        _launch(eng, "cmgan_encoder_train_forward", xin, B, T, F, _encoder_struct(self.params), y, ws, ws.numel())
+        eng._call("cmgan_encoder_train_forward", xin, B, T, F, _encoder_struct(self.params), y, ws, ws.numel())
         self._shape = (B, T, F)
         self._xin = xin
         return y
@@ -700,8 +687,8 @@ class DenseEncoderTrain(_TrainModule):
         dy = eng._in(dy, "dy")
         if tuple(dy.shape) != (B, T, (F - 1) // 2 + 1, 64):
             raise ValueError("dy does not match the forward() output")
-        _launch(eng, "cmgan_encoder_train_backward", self._xin, dy, B, T, F, _encoder_struct(self.params),
-                _encoder_struct(self.grads), self._ws, self._ws.numel())
+        eng._call("cmgan_encoder_train_backward", self._xin, dy, B, T, F, _encoder_struct(self.params),
+                  _encoder_struct(self.grads), self._ws, self._ws.numel())
         return self.grads
 
 
@@ -760,8 +747,8 @@ class DecoderTrain(_TrainModule):
             raise ValueError(f"2 F' - 1 = {F} does not match num_features = {self.num_features} (prelu_out)")
         ws = self._grow(eng.lib.cmgan_decoder_train_workspace_bytes(eng._h, B, T, Fe))
         out = torch.empty((B, T, F) if self.kind == "mask" else (B, T, F, 2), dtype=torch.float32, device=eng.device)
-        _launch(eng, "cmgan_decoder_train_forward", self.KINDS[self.kind], x, B, T, Fe,
-                _decoder_struct(self.params, self.kind), out, ws, ws.numel())
+        eng._call("cmgan_decoder_train_forward", self.KINDS[self.kind], x, B, T, Fe,
+                  _decoder_struct(self.params, self.kind), out, ws, ws.numel())
         self._shape = (B, T, Fe)
         self._x = x
         return out
@@ -776,9 +763,9 @@ class DecoderTrain(_TrainModule):
         if tuple(dout.shape) != ((B, T, F) if self.kind == "mask" else (B, T, F, 2)):
             raise ValueError("dout does not match the forward() output")
         dx = torch.empty_like(self._x)
-        _launch(eng, "cmgan_decoder_train_backward", self.KINDS[self.kind], self._x, dout, B, T, Fe,
-                _decoder_struct(self.params, self.kind), dx, _decoder_struct(self.grads, self.kind), self._ws,
-                self._ws.numel())
+        eng._call("cmgan_decoder_train_backward", self.KINDS[self.kind], self._x, dout, B, T, Fe,
+                  _decoder_struct(self.params, self.kind), dx, _decoder_struct(self.grads, self.kind), self._ws,
+                  self._ws.numel())
         return dx, self.grads
 
 
@@ -821,7 +808,7 @@ class GeneratorTrain(_TrainModule):
         state = self.mask_rng_state(generator)
         n16 = (nbytes + 15) // 16 * 16
         buf = torch.empty(n16, dtype=torch.uint8, device=eng.device)
-        _launch(eng, "cmgan_dropout_masks", buf, n16, 1.0 - p, state)
+        eng._call("cmgan_dropout_masks", buf, n16, 1.0 - p, state)
         return buf[:nbytes]
 
     def mask_rng_state(self, generator: Optional[torch.Generator] = None) -> torch.Tensor:
@@ -886,7 +873,7 @@ class GeneratorTrain(_TrainModule):
             raise ValueError(f"expected [B, 2, T, {eng.cfg.num_features}]")
         with torch.cuda.device(eng.device):
             xin = torch.empty(B, T, F, 3, dtype=torch.float32, device=eng.device)
-            _launch(eng, "cmgan_tscnet_prologue", spec, B, T, xin)
+            eng._call("cmgan_tscnet_prologue", spec, B, T, xin)
             x = self.dense_encoder.forward(xin)                                     # generator.py:181
             for i, blk in enumerate(self.blocks):                                   # :182-185
                 mt, mf = masks[i] if masks is not None else (None, None)
@@ -895,7 +882,7 @@ class GeneratorTrain(_TrainModule):
             cplx = self.complex_decoder.forward(x)                                  # :190
             est_real = torch.empty(B, 1, T, F, dtype=torch.float32, device=eng.device)
             est_imag = torch.empty_like(est_real)
-            _launch(eng, "cmgan_tscnet_epilogue_forward", spec, mask, cplx, B, T, est_real, est_imag)    # :188-199
+            eng._call("cmgan_tscnet_epilogue_forward", spec, mask, cplx, B, T, est_real, est_imag)    # :188-199
         self._saved = (spec, B, T, F)
         return est_real, est_imag
 
@@ -911,7 +898,7 @@ class GeneratorTrain(_TrainModule):
         with torch.cuda.device(eng.device):
             dmask = torch.empty(B, T, F, dtype=torch.float32, device=eng.device)
             dcplx = torch.empty(B, T, F, 2, dtype=torch.float32, device=eng.device)
-            _launch(eng, "cmgan_tscnet_epilogue_backward", spec, d_real, d_imag, B, T, dmask, dcplx)
+            eng._call("cmgan_tscnet_epilogue_backward", spec, d_real, d_imag, B, T, dmask, dcplx)
             dx_m, _ = self.mask_decoder.backward(dmask)
             dx_c, _ = self.complex_decoder.backward(dcplx)
             dx = _add(eng, dx_m, dx_c)
@@ -956,8 +943,8 @@ def generator_train_step(gen: GeneratorTrain, optimizer: "AdamW", clean: torch.T
     clean_cut = clean[:, :La].contiguous()                      # train.py:187: the time term sees the RAW clean batch
     loss, terms = generator_loss_terms(eng, est_real, est_imag, clean_spec, est_audio, clean_cut, loss_weights)
     d_real, d_imag = torch.empty_like(est_real), torch.empty_like(est_imag)
-    _launch(eng, "cmgan_loss_backward", est_real, est_imag, clean_spec, B, T, est_audio, clean_cut, float(loss_weights[0]),
-            float(loss_weights[1]), float(loss_weights[2]), d_real, d_imag)
+    eng._call("cmgan_loss_backward", est_real, est_imag, clean_spec, B, T, est_audio, clean_cut, float(loss_weights[0]),
+              float(loss_weights[1]), float(loss_weights[2]), d_real, d_imag)
     gen.backward(d_real, d_imag)                                # train.py:190 (loss.backward())
     if update:                                                  # False: stop after the backward (GraphedTrainStep)
         gen.allreduce_gradients()                               # DDP's gradient mean, one collective
@@ -1033,7 +1020,7 @@ class DiscriminatorTrain(_TrainModule):
         xy = torch.empty(B, T, F, 2, dtype=torch.float32, device=eng.device)
         er = eng._in(est_real, "est_real") if est_real is not None else None
         ei = eng._in(est_imag, "est_imag") if est_imag is not None else None
-        _launch(eng, "cmgan_mag_pair", clean_spec, er, ei, B, T, xy)
+        eng._call("cmgan_mag_pair", clean_spec, er, ei, B, T, xy)
         return xy
 
     def forward(self, xy: torch.Tensor, mask: Optional[torch.Tensor] = None, train: bool = True, slot: int = 0) -> torch.Tensor:
@@ -1050,8 +1037,8 @@ class DiscriminatorTrain(_TrainModule):
         mask = eng._in(mask, "mask") if mask is not None else None        # float32, contiguous; kept for the backward
         if mask is not None and tuple(mask.shape) != (B, 64):
             raise ValueError(f"mask must be [B, 64] = [{B}, 64]")
-        _launch(eng, "cmgan_disc_forward", xy, B, T, _disc_struct(self.params, self.buffers), mask, 1 if train else 0,
-                score, ws, ws.numel())
+        eng._call("cmgan_disc_forward", xy, B, T, _disc_struct(self.params, self.buffers), mask, 1 if train else 0,
+                  score, ws, ws.numel())
         self._saved[slot] = (xy, mask, B, T)
         return score
 
@@ -1067,8 +1054,8 @@ class DiscriminatorTrain(_TrainModule):
         dxy = torch.empty_like(xy) if need_input_grad else None
         target = self._scratch.views if accumulate else self.grads
         ws = self._ws[slot]
-        _launch(eng, "cmgan_disc_backward", xy, dscore, B, T, _disc_struct(self.params, self.buffers), mask, dxy,
-                _disc_struct(target), ws, ws.numel())
+        eng._call("cmgan_disc_backward", xy, dscore, B, T, _disc_struct(self.params, self.buffers), mask, dxy,
+                  _disc_struct(target), ws, ws.numel())
         if accumulate:
             _add(eng, self.grad_bucket.flat, self._scratch.flat, out=self.grad_bucket.flat)
         return dxy
@@ -1080,7 +1067,7 @@ class DiscriminatorTrain(_TrainModule):
         loss = torch.empty(1, dtype=torch.float32, device=eng.device)
         dscore = torch.empty(B, dtype=torch.float32, device=eng.device)
         target = eng._in(target, "target") if target is not None else None
-        _launch(eng, "cmgan_score_mse", score, target, B, float(scale), loss, dscore)
+        eng._call("cmgan_score_mse", score, target, B, float(scale), loss, dscore)
         return loss[0], dscore
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
@@ -1117,10 +1104,10 @@ def _adversarial_generator_half(gen: GeneratorTrain, disc: DiscriminatorTrain, c
     gan, dscore = disc.score_mse(score, None, scale=float(loss_weights[3]))    # train.py:129-131
     loss = base + float(loss_weights[3]) * gan
     d_real, d_imag = torch.empty_like(est_real), torch.empty_like(est_imag)
-    _launch(eng, "cmgan_loss_backward", est_real, est_imag, clean_spec, B, T, est_audio, clean_cut, float(loss_weights[0]),
-            float(loss_weights[1]), float(loss_weights[2]), d_real, d_imag)
+    eng._call("cmgan_loss_backward", est_real, est_imag, clean_spec, B, T, est_audio, clean_cut, float(loss_weights[0]),
+              float(loss_weights[1]), float(loss_weights[2]), d_real, d_imag)
     dxy = disc.backward(dscore, slot=0, need_input_grad=True)
-    _launch(eng, "cmgan_mag_pair_backward", est_real, est_imag, dxy, B, T, 1.0, d_real, d_imag)
+    eng._call("cmgan_mag_pair_backward", est_real, est_imag, dxy, B, T, 1.0, d_real, d_imag)
     gen.backward(d_real, d_imag)                                              # train.py:190
     ctx = dict(xy=xy, clean_spec=clean_spec, est_audio=est_audio, clean_cut=clean_cut, disc_masks=disc_masks)
     return loss, terms, gan, ctx

@@ -723,6 +723,45 @@ def test_reloading_weights_invalidates_captured_graphs(sd):
     _check("reloaded weights vs oracle", b_eager, O.enhance_batch(sd_b, wav.cpu()))
 
 
+def test_a_workspace_that_grows_under_live_graphs_leaves_no_stale_one(sd):
+    """Graphs of all four kinds (whole-batch, window rows, stream steps / stages) are captured, then a larger batch
+    regrows the main and the branched workspace they point into: every stale graph is evicted or re-captured, so the
+    same calls give the same bits as before and as their eager twins (a stale graph reads freed memory)."""
+    from cmgan_amd import TSCNet
+    from cmgan_amd.streaming import enhance_stream, enhance_windows
+    m = TSCNet(64, 201).load_state_dict(sd).eval()
+    eng = m.engine
+    wav = synthetic_clips(2, 4000, seed=14).to(DEV)
+    long = synthetic_clips(1, 9000, seed=15).to(DEV)
+    clip = synthetic_clips(1, 16000, seed=33).to(DEV)
+    big = synthetic_clips(4, 16000, seed=16).to(DEV)
+    calls = (lambda g: eng.enhance_graphed(wav) if g else eng.enhance(wav),
+             lambda g: eng.enhance_graphed(wav, branches=1) if g else eng.enhance(wav),
+             lambda g: enhance_windows(m, long, window=4000, context=800, batch=2, graph=g),
+             lambda g: enhance_stream(m, clip, window=40, context=12, lookahead=8, graph=g))
+    eager = [f(False).clone() for f in calls]
+    first = [f(True).clone() for f in calls]
+    for a, b in zip(first, eager):
+        assert torch.equal(a, b)
+    branched = lambda: (eng._wss["branched"].data_ptr(), eng._wss["branched"].numel(), eng._ws_token()[2])
+    old_keys, old_main, old_branched = set(eng._graphs), eng._ws_token(), branched()
+    assert {k[1] for k in old_keys} == {1, 2} and eng._row_graphs and any(s.graphs or s.stage_graphs
+                                                                         for s in eng._stream_slots.values())
+    want = eng.enhance(big).clone()
+    assert torch.equal(eng.enhance_graphed(big, branches=1), want) and torch.equal(eng.enhance_graphed(big), want)
+    assert eng._ws_token()[1] > old_main[1] and branched()[1] > old_branched[1]          # both really grew
+    assert not old_keys & set(eng._graphs) and not eng._row_graphs                        # what pointed into them is gone
+    assert not any(s.graphs or s.stage_graphs for s in eng._stream_slots.values())
+    for f, a, b in zip(calls, first, eager):
+        again = f(True)
+        assert torch.equal(again, a) and torch.equal(again, b)
+    for key, ent in eng._graphs.items():
+        assert ent[3] == (eng._ws_token() if key[1] == 1 else branched()), key
+    assert all(ent[3] == eng._ws_token() for ent in eng._row_graphs.values())
+    for s in eng._stream_slots.values():
+        assert all(ent[-1] == eng._ws_token() for ent in list(s.graphs.values()) + list(s.stage_graphs.values()))
+
+
 def test_state_dict_validation_is_complete(sd):
     from cmgan_amd import TSCNet
     m = TSCNet(64, 201)
