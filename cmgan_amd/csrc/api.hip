@@ -408,7 +408,7 @@ static int build_x3_images(const float* payload, const std::map<uint32_t, WEntry
             if (item % 4 == 0) { pad(); d16[id] = img.size(); x3_conv_image(src, 4 * (item / 4 + 1), 6, 4, img); }
         } else if (grp == G_ENC && item == ENC_C2_W) {
             pad(); d16[id] = img.size(); x3_conv_image(src, 4, 3, 4, img);
-        } else if ((grp == G_MASK && item == MK_SP_W) || (grp == G_CPLX && item == CX_SP_W)) {
+        } else if (grp == G_CPLX && item == CX_SP_W) {          // (the mask decoder's is folded: build_mask_head)
             pad(); d16[id] = img.size(); x3_conv_image(src, 4, 3, 8, img);
         }
     }
@@ -416,6 +416,45 @@ static int build_x3_images(const float* payload, const std::map<uint32_t, WEntry
     host_img.swap(img);
     d16_out.swap(d16);
     return CMGAN_OK;
+}
+
+// ---- mask decoder head: sub_pixel (1,3) conv 64 -> 128 + pixel shuffle folded with conv_1 (1,2) 64 -> 1 ----------
+// (generator.py:133-136: nothing non-linear sits between the two.)  Sub-pixel output channel o = r * 64 + c lands at
+// width 2f' + r, channel c (SPConvTranspose2d's view(B, r, C, H, W).permute(0, 2, 3, 4, 1); conv.hip mode 2), so the
+// two conv_1 taps of the pixel-shuffled column (f', r) are
+//   G[k][ci][r][kf] = sum_c w1[c][kf] * Wsp[r * 64 + c][ci][k],   g0[r][kf] = sum_c w1[c][kf] * bsp[r * 64 + c]
+// summed in double and rounded once.  host: G [3][64][2][2] | g0 as the dm row [2][4] (entries 2, 3 zero);
+// dev: G as the A operand of mask_head_kernel, fm [tap 3][kb 4][64][4] with row 2r + kf (rows 4 .. 15 zero) | g0 [4]
+#define MH_HOST_FLOATS 776
+#define MH_DEV_FLOATS (12 * 256 + 64)
+static bool build_mask_head(const float* payload, const std::map<uint32_t, WEntry>& dir, std::vector<float>& host,
+                            std::vector<float>& dev) {
+    const auto sp = dir.find(WID(G_MASK, MK_SP_W)), sb = dir.find(WID(G_MASK, MK_SP_BIAS)),
+               tl = dir.find(WID(G_MASK, MK_TAIL_W));
+    if (sp == dir.end() || sb == dir.end() || tl == dir.end()) return false;
+    const float *fmw = payload + sp->second.off, *bsp = payload + sb->second.off, *tail = payload + tl->second.off;
+    // the index maps of x3_conv_image(src, 4, 3, 8) / packer.fm: lane = (row & 15) + 16 ((col & 15) >> 2), e = col & 3
+    auto wsp = [&](int o, int ci, int k) {
+        return (double)fmw[((((size_t)(ci >> 4) * 3 + k) * 8 + (o >> 4)) * 64 + (o & 15) + 16 * ((ci & 15) >> 2)) * 4 + (ci & 3)];
+    };
+    auto w1 = [&](int c, int kf) { return (double)tail[(c >> 4) * 256 + (kf + 16 * ((c & 15) >> 2)) * 4 + (c & 3)]; };
+    host.assign(MH_HOST_FLOATS, 0.f);
+    dev.assign(MH_DEV_FLOATS, 0.f);
+    for (int r = 0; r < 2; ++r)
+        for (int kf = 0; kf < 2; ++kf) {
+            for (int k = 0; k < 3; ++k)
+                for (int ci = 0; ci < 64; ++ci) {
+                    double s = 0.0;
+                    for (int c = 0; c < 64; ++c) s += w1(c, kf) * wsp(r * 64 + c, ci, k);
+                    host[((k * 64 + ci) * 2 + r) * 2 + kf] = (float)s;
+                    dev[((size_t)(k * 4 + (ci >> 4)) * 64 + (2 * r + kf) + 16 * ((ci & 15) >> 2)) * 4 + (ci & 3)] = (float)s;
+                }
+            double s = 0.0;
+            for (int c = 0; c < 64; ++c) s += w1(c, kf) * (double)bsp[r * 64 + c];
+            host[768 + r * 4 + kf] = (float)s;
+            dev[12 * 256 + 2 * r + kf] = (float)s;
+        }
+    return true;
 }
 
 extern "C" int cmgan_load_weights(cmgan_handle* h, const void* blob, size_t bytes) {
@@ -444,12 +483,16 @@ extern "C" int cmgan_load_weights(cmgan_handle* h, const void* blob, size_t byte
     std::vector<_Float16> img;
     std::map<uint32_t, size_t> d16;
     if (int rc = build_x3_images((const float*)((const char*)blob + head), dir, img, d16)) return rc;
+    std::vector<float> mh_host, mh_dev;                       // the folded mask head, behind the payload (64-float aligned)
+    const bool mh = build_mask_head((const float*)((const char*)blob + head), dir, mh_host, mh_dev);
+    const size_t mh_off = ((size_t)payload + 63) & ~(size_t)63;
     HIPCHK(h, hipSetDevice(h->device));
     float* nw = nullptr;
     _Float16* nw16 = nullptr;
-    hipError_t e = hipMalloc(&nw, (size_t)payload * 4 + 256);
+    hipError_t e = hipMalloc(&nw, (mh_off + MH_DEV_FLOATS) * 4 + 256);
     if (e == hipSuccess) e = hipMalloc(&nw16, img.size() * sizeof(_Float16) + 256);
     if (e == hipSuccess) e = hipMemcpy(nw, (const char*)blob + head, (size_t)payload * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && mh) e = hipMemcpy(nw + mh_off, mh_dev.data(), MH_DEV_FLOATS * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(nw16, img.data(), img.size() * sizeof(_Float16), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipDeviceSynchronize();          // no launch may still be reading the old buffers
     if (e != hipSuccess) {
@@ -464,6 +507,8 @@ extern "C" int cmgan_load_weights(cmgan_handle* h, const void* blob, size_t byte
     h->weight_floats = payload;
     h->dir.swap(dir);
     h->dir16.swap(d16);
+    h->mask_head_tbl.swap(mh_host);
+    h->mask_head_off = mh ? mh_off : 0;
     ++h->weights_generation;
     return CMGAN_OK;
 }
@@ -744,6 +789,7 @@ static bool dense_weights(cmgan_handle* h, int grp, DenseW& d) {
 
 // DilatedDenseNet (generator.py:39-47): slot 0 = x0 (with optional norm-on-load), layer i writes slot i+1.
 // ns(j) -> {scale, shift} storage for norm instance j; returns the instance index used by the last layer.
+// x0_img_ready: see the loop (the complex decoder's block starts from the tensor the mask decoder's block started from).
 // F16X3 mode (imgs != null): layer i is the FIRST consumer of its newest input (x0 for i = 0, else slot i - 1): it
 // normalises it on load as before and also stores its split-fp16 image (imgs[i], i < 3); layers i + 1 .. 3 read that
 // image instead of the raw slot - same values to the bit, without the per-re-read normalise / PReLU / split.
@@ -760,7 +806,7 @@ static void run_dense_block(LaunchCtx ctx, bool x3, const DenseW& d, const float
                             const float* x0_shift, const float* x0_alpha, float* const slots[4], float* partials,
                             float* const nsc[4], float* const nsh[4], int B, int T, int F, float* const* imgs = nullptr,
                             Conv3xFn conv3x = launch_conv3_x3, bool frozen = false,
-                            const RunningNorms* run = nullptr, int j0 = 0) {
+                            const RunningNorms* run = nullptr, int j0 = 0, bool x0_img_ready = false) {
     const int nt = x3 ? conv3x_ntiles(T, F, 64) : conv3_ntiles(T, F);
     for (int i = 0; i < 4; ++i) {
         ConvArgs a{};
@@ -773,6 +819,9 @@ static void run_dense_block(LaunchCtx ctx, bool x3, const DenseW& d, const float
             for (int s = 0; s < ni; ++s) a.in[s] = imgs[s];
             a.img_mask = (1u << ni) - 1u;
             a.img_out = i < CX_NIMG ? imgs[i] : nullptr;
+            // imgs[0] already holds the image of this very x0 (written by the previous block that started from it):
+            // layer 0 reads it like layers 1 .. 3 do instead of splitting and storing the same bytes again
+            if (i == 0 && x0_img_ready && CX_NIMG >= 1) { a.in[0] = imgs[0]; a.img_mask |= 1u; a.img_out = nullptr; }
         }
         a.nslots = i + 1;
         a.w = d.w[i]; a.bias = d.bias[i];
@@ -825,6 +874,9 @@ static int tscnet_impl(cmgan_handle* h, const float* spec, int B, int T, float* 
     // offsets (conformer_x3_addressable, conformer_x3.hip: 83 k frames per clip at F = 201); the fp32 kernels have no limit
     if (h->cfg.mfma_mode != CMGAN_MFMA_F32 && (long)(T - 1) * ((h->cfg.num_features + 1) / 2) * 512 + 512 >= (1l << 32))
         return fail(h, CMGAN_E_BADARG, "tscnet_forward: T too large (T * ceil(F / 2) * 512 must stay below 2^32)");
+    // mask_head_kernel counts the decoder's positions in 32 bits (conv.hip; 2^31 positions are 512 GiB per slot)
+    if (ph_dec && (long)B * T * ((h->cfg.num_features + 1) / 2) >= (1l << 31))
+        return fail(h, CMGAN_E_BADARG, "tscnet_forward: B x T x ceil(F / 2) must stay below 2^31");
     const WsPlan p = plan_ws(h->cfg, B, T);
     if (int rc = check_ws(h, ws, ws_bytes, p.total * sizeof(float))) return rc;
     const int F = h->cfg.num_features, F2 = (F + 1) / 2, W2 = 2 * F2;
@@ -845,9 +897,7 @@ static int tscnet_impl(cmgan_handle* h, const float* spec, int B, int T, float* 
     ok = dense_weights(h, G_DB_E, dbe) && ok;
     ok = dense_weights(h, G_DB_M, dbm) && ok;
     ok = dense_weights(h, G_DB_C, dbc) && ok;
-    const float* mk_spw = W(h, WID(G_MASK, MK_SP_W), ok);
-    const float* mk_spb = W(h, WID(G_MASK, MK_SP_BIAS), ok);
-    const float* mk_tail = W(h, WID(G_MASK, MK_TAIL_W), ok);
+    W(h, WID(G_MASK, MK_SP_W), ok); W(h, WID(G_MASK, MK_SP_BIAS), ok); W(h, WID(G_MASK, MK_TAIL_W), ok);   // folded: mask_head_off
     const float* mk_sca = W(h, WID(G_MASK, MK_SCALARS), ok);
     const float* mk_pout = W(h, WID(G_MASK, MK_PRELU_OUT), ok);
     const float* cx_spw = W(h, WID(G_CPLX, CX_SP_W), ok);
@@ -869,7 +919,6 @@ static int tscnet_impl(cmgan_handle* h, const float* spec, int B, int T, float* 
         if (x3) ok = conf_weights_x3(h, i, cw16[i]) && ok;
     }
     const _Float16* c2w16 = x3 ? W16(h, WID(G_ENC, ENC_C2_W), ok) : nullptr;
-    const _Float16* mk_spw16 = x3 ? W16(h, WID(G_MASK, MK_SP_W), ok) : nullptr;
     const _Float16* cx_spw16 = x3 ? W16(h, WID(G_CPLX, CX_SP_W), ok) : nullptr;
     if (!ok) return CMGAN_E_WEIGHTS;
 
@@ -957,21 +1006,24 @@ static int tscnet_impl(cmgan_handle* h, const float* spec, int B, int T, float* 
         float* sc[4] = {nsc(j0), nsc(j0 + 1), nsc(j0 + 2), nsc(j0 + 3)};
         float* sh[4] = {nsh(j0), nsh(j0 + 1), nsh(j0 + 2), nsh(j0 + 3)};
         float* imgs[3] = {f + p.img[0], f + p.img[1], f + p.img[2]};
+        // both blocks start from xa and nothing writes imgs[0] in between: the second one reuses the first one's image
         run_dense_block(ctx, x3, d, f + p.xa, nullptr, nullptr, nullptr, dslots, partials, sc, sh, B, T, F2, x3 ? imgs : nullptr, conv3x, frozen,
-                        run, j0);
+                        run, j0, dec == 1);
+        if (dec == 0) {
+            // mask head: sub_pixel -> pixel shuffle -> conv_1 are one linear map (build_mask_head), evaluated in fp32 in
+            // every matrix mode straight from the block's last slot; the pixel-shuffled [B, T, 2F', 64] tensor never exists
+            launch_mask_head(ctx, dslots[3], sc[3], sh[3], d.prelu[3], h->d_weights + h->mask_head_off, f + p.dm, B, T, F2);
+            continue;
+        }
         ConvArgs a{};
         a.in[0] = dslots[3]; a.nscale[0] = sc[3]; a.nshift[0] = sh[3]; a.nalpha[0] = d.prelu[3];
-        a.nslots = 1; a.w = dec == 0 ? mk_spw : cx_spw; a.bias = dec == 0 ? mk_spb : cx_spb;
-        a.out = sp; a.partials = dec == 0 ? nullptr : partials;
+        a.nslots = 1; a.w = cx_spw; a.bias = cx_spb;
+        a.out = sp; a.partials = partials;
         a.T = T; a.F = F2; a.dil = 1; a.mode = 2; a.ntiles = nt2;
-        if (x3) conv3x(ctx, a, dec == 0 ? mk_spw16 : cx_spw16, B, 1, 128);
+        if (x3) conv3x(ctx, a, cx_spw16, B, 1, 128);
         else launch_conv3(ctx, a, B, 1, 128);
-        if (dec == 0) {
-            launch_tail_proj(ctx, sp, nullptr, nullptr, nullptr, mk_tail, f + p.dm, B, (long)T * W2);
-        } else {
-            finalize(14, nt2, 128, 1, (double)T * W2, cx_gb, sp, W2);
-            launch_tail_proj(ctx, sp, nsc(14), nsh(14), cx_pr, cx_tail, f + p.dc, B, (long)T * W2);
-        }
+        finalize(14, nt2, 128, 1, (double)T * W2, cx_gb, sp, W2);
+        launch_tail_proj(ctx, sp, nsc(14), nsh(14), cx_pr, cx_tail, f + p.dc, B, (long)T * W2);
     }
     if (run)
         launch_mask_running(ctx, f + p.dm, mk_sca, B, T, F, rn.hist, rn.part, rn.part_doubles, rn.norm(15, B),
@@ -1151,6 +1203,28 @@ extern "C" int cmgan_enhance_branched(cmgan_handle* h, const float* wav, int B, 
     }
     if (rc) return rc;
     return check_launch(h, "enhance_branched");
+}
+
+// ---- the mask decoder head on its own (tests: shapes the whole network does not accept) ----
+extern "C" int cmgan_mask_head_weights(cmgan_handle* h, float* out776) {
+    if (!h) return CMGAN_E_BADARG;
+    if (!out776) return fail(h, CMGAN_E_BADARG, "cmgan_mask_head_weights: bad argument");
+    if (h->mask_head_tbl.size() != MH_HOST_FLOATS) return fail(h, CMGAN_E_WEIGHTS, "mask decoder head weights not loaded");
+    std::copy(h->mask_head_tbl.begin(), h->mask_head_tbl.end(), out776);
+    return CMGAN_OK;
+}
+
+extern "C" int cmgan_mask_head_forward(cmgan_handle* h, const float* y, const float* scale, const float* shift, int B,
+                                       int T, int Fe, float* dm, void* stream) {
+    if (!h) return CMGAN_E_BADARG;
+    if (!y || !scale || !shift || !dm || B <= 0 || T <= 0 || Fe < 1 || (long)B * T * Fe >= (1l << 31))
+        return fail(h, CMGAN_E_BADARG, "cmgan_mask_head_forward: bad argument");
+    bool ok = true;
+    const float* alpha = W(h, WID(G_DB_M, DB_PRELU(3)), ok);
+    if (!ok) return CMGAN_E_WEIGHTS;
+    if (h->mask_head_tbl.size() != MH_HOST_FLOATS) return fail(h, CMGAN_E_WEIGHTS, "mask decoder head weights not loaded");
+    launch_mask_head(begin(h, stream), y, scale, shift, alpha, h->d_weights + h->mask_head_off, dm, B, T, Fe);
+    return check_launch(h, "mask_head");
 }
 
 // ------------------------------------------------------------------------------------

@@ -36,6 +36,10 @@ struct cmgan_handle {
     // x3 (f16 split) operand images, built from the fp32 fragment-major weights at load time
     _Float16* d_w16 = nullptr;
     std::map<uint32_t, size_t> dir16;     // id -> offset in halfs (rel-pos lo plane at id | 0x8000)
+    // mask decoder head: sub_pixel folded with conv_1 at load time (api.hip, build_mask_head).  The device form sits
+    // behind the fp32 payload in d_weights, so it is swapped with it; empty / 0 when the blob lacks the three tensors
+    std::vector<float> mask_head_tbl;     // host copy, the layout cmgan_mask_head_weights documents
+    size_t mask_head_off = 0;             // floats into d_weights
     Profiler prof;
     std::vector<std::string> prof_names;
     // cmgan_enhance_branched: side streams + fork / join events (created by the first call, outside any capture)

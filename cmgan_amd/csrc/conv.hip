@@ -324,7 +324,9 @@ void launch_in_apply(LaunchCtx ctx, const float* in, const float* nscale, const 
 // tail_proj computes the per-position projections d[pos][row] = sum_c Wt[row][c] * sp[pos][c]
 // (rows = (out, kf) pairs, <= 4) with one MFMA chain per 16 positions; the two kf taps are
 // summed across neighbouring positions by the consumers below.
-// The complex path normalises on load (IN + PReLU, generator.py:153-154).
+// The complex path normalises on load (IN + PReLU, generator.py:153-154) and is the only
+// caller left in the forward: the mask path has no norm before conv_1, so its SP is never
+// built (mask_head_kernel below writes the same d rows from the dense block's output).
 // ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void tail_proj_kernel(const float* __restrict__ sp,
                                                         const float* __restrict__ nscale,
@@ -359,6 +361,125 @@ void launch_tail_proj(LaunchCtx ctx, const float* sp, const float* nscale, const
     const long nblk = (total + 15) / 16;
     LAUNCH(ctx, "tail_proj", (tail_proj_kernel<<<(unsigned)((nblk + 3) / 4), 256, 0, ctx.stream>>>(
                                  sp, nscale, nshift, alpha, tailw, d, P2, total)));
+}
+
+// ---------------------------------------------------------------------------------
+// Mask decoder head: sub_pixel (1,3) conv 64 -> 128, pixel shuffle and conv_1 (1,2) 64 -> 1 in one pass
+// (generator.py:133-136).  Nothing non-linear sits between them, so the pair is a linear map from three
+// neighbouring rows of the dense block's last slot to the four numbers tail_proj used to derive from the
+// pixel-shuffled tensor: dm[2f' + r][kf] = g0[r][kf] + sum_k sum_ci G[k][ci][r][kf] * v[f' + k - 1][ci], with
+// v = PReLU(IN(y)) normalised on load and ZERO outside [0, F') (the reference pads the activated tensor).
+// gw (api.hip, build_mask_head): G as the A operand, fm [tap 3][kb 4][64][4] with row 2r + kf, then g0 [4].
+// fp32 MFMAs in every matrix mode: one chain of K = 192 per 16 positions, the 12 A fragments in LDS.
+// A wave walks MH_NB consecutive 16-position blocks.  Every row is loaded ONCE: lane (c, g) holds its own position's
+// channels, the f' - 1 / f' + 1 operands are the neighbouring lanes' values (one DPP row shift each: a DPP row is the 16
+// positions of a lane group), and only lanes c = 0 / c = 15 fetch the row before / after the block.  Entries 2, 3 of a
+// dm row are written as zero (the mask path has no second output).  (Issuing block i + 1's loads ahead of block i's
+// MFMAs from a second register buffer measured the same, 0.10 ms per 32-clip launch: four waves per SIMD already
+// overlap one wave's loads with another's MFMAs.)
+// ---------------------------------------------------------------------------------
+#define MH_NB 8
+struct MhBlock {
+    f32x4 own[4], edge[4];    // raw channels 16 kb + 4g .. + 3 of the lane's own row / of the row beyond the block (c = 0, 15)
+    unsigned row, b;
+    bool ok, okl, okr;        // position exists; its left / right neighbour lies in the same frame
+};
+// lane c takes v of lane c - 1 (0x111 = row_shr:1) or c + 1 (0x101 = row_shl:1) of its 16-lane row, `edge` where the row ends
+template <int CTRL>
+__device__ __forceinline__ float mh_shift(float edge, float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, edge), __builtin_bit_cast(int, v),
+                                                                 CTRL, 0xf, 0xf, false));
+}
+
+__global__ __launch_bounds__(256) void mask_head_kernel(const float* __restrict__ y, const float* __restrict__ nscale,
+                                                        const float* __restrict__ nshift,
+                                                        const float* __restrict__ alpha, const float* __restrict__ gw,
+                                                        float* __restrict__ dm, unsigned T, unsigned Fe,
+                                                        unsigned total) {
+    __shared__ __attribute__((aligned(16))) float wsm[12 * 256 + 64];       // A fragments | PReLU slopes
+    const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) *reinterpret_cast<f32x4*>(&wsm[(tid + 256 * i) * 4]) = ldg4(gw + (tid + 256 * i) * 4);
+    if (tid < 16) *reinterpret_cast<f32x4*>(&wsm[12 * 256 + tid * 4]) = ldg4(alpha + tid * 4);
+    __syncthreads();
+    const unsigned blk0 = (blockIdx.x * 4 + (tid >> 6)) * MH_NB;
+    if (blk0 * 16 >= total) return;
+    const f32x4 g0 = g == 0 ? ldg4(gw + 12 * 256) : splat4(0.f);             // D rows 0 .. 3 live in lane group 0
+    const float* const wl = wsm + lane * 4;
+    const float* const alp = wsm + 12 * 256 + 4 * g;
+
+    auto issue = [&](unsigned p0, MhBlock& k) {
+        const unsigned pos = p0 + c;
+        k.ok = pos < total;
+        k.row = k.ok ? pos : total - 1;                                      // always a readable row
+        const unsigned bt = k.row / Fe, fe = k.row - bt * Fe;
+        k.b = bt / T;
+        k.okl = fe > 0;
+        k.okr = fe + 1 < Fe;
+        const float* yr = y + (long)k.row * 64 + 4 * g;
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb) k.own[kb] = ldg4(yr + 16 * kb);
+        // the neighbour outside the block, where the frame has one (else the value is zeroed at its use); the lanes in
+        // between load their own row again (a cache hit, and no branch)
+        const float* ye = (c == 0 && k.okl) ? yr - 64 : ((c == 15 && k.okr) ? yr + 64 : yr);
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb) k.edge[kb] = ldg4(ye + 16 * kb);
+    };
+    f32x4 sc[4], sh[4];
+    unsigned bcur = 0xffffffffu;
+#pragma unroll 1
+    for (int i = 0; i < MH_NB; ++i) {
+        const unsigned p0 = (blk0 + i) * 16;
+        if (p0 >= total) break;
+        MhBlock k;
+        issue(p0, k);
+        if (k.b != bcur) {                                                   // a new clip: its scale / shift
+            bcur = k.b;
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb) {
+                sc[kb] = ldg4(nscale + k.b * 64 + 16 * kb + 4 * g);
+                sh[kb] = ldg4(nshift + k.b * 64 + 16 * kb + 4 * g);
+            }
+        }
+        f32x4 acc = g0;
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb) {
+            const f32x4 al = *reinterpret_cast<const f32x4*>(alp + 16 * kb);
+            const f32x4 v = norm_prelu4(k.own[kb], sc[kb], sh[kb], al);
+            const f32x4 ev = norm_prelu4(k.edge[kb], sc[kb], sh[kb], al);
+            f32x4 vl, vr;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                vl[e] = mh_shift<0x111>(ev[e], v[e]);
+                vr[e] = mh_shift<0x101>(ev[e], v[e]);
+            }
+            if (!k.okl) vl = splat4(0.f);                                    // first / last bin of a frame: zero padding
+            if (!k.okr) vr = splat4(0.f);
+            const f32x4 a0 = *reinterpret_cast<const f32x4*>(wl + (0 * 4 + kb) * 256);
+            const f32x4 a1 = *reinterpret_cast<const f32x4*>(wl + (1 * 4 + kb) * 256);
+            const f32x4 a2 = *reinterpret_cast<const f32x4*>(wl + (2 * 4 + kb) * 256);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc = mfma16(a0[r], vl[r], acc);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc = mfma16(a1[r], v[r], acc);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc = mfma16(a2[r], vr[r], acc);
+        }
+        if (k.ok && g == 0) {
+            const f32x4 d0 = {acc[0], acc[1], 0.f, 0.f}, d1 = {acc[2], acc[3], 0.f, 0.f};
+            stg4(dm + (long)k.row * 8, d0);
+            stg4(dm + (long)k.row * 8 + 4, d1);
+        }
+    }
+}
+
+// B * T * Fe < 2^31 (the callers check it)
+void launch_mask_head(LaunchCtx ctx, const float* y, const float* nscale, const float* nshift, const float* alpha,
+                      const float* gw, float* dm, int B, int T, int Fe) {
+    const long total = (long)B * T * Fe;
+    const long nblk = (total + 15) / 16;
+    LAUNCH(ctx, "mask_head", (mask_head_kernel<<<(unsigned)((nblk + 4 * MH_NB - 1) / (4 * MH_NB)), 256, 0, ctx.stream>>>(
+                                 y, nscale, nshift, alpha, gw, dm, (unsigned)T, (unsigned)Fe, (unsigned)total)));
 }
 
 // mask value before its InstanceNorm: conv_1 over (f, f+1) + bias

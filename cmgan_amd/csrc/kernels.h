@@ -131,6 +131,10 @@ void launch_in_apply(LaunchCtx, const float* in, const float* nscale, const floa
                      const float* alpha, float* out, int B, long P);
 void launch_tail_proj(LaunchCtx, const float* sp, const float* nscale, const float* nshift,
                       const float* alpha, const float* tailw, float* d, int B, long P2);
+// mask decoder head: dm [B, T * 2Fe, 4] straight from the dense block's last raw slot y [B, T * Fe, 64]; gw = the folded
+// sub_pixel x conv_1 weights (api.hip, build_mask_head); B * T * Fe < 2^31
+void launch_mask_head(LaunchCtx, const float* y, const float* nscale, const float* nshift, const float* alpha,
+                      const float* gw, float* dm, int B, int T, int Fe);
 void launch_mask_stats(LaunchCtx, const float* dm, const float* scalars, int B, int T, int F, float* mstat);
 void launch_final_combine(LaunchCtx, const float* spec, const float* dm, const float* dc, const float* mstat,
                           const float* mk_scalars, const float* prelu_out, const float* cx_bias,

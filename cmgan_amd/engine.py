@@ -939,6 +939,26 @@ class Engine:
         native_call(self, "cmgan_selftest_mfma_x3", ctypes.byref(err))
         return float(err.value)
 
+    def mask_head_weights(self):
+        """The mask decoder's folded sub_pixel x conv_1 table as the library derived it (cmgan_mask_head_weights):
+        (G [3, 64, 2, 2], g0 [2, 2])."""
+        out = np.zeros(776, dtype=np.float32)
+        native_call(self, "cmgan_mask_head_weights", out.ctypes.data_as(ctypes.c_void_p))
+        return out[:768].reshape(3, 64, 2, 2).copy(), out[768:].reshape(2, 4)[:, :2].copy()
+
+    @_on_device
+    def mask_head(self, y: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor) -> torch.Tensor:
+        """The mask decoder's head alone (cmgan_mask_head_forward): y [B, T, Fe, 64], scale / shift [B, 64] ->
+        dm [B, T, 2 Fe, 4]."""
+        y = tensor_arg(y, "y", torch.float32, self.device, "[B, T, Fe, 64]", lambda t: t.dim() == 4 and t.size(3) == 64)
+        B, T, Fe = (int(v) for v in y.shape[:3])
+        ok = lambda t: tuple(t.shape) == (B, 64)
+        scale = tensor_arg(scale, "scale", torch.float32, self.device, "[B, 64]", ok)
+        shift = tensor_arg(shift, "shift", torch.float32, self.device, "[B, 64]", ok)
+        dm = torch.empty(B, T, 2 * Fe, 4, dtype=torch.float32, device=self.device)
+        self._call("cmgan_mask_head_forward", y, scale, shift, B, T, Fe, dm)
+        return dm
+
     def release_workspaces(self):
         """Drop the inference workspaces and every captured graph that points into them (they are re-created on demand):
         ~6 GB each at 32 x 2 s.  bench.py calls this before its training leg."""

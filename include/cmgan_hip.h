@@ -39,7 +39,7 @@ extern "C" {
 #define CMGAN_E_WORKSPACE   -5   /* workspace too small or misaligned              */
 #define CMGAN_E_HIP         -6   /* a HIP runtime call failed (see last_error)     */
 
-#define CMGAN_ABI_VERSION 9
+#define CMGAN_ABI_VERSION 10
 
 typedef struct cmgan_handle cmgan_handle;
 
@@ -150,6 +150,21 @@ int cmgan_stft_compress(cmgan_handle* h, const float* wav_dev, const float* scal
 int cmgan_tscnet_forward(cmgan_handle* h, const float* spec_dev, int B, int T,
                          float* out_real_dev, float* out_imag_dev,
                          void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* The mask decoder's head on its own (tests).  The forward evaluates sub_pixel (1,3) conv 64 -> 128, the pixel shuffle
+ * and conv_1 (1,2) 64 -> 1 (src/models/generator.py:133-136, no non-linearity in between) as ONE linear map whose
+ * weights cmgan_load_weights derives in double and rounds once to fp32:
+ *   G[k][ci][r][kf] = sum_c conv_1.weight[0][c][0][kf] * sub_pixel.conv.weight[r * 64 + c][ci][0][k]
+ *   g0[r][kf]       = sum_c conv_1.weight[0][c][0][kf] * sub_pixel.conv.bias[r * 64 + c]
+ * cmgan_mask_head_weights copies them to HOST memory: out776 = G [3][64][2][2] then g0 as [2][4] (entries 2, 3 of a
+ * row are zero).  cmgan_mask_head_forward runs the kernel on caller tensors with the handle's weights:
+ * y [B, T, Fe, 64] = the mask dense block's last raw output, scale / shift [B][64] = its InstanceNorm as a per-clip
+ * affine pair; with v = PReLU(scale * y + shift) (dense block prelu 4), zero outside [0, Fe),
+ *   dm[((b * T + t) * 2Fe + 2f + r) * 4 + kf] = g0[r][kf] + sum_k sum_ci G[k][ci][r][kf] * v[b, t, f + k - 1, ci]
+ * for kf = 0, 1 and 0 for kf = 2, 3; dm holds B * T * 2Fe * 4 floats.  B, T, Fe >= 1, B * T * Fe < 2^31.            */
+int cmgan_mask_head_weights(cmgan_handle* h, float* out776);
+int cmgan_mask_head_forward(cmgan_handle* h, const float* y_dev, const float* scale_dev, const float* shift_dev,
+                            int B, int T, int Fe, float* dm_dev, void* stream);
 
 /* est_real/est_imag [B,1,T,F] -> waveform wav_out[B, hop*(T-1)], divided by
  * scale_dev[B] when it is not NULL.  Replaces permute + utils.power_uncompress +
