@@ -210,6 +210,56 @@ def check_level_args(device, wav, lengths=None, fs=16000):
     return B, L
 
 
+CHANNEL_TILE = 2048           # samples per block of cmgan_channel (= cmgan_channel_tile())
+CHANNEL_MAX_SECTIONS = 8      # biquads per row (= cmgan_channel_max_sections())
+CHANNEL_MAX_L = 2 ** 31 - 1 - CHANNEL_TILE
+
+
+def channel_workspace_bytes(B: int, L: int, S: int) -> int:
+    """cmgan_channel_workspace_bytes: with N = 2 x (S rounded up to 1, 2, 4 or 8), one int32 [B], one float64
+    [B, 17, N, N] table of matrix powers and two float64 [B, tiles, N] planes, each rounded up to 256 bytes; 0 for a shape
+    the kernels do not take."""
+    if not (1 <= B <= 65535 and 1 <= L <= CHANNEL_MAX_L and 1 <= S <= CHANNEL_MAX_SECTIONS):
+        return 0
+    up = lambda v: (v + 255) & ~255
+    N = 2 * next(p for p in (1, 2, 4, 8) if S <= p)
+    nt = (L + CHANNEL_TILE - 1) // CHANNEL_TILE
+    return up(B * 4) + up(B * 17 * N * N * 8) + 2 * up(B * nt * N * 8)
+
+
+def _row_stride_ok(t, B: int, L: int) -> bool:
+    return t.stride(1) == 1 and (B == 1 or t.stride(0) >= L)
+
+
+def check_channel_args(device, wav, sos, n_sections=None, clip=None, lengths=None, out=None):
+    """Argument rules of Engine.channel (shapes, dtypes and devices; pure host code).  Returns (B, L, S)."""
+    tensor_arg(wav, "wav", torch.float32, device, "[B, L] with B, L >= 1",
+               lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) >= 1, contiguous=False)     # (its own stride rule below)
+    B, L = wav.shape
+    if B > 65535:
+        raise ValueError(f"wav: at most 65535 rows, got {B}")
+    if L > CHANNEL_MAX_L:
+        raise ValueError(f"wav: rows of up to {CHANNEL_MAX_L} samples are supported, got {L}")
+    if not _row_stride_ok(wav, B, L):
+        raise ValueError(f"wav: rows must be contiguous and at least L apart, got strides {tuple(wav.stride())}")
+    tensor_arg(sos, "sos", torch.float64, device, f"[{B}, S, 6] with 1 <= S <= {CHANNEL_MAX_SECTIONS}",
+               lambda t: t.dim() == 3 and t.size(0) == B and 1 <= t.size(1) <= CHANNEL_MAX_SECTIONS and t.size(2) == 6)
+    row = lambda t: tuple(t.shape) == (B,)
+    if n_sections is not None:
+        tensor_arg(n_sections, "n_sections", torch.int32, device, f"[{B}]", row)
+    if clip is not None:
+        tensor_arg(clip, "clip", torch.float64, device, f"[{B}]", row)
+    if lengths is not None:
+        tensor_arg(lengths, "lengths", torch.int32, device, f"[{B}]", row)
+    if out is not None:
+        tensor_arg(out, "out", torch.float32, device, f"[{B}, {L}]", lambda t: tuple(t.shape) == (B, L), contiguous=False)
+        if not _row_stride_ok(out, B, L):
+            raise ValueError(f"out: rows must be contiguous and at least L apart, got strides {tuple(out.stride())}")
+        if out.data_ptr() == wav.data_ptr() and B > 1 and out.stride(0) != wav.stride(0):
+            raise ValueError("out: in place needs the row stride of wav")
+    return B, L, int(sos.size(1))
+
+
 def metric_frames(L: int, fs: int):
     """(WSS / segSNR frames, LLR frames) of an L-sample signal: the two counts of cmgan_amd.metrics."""
     win = int(np.round(30 * fs / 1000))
@@ -272,7 +322,7 @@ class Engine:
             msg = self.lib.cmgan_last_error(None)
             raise _lib.CmganError(rc, msg.decode() if msg else "?")
         #: grow-only uint8 workspaces by name (_grow): "main", "branched" (enhance_graphed(branches > 1)), "conformer",
-        #: "metrics", "mix", "rir", "level" and ("resample", fs_in, fs_out), the rate pair's tap table
+        #: "metrics", "mix", "rir", "level", "channel" and ("resample", fs_in, fs_out), the rate pair's tap table
         self._wss: dict = {}
         self._graphs: dict = {}          # enhance_graphed: input shape -> (graph, in, out, token)
         self._row_graphs: dict = {}      # streaming.enhance_windows: row shape -> (graph, in, out, token)
@@ -925,6 +975,34 @@ class Engine:
                    ws.numel())
         out = SpeechLevel(level[:, 0], level[:, 1], level[:, 2])
         return (out, cnt) if counts else out
+
+    # ---- recording channel ---------------------------------------------------------
+    @_on_device
+    def channel(self, wav: torch.Tensor, sos: torch.Tensor, n_sections: Optional[torch.Tensor] = None,
+                clip: Optional[torch.Tensor] = None, lengths: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None, status: bool = False):
+        """A recording channel per row on the GPU (cmgan_channel, include/cmgan_hip.h): a cascade of up to 8 biquads - an
+        equaliser or microphone response, a band limit - and a clipping level.
+
+        wav float32 [B, L] (rows contiguous, any row stride >= L); sos float64 [B, S, 6] in scipy's layout (b0 b1 b2 a0 a1
+        a2 with a0 = 1; cmgan_amd.mixing has the designs); n_sections int32 [B]: how many of its S sections a row uses
+        (None: all; 0 copies the row); clip float64 [B]: |y| is limited to it (None or +inf: no clipping); lengths int32 [B]
+        (None: every row has L samples; samples from a row's length on are never read, and come out as zeros).  All on
+        this Engine's device and read by the kernels only.  `out` float32 [B, L] is written in place of a new tensor;
+        out=wav runs in place.  Returns the float32 [B, L] result, the arithmetic of scipy.signal.sosfilt in float64 with
+        one rounding to float32; status=True adds an int32 [B] tensor, 1 for the rows that are invalid (a non-finite
+        coefficient, a0 != 1, an unstable section, n_sections outside [0, S], clip NaN or <= 0) and come out as zeros.
+        Bit-reproducible, row-independent (also of S beyond a row's own sections), no synchronisation, graph-capturable
+        after one call at the shape."""
+        B, L, S = check_channel_args(self.device, wav, sos, n_sections, clip, lengths, out)
+        ws = self._grow("channel", int(self.lib.cmgan_channel_workspace_bytes(B, L, S)),
+                        f"[{B}, {L}] with {S} sections is outside what cmgan_channel supports")
+        if out is None:
+            out = torch.empty(B, L, dtype=torch.float32, device=self.device)
+        st = torch.empty(B, dtype=torch.int32, device=self.device) if status else None
+        self._call("cmgan_channel", wav, B, L, wav.stride(0) if B > 1 else L, lengths, sos, n_sections, S, clip, out,
+                   out.stride(0) if B > 1 else L, st, ws, ws.numel())
+        return (out, st) if status else out
 
     # ---- diagnostics ---------------------------------------------------------------
     @_on_device

@@ -13,6 +13,8 @@ takes - with `clean` the training target (the dry clip, or the clip with its ear
     # either a fixed bank       rirs = RirBank.simulate(engine, RoomSampler(), 256)
     # or a fresh room per row of every batch
     mixer = DynamicMixer(engine, noise, rooms=RoomSampler(rt60=(0.2, 0.8)), snr_db=(0, 20), early_ms=50)
+    # the recording channel: a random equaliser, a band limit and clipping per row (Engine.channel / cmgan_channel)
+    mixer = DynamicMixer(engine, noise, rirs, channel=ChannelSampler(p_bandlimit=0.2, p_clip=0.1))
     clean = torch.utils.data.DataLoader(clean_only("data/train", 32000), batch_size=32, pin_memory=True, drop_last=True)
     Trainer(train_ds=MixingLoader(clean, mixer), ...)
 """
@@ -31,7 +33,8 @@ import torch.utils.data
 from .data import _natural_key, fit_length, read_wav
 
 __all__ = ["NoiseBank", "RirBank", "RoomSampler", "sabine_beta", "DynamicMixer", "MixingLoader", "CleanDataset",
-           "clean_only", "Draw", "tile"]
+           "clean_only", "Draw", "tile", "ChannelSampler", "biquad_peaking", "biquad_low_shelf", "biquad_high_shelf",
+           "biquad_lowpass", "biquad_highpass", "butter_lowpass_sos"]
 
 SPEED_OF_SOUND = 343.0        # m/s, the default `c` of Engine.rir
 RIR_TW = 40                   # the default half-width of its fractional-delay filter, in samples
@@ -158,6 +161,174 @@ class RoomSampler:
         return rooms, n_taps
 
 
+# ---- biquad designs: R. Bristow-Johnson's audio-EQ-cookbook formulas, normalised to a0 = 1 --------------------------
+def _f64(v, like=None) -> torch.Tensor:
+    if isinstance(v, torch.Tensor):
+        return v.to(torch.float64)
+    return torch.as_tensor(v, dtype=torch.float64, device=like.device if isinstance(like, torch.Tensor) else None)
+
+
+def _cookbook(f0, q, fs):
+    f0 = _f64(f0)
+    q = _f64(q, f0)
+    w0 = 2.0 * math.pi * f0 / fs
+    return torch.cos(w0), torch.sin(w0) / (2.0 * q)
+
+
+def _sos_rows(b0, b1, b2, a0, a1, a2) -> torch.Tensor:
+    """[..., 6] rows in scipy's layout (b0 b1 b2 a0 a1 a2), divided by a0 so that a0 is exactly 1."""
+    b0, b1, b2, a0, a1, a2 = torch.broadcast_tensors(b0, b1, b2, a0, a1, a2)
+    return torch.stack([b0 / a0, b1 / a0, b2 / a0, torch.ones_like(a0), a1 / a0, a2 / a0], dim=-1)
+
+
+def biquad_peaking(f0, gain_db, q, fs) -> torch.Tensor:
+    """A peaking-EQ section: gain_db at f0 (Hz), bandwidth set by q, unity far from f0.  Plain float64 tensor arithmetic on
+    the device of its arguments (like every design here); returns [..., 6] rows for Engine.channel."""
+    cw, alpha = _cookbook(f0, q, fs)
+    A = torch.pow(10.0, _f64(gain_db, cw) / 40.0)
+    return _sos_rows(1.0 + alpha * A, -2.0 * cw, 1.0 - alpha * A, 1.0 + alpha / A, -2.0 * cw, 1.0 - alpha / A)
+
+
+def biquad_low_shelf(f0, gain_db, q, fs) -> torch.Tensor:
+    """A low-shelf section: gain_db at DC, unity at Nyquist, the midpoint (gain_db / 2) at f0."""
+    cw, alpha = _cookbook(f0, q, fs)
+    A = torch.pow(10.0, _f64(gain_db, cw) / 40.0)
+    r = 2.0 * torch.sqrt(A) * alpha
+    return _sos_rows(A * ((A + 1.0) - (A - 1.0) * cw + r), 2.0 * A * ((A - 1.0) - (A + 1.0) * cw),
+                     A * ((A + 1.0) - (A - 1.0) * cw - r), (A + 1.0) + (A - 1.0) * cw + r,
+                     -2.0 * ((A - 1.0) + (A + 1.0) * cw), (A + 1.0) + (A - 1.0) * cw - r)
+
+
+def biquad_high_shelf(f0, gain_db, q, fs) -> torch.Tensor:
+    """A high-shelf section: gain_db at Nyquist, unity at DC, the midpoint (gain_db / 2) at f0."""
+    cw, alpha = _cookbook(f0, q, fs)
+    A = torch.pow(10.0, _f64(gain_db, cw) / 40.0)
+    r = 2.0 * torch.sqrt(A) * alpha
+    return _sos_rows(A * ((A + 1.0) + (A - 1.0) * cw + r), -2.0 * A * ((A - 1.0) + (A + 1.0) * cw),
+                     A * ((A + 1.0) + (A - 1.0) * cw - r), (A + 1.0) - (A - 1.0) * cw + r,
+                     2.0 * ((A - 1.0) - (A + 1.0) * cw), (A + 1.0) - (A - 1.0) * cw - r)
+
+
+def biquad_lowpass(f0, q, fs) -> torch.Tensor:
+    """A 2nd-order low-pass with corner f0: unity at DC, |H(f0)| = q (q = 1 / sqrt(2): Butterworth, -3.01 dB at f0)."""
+    cw, alpha = _cookbook(f0, q, fs)
+    return _sos_rows(0.5 * (1.0 - cw), 1.0 - cw, 0.5 * (1.0 - cw), 1.0 + alpha, -2.0 * cw, 1.0 - alpha)
+
+
+def biquad_highpass(f0, q, fs) -> torch.Tensor:
+    """A 2nd-order high-pass with corner f0: unity at Nyquist, |H(f0)| = q."""
+    cw, alpha = _cookbook(f0, q, fs)
+    return _sos_rows(0.5 * (1.0 + cw), -(1.0 + cw), 0.5 * (1.0 + cw), 1.0 + alpha, -2.0 * cw, 1.0 - alpha)
+
+
+def butter_lowpass_sos(order: int, fc, fs) -> torch.Tensor:
+    """An even-order (2 .. 8) Butterworth low-pass at fc as [..., order / 2, 6]: the cascade of cookbook low-passes with
+    Q_k = 1 / (2 cos(pi (2k + 1) / (2 order))), which has the frequency response of scipy.signal.butter's design."""
+    if isinstance(order, bool) or int(order) != order or order not in (2, 4, 6, 8):
+        raise ValueError(f"order must be 2, 4, 6 or 8, got {order}")
+    fc = _f64(fc)
+    return torch.stack([biquad_lowpass(fc, 1.0 / (2.0 * math.cos(math.pi * (2 * k + 1) / (2 * order))), fs)
+                        for k in range(order // 2)], dim=-2)
+
+
+def _range(name: str, v, lo_min: float = 0.0, what: str = "0 < low <= high"):
+    try:
+        lo, hi = float(v[0]), float(v[1])
+    except (TypeError, ValueError, IndexError):
+        raise ValueError(f"{name} must be (low, high), got {v}") from None
+    if not lo_min < lo <= hi < math.inf:
+        raise ValueError(f"{name} must be (low, high) with {what}, got {v}")
+    return lo, hi
+
+
+class ChannelSampler:
+    """Random recording channels for Engine.channel: `draw(B, fs, device)` -> `(sos float64 [B, S, 6], n_sections int32
+    [B], n_shared int32 [B], clip_rel float64 [B])`.
+
+    Per row, in this order of the cascade: with probability `p_highpass` a 2nd-order Butterworth high-pass, corner
+    log-uniform in `highpass_hz`; 0 .. `max_eq` (uniform) equaliser sections, each a peaking section, a low shelf or a high
+    shelf with equal probability, f0 log-uniform in `eq_hz` (None: 50 Hz .. 0.45 fs), gain uniform in +-`eq_db`, Q
+    uniform in `eq_q`; with probability `p_bandlimit` a Butterworth low-pass of `bandlimit_order` (even, 2 .. 8), cutoff
+    uniform in `bandlimit_hz`; with probability `p_clip` a clipping level as a fraction of the row's peak, uniform in
+    `clip_rel` (+inf for the other rows).  S = [p_highpass > 0] + max_eq + [p_bandlimit > 0] bandlimit_order / 2 (at least
+    1) is fixed by the options and may not exceed 8; a row's sections are packed to the front, the rest are the identity
+    (1 0 0 1 0 0).  n_shared says how many of a row's leading sections DynamicMixer(channel_on="both") also applies to the
+    target: all of them (the clip is the noisy signal's alone).  Everything is drawn from `generator` (None: the
+    device's default one) on the device with tensor arithmetic: no host synchronisation.  Every cookbook section with
+    0 < f0 < fs / 2 and Q > 0 lies inside the stability triangle, so no row of a draw is invalid."""
+
+    def __init__(self, p_highpass: float = 0.5, highpass_hz=(20.0, 120.0), max_eq: int = 3, eq_hz=None, eq_db: float = 6.0,
+                 eq_q=(0.5, 2.0), p_bandlimit: float = 0.2, bandlimit_hz=(3400.0, 3800.0), bandlimit_order: int = 8,
+                 p_clip: float = 0.1, clip_rel=(0.3, 0.9), generator: Optional[torch.Generator] = None):
+        for name, p in (("p_highpass", p_highpass), ("p_bandlimit", p_bandlimit), ("p_clip", p_clip)):
+            if not 0.0 <= float(p) <= 1.0:
+                raise ValueError(f"{name} must lie in [0, 1], got {p}")
+        self.p_highpass, self.p_bandlimit, self.p_clip = float(p_highpass), float(p_bandlimit), float(p_clip)
+        self.highpass_hz = _range("highpass_hz", highpass_hz)
+        self.eq_hz = None if eq_hz is None else _range("eq_hz", eq_hz)
+        self.eq_q = _range("eq_q", eq_q)
+        self.bandlimit_hz = _range("bandlimit_hz", bandlimit_hz)
+        self.clip_rel = _range("clip_rel", clip_rel)
+        if isinstance(max_eq, bool) or int(max_eq) != max_eq or max_eq < 0:
+            raise ValueError(f"max_eq must be a section count >= 0, got {max_eq}")
+        eq_db = float(eq_db)
+        if not 0.0 <= eq_db < math.inf:
+            raise ValueError(f"eq_db must be >= 0 and finite, got {eq_db}")
+        if isinstance(bandlimit_order, bool) or bandlimit_order not in (2, 4, 6, 8):
+            raise ValueError(f"bandlimit_order must be 2, 4, 6 or 8, got {bandlimit_order}")
+        self.max_eq, self.eq_db, self.bandlimit_order, self.generator = int(max_eq), eq_db, int(bandlimit_order), generator
+        self.n_hp = 1 if self.p_highpass > 0.0 else 0
+        self.n_bl = self.bandlimit_order // 2 if self.p_bandlimit > 0.0 else 0
+        total = self.n_hp + self.max_eq + self.n_bl
+        if total > 8:
+            raise ValueError(f"a high-pass, {self.max_eq} equaliser sections and a band limit of order {bandlimit_order} "
+                             f"are {total} sections; Engine.channel takes up to 8")
+        self.sections = max(total, 1)
+
+    def draw(self, B: int, fs: int, device=None):
+        gen = self.generator
+        device = torch.device(device) if device is not None else (gen.device if gen is not None else torch.device("cpu"))
+        fs = float(fs)
+        eq_hz = self.eq_hz if self.eq_hz is not None else (50.0, 0.45 * fs)
+        for name, (lo, hi) in (("highpass_hz", self.highpass_hz), ("eq_hz", eq_hz), ("bandlimit_hz", self.bandlimit_hz)):
+            if not (lo <= hi and hi < 0.5 * fs):
+                raise ValueError(f"{name} = {(lo, hi)} must lie below fs / 2 = {0.5 * fs} Hz")
+        E = self.max_eq
+        u = torch.rand(B, 7 + 4 * E, dtype=torch.float64, generator=gen, device=device)
+        log_uniform = lambda r, v: math.log(r[0]) + (math.log(r[1]) - math.log(r[0])) * v
+        uniform = lambda r, v: r[0] + (r[1] - r[0]) * v
+        rows, use = [], []
+        if self.n_hp:
+            rows.append(biquad_highpass(torch.exp(log_uniform(self.highpass_hz, u[:, 1])), math.sqrt(0.5), fs)[:, None])
+            use.append((u[:, 0] < self.p_highpass)[:, None])
+        if E:
+            n_eq = torch.clamp((u[:, 2] * (E + 1)).to(torch.int64), max=E)
+            v = u[:, 7:].reshape(B, E, 4)
+            f0 = torch.exp(log_uniform(eq_hz, v[..., 1]))
+            gain = self.eq_db * (2.0 * v[..., 2] - 1.0)
+            q = uniform(self.eq_q, v[..., 3])
+            kind = torch.clamp((v[..., 0] * 3).to(torch.int64), max=2)[..., None]
+            rows.append(torch.where(kind == 0, biquad_peaking(f0, gain, q, fs),
+                                    torch.where(kind == 1, biquad_low_shelf(f0, gain, q, fs),
+                                                biquad_high_shelf(f0, gain, q, fs))))
+            use.append(torch.arange(E, device=device)[None, :] < n_eq[:, None])
+        if self.n_bl:
+            rows.append(butter_lowpass_sos(self.bandlimit_order, uniform(self.bandlimit_hz, u[:, 4]), fs))
+            use.append((u[:, 3] < self.p_bandlimit)[:, None].expand(B, self.n_bl))
+        identity = torch.tensor([1.0, 0.0, 0.0, 1.0, 0.0, 0.0], dtype=torch.float64).to(device, non_blocking=True)
+        if rows:
+            sos, use = torch.cat(rows, dim=1), torch.cat(use, dim=1)
+            sos = torch.where(use[..., None], sos, identity)
+            order = torch.argsort((~use).to(torch.int8), dim=1, stable=True)          # a row's own sections first, in order
+            sos = torch.gather(sos, 1, order[..., None].expand(B, sos.size(1), 6)).contiguous()
+            n_sections = use.sum(dim=1).to(torch.int32)
+        else:
+            sos = identity.expand(B, 1, 6).contiguous()
+            n_sections = torch.zeros(B, dtype=torch.int32, device=device)
+        clip = torch.where(u[:, 5] < self.p_clip, uniform(self.clip_rel, u[:, 6]), torch.full_like(u[:, 6], math.inf))
+        return sos, n_sections, n_sections.clone(), clip
+
+
 class RirBank:
     """Room impulse responses as one float32 [R, Kmax] device allocation, rows zero-padded, plus `length` (int32 [R]).
     Recorded responses come from `from_dir` / `from_arrays`; `simulate` makes the bank on the device from random shoe-box
@@ -213,6 +384,7 @@ class Draw(NamedTuple):
     rir_len: Optional[torch.Tensor]
     rooms: Optional[torch.Tensor] = None      # DynamicMixer(rooms=...): the float64 [B, 15] room table of the batch
     level_db: Optional[torch.Tensor] = None   # DynamicMixer(level_db=...): the float64 [B] target active level in dBFS
+    channel: Optional[tuple] = None           # DynamicMixer(channel=...): (sos, n_sections, n_shared, clip_rel) of the batch
 
 
 class DynamicMixer:
@@ -241,12 +413,28 @@ class DynamicMixer:
     `level_db=(lo, hi)`: a target active level, uniform in dBFS, is drawn per row (after every other draw) and the clean
     row is multiplied in float32 by f32(sqrt(10^(level / 10) / active_ms)) before Engine.mix; the factor is 1 where no
     speech was detected.  This is one measurement and one gain: the thresholds of P.56 are absolute, so measuring the
-    scaled row again gives a slightly different level than the one drawn."""
+    scaled row again gives a slightly different level than the one drawn.
+
+    `channel` (a ChannelSampler): the recording channel (Engine.channel / cmgan_channel).  With None nothing is drawn or
+    run and the outputs, `last_draw` and every generator state are what they are without the argument.  With a sampler, a
+    channel per row is drawn after every other draw, from the sampler's own generator, and kept as `last_draw.channel`;
+    `noisy` goes through the row's sections in place and is then limited to clip = clip_rel x max |noisy| of the row as it
+    was BEFORE the channel (`channel_clip`; no limit where clip_rel is +inf or the row is silent).  `channel_on="noisy"`
+    (the default) leaves the target as it is: the model is asked to undo the channel too.  `channel_on="both"` also passes
+    `target` through the row's first n_shared sections, without clipping: the model is then not asked to undo the
+    microphone or to extend the bandwidth.  The mixer's peak guard (`peak`) acts BEFORE the channel, so a boosting
+    equaliser can exceed it; that is what the clip is for."""
 
     def __init__(self, engine, noise_bank: NoiseBank, rir_bank: Optional[RirBank] = None, snr_db=(0.0, 20.0),
                  early_ms: Optional[float] = 50.0, p_reverb: float = 1.0, peak: float = 0.99,
                  generator: Optional[torch.Generator] = None, sample_rate: int = 16000,
-                 rooms: Optional[RoomSampler] = None, rir_seconds: float = 0.5, snr_on: str = "rms", level_db=None):
+                 rooms: Optional[RoomSampler] = None, rir_seconds: float = 0.5, snr_on: str = "rms", level_db=None,
+                 channel: Optional[ChannelSampler] = None, channel_on: str = "noisy"):
+        if channel_on not in ("noisy", "both"):
+            raise ValueError(f"channel_on must be 'noisy' or 'both', got {channel_on!r}")
+        if channel is not None and not isinstance(channel, ChannelSampler):
+            raise TypeError(f"channel must be a ChannelSampler or None, got {type(channel).__name__}")
+        self.channel, self.channel_on = channel, channel_on
         if snr_on not in ("rms", "active"):
             raise ValueError(f"snr_on must be 'rms' or 'active', got {snr_on!r}")
         if level_db is not None:
@@ -316,7 +504,8 @@ class DynamicMixer:
         if self.level_db is not None:
             lo, hi = self.level_db
             level = lo + (hi - lo) * torch.rand(B, dtype=torch.float64, generator=gen, device=dev)
-        return Draw(start.contiguous(), length.contiguous(), off, snr, idx, rlen, table, level)
+        chan = self.channel.draw(B, self.sample_rate, device=dev) if self.channel is not None else None
+        return Draw(start.contiguous(), length.contiguous(), off, snr, idx, rlen, table, level, chan)
 
     def _simulate(self, d: Draw) -> RirBank:
         """The batch's responses, simulated into the persistent allocation (made anew only when B changes)."""
@@ -358,7 +547,20 @@ class DynamicMixer:
         noisy, target, info = self.engine.mix(clean, self.noise_bank.data, d.noise_start, d.noise_len, d.noise_off,
                                               snr, rir.data if rir is not None else None, d.rir_index, d.rir_len,
                                               peak=self.peak, early=self.early if rir is not None else -1)
+        if d.channel is not None:
+            sos, n_sections, n_shared, clip_rel = d.channel
+            self.engine.channel(noisy, sos, n_sections, self.channel_clip(clip_rel, noisy), out=noisy)
+            if self.channel_on == "both":
+                self.engine.channel(target, sos, n_shared, out=target)
         return target, noisy, info
+
+    @staticmethod
+    def channel_clip(clip_rel: torch.Tensor, noisy: torch.Tensor) -> torch.Tensor:
+        """The float64 [B] clipping level of Engine.channel for a drawn `clip_rel`: clip_rel x max |noisy| per row, and
+        +inf (no limit) where clip_rel is +inf or the row is silent."""
+        top = noisy.abs().amax(dim=1).to(torch.float64)
+        on = torch.isfinite(clip_rel) & (top > 0)
+        return torch.where(on, torch.where(on, clip_rel, torch.ones_like(clip_rel)) * top, torch.full_like(top, math.inf))
 
 
 class CleanDataset(torch.utils.data.Dataset):

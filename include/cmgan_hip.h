@@ -39,7 +39,7 @@ extern "C" {
 #define CMGAN_E_WORKSPACE   -5   /* workspace too small or misaligned              */
 #define CMGAN_E_HIP         -6   /* a HIP runtime call failed (see last_error)     */
 
-#define CMGAN_ABI_VERSION 10
+#define CMGAN_ABI_VERSION 11
 
 typedef struct cmgan_handle cmgan_handle;
 
@@ -732,6 +732,41 @@ int cmgan_speech_level_tile(void);
 size_t cmgan_speech_level_workspace_bytes(int B, int L);
 int cmgan_speech_level(cmgan_handle* h, const float* x_dev, int B, int L, long long ld, const int* lengths_dev, int fs,
                        double* level_dev, long long* counts_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- Recording channel (the reference has no augmentation: src/data/dataloader.py:13-50 replays pairs mixed beforehand) -
+ * Per row a cascade of biquads (microphone / equaliser response, band limit) and a clipping level, for B rows
+ * x_dev[b * ldx + i] of float32 samples, written to y_dev[b * ldy + i].  All per-row tables are in DEVICE memory and read by
+ * the kernels only: lengths_dev int32 [B] (NULL: n = L), sos_dev float64 [B][S][6] in scipy's layout b0 b1 b2 a0 a1 a2,
+ * n_sections_dev int32 [B] (NULL: S for every row), clip_dev float64 [B] (NULL: no clipping; +inf: none for that row),
+ * status_dev int32 [B] (may be NULL).  S is a host int in 1 .. cmgan_channel_max_sections() = 8.  For row b, with
+ * n = clamp(lengths[b], 0, L) and m = n_sections[b]:
+ *   sections 0 .. m-1 in order, each from zero state in float64 (transposed direct form II, scipy.signal.sosfilt's loop):
+ *       y_i = b0 u_i + z1,   z1 <- b1 u_i - a1 y_i + z2,   z2 <- b2 u_i - a2 y_i
+ *   the result limited to [-clip[b], clip[b]], rounded ONCE to float32, stored for i < n;  y[b, i] = 0 for n <= i < L.
+ * m = 0 copies the row (and clips it).  Samples of x at i >= n are never read.  A row is INVALID - status 1 (else 0) and
+ * L zeros - when a coefficient of a section it uses is not finite, a0 != 1, a section lies outside the stability triangle
+ * (|a2| < 1 and |a1| < 1 + a2), m is outside [0, S], or clip[b] is NaN or <= 0.  A non-finite sample at position i leaves
+ * the samples before i as defined; from i on the row is not specified (with a recursive section: non-finite).
+ * Method.  The cascade is one linear system in the 2 m states z; a segment of k samples run from zero state, ending in Z,
+ * acts on an incoming state as z' = A^k z + Z.  A block owns a tile of cmgan_channel_tile() samples, a thread 8 of them:
+ * a prepare launch judges every row and tabulates the powers of A the scans need by repeated squaring, the tiles' end
+ * states are found per tile and folded in ascending order, and every thread then runs its samples from its entry state.
+ * All arithmetic is float64 on the VALU; no atomics; every reduction runs in an order that depends on the tile grid alone,
+ * so the same bits come out from run to run, and row b's bits depend neither on B, nor on the other rows, nor on L beyond
+ * n, nor on S beyond the row's own m.
+ * y_dev == x_dev with ldy == ldx (in place) is allowed; any other intersection of [x, x + (B-1) ldx + L) with y's span is
+ * CMGAN_E_BADARG.  Checked before any launch and before the handle is looked at (the message of a call with h == NULL is
+ * read with cmgan_last_error(NULL)): null x / sos / y, misaligned pointers (4 bytes for float32 / int32, 8 for float64),
+ * 1 <= B <= 65535, 1 <= L <= 2^31 - 1 - cmgan_channel_tile(), ldx >= L, ldy >= L, 1 <= S <= 8, the overlap above, a
+ * workspace that is null, not 256-byte aligned or smaller than cmgan_channel_workspace_bytes(B, L, S) (0 for an unsupported
+ * shape; non-decreasing in B, L and S); each is CMGAN_E_BADARG.  Four launches, no synchronisation, no allocation;
+ * graph-capturable, and a replay reads the current contents of every device table.                                    */
+int cmgan_channel_tile(void);
+int cmgan_channel_max_sections(void);
+size_t cmgan_channel_workspace_bytes(int B, int L, int S);
+int cmgan_channel(cmgan_handle* h, const float* x_dev, int B, int L, long long ldx, const int* lengths_dev,
+                  const double* sos_dev, const int* n_sections_dev, int S, const double* clip_dev, float* y_dev,
+                  long long ldy, int* status_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* Names + durations (ms) of the kernels of the most recent forward when
  * profiling is enabled with cmgan_set_profiling(h, 1): HIP events are recorded
