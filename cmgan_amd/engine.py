@@ -260,6 +260,43 @@ def check_channel_args(device, wav, sos, n_sections=None, clip=None, lengths=Non
     return B, L, int(sos.size(1))
 
 
+WARP_TILE = 256               # outputs per block of cmgan_warp (= cmgan_warp_tile())
+WARP_MAX_RATE = 4.0           # rates in [1 / 4, 4] (= cmgan_warp_max_rate())
+WARP_ZEROS = (4, 64)          # zero crossings on either side of the filter's centre (64 = cmgan_warp_max_zeros())
+WARP_ROLLOFF = (0.5, 1.0)     # the cutoff as a fraction of the lower Nyquist rate
+
+
+def check_warp_args(device, wav, rate, n_out=None, lengths=None, zeros=24, rolloff=0.95, out=None):
+    """Argument rules of Engine.warp (shapes, dtypes, devices and host scalars; pure host code).  Returns (B, L, N); N is
+    None when neither n_out nor out says it (Engine.warp then takes cmgan_warp_out_len(L, 1 / 4))."""
+    tensor_arg(wav, "wav", torch.float32, device, "[B, L] with B, L >= 1",
+               lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) >= 1, contiguous=False)     # (its own stride rule below)
+    B, L = wav.shape
+    if B > 65535:
+        raise ValueError(f"wav: at most 65535 rows, got {B}")
+    if not _row_stride_ok(wav, B, L):
+        raise ValueError(f"wav: rows must be contiguous and at least L apart, got strides {tuple(wav.stride())}")
+    row = lambda t: tuple(t.shape) == (B,)
+    tensor_arg(rate, "rate", torch.float64, device, f"[{B}]", row)
+    if lengths is not None:
+        tensor_arg(lengths, "lengths", torch.int32, device, f"[{B}]", row)
+    if n_out is not None and (isinstance(n_out, bool) or int(n_out) != n_out or not 1 <= n_out <= 2 ** 31 - 1):
+        raise ValueError(f"n_out must be an output length in [1, 2^31 - 1] or None, got {n_out}")
+    if isinstance(zeros, bool) or int(zeros) != zeros or not WARP_ZEROS[0] <= zeros <= WARP_ZEROS[1]:
+        raise ValueError(f"zeros must be a whole number in [{WARP_ZEROS[0]}, {WARP_ZEROS[1]}], got {zeros}")
+    if isinstance(rolloff, bool) or not WARP_ROLLOFF[0] <= float(rolloff) <= WARP_ROLLOFF[1]:
+        raise ValueError(f"rolloff must lie in [{WARP_ROLLOFF[0]}, {WARP_ROLLOFF[1]}], got {rolloff}")
+    N = None if n_out is None else int(n_out)
+    if out is not None:
+        tensor_arg(out, "out", torch.float32, device, f"[{B}, N]" if N is None else f"[{B}, {N}]",
+                   lambda t: t.dim() == 2 and t.size(0) == B and t.size(1) >= 1 and (N is None or t.size(1) == N),
+                   contiguous=False)
+        N = int(out.size(1))
+        if not _row_stride_ok(out, B, N):
+            raise ValueError(f"out: rows must be contiguous and at least N apart, got strides {tuple(out.stride())}")
+    return B, L, N
+
+
 def metric_frames(L: int, fs: int):
     """(WSS / segSNR frames, LLR frames) of an L-sample signal: the two counts of cmgan_amd.metrics."""
     win = int(np.round(30 * fs / 1000))
@@ -1003,6 +1040,38 @@ class Engine:
         self._call("cmgan_channel", wav, B, L, wav.stride(0) if B > 1 else L, lengths, sos, n_sections, S, clip, out,
                    out.stride(0) if B > 1 else L, st, ws, ws.numel())
         return (out, st) if status else out
+
+    # ---- speed perturbation ---------------------------------------------------------
+    @_on_device
+    def warp(self, wav: torch.Tensor, rate: torch.Tensor, n_out: Optional[int] = None, lengths: Optional[torch.Tensor] = None,
+             zeros: int = 24, rolloff: float = 0.95, out: Optional[torch.Tensor] = None, info: bool = False):
+        """Speed perturbation per row on the GPU (cmgan_warp, include/cmgan_hip.h): every row is resampled by its own rate
+        with a Hann-windowed sinc, so that tempo and pitch move together.
+
+        wav float32 [B, L] (rows contiguous, any row stride >= L); rate float64 [B]: input samples per output sample, any
+        value in [1 / 4, 4] (> 1 is faster and higher; 1.0001 is a sound card's clock drift); lengths int32 [B] (None:
+        every row has L samples; samples from a row's length on are never read).  All on this Engine's device and read by
+        the kernel only.  n_out: the output length N; None takes cmgan_warp_out_len(L, 1 / 4), room for the slowest valid
+        rate - pass it in real use (cmgan_amd.mixing.warp_len(L, rate) is the length one rate gives).  zeros (4 .. 64)
+        zero crossings on either side of the filter's centre; rolloff (0.5 .. 1) the cutoff as a fraction of the lower of
+        the two Nyquist rates.  `out` float32 [B, N] is written in place of a new tensor; it may not overlap wav.
+        Returns the float32 [B, N] result: row b holds out_len[b] = min(N, #{i : fl(i rate[b]) < lengths[b]}) samples,
+        float64 sums with one rounding to float32, then zeros; rate = 1 with rolloff = 1 copies the row bit for bit.
+        info=True adds (out_len int32 [B], status int32 [B]): status 1 marks the rows that are invalid (a rate that is
+        not a finite number in [1 / 4, 4], a length outside [0, L]) and come out as zeros with out_len 0.
+        Bit-reproducible, row-independent, one launch, no workspace, no synchronisation, graph-capturable."""
+        B, L, N = check_warp_args(self.device, wav, rate, n_out, lengths, zeros, rolloff, out)
+        if N is None:
+            N = int(self.lib.cmgan_warp_out_len(L, 1.0 / WARP_MAX_RATE))
+            if N > 2 ** 31 - 1:
+                raise ValueError(f"wav: rows of {L} samples need n_out; the default, {N}, is beyond 2^31 - 1")
+        if out is None:
+            out = torch.empty(B, N, dtype=torch.float32, device=self.device)
+        n = torch.empty(B, dtype=torch.int32, device=self.device) if info else None
+        st = torch.empty(B, dtype=torch.int32, device=self.device) if info else None
+        self._call("cmgan_warp", wav, B, L, wav.stride(0) if B > 1 else L, lengths, rate, int(zeros), float(rolloff), out, N,
+                   out.stride(0) if B > 1 else N, n, st)
+        return (out, n, st) if info else out
 
     # ---- diagnostics ---------------------------------------------------------------
     @_on_device

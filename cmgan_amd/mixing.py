@@ -17,6 +17,10 @@ takes - with `clean` the training target (the dry clip, or the clip with its ear
     mixer = DynamicMixer(engine, noise, rirs, channel=ChannelSampler(p_bandlimit=0.2, p_clip=0.1))
     clean = torch.utils.data.DataLoader(clean_only("data/train", 32000), batch_size=32, pin_memory=True, drop_last=True)
     Trainer(train_ds=MixingLoader(clean, mixer), ...)
+    # speed perturbation: every row resampled by a rate of its own (Engine.warp / cmgan_warp).  The batch comes out
+    # warp_len(L, hi) samples long, so the loader cuts clips hi times longer than the batch it wants
+    mixer = DynamicMixer(engine, noise, rirs, speed=(0.9, 1.1))
+    clean = torch.utils.data.DataLoader(clean_only("data/train", cut_len=math.ceil(32000 * 1.1)), batch_size=32, ...)
 """
 from __future__ import annotations
 
@@ -34,10 +38,20 @@ from .data import _natural_key, fit_length, read_wav
 
 __all__ = ["NoiseBank", "RirBank", "RoomSampler", "sabine_beta", "DynamicMixer", "MixingLoader", "CleanDataset",
            "clean_only", "Draw", "tile", "ChannelSampler", "biquad_peaking", "biquad_low_shelf", "biquad_high_shelf",
-           "biquad_lowpass", "biquad_highpass", "butter_lowpass_sos"]
+           "biquad_lowpass", "biquad_highpass", "butter_lowpass_sos", "warp_len"]
 
 SPEED_OF_SOUND = 343.0        # m/s, the default `c` of Engine.rir
 RIR_TW = 40                   # the default half-width of its fractional-delay filter, in samples
+SPEED_RANGE = (0.25, 4.0)     # the rates Engine.warp takes (cmgan_warp_max_rate)
+
+
+def warp_len(L: int, rate: float) -> int:
+    """How many samples Engine.warp makes of a row of L at `rate` (cmgan_warp_out_len): #{i >= 0 : fl(i rate) < L}."""
+    from . import _lib
+    n = int(_lib.load().cmgan_warp_out_len(int(L), float(rate)))
+    if n < 0:
+        raise ValueError(f"warp_len needs L >= 0 and a rate in [{SPEED_RANGE[0]}, {SPEED_RANGE[1]}], got L = {L}, rate = {rate}")
+    return n
 
 
 def tile() -> int:
@@ -385,6 +399,7 @@ class Draw(NamedTuple):
     rooms: Optional[torch.Tensor] = None      # DynamicMixer(rooms=...): the float64 [B, 15] room table of the batch
     level_db: Optional[torch.Tensor] = None   # DynamicMixer(level_db=...): the float64 [B] target active level in dBFS
     channel: Optional[tuple] = None           # DynamicMixer(channel=...): (sos, n_sections, n_shared, clip_rel) of the batch
+    speed: Optional[torch.Tensor] = None      # DynamicMixer(speed=...): the float64 [B] rate of Engine.warp per row
 
 
 class DynamicMixer:
@@ -423,13 +438,36 @@ class DynamicMixer:
     (the default) leaves the target as it is: the model is asked to undo the channel too.  `channel_on="both"` also passes
     `target` through the row's first n_shared sections, without clipping: the model is then not asked to undo the
     microphone or to extend the bandwidth.  The mixer's peak guard (`peak`) acts BEFORE the channel, so a boosting
-    equaliser can exceed it; that is what the clip is for."""
+    equaliser can exceed it; that is what the clip is for.
+
+    `speed=(lo, hi)` with 1/4 <= lo <= hi <= 4: speed perturbation (Engine.warp / cmgan_warp), the one stage that changes
+    the talker: tempo and pitch move together.  With None (the default) nothing is drawn or run and the outputs,
+    `last_draw` (apart from its trailing `speed=None`) and every generator state are what they are without the argument.
+    With a range, a float64 rate per row - input samples per output sample, > 1 is faster and higher - is drawn from the
+    mixer's generator after the `level_db` draw: uniform in [lo, hi], and exactly 1.0 with probability 1 - `p_speed`;
+    it is kept as `last_draw.speed`.  The clean batch goes through Engine.warp FIRST, before the level measurement and
+    before Engine.mix, with n_out = N = warp_len(L, hi): every rate <= hi makes at least N outputs of L samples, so all
+    rows are full and target and noisy are [B, N].  The loader should therefore cut clips hi times longer than the batch
+    it wants: `clean_only(dir, cut_len=math.ceil(32000 * hi))` for batches of 32000.  A row drawn as 1.0 passes the same
+    filter (`speed_zeros`, `speed_rolloff`) as the others - it is band-limited at the rolloff, not copied."""
 
     def __init__(self, engine, noise_bank: NoiseBank, rir_bank: Optional[RirBank] = None, snr_db=(0.0, 20.0),
                  early_ms: Optional[float] = 50.0, p_reverb: float = 1.0, peak: float = 0.99,
                  generator: Optional[torch.Generator] = None, sample_rate: int = 16000,
                  rooms: Optional[RoomSampler] = None, rir_seconds: float = 0.5, snr_on: str = "rms", level_db=None,
-                 channel: Optional[ChannelSampler] = None, channel_on: str = "noisy"):
+                 channel: Optional[ChannelSampler] = None, channel_on: str = "noisy", speed=None, p_speed: float = 1.0,
+                 speed_zeros: int = 24, speed_rolloff: float = 0.95):
+        if speed is not None:
+            try:
+                speed = (float(speed[0]), float(speed[1]))
+            except (TypeError, ValueError, IndexError):
+                raise ValueError(f"speed must be None or (low, high), got {speed}") from None
+            if not SPEED_RANGE[0] <= speed[0] <= speed[1] <= SPEED_RANGE[1]:
+                raise ValueError(f"speed must be (low, high) with {SPEED_RANGE[0]} <= low <= high <= {SPEED_RANGE[1]}, got {speed}")
+        if not 0.0 <= float(p_speed) <= 1.0:
+            raise ValueError(f"p_speed must lie in [0, 1], got {p_speed}")
+        self.speed, self.p_speed = speed, float(p_speed)
+        self.speed_zeros, self.speed_rolloff = int(speed_zeros), float(speed_rolloff)
         if channel_on not in ("noisy", "both"):
             raise ValueError(f"channel_on must be 'noisy' or 'both', got {channel_on!r}")
         if channel is not None and not isinstance(channel, ChannelSampler):
@@ -504,8 +542,14 @@ class DynamicMixer:
         if self.level_db is not None:
             lo, hi = self.level_db
             level = lo + (hi - lo) * torch.rand(B, dtype=torch.float64, generator=gen, device=dev)
+        speed = None
+        if self.speed is not None:
+            lo, hi = self.speed
+            u = torch.rand(B, 2, dtype=torch.float64, generator=gen, device=dev)
+            speed = torch.clamp(lo + (hi - lo) * u[:, 0], lo, hi)          # (the sum may round past hi)
+            speed = torch.where(u[:, 1] < self.p_speed, speed, torch.ones_like(speed)).contiguous()
         chan = self.channel.draw(B, self.sample_rate, device=dev) if self.channel is not None else None
-        return Draw(start.contiguous(), length.contiguous(), off, snr, idx, rlen, table, level, chan)
+        return Draw(start.contiguous(), length.contiguous(), off, snr, idx, rlen, table, level, chan, speed)
 
     def _simulate(self, d: Draw) -> RirBank:
         """The batch's responses, simulated into the persistent allocation (made anew only when B changes)."""
@@ -535,6 +579,9 @@ class DynamicMixer:
         d = self.last_draw = self.draw(clean.size(0))
         rir = self.rir_bank if self.rooms is None else self._simulate(d)
         snr = d.snr_db
+        if d.speed is not None:
+            clean = self.engine.warp(clean, d.speed, warp_len(clean.size(1), self.speed[1]), zeros=self.speed_zeros,
+                                     rolloff=self.speed_rolloff)
         if self.snr_on == "active" or d.level_db is not None:
             lv = self.last_level = self.engine.speech_level(clean, fs=self.sample_rate)
             if self.snr_on == "active":
@@ -590,6 +637,7 @@ class MixingLoader:
     """Wraps a loader of clean clips - batches `(clean [B, L], length [B])`, or any tuple whose first element is the
     clean batch and whose last is the lengths - and yields `(target, noisy, length)` with target / noisy float32 device
     tensors: the `(clean, noisy, length)` batches of `load_data`, so `Trainer(train_ds=MixingLoader(...))` works as is.
+    With `DynamicMixer(speed=...)` the batch is `warp_len(L, hi)` samples long and the lengths are clamped to that.
 
     Stream ordering.  The clean batch is copied to the device (non-blocking from pinned memory) and mixed on the stream
     that is CURRENT when the batch is requested.  `DevicePrefetcher._stage` requests a batch on the compute stream, then
@@ -618,6 +666,8 @@ class MixingLoader:
                 clean, length = batch[0], batch[-1]
             clean = clean.to(device=dev, dtype=torch.float32, non_blocking=True).contiguous()
             target, noisy, info = self.mixer(clean)
+            if self.mixer.speed is not None:                           # the batch is not as long as the clips it was made of
+                length = torch.as_tensor(length).clamp(max=noisy.size(1))
             self._alive.append((clean, target, noisy, info, self.mixer.last_draw))
             self.last_info = info
             yield target, noisy, length

@@ -39,7 +39,7 @@ extern "C" {
 #define CMGAN_E_WORKSPACE   -5   /* workspace too small or misaligned              */
 #define CMGAN_E_HIP         -6   /* a HIP runtime call failed (see last_error)     */
 
-#define CMGAN_ABI_VERSION 11
+#define CMGAN_ABI_VERSION 12
 
 typedef struct cmgan_handle cmgan_handle;
 
@@ -767,6 +767,44 @@ size_t cmgan_channel_workspace_bytes(int B, int L, int S);
 int cmgan_channel(cmgan_handle* h, const float* x_dev, int B, int L, long long ldx, const int* lengths_dev,
                   const double* sos_dev, const int* n_sections_dev, int S, const double* clip_dev, float* y_dev,
                   long long ldy, int* status_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- Speed perturbation (the reference has no counterpart: its data path replays fixed pairs, src/data/dataloader.py) ---
+ * Every row of a [B, L] float32 batch x_dev[b * ldx + k] is resampled by its OWN rate into N outputs y_dev[b * ldy + i]:
+ * band-limited interpolation with a Hann-windowed sinc.  rate_dev float64 [B] (input samples per output sample: > 1 is
+ * faster and higher), lengths_dev int32 [B] (NULL: n = L), out_len_dev and status_dev int32 [B] (each may be NULL) are in
+ * DEVICE memory and read / written by the kernel only; zeros (4 .. cmgan_warp_max_zeros() = 64 zero crossings on either
+ * side) and rolloff (0.5 .. 1, the cutoff as a fraction of the lower Nyquist rate) are host values.  In float64, for row
+ * b with n = lengths[b] and r = rate[b]:
+ *   t_i  = fl(i r)                                 the time of output i: ONE rounded product
+ *   M    = min(N, #{i >= 0 : t_i < n})             out_len[b]; what cmgan_warp_out_len(n, r) returns before the min
+ *   fc   = rolloff (r > 1 ? 1 / r : 1),  W = zeros / fc
+ *   h(d) = fc sinc(fc d) (0.5 + 0.5 cospi(d / W)) for |d| < W, else 0;   sinc(z) = sinpi(z) / (pi z), sinc(0) = 1
+ *   y[b, i] = f32( sum_k x[b, k] h(t_i - k) )      over the integers k with |t_i - k| < W and 0 <= k < n, ascending;
+ *                                                  ONE rounding to float32;  y[b, i] = 0 for M <= i < N
+ * Samples of x at k >= n are never read.  r = 1 with rolloff = 1 copies the row bit for bit.  A row is INVALID - status 1
+ * (else 0), out_len 0 and N zeros - when its rate is not a finite number in [1 / cmgan_warp_max_rate(),
+ * cmgan_warp_max_rate()] = [1/4, 4] or its length lies outside [0, L].  An output whose support holds a non-finite sample
+ * is non-finite; the others are not affected.
+ * Method.  A block owns cmgan_warp_tile() consecutive outputs of one row, a thread one of them; the input span of the
+ * tile is staged on chip.  The sine of the sinc and the cosine of the window fall by a constant angle from tap to tap: a
+ * thread evaluates sinpi / cospi at its first tap and turns the two (sin, cos) pairs by the angle-addition identities
+ * from there; the taps with |d| < 1 take sinpi(fc d) and cospi(d / W) directly.  With fc = 1 the turn is exactly
+ * (-1, 0), so integer times keep an exact zero sine.  No atomics, no workspace; row b's bits depend neither on B, nor
+ * on the other rows, nor on the padding behind ldx / ldy, nor on L beyond n.
+ * cmgan_warp_out_len is pure host arithmetic: ceil(n / r) corrected by single steps until fl((M - 1) r) < n <= fl(M r);
+ * -1 for n < 0, n > 2^50 or a rate outside [1/4, 4].
+ * Checked before the launch and before the handle is looked at (the message of a call with h == NULL is read with
+ * cmgan_last_error(NULL)): null x / rate / y, misaligned pointers (4 bytes for float32 / int32, 8 for the rates),
+ * 1 <= B <= 65535, L >= 1, N >= 1, ldx >= L, ldy >= N, 4 <= zeros <= 64, 0.5 <= rolloff <= 1, any intersection of
+ * [x, x + (B-1) ldx + L) with [y, y + (B-1) ldy + N); each is CMGAN_E_BADARG.  One launch, no synchronisation, no
+ * allocation; graph-capturable, and a replay reads the current contents of x, the rates and the lengths.            */
+int cmgan_warp_tile(void);
+double cmgan_warp_max_rate(void);
+int cmgan_warp_max_zeros(void);
+long long cmgan_warp_out_len(long long n, double rate);
+int cmgan_warp(cmgan_handle* h, const float* x_dev, int B, int L, long long ldx, const int* lengths_dev,
+               const double* rate_dev, int zeros, double rolloff, float* y_dev, int N, long long ldy, int* out_len_dev,
+               int* status_dev, void* stream);
 
 /* Names + durations (ms) of the kernels of the most recent forward when
  * profiling is enabled with cmgan_set_profiling(h, 1): HIP events are recorded
