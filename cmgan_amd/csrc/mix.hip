@@ -33,15 +33,9 @@
 #include <stdint.h>
 
 #include "api_internal.h"
+#include "mix_common.hip.h"
 
 namespace {
-
-constexpr int MX_TPB = 256;                 // threads of every kernel here
-constexpr int MX_OPT = 4;                   // outputs per thread of mix_conv: outputs t, t + 256, t + 512, t + 768 of the tile
-constexpr int MX_TILE = MX_TPB * MX_OPT;    // outputs per block
-constexpr int MX_KC = 1024;                 // taps per LDS chunk: 8 KiB of taps + 16 KiB of clean span, both float64
-constexpr int MX_MAX_K = 65536;             // longest RIR (4 s at 16 kHz)
-constexpr int MX_MAX_L = 0x7fffffff - MX_TILE;   // a tile's sample indices stay in an int
 
 struct MixArgs {
     const float* clean;
@@ -70,68 +64,12 @@ struct MixArgs {
     int B, L, R, Kmax, early, nt;
 };
 
-// the row's noise segment: valid only if it lies inside the bank; `off` is noise_off mod noise_len in [0, len)
-struct NoiseRow {
-    const float* p;
-    long long len, off;
-};
-
 __device__ inline NoiseRow mix_noise_row(const MixArgs& a, int b) {
-    NoiseRow r;
-    const long long st = a.n_start[b];
-    r.len = a.n_len[b];
-    const bool ok = st >= 0 && r.len >= 1 && st <= a.bank_len && r.len <= a.bank_len - st;
-    if (!ok) {
-        r.p = nullptr;
-        r.len = 1;
-        r.off = 0;
-        return r;
-    }
-    r.p = a.bank + st;
-    const long long o = a.n_off[b] % r.len;
-    r.off = o < 0 ? o + r.len : o;
-    return r;
-}
-
-__device__ inline double mix_noise(const NoiseRow& r, int i) {
-    return r.p ? (double)r.p[(r.off + i) % r.len] : 0.0;
-}
-
-// v = speech + g n: one expression for mix_vmax and mix_apply, so both see the same bits
-__device__ inline double mix_v(double speech, double g, double n) { return fma(g, n, speech); }
-
-__device__ inline double block_sum(double v, double* red) {          // fixed order: halves folded, every thread calls
-    const int t = threadIdx.x;
-    red[t] = v;
-    __syncthreads();
-    for (int s = MX_TPB / 2; s > 0; s >>= 1) {
-        if (t < s) red[t] += red[t + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
-__device__ inline double block_max(double v, double* red) {
-    const int t = threadIdx.x;
-    red[t] = v;
-    __syncthreads();
-    for (int s = MX_TPB / 2; s > 0; s >>= 1) {
-        if (t < s) red[t] = fmax(red[t], red[t + s]);
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
+    return mx_segment(a.bank, a.bank_len, a.n_start[b], a.n_len[b], a.n_off[b]);
 }
 
 __device__ inline void mix_rir_row(const MixArgs& a, int b, const float*& h, int& K) {
-    int idx = a.rir_index[b];
-    idx = idx < 0 ? 0 : (idx >= a.R ? a.R - 1 : idx);
-    K = a.rir_len[b];
-    K = K < 1 ? 1 : (K > a.Kmax ? a.Kmax : K);
-    h = a.rir + (size_t)idx * a.Kmax;
+    mx_rir_row(a.rir, a.R, a.Kmax, a.rir_index[b], a.rir_len[b], h, K);
 }
 
 // ------------------------------------------------------------------------------------------ kernels
@@ -142,24 +80,8 @@ __global__ __launch_bounds__(MX_TPB) void mix_direct(MixArgs a) {
     const float* h;
     int K;
     mix_rir_row(a, b, h, K);
-    float best = -1.f;
-    int at = 0x7fffffff;
-    for (int k = t; k < K; k += MX_TPB) {
-        const float v = fabsf(h[k]);
-        if (v > best) { best = v; at = k; }                  // ascending k: the first of equals stays
-    }
-    s_v[t] = best;
-    s_i[t] = at;
-    __syncthreads();
-    for (int s = MX_TPB / 2; s > 0; s >>= 1) {
-        if (t < s) {
-            const float v = s_v[t + s];
-            const int i = s_i[t + s];
-            if (v > s_v[t] || (v == s_v[t] && i < s_i[t])) { s_v[t] = v; s_i[t] = i; }
-        }
-        __syncthreads();
-    }
-    if (t == 0) a.d[b] = s_i[0] < K ? s_i[0] : 0;            // (all NaN: tap 0)
+    const int d = mx_direct_index(h, K, s_v, s_i);
+    if (t == 0) a.d[b] = d;
 }
 
 __global__ __launch_bounds__(MX_TPB) void mix_conv(MixArgs a) {
@@ -313,10 +235,6 @@ __global__ __launch_bounds__(MX_TPB) void mix_apply(MixArgs a) {
         }
     }
 }
-
-inline size_t mx_up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-inline int mx_tiles(int L) { return (L + MX_TILE - 1) / MX_TILE; }
 
 struct MixLayout {
     size_t d, part, rows, total;       // byte offsets: d | 3 partial planes from `part` | 2 float64 row planes from `rows`

@@ -1,0 +1,463 @@
+// scene.hip - dynamic mixing with the noises INSIDE the room (cmgan_scene, include/cmgan_hip.h): cmgan_mix (mix.hip) adds
+// one dry noise segment to the reverberant speech; here up to SC_MAX_S further sources per row - point noises, interfering
+// talkers - are each convolved with a room response of their own and mixed in at an SNR of their own.  The reference has
+// no counterpart: its data path replays pairs mixed beforehand (src/data/dataloader.py:13-50).
+//
+//   speech, target, d   exactly as cmgan_mix defines them (mix.hip)
+//   n0[i]    = bank[start0 + (off0 + i) mod len0]                          the dry noise of cmgan_mix (no bank: none)
+//   for j = 1 .. S_b,  S_b = clamp(n_src[b], 0, S):
+//     seg_j[m] = src_bank[start_j + ((off_j + m) mod len_j)]               every integer m: the segment loops both ways
+//     c_j[i]   = sum_{k < K_j} h_j[k] seg_j[i - k]                         h_j = rir[src_rir_index[b, j]], K_j = src_rir_len[b, j]
+//                                                                          (no bank: h_j = [1]); the delay STAYS
+//     P_j = mean(c_j^2),  g_j = sqrt(Ps / (P_j 10^(snr_j / 10)))           0 when Ps == 0 or P_j == 0
+//   v = speech + g0 n0 + g_1 c_1 + ... + g_S c_S                           an fma chain in ascending j
+//   m = max |v|, s = m > peak ? peak / m : 1;   noisy = f32(v s), target = f32(target s)
+//
+// Float32 samples in and out; every product and sum in float64 on the VALU, one rounding to float32 at the store.  Six
+// launches (five without a RIR bank), the kernels of mix.hip with one more grid axis:
+//   scene_direct  one block per row: d of the talker's response
+//   scene_conv    grid (tiles, 1 + S, B).  Slice j = 0 is mix_conv: the talker's convolution over a zero-padded span of the
+//                 clip, speech and target accumulators, the partial sums of speech^2 and n0^2.  Slice j >= 1 is source j:
+//                 the same MX_TILE outputs and MX_KC-tap chunks, but ALL K_j taps reach a sample (the segment has no
+//                 end), and the staged span is the LOOPED segment: a thread takes its first position mod len_j once per
+//                 chunk and steps it by (MX_TPB mod len_j) with one conditional subtraction per staged sample, so a
+//                 segment of 1 sample and one of 10^7 cost the same and the tap loop never sees a modulo.  c_j goes to
+//                 the workspace in float64, the block's sum of c_j^2 to a partial slot.  A block of a source beyond S_b
+//                 returns before it reads anything.
+//   scene_gain    one block per row: partials in ascending slot order -> Ps, Pn, g0, P_j, g_j
+//   scene_vmax    per tile: max |v| -> one partial slot        scene_scale  one block per row: the maxima -> s
+//   scene_apply   noisy = f32(v s), target = f32(target s) or clean's bits
+// The tile geometry, the reductions and the order of every sum are those of mix.hip (mix_common.hip.h), so S = 0 with a
+// dry-noise bank gives the bits of cmgan_mix.  No atomics; a row's bits depend neither on B, nor on the other rows or
+// their n_src, nor on what lies behind ld or in the source slots beyond S_b.  Untrusted tables as in cmgan_mix: an empty
+// segment or one that leaves its bank is silence (c_j = 0, P_j = 0, g_j = 0), RIR indices are clamped to [0, R), lengths
+// to [1, Kmax], offsets may be any int64.
+#include <math.h>
+#include <stdint.h>
+
+#include "api_internal.h"
+#include "mix_common.hip.h"
+
+namespace {
+
+constexpr int SC_MAX_S = 4;                 // located sources per row
+
+struct SceneArgs {
+    const float* clean;
+    const float* bank;               // dry noise (null: none)
+    const long long* n_start;
+    const long long* n_len;
+    const long long* n_off;
+    const float* snr_db;
+    const float* src_bank;           // the sources' bank, tables [B, S]
+    const int* n_src;
+    const long long* s_start;
+    const long long* s_len;
+    const long long* s_off;
+    const float* s_snr_db;
+    const float* rir;
+    const int* rir_index;
+    const int* rir_len;
+    const int* s_rir_index;
+    const int* s_rir_len;
+    float* noisy;
+    float* target;
+    double* g;                       // [B, 1 + S]
+    double* p;                       // [B, 1 + S]: Pn, P_1 .. P_S
+    double* ps;
+    double* scale;
+    int* d;                          // workspace: direct-path index per row
+    double* part_ps;                 // workspace: [B][nt] each
+    double* part_pn;
+    double* part_m;
+    double* part_pc;                 // workspace: [B][S][nt]
+    double* speech;                  // workspace: [B][L] float64 each
+    double* tgt;
+    double* c;                       // workspace: [B][S][L]
+    long long ld, ld_out, bank_len, src_bank_len;
+    double peak;
+    int B, L, R, Kmax, early, nt, S;
+};
+
+__device__ inline int scene_count(const SceneArgs& a, int b) {
+    if (a.S == 0) return 0;
+    const int n = a.n_src[b];
+    return n < 0 ? 0 : (n > a.S ? a.S : n);
+}
+
+__device__ inline NoiseRow scene_noise_row(const SceneArgs& a, int b) {
+    if (!a.bank) return mx_segment(nullptr, 0, 0, 0, 0);
+    return mx_segment(a.bank, a.bank_len, a.n_start[b], a.n_len[b], a.n_off[b]);
+}
+
+// v of sample i of row b (e = b L + i): the fma chain in ascending j over the row's own sources; one expression for
+// scene_vmax and scene_apply, so both see the same bits
+__device__ inline double scene_v(const SceneArgs& a, int b, int sb, size_t e, int i, const NoiseRow& nr, const double* g) {
+    double v = a.speech[e];
+    if (a.bank) v = mix_v(v, g[0], mix_noise(nr, i));
+#pragma unroll
+    for (int j = 1; j <= SC_MAX_S; ++j)
+        if (j <= sb) v = fma(g[j], a.c[((size_t)b * a.S + (j - 1)) * a.L + i], v);
+    return v;
+}
+
+__device__ inline void scene_gains(const SceneArgs& a, int b, int sb, double* g) {
+    g[0] = a.g[(size_t)b * (1 + a.S)];
+#pragma unroll
+    for (int j = 1; j <= SC_MAX_S; ++j) g[j] = j <= sb ? a.g[(size_t)b * (1 + a.S) + j] : 0.0;
+}
+
+// ------------------------------------------------------------------------------------------ kernels
+__global__ __launch_bounds__(MX_TPB) void scene_direct(SceneArgs a) {
+    __shared__ float s_v[MX_TPB];
+    __shared__ int s_i[MX_TPB];
+    const int b = blockIdx.x;
+    const float* h;
+    int K;
+    mx_rir_row(a.rir, a.R, a.Kmax, a.rir_index[b], a.rir_len[b], h, K);
+    const int d = mx_direct_index(h, K, s_v, s_i);
+    if (threadIdx.x == 0) a.d[b] = d;
+}
+
+__global__ __launch_bounds__(MX_TPB) void scene_conv(SceneArgs a) {
+    __shared__ double s_x[MX_TILE + MX_KC];
+    __shared__ double s_h[MX_KC];
+    __shared__ double s_red[MX_TPB];
+    const int t = threadIdx.x, src = blockIdx.y, b = blockIdx.z;
+    if (src > scene_count(a, b)) return;                     // (the whole block: src and b are its own)
+    const int i0 = blockIdx.x * MX_TILE;
+    const int cnt = a.L - i0 < MX_TILE ? a.L - i0 : MX_TILE;
+    const float* row = a.clean + (size_t)b * a.ld;
+    const float* h = nullptr;
+    int K = 1, d = 0;
+    long long kt = -1, k_lo = 0, k_hi;
+    NoiseRow seg = mx_segment(nullptr, 0, 0, 0, 0);
+    size_t es = 0;                                           // the source's slot b S + src - 1
+    if (src == 0) {                                          // the talker: the tap range of mix_conv
+        if (a.rir) {
+            mx_rir_row(a.rir, a.R, a.Kmax, a.rir_index[b], a.rir_len[b], h, K);
+            d = a.d[b];
+        }
+        if (a.early >= 0) {
+            kt = (long long)d + a.early;
+            if (kt > K - 1) kt = K - 1;
+        }
+        k_lo = (long long)i0 + d - (a.L - 1);
+        if (k_lo < 0) k_lo = 0;
+        k_hi = (long long)i0 + cnt - 1 + d;
+        if (k_hi > K - 1) k_hi = K - 1;
+    } else {                                                 // a source: every tap meets a sample of the looping segment
+        es = (size_t)b * a.S + (src - 1);
+        seg = mx_segment(a.src_bank, a.src_bank_len, a.s_start[es], a.s_len[es], a.s_off[es]);
+        if (a.rir) mx_rir_row(a.rir, a.R, a.Kmax, a.s_rir_index[es], a.s_rir_len[es], h, K);
+        k_hi = seg.p ? K - 1 : -1;                           // silence: no tap, c = 0
+    }
+    double acc_s[MX_OPT], acc_t[MX_OPT];
+#pragma unroll
+    for (int r = 0; r < MX_OPT; ++r) acc_s[r] = acc_t[r] = 0.0;
+    for (long long k0 = k_lo; k0 <= k_hi; k0 += MX_KC) {
+        const int kc = k_hi - k0 + 1 < MX_KC ? (int)(k_hi - k0 + 1) : MX_KC;
+        for (int j = t; j < kc; j += MX_TPB) s_h[j] = h ? (double)h[k0 + j] : 1.0;
+        // s_x[q] = signal[x0 + q]: output o of the tile meets tap k0 + j at s_x[o + kc - 1 - j]
+        const long long x0 = (long long)i0 + d - (k0 + kc - 1);
+        if (src == 0) {
+            for (int q = t; q < MX_TILE + kc - 1; q += MX_TPB) {
+                const long long x = x0 + q;
+                s_x[q] = (x >= 0 && x < a.L) ? (double)row[x] : 0.0;
+            }
+        } else {
+            long long pos = (seg.off + x0 + t) % seg.len;    // the one modulo of this thread and chunk; x0 may be < 0
+            if (pos < 0) pos += seg.len;
+            const long long step = MX_TPB % seg.len;
+            for (int q = t; q < MX_TILE + kc - 1; q += MX_TPB) {
+                s_x[q] = (double)seg.p[pos];
+                pos += step;
+                if (pos >= seg.len) pos -= seg.len;
+            }
+        }
+        __syncthreads();
+        long long nb_ll = kt - k0 + 1;                       // taps of the chunk that also feed the target
+        const int nb = nb_ll < 0 ? 0 : (nb_ll > kc ? kc : (int)nb_ll);
+        const double* xs = s_x + t + kc - 1;
+        int j = 0;
+        for (; j < nb; ++j) {
+            const double hv = s_h[j];
+#pragma unroll
+            for (int r = 0; r < MX_OPT; ++r) {
+                const double xv = xs[r * MX_TPB - j];
+                acc_s[r] = fma(hv, xv, acc_s[r]);
+                acc_t[r] = fma(hv, xv, acc_t[r]);
+            }
+        }
+        for (; j + 1 < kc; j += 2) {
+            const double h0 = s_h[j], h1 = s_h[j + 1];
+#pragma unroll
+            for (int r = 0; r < MX_OPT; ++r) {
+                acc_s[r] = fma(h0, xs[r * MX_TPB - j], acc_s[r]);
+                acc_s[r] = fma(h1, xs[r * MX_TPB - j - 1], acc_s[r]);
+            }
+        }
+        for (; j < kc; ++j) {
+            const double hv = s_h[j];
+#pragma unroll
+            for (int r = 0; r < MX_OPT; ++r) acc_s[r] = fma(hv, xs[r * MX_TPB - j], acc_s[r]);
+        }
+        __syncthreads();
+    }
+    if (src == 0) {
+        const NoiseRow nr = scene_noise_row(a, b);
+        double ps = 0.0, pn = 0.0;
+#pragma unroll
+        for (int r = 0; r < MX_OPT; ++r) {
+            const int o = t + r * MX_TPB;
+            if (o < cnt) {
+                const size_t e = (size_t)b * a.L + i0 + o;
+                a.speech[e] = acc_s[r];
+                if (a.early >= 0) a.tgt[e] = acc_t[r];
+                ps = fma(acc_s[r], acc_s[r], ps);
+                const double n = mix_noise(nr, i0 + o);
+                pn = fma(n, n, pn);
+            }
+        }
+        ps = block_sum(ps, s_red);
+        pn = block_sum(pn, s_red);
+        if (t == 0) {
+            a.part_ps[(size_t)b * a.nt + blockIdx.x] = ps;
+            a.part_pn[(size_t)b * a.nt + blockIdx.x] = pn;
+        }
+    } else {
+        double pc = 0.0;
+#pragma unroll
+        for (int r = 0; r < MX_OPT; ++r) {
+            const int o = t + r * MX_TPB;
+            if (o < cnt) {
+                a.c[es * a.L + i0 + o] = acc_s[r];
+                pc = fma(acc_s[r], acc_s[r], pc);
+            }
+        }
+        pc = block_sum(pc, s_red);
+        if (t == 0) a.part_pc[es * a.nt + blockIdx.x] = pc;
+    }
+}
+
+__global__ __launch_bounds__(MX_TPB) void scene_gain(SceneArgs a) {
+    __shared__ double s_red[MX_TPB];
+    const int t = threadIdx.x, b = blockIdx.x;
+    const int sb = scene_count(a, b);
+    double ps = 0.0, pn = 0.0;
+    for (int k = t; k < a.nt; k += MX_TPB) {
+        ps += a.part_ps[(size_t)b * a.nt + k];
+        pn += a.part_pn[(size_t)b * a.nt + k];
+    }
+    ps = block_sum(ps, s_red) / (double)a.L;
+    pn = block_sum(pn, s_red) / (double)a.L;
+    double* g = a.g + (size_t)b * (1 + a.S);
+    double* p = a.p + (size_t)b * (1 + a.S);
+    if (t == 0) {
+        double g0 = 0.0;
+        if (a.bank && ps != 0.0 && pn != 0.0) g0 = sqrt(ps / (pn * pow(10.0, (double)a.snr_db[b] / 10.0)));
+        a.ps[b] = ps;
+        p[0] = pn;
+        g[0] = g0;
+    }
+    for (int j = 1; j <= a.S; ++j) {
+        double pc = 0.0, gj = 0.0;
+        if (j <= sb) {                                       // (sb is the block's own: no thread skips the barrier)
+            const size_t es = (size_t)b * a.S + (j - 1);
+            for (int k = t; k < a.nt; k += MX_TPB) pc += a.part_pc[es * a.nt + k];
+            pc = block_sum(pc, s_red) / (double)a.L;
+            if (t == 0 && ps != 0.0 && pc != 0.0) gj = sqrt(ps / (pc * pow(10.0, (double)a.s_snr_db[es] / 10.0)));
+        }
+        if (t == 0) {
+            p[j] = pc;
+            g[j] = gj;
+        }
+    }
+}
+
+__global__ __launch_bounds__(MX_TPB) void scene_vmax(SceneArgs a) {
+    __shared__ double s_red[MX_TPB];
+    const int t = threadIdx.x, b = blockIdx.y;
+    const int i0 = blockIdx.x * MX_TILE;
+    const int sb = scene_count(a, b);
+    const NoiseRow nr = scene_noise_row(a, b);
+    double g[1 + SC_MAX_S];
+    scene_gains(a, b, sb, g);
+    double m = 0.0;
+#pragma unroll
+    for (int r = 0; r < MX_OPT; ++r) {
+        const int i = i0 + t + r * MX_TPB;
+        if (i < a.L) m = fmax(m, fabs(scene_v(a, b, sb, (size_t)b * a.L + i, i, nr, g)));
+    }
+    m = block_max(m, s_red);
+    if (t == 0) a.part_m[(size_t)b * a.nt + blockIdx.x] = m;
+}
+
+__global__ __launch_bounds__(MX_TPB) void scene_scale(SceneArgs a) {
+    __shared__ double s_red[MX_TPB];
+    const int t = threadIdx.x, b = blockIdx.x;
+    double m = 0.0;
+    for (int k = t; k < a.nt; k += MX_TPB) m = fmax(m, a.part_m[(size_t)b * a.nt + k]);
+    m = block_max(m, s_red);
+    if (t == 0) a.scale[b] = m > a.peak ? a.peak / m : 1.0;
+}
+
+__global__ __launch_bounds__(MX_TPB) void scene_apply(SceneArgs a) {
+    const int t = threadIdx.x, b = blockIdx.y;
+    const int i0 = blockIdx.x * MX_TILE;
+    const int sb = scene_count(a, b);
+    const NoiseRow nr = scene_noise_row(a, b);
+    double g[1 + SC_MAX_S];
+    scene_gains(a, b, sb, g);
+    const double s = a.scale[b];
+#pragma unroll
+    for (int r = 0; r < MX_OPT; ++r) {
+        const int i = i0 + t + r * MX_TPB;
+        if (i >= a.L) continue;
+        const size_t e = (size_t)b * a.L + i;
+        const size_t eo = (size_t)b * a.ld_out + i;
+        a.noisy[eo] = (float)(scene_v(a, b, sb, e, i, nr, g) * s);
+        if (a.early >= 0) {
+            a.target[eo] = (float)(a.tgt[e] * s);
+        } else {
+            const float c = a.clean[(size_t)b * a.ld + i];
+            a.target[eo] = s == 1.0 ? c : (float)((double)c * s);
+        }
+    }
+}
+
+struct SceneLayout {
+    // byte offsets: d | the partial planes Ps, Pn, m, then S of P_j | the float64 row planes speech, target, then S of c_j
+    size_t d, part, rows, total;
+    size_t part_stride, row_stride;
+};
+
+inline SceneLayout sc_layout(int B, int L, int S) {
+    SceneLayout l;
+    l.d = 0;
+    l.part = mx_up256((size_t)B * sizeof(int));
+    l.part_stride = mx_up256((size_t)B * mx_tiles(L) * sizeof(double));
+    l.rows = l.part + (3 + (size_t)S) * l.part_stride;
+    l.row_stride = mx_up256((size_t)B * L * sizeof(double));
+    l.total = l.rows + (2 + (size_t)S) * l.row_stride;
+    return l;
+}
+
+inline bool sc_shape_ok(int B, int L, int Kmax, int S) {
+    return B >= 1 && B <= 65535 && L >= 1 && L <= MX_MAX_L && Kmax >= 1 && Kmax <= MX_MAX_K && S >= 0 && S <= SC_MAX_S;
+}
+
+}  // namespace
+
+extern "C" int cmgan_scene_max_sources(void) { return SC_MAX_S; }
+
+extern "C" size_t cmgan_scene_workspace_bytes(const cmgan_handle* h, int B, int L, int Kmax, int S) {
+    (void)h;
+    return sc_shape_ok(B, L, Kmax, S) ? sc_layout(B, L, S).total : 0;
+}
+
+extern "C" int cmgan_scene(cmgan_handle* h, const float* clean, int B, int L, long long ld, const float* noise_bank,
+                           long long bank_len, const long long* noise_start, const long long* noise_len,
+                           const long long* noise_off, const float* snr_db, const float* src_bank, long long src_bank_len,
+                           int S, const int* n_src, const long long* src_start, const long long* src_len,
+                           const long long* src_off, const float* src_snr_db, const float* rir_bank, int R, int Kmax,
+                           const int* rir_index, const int* rir_len, const int* src_rir_index, const int* src_rir_len,
+                           float peak, int early, float* noisy, float* target, long long ld_out, double* g, double* p,
+                           double* ps, double* scale, void* ws, size_t ws_bytes, void* stream) {
+    // every argument is judged before the handle is, so that the errors below need no GPU (the message of a call
+    // without a handle is read with cmgan_last_error(NULL))
+    if (!clean || !noisy || !target || !g || !p || !ps || !scale) return fail(h, CMGAN_E_BADARG, "cmgan_scene: null pointer");
+    if (noise_bank && (!noise_start || !noise_len || !noise_off || !snr_db))
+        return fail(h, CMGAN_E_BADARG, "cmgan_scene: a dry-noise bank needs noise_start, noise_len, noise_off and snr_db");
+    if (S < 0 || S > SC_MAX_S)
+        return fail(h, CMGAN_E_BADARG, "cmgan_scene: 0 <= S <= %d located sources per row (S=%d)", SC_MAX_S, S);
+    if (S > 0 && (!src_bank || !n_src || !src_start || !src_len || !src_off || !src_snr_db))
+        return fail(h, CMGAN_E_BADARG, "cmgan_scene: S > 0 needs src_bank, n_src, src_start, src_len, src_off and src_snr_db");
+    if (rir_bank && (!rir_index || !rir_len))
+        return fail(h, CMGAN_E_BADARG, "cmgan_scene: a RIR bank needs rir_index and rir_len");
+    if (rir_bank && S > 0 && (!src_rir_index || !src_rir_len))
+        return fail(h, CMGAN_E_BADARG, "cmgan_scene: a RIR bank with S > 0 needs src_rir_index and src_rir_len");
+    if (((uintptr_t)clean | (uintptr_t)noise_bank | (uintptr_t)snr_db | (uintptr_t)src_bank | (uintptr_t)n_src
+         | (uintptr_t)src_snr_db | (uintptr_t)rir_bank | (uintptr_t)rir_index | (uintptr_t)rir_len | (uintptr_t)src_rir_index
+         | (uintptr_t)src_rir_len | (uintptr_t)noisy | (uintptr_t)target) & 3)
+        return fail(h, CMGAN_E_BADARG, "cmgan_scene: float32 / int32 buffers must be 4-byte aligned");
+    if (((uintptr_t)noise_start | (uintptr_t)noise_len | (uintptr_t)noise_off | (uintptr_t)src_start | (uintptr_t)src_len
+         | (uintptr_t)src_off | (uintptr_t)g | (uintptr_t)p | (uintptr_t)ps | (uintptr_t)scale) & 7)
+        return fail(h, CMGAN_E_BADARG, "cmgan_scene: int64 / float64 buffers must be 8-byte aligned");
+    if (B <= 0 || B > 65535 || L < 1 || ld < L || ld_out < L)
+        return fail(h, CMGAN_E_BADARG, "cmgan_scene: need 0 < B <= 65535, L >= 1, ld >= L, ld_out >= L (B=%d L=%d ld=%lld "
+                    "ld_out=%lld)", B, L, ld, ld_out);
+    if ((noise_bank && bank_len < 1) || (S > 0 && src_bank_len < 1))
+        return fail(h, CMGAN_E_BADARG, "cmgan_scene: a bank needs at least one sample (bank_len=%lld src_bank_len=%lld)",
+                    bank_len, src_bank_len);
+    if (!(peak > 0.f) || !(peak <= 3.0e38f))
+        return fail(h, CMGAN_E_BADARG, "cmgan_scene: peak must be positive and finite (%g)", (double)peak);
+    if (early < -1) return fail(h, CMGAN_E_BADARG, "cmgan_scene: early must be -1 (dry target) or >= 0 (%d)", early);
+    if (!rir_bank) {
+        R = 1;
+        Kmax = 1;
+    }
+    if (R < 1 || Kmax < 1) return fail(h, CMGAN_E_BADARG, "cmgan_scene: a RIR bank needs R >= 1 and Kmax >= 1 (R=%d Kmax=%d)", R, Kmax);
+    if (Kmax > MX_MAX_K)
+        return fail(h, CMGAN_E_UNSUPPORTED, "cmgan_scene: RIRs of up to %d taps are supported (Kmax=%d)", MX_MAX_K, Kmax);
+    if (L > MX_MAX_L)
+        return fail(h, CMGAN_E_UNSUPPORTED, "cmgan_scene: rows of up to %d samples are supported (L=%d)", MX_MAX_L, L);
+    if (!h) return fail(nullptr, CMGAN_E_BADARG, "cmgan_scene: null handle");
+    const SceneLayout l = sc_layout(B, L, S);
+    if (int rc = check_ws(h, ws, ws_bytes, l.total)) return rc;
+    const LaunchCtx ctx = begin(h, stream);
+    hipStream_t s = ctx.stream;
+    char* w = (char*)ws;
+    SceneArgs a;
+    a.clean = clean;
+    a.bank = noise_bank;
+    a.n_start = noise_start;
+    a.n_len = noise_len;
+    a.n_off = noise_off;
+    a.snr_db = snr_db;
+    a.src_bank = src_bank;
+    a.n_src = n_src;
+    a.s_start = src_start;
+    a.s_len = src_len;
+    a.s_off = src_off;
+    a.s_snr_db = src_snr_db;
+    a.rir = rir_bank;
+    a.rir_index = rir_index;
+    a.rir_len = rir_len;
+    a.s_rir_index = src_rir_index;
+    a.s_rir_len = src_rir_len;
+    a.noisy = noisy;
+    a.target = target;
+    a.g = g;
+    a.p = p;
+    a.ps = ps;
+    a.scale = scale;
+    a.d = (int*)(w + l.d);
+    a.part_ps = (double*)(w + l.part);
+    a.part_pn = (double*)(w + l.part + l.part_stride);
+    a.part_m = (double*)(w + l.part + 2 * l.part_stride);
+    a.part_pc = (double*)(w + l.part + 3 * l.part_stride);
+    a.speech = (double*)(w + l.rows);
+    a.tgt = (double*)(w + l.rows + l.row_stride);
+    a.c = (double*)(w + l.rows + 2 * l.row_stride);
+    a.ld = ld;
+    a.ld_out = ld_out;
+    a.bank_len = bank_len;
+    a.src_bank_len = src_bank_len;
+    a.peak = (double)peak;
+    a.B = B;
+    a.L = L;
+    a.R = R;
+    a.Kmax = Kmax;
+    a.early = early;
+    a.nt = mx_tiles(L);
+    a.S = S;
+    const dim3 grid(a.nt, B);
+    if (rir_bank) LAUNCH(ctx, "scene_direct", scene_direct<<<B, MX_TPB, 0, s>>>(a));
+    LAUNCH(ctx, "scene_conv", scene_conv<<<dim3(a.nt, 1 + S, B), MX_TPB, 0, s>>>(a));
+    LAUNCH(ctx, "scene_gain", scene_gain<<<B, MX_TPB, 0, s>>>(a));
+    LAUNCH(ctx, "scene_vmax", scene_vmax<<<grid, MX_TPB, 0, s>>>(a));
+    LAUNCH(ctx, "scene_scale", scene_scale<<<B, MX_TPB, 0, s>>>(a));
+    LAUNCH(ctx, "scene_apply", scene_apply<<<grid, MX_TPB, 0, s>>>(a));
+    return check_launch(h, "scene");
+}

@@ -128,6 +128,94 @@ def check_mix_args(device, clean, noise_bank, noise_start, noise_len, noise_off,
     return B, L, R, Kmax
 
 
+class SceneInfo(NamedTuple):
+    """Engine.scene: float64 device tensors - the gains g0 (dry noise), g_1 .. g_S and the powers Pn, P_1 .. P_S as
+    [B, 1 + S] (0 in the columns beyond a row's own sources), the peak scale and the speech power as [B]."""
+    g: torch.Tensor
+    scale: torch.Tensor
+    Ps: torch.Tensor
+    P: torch.Tensor
+
+
+SCENE_MAX_SOURCES = 4         # located sources per row (= cmgan_scene_max_sources())
+
+
+def check_scene_args(device, clean, noise_bank=None, noise_start=None, noise_len=None, noise_off=None, snr_db=None,
+                     n_src=None, src_bank=None, src_start=None, src_len=None, src_off=None, src_snr_db=None, rir_bank=None,
+                     rir_index=None, rir_len=None, src_rir_index=None, src_rir_len=None, peak: float = 0.99, early: int = -1):
+    """Argument rules of Engine.scene (shapes, dtypes, devices and host scalars; pure host code).  Returns (B, L, R, Kmax, S)."""
+    tensor_arg(clean, "clean", torch.float32, device, "[B, L] with B, L >= 1",
+               lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) >= 1)
+    B, L = clean.shape
+    if B > 65535:
+        raise ValueError(f"clean: at most 65535 rows, got {B}")
+    row = lambda t: tuple(t.shape) == (B,)
+    dry = (("noise_start", noise_start, torch.int64), ("noise_len", noise_len, torch.int64),
+           ("noise_off", noise_off, torch.int64), ("snr_db", snr_db, torch.float32))
+    if noise_bank is None:
+        given = [name for name, t, _ in dry if t is not None]
+        if given:
+            raise ValueError(f"{' / '.join(given)} given without a noise_bank")
+    else:
+        tensor_arg(noise_bank, "noise_bank", torch.float32, device, "a flat bank of >= 1 samples",
+                   lambda t: t.dim() == 1 and t.numel() >= 1)
+        for name, t, dtype in dry:
+            if t is None:
+                raise ValueError(f"a noise_bank needs {name}")
+            tensor_arg(t, name, dtype, device, f"[{B}]", row)
+    src = (("src_start", src_start, torch.int64), ("src_len", src_len, torch.int64), ("src_off", src_off, torch.int64),
+           ("src_snr_db", src_snr_db, torch.float32))
+    S = 0
+    if n_src is None:
+        given = [name for name, t in (("src_bank", src_bank), *((n, t) for n, t, _ in src), ("src_rir_index", src_rir_index),
+                                      ("src_rir_len", src_rir_len)) if t is not None]
+        if given:
+            raise ValueError(f"{' / '.join(given)} given without n_src")
+    else:
+        tensor_arg(n_src, "n_src", torch.int32, device, f"[{B}]", row)
+        if src_bank is None:
+            raise ValueError("n_src needs a src_bank")
+        tensor_arg(src_bank, "src_bank", torch.float32, device, "a flat bank of >= 1 samples",
+                   lambda t: t.dim() == 1 and t.numel() >= 1)
+        if src_start is None:
+            raise ValueError("n_src needs src_start")
+        tensor_arg(src_start, "src_start", torch.int64, device, f"[{B}, S] with 1 <= S <= {SCENE_MAX_SOURCES}",
+                   lambda t: t.dim() == 2 and t.size(0) == B and 1 <= t.size(1) <= SCENE_MAX_SOURCES)
+        S = int(src_start.size(1))
+        table = lambda t: tuple(t.shape) == (B, S)
+        for name, t, dtype in src[1:]:
+            if t is None:
+                raise ValueError(f"n_src needs {name}")
+            tensor_arg(t, name, dtype, device, f"[{B}, {S}]", table)
+    R, Kmax = 0, 0
+    if rir_bank is None:
+        given = [name for name, t in (("rir_index", rir_index), ("rir_len", rir_len), ("src_rir_index", src_rir_index),
+                                      ("src_rir_len", src_rir_len)) if t is not None]
+        if given:
+            raise ValueError(f"{' / '.join(given)} given without a rir_bank")
+    else:
+        tensor_arg(rir_bank, "rir_bank", torch.float32, device, "[R, Kmax] with R, Kmax >= 1",
+                   lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) >= 1)
+        R, Kmax = rir_bank.shape
+        if Kmax > MIX_MAX_TAPS:
+            raise ValueError(f"rir_bank: RIRs of up to {MIX_MAX_TAPS} taps are supported, got Kmax = {Kmax}")
+        if rir_index is None or rir_len is None:
+            raise ValueError("a rir_bank needs rir_index and rir_len")
+        tensor_arg(rir_index, "rir_index", torch.int32, device, f"[{B}]", row)
+        tensor_arg(rir_len, "rir_len", torch.int32, device, f"[{B}]", row)
+        if S:
+            if src_rir_index is None or src_rir_len is None:
+                raise ValueError("a rir_bank with sources needs src_rir_index and src_rir_len")
+            tensor_arg(src_rir_index, "src_rir_index", torch.int32, device, f"[{B}, {S}]", table)
+            tensor_arg(src_rir_len, "src_rir_len", torch.int32, device, f"[{B}, {S}]", table)
+    peak = float(peak)
+    if not (peak > 0.0 and peak < float("inf")):
+        raise ValueError(f"peak must be positive and finite, got {peak}")
+    if int(early) != early or early < -1:
+        raise ValueError(f"early must be -1 (dry target) or a sample count >= 0, got {early}")
+    return B, L, R, Kmax, S
+
+
 RIR_MAX_TAPS = 65536          # longest response of cmgan_rir (= MIX_MAX_TAPS: its output is a bank of cmgan_mix)
 RIR_MAX_IMAGES = 255          # largest image index per axis
 RIR_MAX_TW = 64               # largest half-width of the fractional-delay filter
@@ -359,7 +447,7 @@ class Engine:
             msg = self.lib.cmgan_last_error(None)
             raise _lib.CmganError(rc, msg.decode() if msg else "?")
         #: grow-only uint8 workspaces by name (_grow): "main", "branched" (enhance_graphed(branches > 1)), "conformer",
-        #: "metrics", "mix", "rir", "level", "channel" and ("resample", fs_in, fs_out), the rate pair's tap table
+        #: "metrics", "mix", "scene", "rir", "level", "channel" and ("resample", fs_in, fs_out), the rate pair's tap table
         self._wss: dict = {}
         self._graphs: dict = {}          # enhance_graphed: input shape -> (graph, in, out, token)
         self._row_graphs: dict = {}      # streaming.enhance_windows: row shape -> (graph, in, out, token)
@@ -964,6 +1052,45 @@ class Engine:
                    Kmax, rir_index, rir_len, snr_db, float(peak), int(early), noisy, target, L, info[0], info[1], info[2],
                    info[3], ws, ws.numel())
         return noisy, target, MixInfo(info[0], info[1], info[2], info[3])
+
+    # ---- scenes: located sources ----------------------------------------------------
+    @_on_device
+    def scene(self, clean: torch.Tensor, noise_bank: Optional[torch.Tensor] = None, noise_start: Optional[torch.Tensor] = None,
+              noise_len: Optional[torch.Tensor] = None, noise_off: Optional[torch.Tensor] = None,
+              snr_db: Optional[torch.Tensor] = None, n_src: Optional[torch.Tensor] = None,
+              src_bank: Optional[torch.Tensor] = None, src_start: Optional[torch.Tensor] = None,
+              src_len: Optional[torch.Tensor] = None, src_off: Optional[torch.Tensor] = None,
+              src_snr_db: Optional[torch.Tensor] = None, rir_bank: Optional[torch.Tensor] = None,
+              rir_index: Optional[torch.Tensor] = None, rir_len: Optional[torch.Tensor] = None,
+              src_rir_index: Optional[torch.Tensor] = None, src_rir_len: Optional[torch.Tensor] = None, peak: float = 0.99,
+              early: int = -1):
+        """Engine.mix with point noise sources and interfering talkers inside the room (cmgan_scene, include/cmgan_hip.h).
+
+        clean, the dry noise (noise_bank .. snr_db; all None: no dry noise), the talker's rir_bank / rir_index / rir_len,
+        peak and early are Engine.mix's.  The located sources: n_src int32 [B], how many of the S <= 4 table columns a row
+        uses (clamped to [0, S]; None: no sources, and no other src_ argument); src_bank flat float32 - the noise bank
+        again, or a bank of speech for interfering talkers; src_start / src_len / src_off int64 [B, S], the looping
+        segment of each source; src_snr_db float32 [B, S], the speech-to-source ratio; with a rir_bank src_rir_index /
+        src_rir_len int32 [B, S], rows of the same bank (without one the sources are dry).  Source j of row b is its
+        segment, looping both ways, convolved with its response WITHOUT delay removal and scaled to its SNR.  The columns
+        beyond a row's n_src are never read.  All on this Engine's device; the tables are read by the kernels only.
+        Returns (noisy [B, L], target [B, L], SceneInfo).  Float64 arithmetic, one rounding to float32; bit-reproducible,
+        row-independent, no synchronisation, graph-capturable after one call at the shape; with n_src=None and a dry
+        noise the outputs are Engine.mix's, bit for bit."""
+        B, L, R, Kmax, S = check_scene_args(self.device, clean, noise_bank, noise_start, noise_len, noise_off, snr_db, n_src,
+                                            src_bank, src_start, src_len, src_off, src_snr_db, rir_bank, rir_index, rir_len,
+                                            src_rir_index, src_rir_len, peak, early)
+        ws = self._grow("scene", int(self.lib.cmgan_scene_workspace_bytes(self._h, B, L, max(Kmax, 1), S)),
+                        f"[{B}, {L}] with {Kmax} taps and {S} sources is outside what cmgan_scene supports")
+        noisy = torch.empty(B, L, dtype=torch.float32, device=self.device)
+        target = torch.empty(B, L, dtype=torch.float32, device=self.device)
+        gp = torch.empty(2, B, 1 + S, dtype=torch.float64, device=self.device)
+        info = torch.empty(2, B, dtype=torch.float64, device=self.device)
+        self._call("cmgan_scene", clean, B, L, L, noise_bank, noise_bank.numel() if noise_bank is not None else 0,
+                   noise_start, noise_len, noise_off, snr_db, src_bank, src_bank.numel() if src_bank is not None else 0, S,
+                   n_src, src_start, src_len, src_off, src_snr_db, rir_bank, R, Kmax, rir_index, rir_len, src_rir_index,
+                   src_rir_len, float(peak), int(early), noisy, target, L, gp[0], gp[1], info[0], info[1], ws, ws.numel())
+        return noisy, target, SceneInfo(gp[0], info[1], info[0], gp[1])
 
     # ---- room impulse responses ----------------------------------------------------
     @_on_device

@@ -37,7 +37,7 @@ import torch.utils.data
 from .data import _natural_key, fit_length, read_wav
 
 __all__ = ["NoiseBank", "RirBank", "RoomSampler", "sabine_beta", "DynamicMixer", "MixingLoader", "CleanDataset",
-           "clean_only", "Draw", "tile", "ChannelSampler", "biquad_peaking", "biquad_low_shelf", "biquad_high_shelf",
+           "clean_only", "Draw", "SceneDraw", "tile", "ChannelSampler", "biquad_peaking", "biquad_low_shelf", "biquad_high_shelf",
            "biquad_lowpass", "biquad_highpass", "butter_lowpass_sos", "warp_len"]
 
 SPEED_OF_SOUND = 343.0        # m/s, the default `c` of Engine.rir
@@ -173,6 +173,22 @@ class RoomSampler:
         rooms = torch.cat([size, source, receiver, beta[:, None].expand(R, 6)], dim=1).contiguous()
         n_taps = torch.ceil(rt * fs).clamp(1, K).to(torch.int32)
         return rooms, n_taps
+
+    def draw_sources(self, rooms: torch.Tensor, n: int) -> torch.Tensor:
+        """Further source positions in rooms that `draw` made: float64 [R, n, 15] tables for a drawn [R, 15] one.  Row
+        (r, j) keeps room r's size, receiver and reflection coefficients; its source is uniform in the room shrunk by
+        `margin`, independent of the room's own, drawn from `generator` on the device of `rooms` (so: after the room
+        draws).  `tables.reshape(R * n, 15)` with each room's n_taps repeated n times is one Engine.rir call."""
+        if not isinstance(rooms, torch.Tensor) or rooms.dtype != torch.float64 or rooms.dim() != 2 or rooms.size(1) != 15:
+            raise ValueError("rooms must be a float64 [R, 15] table of RoomSampler.draw")
+        if isinstance(n, bool) or int(n) != n or n < 1:
+            raise ValueError(f"n must be a source count >= 1, got {n}")
+        R, n = rooms.size(0), int(n)
+        u = torch.rand(R, n, 3, dtype=torch.float64, generator=self.generator, device=rooms.device)
+        inner = rooms[:, None, 0:3] - 2.0 * self.margin
+        out = rooms[:, None, :].expand(R, n, 15).clone()
+        out[:, :, 3:6] = self.margin + inner * u
+        return out
 
 
 # ---- biquad designs: R. Bristow-Johnson's audio-EQ-cookbook formulas, normalised to a0 = 1 --------------------------
@@ -402,6 +418,29 @@ class Draw(NamedTuple):
     speed: Optional[torch.Tensor] = None      # DynamicMixer(speed=...): the float64 [B] rate of Engine.warp per row
 
 
+class SceneDraw(NamedTuple):
+    """What a DynamicMixer(sources=...) drew for a batch: the fields of Draw, then the per-source arguments of Engine.scene,
+    [B] and [B, S] device tensors with S = the upper end of `sources`."""
+    noise_start: torch.Tensor
+    noise_len: torch.Tensor
+    noise_off: torch.Tensor
+    snr_db: torch.Tensor
+    rir_index: Optional[torch.Tensor]
+    rir_len: Optional[torch.Tensor]
+    rooms: Optional[torch.Tensor] = None
+    level_db: Optional[torch.Tensor] = None
+    channel: Optional[tuple] = None
+    speed: Optional[torch.Tensor] = None
+    n_src: Optional[torch.Tensor] = None          # int32 [B]: how many of the S columns a row uses
+    src_start: Optional[torch.Tensor] = None
+    src_len: Optional[torch.Tensor] = None
+    src_off: Optional[torch.Tensor] = None
+    src_snr_db: Optional[torch.Tensor] = None
+    src_rir_index: Optional[torch.Tensor] = None  # None without a rir_bank or rooms: the sources are dry
+    src_rir_len: Optional[torch.Tensor] = None
+    src_rooms: Optional[torch.Tensor] = None      # with rooms=...: the float64 [B, S, 15] tables of RoomSampler.draw_sources
+
+
 class DynamicMixer:
     """`mixer(clean_dev)` -> `(target, noisy, MixInfo)` for a float32 [B, L] device batch of clean speech.
 
@@ -449,14 +488,53 @@ class DynamicMixer:
     before Engine.mix, with n_out = N = warp_len(L, hi): every rate <= hi makes at least N outputs of L samples, so all
     rows are full and target and noisy are [B, N].  The loader should therefore cut clips hi times longer than the batch
     it wants: `clean_only(dir, cut_len=math.ceil(32000 * hi))` for batches of 32000.  A row drawn as 1.0 passes the same
-    filter (`speed_zeros`, `speed_rolloff`) as the others - it is band-limited at the rolloff, not copied."""
+    filter (`speed_zeros`, `speed_rolloff`) as the others - it is band-limited at the rolloff, not copied.
+
+    `sources=(lo, hi)` with 0 <= lo <= hi, 1 <= hi <= 4: point noise sources and interfering talkers INSIDE the room
+    (Engine.scene / cmgan_scene).  With None (the default) the mixer calls Engine.mix and the outputs, `last_draw` (apart
+    from its trailing `speed=None`) and every generator state are what they are without the argument: `last_draw` is a
+    Draw.  With a range `last_draw` is a SceneDraw, Draw's fields followed by the sources' (None by default); each
+    row gets a source count uniform in [lo, hi] and, for each of the S = hi table columns, an item and an offset of
+    `source_bank` (a NoiseBank; None: the noise bank - a bank of speech gives interfering talkers) and a
+    speech-to-source ratio uniform in `source_snr_db`; with `snr_on="active"` that ratio relates to the active speech
+    power like `snr_db`.  These come from the mixer's generator after every other draw.  With a `rir_bank` every source
+    draws a response of the bank (the identity of p_reverb excluded); with `rooms`, `RoomSampler.draw_sources` then draws
+    every source a position in its row's room (from the sampler's generator, kept as `last_draw.src_rooms`) and ONE more
+    Engine.rir call simulates the B S responses into the rows behind the talkers' (and the identity) of the same
+    persistent bank; with neither the sources are dry.  A source keeps its room's own response length whether or not the
+    talker's row was drawn dry, and its delay: it is not aligned with the talker.  The mixer then returns a SceneInfo.
+    `dry_noise=False` (only with sources) drops the noise that is added without a room, so every noise is located; the
+    noise draws are made as before and not used."""
 
     def __init__(self, engine, noise_bank: NoiseBank, rir_bank: Optional[RirBank] = None, snr_db=(0.0, 20.0),
                  early_ms: Optional[float] = 50.0, p_reverb: float = 1.0, peak: float = 0.99,
                  generator: Optional[torch.Generator] = None, sample_rate: int = 16000,
                  rooms: Optional[RoomSampler] = None, rir_seconds: float = 0.5, snr_on: str = "rms", level_db=None,
                  channel: Optional[ChannelSampler] = None, channel_on: str = "noisy", speed=None, p_speed: float = 1.0,
-                 speed_zeros: int = 24, speed_rolloff: float = 0.95):
+                 speed_zeros: int = 24, speed_rolloff: float = 0.95, sources=None, source_bank: Optional[NoiseBank] = None,
+                 source_snr_db=(0.0, 20.0), dry_noise: bool = True):
+        if sources is not None:
+            try:
+                lo_n, hi_n = sources
+            except (TypeError, ValueError):
+                raise ValueError(f"sources must be None or (low, high), got {sources}") from None
+            if any(isinstance(v, bool) or not isinstance(v, int) for v in (lo_n, hi_n)) or not (0 <= lo_n <= hi_n and 1 <= hi_n <= 4):
+                raise ValueError(f"sources must be (low, high) whole numbers with 0 <= low <= high and 1 <= high <= 4, got {sources}")
+            sources = (int(lo_n), int(hi_n))
+            try:
+                source_snr_db = (float(source_snr_db[0]), float(source_snr_db[1]))
+            except (TypeError, ValueError, IndexError):
+                raise ValueError(f"source_snr_db must be (low, high), got {source_snr_db}") from None
+            if not source_snr_db[0] <= source_snr_db[1]:
+                raise ValueError(f"source_snr_db must be (low, high) with low <= high, got {source_snr_db}")
+            if source_bank is not None and source_bank.device != engine.device:
+                raise RuntimeError(f"source_bank is on {source_bank.device} but the engine is bound to {engine.device}")
+        elif source_bank is not None:
+            raise ValueError("source_bank given without sources")
+        elif not dry_noise:
+            raise ValueError("dry_noise=False needs sources: the batch would hold no noise at all")
+        self.sources, self.source_snr_db, self.dry_noise = sources, source_snr_db, bool(dry_noise)
+        self.source_bank = source_bank if source_bank is not None else noise_bank
         if speed is not None:
             try:
                 speed = (float(speed[0]), float(speed[1]))
@@ -514,7 +592,7 @@ class DynamicMixer:
                 raise ValueError(f"responses of {rir_seconds} s in rooms as small as {rooms.lo} need image ranges "
                                  f"{self.n_images}; up to 255 are supported")
 
-    def draw(self, B: int) -> Draw:
+    def draw(self, B: int):
         dev, gen, nb = self.engine.device, self.generator, self.noise_bank
         item = torch.randint(0, len(nb), (B,), generator=gen, device=dev)
         start, length = nb.start[item], nb.length[item]
@@ -533,6 +611,7 @@ class DynamicMixer:
         table = None
         if self.rooms is not None:
             table, rlen = self.rooms.draw(B, self.rir_taps, self.sample_rate, device=dev)
+            room_taps = rlen
             idx = torch.arange(B, dtype=torch.int32, device=dev)
             if self.p_reverb < 1.0:
                 wet = torch.rand(B, dtype=torch.float32, generator=gen, device=dev) < self.p_reverb
@@ -549,21 +628,47 @@ class DynamicMixer:
             speed = torch.clamp(lo + (hi - lo) * u[:, 0], lo, hi)          # (the sum may round past hi)
             speed = torch.where(u[:, 1] < self.p_speed, speed, torch.ones_like(speed)).contiguous()
         chan = self.channel.draw(B, self.sample_rate, device=dev) if self.channel is not None else None
-        return Draw(start.contiguous(), length.contiguous(), off, snr, idx, rlen, table, level, chan, speed)
+        drawn = Draw(start.contiguous(), length.contiguous(), off, snr, idx, rlen, table, level, chan, speed)
+        if self.sources is not None:
+            S, sb = self.sources[1], self.source_bank
+            n_src = torch.randint(self.sources[0], S + 1, (B,), generator=gen, device=dev).to(torch.int32)
+            s_item = torch.randint(0, len(sb), (B, S), generator=gen, device=dev)
+            s_start, s_len = sb.start[s_item].contiguous(), sb.length[s_item].contiguous()
+            u = torch.rand(B, S, dtype=torch.float64, generator=gen, device=dev)
+            s_off = torch.minimum((u * s_len).to(torch.int64), s_len - 1)
+            lo, hi = self.source_snr_db
+            s_snr = (lo + (hi - lo) * torch.rand(B, S, dtype=torch.float32, generator=gen, device=dev)).contiguous()
+            s_idx = s_rlen = s_rooms = None
+            if self.rir_bank is not None:
+                s_idx = torch.randint(0, self.n_rirs, (B, S), generator=gen, device=dev)
+                s_rlen = self.rir_bank.length[s_idx].contiguous()
+                s_idx = s_idx.to(torch.int32)
+            if self.rooms is not None:
+                s_rooms = self.rooms.draw_sources(table, S)
+                base = B + (1 if self.p_reverb < 1.0 else 0)               # behind the talkers' rows and the identity
+                s_idx = base + torch.arange(B * S, dtype=torch.int32, device=dev).reshape(B, S)
+                s_rlen = room_taps[:, None].expand(B, S).contiguous()
+            return SceneDraw(*drawn, n_src, s_start, s_len, s_off, s_snr, s_idx, s_rlen, s_rooms)
+        return drawn
 
     def _simulate(self, d: Draw) -> RirBank:
         """The batch's responses, simulated into the persistent allocation (made anew only when B changes)."""
         B, K = d.rooms.size(0), self.rir_taps
-        rows = B + (1 if self.p_reverb < 1.0 else 0)
+        base = B + (1 if self.p_reverb < 1.0 else 0)
+        n_s = self.sources[1] if self.sources is not None else 0
+        rows = base + B * n_s
         if self.last_bank is None or self.last_bank.data.size(0) != rows:
             data = torch.zeros(rows, K, dtype=torch.float32, device=self.engine.device)
             length = torch.ones(rows, dtype=torch.int32, device=self.engine.device)
-            if rows > B:
+            if base > B:
                 data[B, 0] = 1.0                                  # the identity of the dry rows
             self.last_bank = RirBank(data, length)
         sim = self.last_bank
         # rir_len is the sampler's n_taps, or 1 for a dry row (whose response is then one tap that no row uses)
         self.engine.rir(d.rooms, d.rir_len, K, self.n_images, fs=self.sample_rate, out=(sim.data[:B], sim.length[:B]))
+        if n_s:                                                   # the sources' responses: one call of B S rows
+            self.engine.rir(d.src_rooms.reshape(B * n_s, 15), d.src_rir_len.reshape(B * n_s), K, self.n_images,
+                            fs=self.sample_rate, out=(sim.data[base:], sim.length[base:]))
         return sim
 
     @staticmethod
@@ -591,9 +696,19 @@ class DynamicMixer:
                 snr = (d.snr_db.to(torch.float64) - delta).to(torch.float32).contiguous()
             if d.level_db is not None:
                 clean = (clean * self.level_gain(lv, d.level_db)[:, None]).contiguous()
-        noisy, target, info = self.engine.mix(clean, self.noise_bank.data, d.noise_start, d.noise_len, d.noise_off,
-                                              snr, rir.data if rir is not None else None, d.rir_index, d.rir_len,
-                                              peak=self.peak, early=self.early if rir is not None else -1)
+        early = self.early if rir is not None else -1
+        if self.sources is None:
+            noisy, target, info = self.engine.mix(clean, self.noise_bank.data, d.noise_start, d.noise_len, d.noise_off,
+                                                  snr, rir.data if rir is not None else None, d.rir_index, d.rir_len,
+                                                  peak=self.peak, early=early)
+        else:
+            src_snr = d.src_snr_db
+            if self.snr_on == "active":
+                src_snr = (src_snr.to(torch.float64) - delta[:, None]).to(torch.float32).contiguous()
+            dry = (self.noise_bank.data, d.noise_start, d.noise_len, d.noise_off, snr) if self.dry_noise else (None,) * 5
+            noisy, target, info = self.engine.scene(clean, *dry, d.n_src, self.source_bank.data, d.src_start, d.src_len,
+                                                    d.src_off, src_snr, rir.data if rir is not None else None, d.rir_index,
+                                                    d.rir_len, d.src_rir_index, d.src_rir_len, peak=self.peak, early=early)
         if d.channel is not None:
             sos, n_sections, n_shared, clip_rel = d.channel
             self.engine.channel(noisy, sos, n_sections, self.channel_clip(clip_rel, noisy), out=noisy)

@@ -39,7 +39,7 @@ extern "C" {
 #define CMGAN_E_WORKSPACE   -5   /* workspace too small or misaligned              */
 #define CMGAN_E_HIP         -6   /* a HIP runtime call failed (see last_error)     */
 
-#define CMGAN_ABI_VERSION 12
+#define CMGAN_ABI_VERSION 13
 
 typedef struct cmgan_handle cmgan_handle;
 
@@ -658,6 +658,50 @@ int cmgan_mix(cmgan_handle* h, const float* clean_dev, int B, int L, long long l
               const int* rir_len_dev, const float* snr_db_dev, float peak, int early, float* noisy_dev,
               float* target_dev, long long ld_out, double* g_dev, double* scale_dev, double* ps_dev, double* pn_dev,
               void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- Scenes: located noise sources and interfering talkers (no counterpart in the reference, see "Dynamic mixing") ------
+ * cmgan_mix with up to S <= cmgan_scene_max_sources() = 4 further sources per row, each INSIDE the room: convolved with a
+ * response of its own and mixed in at an SNR of its own.  speech, target and d are exactly those of cmgan_mix, and so is
+ * the dry noise n0 with its tables; noise_bank_dev == NULL drops the n0 term (its four tables are then ignored).  The
+ * sources read ONE flat float32 bank src_bank_dev of src_bank_len samples - the noise bank again, or any other: a bank of
+ * speech gives interfering talkers - through tables in DEVICE memory, row-major [B, S]: src_start, src_len, src_off
+ * (int64), src_snr_db (float32), src_rir_index, src_rir_len (int32, rows of the SAME rir_bank_dev as the talker; without
+ * a bank every source is dry, h_j = [1]), and n_src int32 [B].  With S == 0 all of these are ignored.  For row b, with
+ * S_b = n_src[b] clamped to [0, S], and for j = 1 .. S_b (table column j - 1):
+ *   segment   seg_j[m] = src_bank[src_start + ((src_off + m) mod src_len)] for EVERY integer m: it loops both ways
+ *   source    c_j[i] = sum_{k = 0 .. K_j - 1} h_j[k] seg_j[i - k], 0 <= i < L, h_j = rir[src_rir_index], K_j = src_rir_len.
+ *             The direct-path delay is NOT removed: a source further from the microphone than the talker arrives later
+ *   gain      P_j = mean(c_j^2), g_j = sqrt(Ps / (P_j 10^(src_snr_db / 10))); g_j = 0 when Ps == 0 or P_j == 0
+ *   mix       v = speech + g0 n0 + g_1 c_1 + ... + g_{S_b} c_{S_b}, one fused multiply-add per term in this order; m, s and
+ *             the outputs as in cmgan_mix
+ *   outputs   noisy_dev, target_dev as in cmgan_mix; g_dev float64 [B, 1 + S] = g0, g_1 .. g_S and p_dev float64
+ *             [B, 1 + S] = Pn, P_1 .. P_S (both 0 in the columns beyond S_b, and in column 0 without a dry-noise bank);
+ *             ps_dev, scale_dev float64 [B]
+ * Arithmetic, reductions and guarantees are those of cmgan_mix: float64 products and sums, taps in ascending k, one rounding
+ * to float32; two-stage reductions in a fixed order that depends on L alone; no atomics.  Row b's outputs depend neither
+ * on B, nor on the other rows or their n_src, nor on the table columns beyond S_b, which are never read.  With S == 0 and a
+ * dry-noise bank every output has the bits of cmgan_mix.  Untrusted tables as there: a source segment that is empty or
+ * leaves [0, src_bank_len) is silence (c_j = 0, P_j = 0, g_j = 0), RIR indices are clamped to [0, R), lengths to [1, Kmax];
+ * offsets may be any int64.
+ * Method.  The source index is a grid axis of the convolution kernel: slice 0 is the talker's convolution of cmgan_mix,
+ * slice j source j over the same tiles of cmgan_mix_tile() outputs; a block stages a chunk of taps and the LOOPED span
+ * they reach on chip in float64, the modulo taken once per thread and chunk and advanced by a conditional subtraction per
+ * staged sample, so src_len = 1 and src_len >> L cost the same.
+ * Supported: the shapes of cmgan_mix and 0 <= S <= 4.  Every argument is checked before the handle is (cmgan_last_error(NULL)
+ * reads the message of a call with h == NULL): CMGAN_E_BADARG / CMGAN_E_UNSUPPORTED before any launch.
+ * Workspace: cmgan_scene_workspace_bytes (h may be NULL; 0 for an unsupported shape; non-decreasing in B, L, Kmax and S),
+ * 256-byte aligned; it holds the float64 speech, target and c_j rows between the launches.  Six launches (five without a
+ * RIR bank), no synchronisation, no allocation; graph-capturable, and a replay reads the tables' current contents.     */
+int cmgan_scene_max_sources(void);
+size_t cmgan_scene_workspace_bytes(const cmgan_handle* h, int B, int L, int Kmax, int S);
+int cmgan_scene(cmgan_handle* h, const float* clean_dev, int B, int L, long long ld, const float* noise_bank_dev,
+                long long bank_len, const long long* noise_start_dev, const long long* noise_len_dev,
+                const long long* noise_off_dev, const float* snr_db_dev, const float* src_bank_dev, long long src_bank_len,
+                int S, const int* n_src_dev, const long long* src_start_dev, const long long* src_len_dev,
+                const long long* src_off_dev, const float* src_snr_db_dev, const float* rir_bank_dev, int R, int Kmax,
+                const int* rir_index_dev, const int* rir_len_dev, const int* src_rir_index_dev, const int* src_rir_len_dev,
+                float peak, int early, float* noisy_dev, float* target_dev, long long ld_out, double* g_dev, double* p_dev,
+                double* ps_dev, double* scale_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---- Room impulse responses (the reference ships no impulse responses and no simulator; its --cut_len help names
  * "denoise and dereverberation", src/data/dataloader.py:13-50 replays pairs mixed beforehand) --------------------------
