@@ -26,12 +26,12 @@
 #include <stdint.h>
 
 #include "api_internal.h"
+#include "warp_common.hip.h"
 
 namespace {
 
 constexpr int WP_TPB = 256;                 // threads of warp_rows
 constexpr int WP_TILE = WP_TPB;             // outputs per block, one per thread
-constexpr double WP_MAX_RATE = 4.0;         // rates in [1 / WP_MAX_RATE, WP_MAX_RATE]
 constexpr int WP_MIN_ZEROS = 4, WP_MAX_ZEROS = 64;
 constexpr double WP_MIN_ROLLOFF = 0.5;
 constexpr int WP_MAX_W = 512;               // zeros / fc <= 64 x 4 / 0.5
@@ -39,27 +39,7 @@ constexpr int WP_SPAN = 4 * WP_TILE + 2 * WP_MAX_W + 64;   // floats of LDS: the
 constexpr long long WP_MAX_N = 1LL << 50;   // cmgan_warp_out_len: lengths whose products stay exact integers
 constexpr double WP_PI = 3.14159265358979323846;
 
-// one rounded float64 product, never fused with a following sum
-__host__ __device__ inline double wp_mul(double a, double b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __dmul_rn(a, b);
-#else
-    volatile double p = a * b;
-    return p;
-#endif
-}
-
-__host__ __device__ inline bool wp_rate_ok(double r) { return r >= 1.0 / WP_MAX_RATE && r <= WP_MAX_RATE; }   // a NaN: false
-
-// #{i >= 0 : fl(i r) < n}: ceil(n / r), then single steps until fl((M - 1) r) < n <= fl(M r)
-__host__ __device__ inline long long wp_count(long long n, double r) {
-    if (n <= 0) return 0;
-    const double nd = (double)n;
-    long long M = (long long)ceil(nd / r);
-    while (M > 0 && wp_mul((double)(M - 1), r) >= nd) --M;
-    while (wp_mul((double)M, r) < nd) ++M;
-    return M;
-}
+// (wp_mul, wp_rate_ok and wp_count: warp_common.hip.h, shared with stretch.hip)
 
 // the integers k with |t - k| < W, judged on the float64 difference: [k0, k1] before the clamp to the row
 __device__ inline void wp_support(double t, double W, long long& k0, long long& k1) {

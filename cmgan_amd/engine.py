@@ -385,6 +385,55 @@ def check_warp_args(device, wav, rate, n_out=None, lengths=None, zeros=24, rollo
     return B, L, N
 
 
+STRETCH_HOP = (16, 1024)      # samples per frame of cmgan_stretch (1024 = cmgan_stretch_max_hop())
+STRETCH_SEARCH = (0, 1024)    # its search range on either side, in samples (1024 = cmgan_stretch_max_search())
+PITCH_FACTOR = (0.5, 2.0)     # frequency ratios of Engine.pitch_shift: an octave either way
+
+
+def check_stretch_args(device, wav, rate, n_out=None, lengths=None, hop=256, search=160, out=None):
+    """Argument rules of Engine.stretch (shapes, dtypes, devices and host scalars; pure host code).  Returns (B, L, N); N
+    is None when neither n_out nor out says it (Engine.stretch then takes cmgan_warp_out_len(L, 1 / 4))."""
+    tensor_arg(wav, "wav", torch.float32, device, "[B, L] with B, L >= 1",
+               lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) >= 1, contiguous=False)     # (its own stride rule below)
+    B, L = wav.shape
+    if B > 65535:
+        raise ValueError(f"wav: at most 65535 rows, got {B}")
+    if not _row_stride_ok(wav, B, L):
+        raise ValueError(f"wav: rows must be contiguous and at least L apart, got strides {tuple(wav.stride())}")
+    row = lambda t: tuple(t.shape) == (B,)
+    tensor_arg(rate, "rate", torch.float64, device, f"[{B}]", row)
+    if lengths is not None:
+        tensor_arg(lengths, "lengths", torch.int32, device, f"[{B}]", row)
+    if n_out is not None and (isinstance(n_out, bool) or int(n_out) != n_out or not 1 <= n_out <= 2 ** 31 - 1):
+        raise ValueError(f"n_out must be an output length in [1, 2^31 - 1] or None, got {n_out}")
+    if isinstance(hop, bool) or int(hop) != hop or not STRETCH_HOP[0] <= hop <= STRETCH_HOP[1]:
+        raise ValueError(f"hop must be a whole number in [{STRETCH_HOP[0]}, {STRETCH_HOP[1]}], got {hop}")
+    if isinstance(search, bool) or int(search) != search or not STRETCH_SEARCH[0] <= search <= STRETCH_SEARCH[1]:
+        raise ValueError(f"search must be a whole number in [{STRETCH_SEARCH[0]}, {STRETCH_SEARCH[1]}], got {search}")
+    N = None if n_out is None else int(n_out)
+    if out is not None:
+        tensor_arg(out, "out", torch.float32, device, f"[{B}, N]" if N is None else f"[{B}, {N}]",
+                   lambda t: t.dim() == 2 and t.size(0) == B and t.size(1) >= 1 and (N is None or t.size(1) == N),
+                   contiguous=False)
+        N = int(out.size(1))
+        if not _row_stride_ok(out, B, N):
+            raise ValueError(f"out: rows must be contiguous and at least N apart, got strides {tuple(out.stride())}")
+    return B, L, N
+
+
+def check_pitch_args(device, wav, factor, n_out=None, hop=256, search=160, zeros=24, rolloff=0.95):
+    """Argument rules of Engine.pitch_shift, all judged before its first launch: those of Engine.stretch and Engine.warp,
+    with `factor` a float64 [B] device tensor (its VALUES are judged on the device: a row outside [1/2, 2] comes out as
+    zeros).  Returns (B, L)."""
+    tensor_arg(wav, "wav", torch.float32, device, "[B, L] with B, L >= 1",
+               lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) >= 1, contiguous=False)
+    B = wav.size(0)
+    tensor_arg(factor, "factor", torch.float64, device, f"[{B}]", lambda t: tuple(t.shape) == (B,))
+    check_stretch_args(device, wav, factor, None, None, hop, search)
+    check_warp_args(device, wav, factor, n_out, None, zeros, rolloff)
+    return B, int(wav.size(1))
+
+
 def metric_frames(L: int, fs: int):
     """(WSS / segSNR frames, LLR frames) of an L-sample signal: the two counts of cmgan_amd.metrics."""
     win = int(np.round(30 * fs / 1000))
@@ -1199,6 +1248,69 @@ class Engine:
         self._call("cmgan_warp", wav, B, L, wav.stride(0) if B > 1 else L, lengths, rate, int(zeros), float(rolloff), out, N,
                    out.stride(0) if B > 1 else N, n, st)
         return (out, n, st) if info else out
+
+    # ---- tempo and pitch perturbation -------------------------------------------------
+    @_on_device
+    def stretch(self, wav: torch.Tensor, rate: torch.Tensor, n_out: Optional[int] = None, lengths: Optional[torch.Tensor] = None,
+                hop: int = 256, search: int = 160, out: Optional[torch.Tensor] = None, info: bool = False):
+        """Tempo perturbation per row on the GPU (cmgan_stretch, include/cmgan_hip.h): every row is time-stretched by its
+        own rate with the pitch kept, by WSOLA (waveform-similarity overlap-add): frames of `hop` samples are spliced
+        where the waveform continues best, found within +-`search` samples of the nominal position.
+
+        wav float32 [B, L] (rows contiguous, any row stride >= L); rate float64 [B]: input time per output time, any value
+        in [1 / 4, 4] (> 1 is faster, the sense of Engine.warp); lengths int32 [B] (None: every row has L samples; samples
+        from a row's length on are never read).  All on this Engine's device and read by the kernel only.  n_out: the
+        output length N; None takes cmgan_warp_out_len(L, 1 / 4), room for the slowest valid rate - pass it in real use
+        (cmgan_amd.mixing.warp_len(L, rate) is the length one rate gives, the same as Engine.warp's).  hop (16 .. 1024)
+        and search (0 .. 1024) in samples: the defaults are 16 ms and +-10 ms at 16 kHz, which suits speech.  `out`
+        float32 [B, N] is written in place of a new tensor; it may not overlap wav.
+        Returns the float32 [B, N] result: row b holds out_len[b] = min(N, #{i : fl(i rate[b]) < lengths[b]}) samples,
+        then zeros; a frame that continues the previous one is the input bit for bit, so rate = 1 copies the row.
+        info=True returns (y, out_len int32 [B], status int32 [B], pos int32 [B, ceil(N / hop)], searched int32 [B]):
+        status 1 marks the rows that are invalid (a rate that is not a finite number in [1 / 4, 4], a length outside
+        [0, L]) and come out as zeros with out_len 0; pos holds the input position every frame was taken from (-1 behind a
+        row's last frame), searched how many frames were searched.  The positions are exact: a host model finds the same.
+        Bit-reproducible, row-independent, one launch (one block per row), no workspace, no synchronisation,
+        graph-capturable."""
+        B, L, N = check_stretch_args(self.device, wav, rate, n_out, lengths, hop, search, out)
+        if N is None:
+            N = int(self.lib.cmgan_warp_out_len(L, 1.0 / WARP_MAX_RATE))
+            if N > 2 ** 31 - 1:
+                raise ValueError(f"wav: rows of {L} samples need n_out; the default, {N}, is beyond 2^31 - 1")
+        if out is None:
+            out = torch.empty(B, N, dtype=torch.float32, device=self.device)
+        n = st = pos = srch = None
+        if info:
+            n, st, srch = (torch.empty(B, dtype=torch.int32, device=self.device) for _ in range(3))
+            pos = torch.empty(B, -(-N // int(hop)), dtype=torch.int32, device=self.device)
+        self._call("cmgan_stretch", wav, B, L, wav.stride(0) if B > 1 else L, lengths, rate, int(hop), int(search), out, N,
+                   out.stride(0) if B > 1 else N, n, st, pos, srch)
+        return (out, n, st, pos, srch) if info else out
+
+    @_on_device
+    def pitch_shift(self, wav: torch.Tensor, factor: torch.Tensor, n_out: Optional[int] = None, hop: int = 256,
+                    search: int = 160, zeros: int = 24, rolloff: float = 0.95):
+        """Pitch perturbation per row on the GPU without a tempo change: Engine.stretch at rate 1 / factor, which makes
+        the row `factor` times as long at its own pitch, then Engine.warp at rate `factor`, which brings it back to its
+        length and multiplies every frequency by `factor`.
+
+        wav float32 [B, L]; factor float64 [B] on this Engine's device, a frequency ratio in [1 / 2, 2] (2^(s / 12) for s
+        semitones), read on the device only.  n_out: the output length (None: L).  hop / search are Engine.stretch's,
+        zeros / rolloff Engine.warp's.  Returns float32 [B, n_out].  A row holds min(n_out, M2) samples and zeros after
+        them, M2 = warp_len(warp_len(L, 1 / factor), factor): L up to the two roundings of the length, and the pitch is
+        `factor` times the input's up to the same.  A row whose factor is not a finite number in [1 / 2, 2] comes out as
+        zeros.  factor = 1 gives Engine.warp's output at rate 1 (the stretch is then a copy).  The stretch is WSOLA tuned to
+        speech (frames of 16 ms, splices searched within +-10 ms at the defaults): it is not meant for music, whose
+        polyphony has no single period to splice at.  Two launches and an intermediate of warp_len(L, 1 / 2) samples per
+        row; no synchronisation."""
+        B, L = check_pitch_args(self.device, wav, factor, n_out, hop, search, zeros, rolloff)
+        ok = (factor >= PITCH_FACTOR[0]) & (factor <= PITCH_FACTOR[1])                      # a NaN: False
+        f = torch.where(ok, factor, torch.full_like(factor, float("nan")))                   # (an invalid row of both calls)
+        N1 = int(self.lib.cmgan_warp_out_len(L, PITCH_FACTOR[0]))
+        if N1 > 2 ** 31 - 1:
+            raise ValueError(f"wav: rows of {L} samples are too long: the stretched batch would need {N1} samples per row")
+        long, n1, _, _, _ = self.stretch(wav, 1.0 / f, N1, hop=hop, search=search, info=True)
+        return self.warp(long, f, L if n_out is None else n_out, n1, zeros, rolloff)
 
     # ---- diagnostics ---------------------------------------------------------------
     @_on_device

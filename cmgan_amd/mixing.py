@@ -21,6 +21,9 @@ takes - with `clean` the training target (the dry clip, or the clip with its ear
     # warp_len(L, hi) samples long, so the loader cuts clips hi times longer than the batch it wants
     mixer = DynamicMixer(engine, noise, rirs, speed=(0.9, 1.1))
     clean = torch.utils.data.DataLoader(clean_only("data/train", cut_len=math.ceil(32000 * 1.1)), batch_size=32, ...)
+    # tempo and pitch perturbation: a time stretch that keeps the pitch (Engine.stretch / cmgan_stretch, WSOLA), and that
+    # stretch followed by a warp.  stretch_len(L, tempo=, pitch=, speed=) is the batch length clips of L samples give
+    mixer = DynamicMixer(engine, noise, rirs, tempo=(0.9, 1.1), pitch=(-2, 2))
 """
 from __future__ import annotations
 
@@ -38,7 +41,7 @@ from .data import _natural_key, fit_length, read_wav
 
 __all__ = ["NoiseBank", "RirBank", "RoomSampler", "sabine_beta", "DynamicMixer", "MixingLoader", "CleanDataset",
            "clean_only", "Draw", "SceneDraw", "tile", "ChannelSampler", "biquad_peaking", "biquad_low_shelf", "biquad_high_shelf",
-           "biquad_lowpass", "biquad_highpass", "butter_lowpass_sos", "warp_len"]
+           "biquad_lowpass", "biquad_highpass", "butter_lowpass_sos", "warp_len", "stretch_len", "StretchDraw"]
 
 SPEED_OF_SOUND = 343.0        # m/s, the default `c` of Engine.rir
 RIR_TW = 40                   # the default half-width of its fractional-delay filter, in samples
@@ -52,6 +55,39 @@ def warp_len(L: int, rate: float) -> int:
     if n < 0:
         raise ValueError(f"warp_len needs L >= 0 and a rate in [{SPEED_RANGE[0]}, {SPEED_RANGE[1]}], got L = {L}, rate = {rate}")
     return n
+
+
+PITCH_RANGE = 12.0            # semitones either way: the factors 1/2 .. 2 of Engine.pitch_shift
+
+
+def _pair(value, name: str, what: str):
+    try:
+        return float(value[0]), float(value[1])
+    except (TypeError, ValueError, IndexError):
+        raise ValueError(f"{name} must be None or (low, high){what}, got {value}") from None
+
+
+def _stretch_ranges(tempo=None, pitch=None, speed=None, p_tempo: float = 1.0, p_pitch: float = 1.0, p_speed: float = 1.0):
+    """The ranges of the rates DynamicMixer(tempo=, pitch=, speed=) can draw: ((t_lo, t_hi), (p_lo, p_hi), (v_lo, v_hi)),
+    with t the tempo, p = 2^(semitones / 12) the pitch factor and v the speed.  An argument that is None gives (1, 1); with
+    a probability below 1 the value 1.0 belongs to the range."""
+    def widen(r, p):
+        return (min(r[0], 1.0), max(r[1], 1.0)) if p < 1.0 else r
+    t = widen(tempo, p_tempo) if tempo is not None else (1.0, 1.0)
+    f = widen((2.0 ** (pitch[0] / 12.0), 2.0 ** (pitch[1] / 12.0)), p_pitch) if pitch is not None else (1.0, 1.0)
+    v = widen(speed, p_speed) if speed is not None else (1.0, 1.0)
+    return t, f, v
+
+
+def stretch_len(L: int, tempo=None, pitch=None, speed=None, p_tempo: float = 1.0, p_pitch: float = 1.0,
+                p_speed: float = 1.0) -> int:
+    """The batch length DynamicMixer(tempo=, pitch=, speed=, ...) makes of clips of L samples: N1 = warp_len(L, t_hi /
+    p_lo) after Engine.stretch, then warp_len(N1, v_hi p_hi) after the one Engine.warp (which runs unless only `tempo`
+    is given).  tempo and speed are (low, high) rates, pitch (low, high) in semitones, each or None; with a probability
+    below 1 the rate 1.0 counts as part of its range."""
+    (_, t_hi), (p_lo, p_hi), (_, v_hi) = _stretch_ranges(tempo, pitch, speed, p_tempo, p_pitch, p_speed)
+    n = warp_len(L, t_hi / p_lo)
+    return n if pitch is None and speed is None else warp_len(n, v_hi * p_hi)
 
 
 def tile() -> int:
@@ -418,6 +454,16 @@ class Draw(NamedTuple):
     speed: Optional[torch.Tensor] = None      # DynamicMixer(speed=...): the float64 [B] rate of Engine.warp per row
 
 
+class StretchDraw(NamedTuple):
+    """What a DynamicMixer(tempo=..., pitch=...) drew for a batch, float64 [B] device tensors: the tempo t, the pitch
+    factor p = 2^(semitones / 12), and the rates of the two calls they give with the speed v of Draw.speed (1 without
+    `speed`): Engine.stretch at t / p, then Engine.warp at v p (None when no warp runs: `tempo` alone, without `speed`)."""
+    tempo: torch.Tensor
+    pitch_factor: torch.Tensor
+    stretch_rate: torch.Tensor
+    warp_rate: Optional[torch.Tensor]
+
+
 class SceneDraw(NamedTuple):
     """What a DynamicMixer(sources=...) drew for a batch: the fields of Draw, then the per-source arguments of Engine.scene,
     [B] and [B, S] device tensors with S = the upper end of `sources`."""
@@ -490,6 +536,23 @@ class DynamicMixer:
     it wants: `clean_only(dir, cut_len=math.ceil(32000 * hi))` for batches of 32000.  A row drawn as 1.0 passes the same
     filter (`speed_zeros`, `speed_rolloff`) as the others - it is band-limited at the rolloff, not copied.
 
+    `tempo=(lo, hi)` (rates, > 1 is faster) and `pitch=(lo, hi)` in SEMITONES, |.| <= 12: tempo and pitch perturbation, each
+    on its own (Engine.stretch / cmgan_stretch: a WSOLA time stretch that keeps the pitch, tuned to speech - `stretch_hop`,
+    `stretch_search` - and not meant for music).  With both None (the default) nothing is drawn or run and the outputs,
+    `last_draw` and every generator state are what they are without the arguments; `Draw` and `SceneDraw` are the same
+    either way.  Otherwise, per row and from the mixer's generator AFTER every other draw (the sources' included): a tempo
+    t uniform in its range, or exactly 1.0 with probability 1 - `p_tempo`, and a pitch factor p = 2^(semitones / 12) with
+    the semitones uniform in their range, or exactly 1.0 with probability 1 - `p_pitch`; they are kept, with the two rates
+    below, as `mixer.last_stretch` (a StretchDraw; None when the stage is off).  With v the row's speed draw (1 without
+    `speed`), the clean batch goes FIRST through Engine.stretch at rate t / p with n_out = N1 = warp_len(L, t_hi / p_lo),
+    then through ONE Engine.warp at rate v p with n_out = warp_len(N1, v_hi p_hi): the stretch changes the duration by p / t
+    at the pitch it has, the warp moves tempo and pitch together by v p, so the duration changes by 1 / (t v) and the
+    pitch by v p.  The speed stage's own warp is folded into that one (otherwise the speed path is as it was), and with
+    `tempo` alone, without `speed`, no warp runs.  Where a probability is below 1, the value 1.0 counts as part of its
+    range in these bounds, so all rows come out full; target and noisy are [B, stretch_len(L, tempo, pitch, speed, ...)].
+    The loader should cut clips of about N (t_hi / p_lo) (v_hi p_hi) samples for batches of N: pick the smallest L with
+    stretch_len(L, ...) >= N.  Ranges whose rates t / p or v p can leave [1/4, 4] are refused.
+
     `sources=(lo, hi)` with 0 <= lo <= hi, 1 <= hi <= 4: point noise sources and interfering talkers INSIDE the room
     (Engine.scene / cmgan_scene).  With None (the default) the mixer calls Engine.mix and the outputs, `last_draw` (apart
     from its trailing `speed=None`) and every generator state are what they are without the argument: `last_draw` is a
@@ -512,7 +575,8 @@ class DynamicMixer:
                  rooms: Optional[RoomSampler] = None, rir_seconds: float = 0.5, snr_on: str = "rms", level_db=None,
                  channel: Optional[ChannelSampler] = None, channel_on: str = "noisy", speed=None, p_speed: float = 1.0,
                  speed_zeros: int = 24, speed_rolloff: float = 0.95, sources=None, source_bank: Optional[NoiseBank] = None,
-                 source_snr_db=(0.0, 20.0), dry_noise: bool = True):
+                 source_snr_db=(0.0, 20.0), dry_noise: bool = True, tempo=None, p_tempo: float = 1.0, pitch=None,
+                 p_pitch: float = 1.0, stretch_hop: int = 256, stretch_search: int = 160):
         if sources is not None:
             try:
                 lo_n, hi_n = sources
@@ -546,6 +610,33 @@ class DynamicMixer:
             raise ValueError(f"p_speed must lie in [0, 1], got {p_speed}")
         self.speed, self.p_speed = speed, float(p_speed)
         self.speed_zeros, self.speed_rolloff = int(speed_zeros), float(speed_rolloff)
+        if tempo is not None:
+            tempo = _pair(tempo, "tempo", "")
+            if not SPEED_RANGE[0] <= tempo[0] <= tempo[1] <= SPEED_RANGE[1]:
+                raise ValueError(f"tempo must be (low, high) with {SPEED_RANGE[0]} <= low <= high <= {SPEED_RANGE[1]}, got {tempo}")
+        if pitch is not None:
+            pitch = _pair(pitch, "pitch", " in semitones")
+            if not -PITCH_RANGE <= pitch[0] <= pitch[1] <= PITCH_RANGE:
+                raise ValueError(f"pitch must be (low, high) semitones with {-PITCH_RANGE} <= low <= high <= {PITCH_RANGE}, "
+                                 f"got {pitch}")
+        for name, p in (("p_tempo", p_tempo), ("p_pitch", p_pitch)):
+            if not 0.0 <= float(p) <= 1.0:
+                raise ValueError(f"{name} must lie in [0, 1], got {p}")
+        if isinstance(stretch_hop, bool) or int(stretch_hop) != stretch_hop or not 16 <= stretch_hop <= 1024:
+            raise ValueError(f"stretch_hop must be a whole number in [16, 1024], got {stretch_hop}")
+        if isinstance(stretch_search, bool) or int(stretch_search) != stretch_search or not 0 <= stretch_search <= 1024:
+            raise ValueError(f"stretch_search must be a whole number in [0, 1024], got {stretch_search}")
+        self.tempo, self.p_tempo, self.pitch, self.p_pitch = tempo, float(p_tempo), pitch, float(p_pitch)
+        self.stretch_hop, self.stretch_search = int(stretch_hop), int(stretch_search)
+        self.last_stretch: Optional[StretchDraw] = None
+        if tempo is not None or pitch is not None:
+            (t_lo, t_hi), (f_lo, f_hi), (v_lo, v_hi) = self._ranges()
+            if not (SPEED_RANGE[0] <= t_lo / f_hi and t_hi / f_lo <= SPEED_RANGE[1]):
+                raise ValueError(f"tempo / pitch: the stretch rates, {t_lo / f_hi:.4g} .. {t_hi / f_lo:.4g}, must stay in "
+                                 f"[{SPEED_RANGE[0]}, {SPEED_RANGE[1]}] (tempo = {tempo}, pitch = {pitch})")
+            if not (SPEED_RANGE[0] <= v_lo * f_lo and v_hi * f_hi <= SPEED_RANGE[1]):
+                raise ValueError(f"speed x pitch: the warp rates, {v_lo * f_lo:.4g} .. {v_hi * f_hi:.4g}, must stay in "
+                                 f"[{SPEED_RANGE[0]}, {SPEED_RANGE[1]}] (speed = {speed}, pitch = {pitch})")
         if channel_on not in ("noisy", "both"):
             raise ValueError(f"channel_on must be 'noisy' or 'both', got {channel_on!r}")
         if channel is not None and not isinstance(channel, ChannelSampler):
@@ -651,6 +742,39 @@ class DynamicMixer:
             return SceneDraw(*drawn, n_src, s_start, s_len, s_off, s_snr, s_idx, s_rlen, s_rooms)
         return drawn
 
+    def _ranges(self):
+        return _stretch_ranges(self.tempo, self.pitch, self.speed, self.p_tempo, self.p_pitch, self.p_speed)
+
+    def stretch_len(self, L: int) -> int:
+        """The batch length this mixer makes of clips of L samples (`stretch_len` with the mixer's ranges; `warp_len(L,
+        hi)` with `speed` alone, L without any of the three)."""
+        if self.tempo is None and self.pitch is None:
+            return L if self.speed is None else warp_len(L, self.speed[1])
+        return stretch_len(L, self.tempo, self.pitch, self.speed, self.p_tempo, self.p_pitch, self.p_speed)
+
+    def draw_stretch(self, B: int, speed: Optional[torch.Tensor] = None) -> Optional[StretchDraw]:
+        """The tempo and pitch draws of a batch (None when both are off), made after `draw`; `speed` is its Draw.speed."""
+        if self.tempo is None and self.pitch is None:
+            return None
+        dev, gen = self.engine.device, self.generator
+        one = torch.ones(B, dtype=torch.float64, device=dev)
+        t = f = one
+        if self.tempo is not None:
+            lo, hi = self.tempo
+            u = torch.rand(B, 2, dtype=torch.float64, generator=gen, device=dev)
+            t = torch.clamp(lo + (hi - lo) * u[:, 0], lo, hi)              # (the sum may round past hi)
+            t = torch.where(u[:, 1] < self.p_tempo, t, one)
+        if self.pitch is not None:
+            lo, hi = self.pitch
+            u = torch.rand(B, 2, dtype=torch.float64, generator=gen, device=dev)
+            # clamped to the host's own 2^(lo / 12), 2^(hi / 12): the bounds the batch length was worked out from
+            f = torch.clamp(torch.exp2((lo + (hi - lo) * u[:, 0]) / 12.0), 2.0 ** (lo / 12.0), 2.0 ** (hi / 12.0))
+            f = torch.where(u[:, 1] < self.p_pitch, f, one)
+        warp = None
+        if self.pitch is not None or speed is not None:
+            warp = (f if speed is None else speed * f).contiguous()
+        return StretchDraw(t.contiguous(), f.contiguous(), (t / f).contiguous(), warp)
+
     def _simulate(self, d: Draw) -> RirBank:
         """The batch's responses, simulated into the persistent allocation (made anew only when B changes)."""
         B, K = d.rooms.size(0), self.rir_taps
@@ -684,7 +808,15 @@ class DynamicMixer:
         d = self.last_draw = self.draw(clean.size(0))
         rir = self.rir_bank if self.rooms is None else self._simulate(d)
         snr = d.snr_db
-        if d.speed is not None:
+        s = self.last_stretch = self.draw_stretch(clean.size(0), d.speed)
+        if s is not None:
+            (_, t_hi), (f_lo, f_hi), (_, v_hi) = self._ranges()
+            N1 = warp_len(clean.size(1), t_hi / f_lo)
+            clean = self.engine.stretch(clean, s.stretch_rate, N1, hop=self.stretch_hop, search=self.stretch_search)
+            if s.warp_rate is not None:                               # the speed stage's warp is this one
+                clean = self.engine.warp(clean, s.warp_rate, warp_len(N1, v_hi * f_hi), zeros=self.speed_zeros,
+                                         rolloff=self.speed_rolloff)
+        elif d.speed is not None:
             clean = self.engine.warp(clean, d.speed, warp_len(clean.size(1), self.speed[1]), zeros=self.speed_zeros,
                                      rolloff=self.speed_rolloff)
         if self.snr_on == "active" or d.level_db is not None:
@@ -752,7 +884,8 @@ class MixingLoader:
     """Wraps a loader of clean clips - batches `(clean [B, L], length [B])`, or any tuple whose first element is the
     clean batch and whose last is the lengths - and yields `(target, noisy, length)` with target / noisy float32 device
     tensors: the `(clean, noisy, length)` batches of `load_data`, so `Trainer(train_ds=MixingLoader(...))` works as is.
-    With `DynamicMixer(speed=...)` the batch is `warp_len(L, hi)` samples long and the lengths are clamped to that.
+    With `DynamicMixer(speed=...)` the batch is `warp_len(L, hi)` samples long and the lengths are clamped to that; with
+    `tempo=` / `pitch=` it is `mixer.stretch_len(L)` long, and they are clamped likewise.
 
     Stream ordering.  The clean batch is copied to the device (non-blocking from pinned memory) and mixed on the stream
     that is CURRENT when the batch is requested.  `DevicePrefetcher._stage` requests a batch on the compute stream, then
@@ -781,7 +914,7 @@ class MixingLoader:
                 clean, length = batch[0], batch[-1]
             clean = clean.to(device=dev, dtype=torch.float32, non_blocking=True).contiguous()
             target, noisy, info = self.mixer(clean)
-            if self.mixer.speed is not None:                           # the batch is not as long as the clips it was made of
+            if self.mixer.speed is not None or self.mixer.last_stretch is not None:   # the batch is not as long as the clips it was made of
                 length = torch.as_tensor(length).clamp(max=noisy.size(1))
             self._alive.append((clean, target, noisy, info, self.mixer.last_draw))
             self.last_info = info

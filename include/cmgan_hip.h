@@ -39,7 +39,7 @@ extern "C" {
 #define CMGAN_E_WORKSPACE   -5   /* workspace too small or misaligned              */
 #define CMGAN_E_HIP         -6   /* a HIP runtime call failed (see last_error)     */
 
-#define CMGAN_ABI_VERSION 13
+#define CMGAN_ABI_VERSION 14
 
 typedef struct cmgan_handle cmgan_handle;
 
@@ -849,6 +849,53 @@ long long cmgan_warp_out_len(long long n, double rate);
 int cmgan_warp(cmgan_handle* h, const float* x_dev, int B, int L, long long ldx, const int* lengths_dev,
                const double* rate_dev, int zeros, double rolloff, float* y_dev, int N, long long ldy, int* out_len_dev,
                int* status_dev, void* stream);
+
+/* ---- Tempo perturbation (the reference has no counterpart: its data path replays fixed pairs, src/data/dataloader.py) ---
+ * Every row of a [B, L] float32 batch x_dev[b * ldx + k] is time-stretched by its OWN rate into N outputs
+ * y_dev[b * ldy + i] with the pitch kept: WSOLA (waveform-similarity overlap-add, Verhelst & Roelands 1993), the
+ * time-domain method that splices the waveform at pitch-synchronous points.  rate_dev float64 [B] (input time per output
+ * time: > 1 is faster, the sense of cmgan_warp), lengths_dev int32 [B] (NULL: n = L), out_len_dev, status_dev and
+ * searched_dev int32 [B] and pos_dev int32 [B][ceil(N / hop)] (each may be NULL) are in DEVICE memory and read / written
+ * by the kernel only; hop = H (16 .. cmgan_stretch_max_hop() = 1024) and search = D (0 .. cmgan_stretch_max_search() =
+ * 1024) are host values.  For row b with n = lengths[b] and r = rate[b]; x[k] reads as 0 for every k outside [0, n):
+ *   M    = min(N, #{i >= 0 : fl(i r) < n})         out_len[b]: cmgan_warp's count, so stretch and warp agree on lengths;
+ *                                                  K = ceil(M / H) frames, the last one may be partial
+ *   p_k  = floor(fl((k H) r))                      the nominal position: k H is an exact integer, ONE rounded float64
+ *                                                  product per frame; k H < M gives 0 <= p_k < n
+ *   q_0  = c_0 = 0;   c_k = q_{k-1} + H            the natural continuation of the previous segment, for k >= 1
+ *   q_k  = c_k                                     if |c_k - p_k| <= D and 0 <= c_k < n: no search, the frame is a copy
+ *   q_k  = the candidate q = p_k + d, |d| <= D, 0 <= q < n (d = 0 is always one), with the largest score otherwise:
+ *          s(d) = 2 C - E,   C = sum_{i=0}^{H-1} x[q + i] x[c_k + i],   E = sum_{i=0}^{H-1} x[q + i]^2,
+ *          each a float64 sum in ascending i (maximising 2 C - E minimises the squared difference to the continuation);
+ *          a NaN score counts as -inf; among equal maxima the earliest in the order d = 0, -1, +1, -2, +2, ... wins, so
+ *          silence, a constant row and an all-NaN row take d = 0
+ *   f[i] = 0.5 - 0.5 cospi(i / H),   g[i] = fl(1 - f[i])          float64: a 50 % Hann overlap-add of x[q_k .. q_k + 2 H)
+ *   y[b, k H + i] = f32( f[i] x[q_k + i] + g[i] x[c_k + i] )      for 0 <= i < H and k H + i < M;   y[b, i] = 0 for M <= i < N
+ *   pos[b, k] = q_k for k < K and -1 for K <= k < ceil(N / H);   searched[b] = the frames that were searched
+ * Where q_k = c_k the frame is the input bit for bit (finite samples): r = 1 copies the row, r = 1.0001 copies long runs and
+ * splices rarely.  A product of two float32 values is exact in float64, so fused and unfused multiply-adds give the same
+ * sums in ascending order and the positions q_k are exactly reproducible: a host model finds the same ones.  Only the
+ * cross-fade line depends on the contraction of multiply-adds and on the device's cospi.  Samples of x at k >= n are never
+ * read.  A row is INVALID - status 1 (else 0), out_len 0, N zeros, every pos -1, searched 0 - when its rate is not a finite
+ * number in [1 / cmgan_warp_max_rate(), cmgan_warp_max_rate()] = [1/4, 4] or its length lies outside [0, L]; n = 0 is
+ * valid with out_len 0.  Non-finite samples are no error: the rules above stay defined (a NaN score counts as -inf), the
+ * outputs follow IEEE arithmetic, and no other row is affected.
+ * Method.  The frames of a row form a serial chain, so one block owns a row and walks its frames: a batch of B rows keeps B
+ * compute units busy.  A searched frame stages the candidate span and the continuation on chip; every candidate has a
+ * thread of its own, which runs both sums in one ascending chain; the best (score, visiting rank) is reduced by wave
+ * shuffles and one step through LDS, in an order that cannot change the winner because the order on that key is total.
+ * No atomics, no workspace; row b's bits depend neither on B, nor on the other rows, nor on the padding behind ldx / ldy,
+ * nor on L beyond n.
+ * Checked before the launch and before the handle is looked at (the message of a call with h == NULL is read with
+ * cmgan_last_error(NULL)): null x / rate / y, misaligned pointers (4 bytes for float32 / int32, 8 for the rates),
+ * 1 <= B <= 65535, L >= 1, N >= 1, ldx >= L, ldy >= N, 16 <= hop <= 1024, 0 <= search <= 1024, any intersection of
+ * [x, x + (B-1) ldx + L) with [y, y + (B-1) ldy + N); each is CMGAN_E_BADARG.  One launch, no synchronisation, no
+ * allocation; graph-capturable, and a replay reads the current contents of x, the rates and the lengths.            */
+int cmgan_stretch_max_hop(void);
+int cmgan_stretch_max_search(void);
+int cmgan_stretch(cmgan_handle* h, const float* x_dev, int B, int L, long long ldx, const int* lengths_dev,
+                  const double* rate_dev, int hop, int search, float* y_dev, int N, long long ldy, int* out_len_dev,
+                  int* status_dev, int* pos_dev, int* searched_dev, void* stream);
 
 /* Names + durations (ms) of the kernels of the most recent forward when
  * profiling is enabled with cmgan_set_profiling(h, 1): HIP events are recorded
