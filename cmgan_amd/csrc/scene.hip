@@ -1,44 +1,155 @@
-// scene.hip - dynamic mixing with the noises INSIDE the room (cmgan_scene, include/cmgan_hip.h): cmgan_mix (mix.hip) adds
-// one dry noise segment to the reverberant speech; here up to SC_MAX_S further sources per row - point noises, interfering
-// talkers - are each convolved with a room response of their own and mixed in at an SNR of their own.  The reference has
-// no counterpart: its data path replays pairs mixed beforehand (src/data/dataloader.py:13-50).
+// scene.hip - dynamic mixing of a [B, L] float32 batch of clean speech into (noisy, target) training pairs on the device:
+// cmgan_mix and cmgan_scene (include/cmgan_hip.h), one implementation.  cmgan_mix adds one dry noise segment to the
+// reverberant speech; cmgan_scene also puts up to SC_MAX_S further sources per row - point noises, interfering talkers -
+// INSIDE the room, each convolved with a room response of its own and mixed in at an SNR of its own.  cmgan_mix is
+// cmgan_scene with S = 0 and a dry-noise bank that must be there.  The reference only replays pairs somebody mixed before
+// (src/data/dataloader.py:13-50 reads clean/x.wav and noisy/x.wav); its --cut_len help names "denoise and
+// dereverberation" as the task.
 //
-//   speech, target, d   exactly as cmgan_mix defines them (mix.hip)
-//   n0[i]    = bank[start0 + (off0 + i) mod len0]                          the dry noise of cmgan_mix (no bank: none)
+//   h = rir[rir_index[b], 0:K], K = rir_len[b], d = first argmax |h|        (no bank: h = [1], d = 0)
+//   speech[i] = sum_{k < K} h[k] clean[b, i + d - k]                         clean = 0 outside [0, L)
+//   target    = clean (early == -1) or the same sum over the taps k <= d + early
+//   n0[i]     = bank[noise_start[b] + (noise_off[b] + i) mod noise_len[b]]   the dry noise (cmgan_scene without a bank: none)
+//   Ps = mean(speech^2), Pn = mean(n0^2), g0 = sqrt(Ps / (Pn 10^(snr_db / 10)))    (g0 = 0 when Ps == 0 or Pn == 0)
 //   for j = 1 .. S_b,  S_b = clamp(n_src[b], 0, S):
 //     seg_j[m] = src_bank[start_j + ((off_j + m) mod len_j)]               every integer m: the segment loops both ways
 //     c_j[i]   = sum_{k < K_j} h_j[k] seg_j[i - k]                         h_j = rir[src_rir_index[b, j]], K_j = src_rir_len[b, j]
 //                                                                          (no bank: h_j = [1]); the delay STAYS
 //     P_j = mean(c_j^2),  g_j = sqrt(Ps / (P_j 10^(snr_j / 10)))           0 when Ps == 0 or P_j == 0
 //   v = speech + g0 n0 + g_1 c_1 + ... + g_S c_S                           an fma chain in ascending j
-//   m = max |v|, s = m > peak ? peak / m : 1;   noisy = f32(v s), target = f32(target s)
+//   m = max |v|, s = m > peak ? peak / m : 1
+//   noisy = f32(v s), target = f32(target s)                                  (s == 1, early == -1: target is clean's bits)
 //
 // Float32 samples in and out; every product and sum in float64 on the VALU, one rounding to float32 at the store.  Six
-// launches (five without a RIR bank), the kernels of mix.hip with one more grid axis:
-//   scene_direct  one block per row: d of the talker's response
-//   scene_conv    grid (tiles, 1 + S, B).  Slice j = 0 is mix_conv: the talker's convolution over a zero-padded span of the
-//                 clip, speech and target accumulators, the partial sums of speech^2 and n0^2.  Slice j >= 1 is source j:
-//                 the same MX_TILE outputs and MX_KC-tap chunks, but ALL K_j taps reach a sample (the segment has no
-//                 end), and the staged span is the LOOPED segment: a thread takes its first position mod len_j once per
-//                 chunk and steps it by (MX_TPB mod len_j) with one conditional subtraction per staged sample, so a
-//                 segment of 1 sample and one of 10^7 cost the same and the tap loop never sees a modulo.  c_j goes to
-//                 the workspace in float64, the block's sum of c_j^2 to a partial slot.  A block of a source beyond S_b
-//                 returns before it reads anything.
-//   scene_gain    one block per row: partials in ascending slot order -> Ps, Pn, g0, P_j, g_j
-//   scene_vmax    per tile: max |v| -> one partial slot        scene_scale  one block per row: the maxima -> s
+// launches per call (five without a RIR bank), no host synchronisation, no atomics, and every reduction in a fixed order
+// that depends on L alone, so a row's bits depend neither on B, nor on the other rows or their n_src, nor on what lies
+// behind ld or in the source slots beyond S_b:
+//   scene_direct  one block per row: d, the first index of the largest |h| of the talker's response
+//   scene_conv    grid (tiles, 1 + S, B): a block computes a tile of MX_TILE consecutive outputs of one row, MX_OPT per
+//                 thread.  Slice j = 0 is the talker.  It walks the taps that can reach a sample of the clip from its tile,
+//                 k in [max(0, i0 + d - (L - 1)), min(K - 1, i0 + n - 1 + d)], in chunks of MX_KC: a chunk's taps and the
+//                 clean span they reach are staged in LDS as float64 (zero where the clip has no sample), then every thread
+//                 runs the chunk's taps in ascending order, one tap value (an LDS broadcast) feeding MX_OPT speech
+//                 accumulators and - for the taps k <= d + early - as many target accumulators from the same loads.  K
+//                 beyond the LDS span is more chunks; K > L is fewer: the taps left out multiply zeros only.  The float64
+//                 speech / target rows go to the workspace, and the block's sums of speech^2 and n0^2 to one partial slot
+//                 each.  Slice j >= 1 is source j: the same MX_TILE outputs and MX_KC-tap chunks, but ALL K_j taps reach a
+//                 sample (the segment has no end), and the staged span is the LOOPED segment: a thread takes its first
+//                 position mod len_j once per chunk and steps it by (MX_TPB mod len_j) with one conditional subtraction
+//                 per staged sample, so a segment of 1 sample and one of 10^7 cost the same and the tap loop never sees a
+//                 modulo.  c_j goes to the workspace in float64, the block's sum of c_j^2 to a partial slot.  A block of
+//                 a source beyond S_b returns before it reads anything.
+//   scene_gain    one block per row: the partials in ascending slot order -> Ps, Pn, g0, P_j, g_j
+//   scene_vmax    per tile: max |v| -> one partial slot
+//   scene_scale   one block per row: the partial maxima -> s
 //   scene_apply   noisy = f32(v s), target = f32(target s) or clean's bits
-// The tile geometry, the reductions and the order of every sum are those of mix.hip (mix_common.hip.h), so S = 0 with a
-// dry-noise bank gives the bits of cmgan_mix.  No atomics; a row's bits depend neither on B, nor on the other rows or
-// their n_src, nor on what lies behind ld or in the source slots beyond S_b.  Untrusted tables as in cmgan_mix: an empty
-// segment or one that leaves its bank is silence (c_j = 0, P_j = 0, g_j = 0), RIR indices are clamped to [0, R), lengths
-// to [1, Kmax], offsets may be any int64.
+// The per-row tables are read on the device only.  An entry that would make a kernel read outside its bank is not
+// trusted: a segment that leaves its bank or has no sample counts as silence (c_j = 0, P_j = 0, g_j = 0), a RIR index is
+// clamped to [0, R), a RIR length to [1, Kmax], offsets may be any int64.
 #include <math.h>
 #include <stdint.h>
 
+#include <hip/hip_runtime.h>
+
 #include "api_internal.h"
-#include "mix_common.hip.h"
 
 namespace {
+
+constexpr int MX_TPB = 256;                 // threads of every kernel here
+constexpr int MX_OPT = 4;                   // outputs per thread of the convolutions: outputs t, t + 256, t + 512, t + 768 of the tile
+constexpr int MX_TILE = MX_TPB * MX_OPT;    // outputs per block
+constexpr int MX_KC = 1024;                 // taps per LDS chunk: 8 KiB of taps + 16 KiB of signal span, both float64
+constexpr int MX_MAX_K = 65536;             // longest RIR (4 s at 16 kHz)
+constexpr int MX_MAX_L = 0x7fffffff - MX_TILE;   // a tile's sample indices stay in an int
+
+// a row's bank segment: valid only if it lies inside the bank; `off` is the row's offset mod len in [0, len)
+struct NoiseRow {
+    const float* p;
+    long long len, off;
+};
+
+__device__ inline NoiseRow mx_segment(const float* bank, long long bank_len, long long st, long long len, long long off) {
+    NoiseRow r;
+    r.len = len;
+    const bool ok = bank && st >= 0 && r.len >= 1 && st <= bank_len && r.len <= bank_len - st;
+    if (!ok) {
+        r.p = nullptr;
+        r.len = 1;
+        r.off = 0;
+        return r;
+    }
+    r.p = bank + st;
+    const long long o = off % r.len;
+    r.off = o < 0 ? o + r.len : o;
+    return r;
+}
+
+__device__ inline double mix_noise(const NoiseRow& r, int i) {
+    return r.p ? (double)r.p[(r.off + i) % r.len] : 0.0;
+}
+
+// v = speech + g n: one expression for the maximum and the store, so both see the same bits
+__device__ inline double mix_v(double speech, double g, double n) { return fma(g, n, speech); }
+
+__device__ inline double block_sum(double v, double* red) {          // fixed order: halves folded, every thread calls
+    const int t = threadIdx.x;
+    red[t] = v;
+    __syncthreads();
+    for (int s = MX_TPB / 2; s > 0; s >>= 1) {
+        if (t < s) red[t] += red[t + s];
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+
+__device__ inline double block_max(double v, double* red) {
+    const int t = threadIdx.x;
+    red[t] = v;
+    __syncthreads();
+    for (int s = MX_TPB / 2; s > 0; s >>= 1) {
+        if (t < s) red[t] = fmax(red[t], red[t + s]);
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+
+// a RIR table entry is not trusted: the index is clamped to [0, R), the length to [1, Kmax]
+__device__ inline void mx_rir_row(const float* rir, int R, int Kmax, int idx, int len, const float*& h, int& K) {
+    idx = idx < 0 ? 0 : (idx >= R ? R - 1 : idx);
+    K = len < 1 ? 1 : (len > Kmax ? Kmax : len);
+    h = rir + (size_t)idx * Kmax;
+}
+
+// the direct path: the FIRST index at which |h[0:K]| is largest (all NaN: tap 0); every thread calls, thread 0 gets it
+__device__ inline int mx_direct_index(const float* h, int K, float* s_v, int* s_i) {
+    const int t = threadIdx.x;
+    float best = -1.f;
+    int at = 0x7fffffff;
+    for (int k = t; k < K; k += MX_TPB) {
+        const float v = fabsf(h[k]);
+        if (v > best) { best = v; at = k; }                  // ascending k: the first of equals stays
+    }
+    s_v[t] = best;
+    s_i[t] = at;
+    __syncthreads();
+    for (int s = MX_TPB / 2; s > 0; s >>= 1) {
+        if (t < s) {
+            const float v = s_v[t + s];
+            const int i = s_i[t + s];
+            if (v > s_v[t] || (v == s_v[t] && i < s_i[t])) { s_v[t] = v; s_i[t] = i; }
+        }
+        __syncthreads();
+    }
+    return s_i[0] < K ? s_i[0] : 0;
+}
+
+inline size_t mx_up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+inline int mx_tiles(int L) { return (L + MX_TILE - 1) / MX_TILE; }
 
 constexpr int SC_MAX_S = 4;                 // located sources per row
 
@@ -133,7 +244,7 @@ __global__ __launch_bounds__(MX_TPB) void scene_conv(SceneArgs a) {
     long long kt = -1, k_lo = 0, k_hi;
     NoiseRow seg = mx_segment(nullptr, 0, 0, 0, 0);
     size_t es = 0;                                           // the source's slot b S + src - 1
-    if (src == 0) {                                          // the talker: the tap range of mix_conv
+    if (src == 0) {                                          // the talker: the taps that reach the clip
         if (a.rir) {
             mx_rir_row(a.rir, a.R, a.Kmax, a.rir_index[b], a.rir_len[b], h, K);
             d = a.d[b];
@@ -347,62 +458,53 @@ inline bool sc_shape_ok(int B, int L, int Kmax, int S) {
     return B >= 1 && B <= 65535 && L >= 1 && L <= MX_MAX_L && Kmax >= 1 && Kmax <= MX_MAX_K && S >= 0 && S <= SC_MAX_S;
 }
 
-}  // namespace
-
-extern "C" int cmgan_scene_max_sources(void) { return SC_MAX_S; }
-
-extern "C" size_t cmgan_scene_workspace_bytes(const cmgan_handle* h, int B, int L, int Kmax, int S) {
-    (void)h;
-    return sc_shape_ok(B, L, Kmax, S) ? sc_layout(B, L, S).total : 0;
-}
-
-extern "C" int cmgan_scene(cmgan_handle* h, const float* clean, int B, int L, long long ld, const float* noise_bank,
-                           long long bank_len, const long long* noise_start, const long long* noise_len,
-                           const long long* noise_off, const float* snr_db, const float* src_bank, long long src_bank_len,
-                           int S, const int* n_src, const long long* src_start, const long long* src_len,
-                           const long long* src_off, const float* src_snr_db, const float* rir_bank, int R, int Kmax,
-                           const int* rir_index, const int* rir_len, const int* src_rir_index, const int* src_rir_len,
-                           float peak, int early, float* noisy, float* target, long long ld_out, double* g, double* p,
-                           double* ps, double* scale, void* ws, size_t ws_bytes, void* stream) {
-    // every argument is judged before the handle is, so that the errors below need no GPU (the message of a call
-    // without a handle is read with cmgan_last_error(NULL))
-    if (!clean || !noisy || !target || !g || !p || !ps || !scale) return fail(h, CMGAN_E_BADARG, "cmgan_scene: null pointer");
+// cmgan_scene, and cmgan_mix as its S = 0 case: `api` is the name of the entry point that was called, for the messages.
+// Every argument is judged before the handle is, so that the errors below need no GPU (the message of a call without a
+// handle is read with cmgan_last_error(NULL)).
+int mix_scene(const char* api, cmgan_handle* h, const float* clean, int B, int L, long long ld, const float* noise_bank,
+              long long bank_len, const long long* noise_start, const long long* noise_len, const long long* noise_off,
+              const float* snr_db, const float* src_bank, long long src_bank_len, int S, const int* n_src,
+              const long long* src_start, const long long* src_len, const long long* src_off, const float* src_snr_db,
+              const float* rir_bank, int R, int Kmax, const int* rir_index, const int* rir_len, const int* src_rir_index,
+              const int* src_rir_len, float peak, int early, float* noisy, float* target, long long ld_out, double* g,
+              double* p, double* ps, double* scale, void* ws, size_t ws_bytes, void* stream) {
+    if (!clean || !noisy || !target || !g || !p || !ps || !scale) return fail(h, CMGAN_E_BADARG, "%s: null pointer", api);
     if (noise_bank && (!noise_start || !noise_len || !noise_off || !snr_db))
-        return fail(h, CMGAN_E_BADARG, "cmgan_scene: a dry-noise bank needs noise_start, noise_len, noise_off and snr_db");
+        return fail(h, CMGAN_E_BADARG, "%s: a dry-noise bank needs noise_start, noise_len, noise_off and snr_db", api);
     if (S < 0 || S > SC_MAX_S)
-        return fail(h, CMGAN_E_BADARG, "cmgan_scene: 0 <= S <= %d located sources per row (S=%d)", SC_MAX_S, S);
+        return fail(h, CMGAN_E_BADARG, "%s: 0 <= S <= %d located sources per row (S=%d)", api, SC_MAX_S, S);
     if (S > 0 && (!src_bank || !n_src || !src_start || !src_len || !src_off || !src_snr_db))
-        return fail(h, CMGAN_E_BADARG, "cmgan_scene: S > 0 needs src_bank, n_src, src_start, src_len, src_off and src_snr_db");
+        return fail(h, CMGAN_E_BADARG, "%s: S > 0 needs src_bank, n_src, src_start, src_len, src_off and src_snr_db", api);
     if (rir_bank && (!rir_index || !rir_len))
-        return fail(h, CMGAN_E_BADARG, "cmgan_scene: a RIR bank needs rir_index and rir_len");
+        return fail(h, CMGAN_E_BADARG, "%s: a RIR bank needs rir_index and rir_len", api);
     if (rir_bank && S > 0 && (!src_rir_index || !src_rir_len))
-        return fail(h, CMGAN_E_BADARG, "cmgan_scene: a RIR bank with S > 0 needs src_rir_index and src_rir_len");
+        return fail(h, CMGAN_E_BADARG, "%s: a RIR bank with S > 0 needs src_rir_index and src_rir_len", api);
     if (((uintptr_t)clean | (uintptr_t)noise_bank | (uintptr_t)snr_db | (uintptr_t)src_bank | (uintptr_t)n_src
          | (uintptr_t)src_snr_db | (uintptr_t)rir_bank | (uintptr_t)rir_index | (uintptr_t)rir_len | (uintptr_t)src_rir_index
          | (uintptr_t)src_rir_len | (uintptr_t)noisy | (uintptr_t)target) & 3)
-        return fail(h, CMGAN_E_BADARG, "cmgan_scene: float32 / int32 buffers must be 4-byte aligned");
+        return fail(h, CMGAN_E_BADARG, "%s: float32 / int32 buffers must be 4-byte aligned", api);
     if (((uintptr_t)noise_start | (uintptr_t)noise_len | (uintptr_t)noise_off | (uintptr_t)src_start | (uintptr_t)src_len
          | (uintptr_t)src_off | (uintptr_t)g | (uintptr_t)p | (uintptr_t)ps | (uintptr_t)scale) & 7)
-        return fail(h, CMGAN_E_BADARG, "cmgan_scene: int64 / float64 buffers must be 8-byte aligned");
+        return fail(h, CMGAN_E_BADARG, "%s: int64 / float64 buffers must be 8-byte aligned", api);
     if (B <= 0 || B > 65535 || L < 1 || ld < L || ld_out < L)
-        return fail(h, CMGAN_E_BADARG, "cmgan_scene: need 0 < B <= 65535, L >= 1, ld >= L, ld_out >= L (B=%d L=%d ld=%lld "
-                    "ld_out=%lld)", B, L, ld, ld_out);
+        return fail(h, CMGAN_E_BADARG, "%s: need 0 < B <= 65535, L >= 1, ld >= L, ld_out >= L (B=%d L=%d ld=%lld "
+                    "ld_out=%lld)", api, B, L, ld, ld_out);
     if ((noise_bank && bank_len < 1) || (S > 0 && src_bank_len < 1))
-        return fail(h, CMGAN_E_BADARG, "cmgan_scene: a bank needs at least one sample (bank_len=%lld src_bank_len=%lld)",
+        return fail(h, CMGAN_E_BADARG, "%s: a bank needs at least one sample (bank_len=%lld src_bank_len=%lld)", api,
                     bank_len, src_bank_len);
     if (!(peak > 0.f) || !(peak <= 3.0e38f))
-        return fail(h, CMGAN_E_BADARG, "cmgan_scene: peak must be positive and finite (%g)", (double)peak);
-    if (early < -1) return fail(h, CMGAN_E_BADARG, "cmgan_scene: early must be -1 (dry target) or >= 0 (%d)", early);
+        return fail(h, CMGAN_E_BADARG, "%s: peak must be positive and finite (%g)", api, (double)peak);
+    if (early < -1) return fail(h, CMGAN_E_BADARG, "%s: early must be -1 (dry target) or >= 0 (%d)", api, early);
     if (!rir_bank) {
         R = 1;
         Kmax = 1;
     }
-    if (R < 1 || Kmax < 1) return fail(h, CMGAN_E_BADARG, "cmgan_scene: a RIR bank needs R >= 1 and Kmax >= 1 (R=%d Kmax=%d)", R, Kmax);
+    if (R < 1 || Kmax < 1) return fail(h, CMGAN_E_BADARG, "%s: a RIR bank needs R >= 1 and Kmax >= 1 (R=%d Kmax=%d)", api, R, Kmax);
     if (Kmax > MX_MAX_K)
-        return fail(h, CMGAN_E_UNSUPPORTED, "cmgan_scene: RIRs of up to %d taps are supported (Kmax=%d)", MX_MAX_K, Kmax);
+        return fail(h, CMGAN_E_UNSUPPORTED, "%s: RIRs of up to %d taps are supported (Kmax=%d)", api, MX_MAX_K, Kmax);
     if (L > MX_MAX_L)
-        return fail(h, CMGAN_E_UNSUPPORTED, "cmgan_scene: rows of up to %d samples are supported (L=%d)", MX_MAX_L, L);
-    if (!h) return fail(nullptr, CMGAN_E_BADARG, "cmgan_scene: null handle");
+        return fail(h, CMGAN_E_UNSUPPORTED, "%s: rows of up to %d samples are supported (L=%d)", api, MX_MAX_L, L);
+    if (!h) return fail(nullptr, CMGAN_E_BADARG, "%s: null handle", api);
     const SceneLayout l = sc_layout(B, L, S);
     if (int rc = check_ws(h, ws, ws_bytes, l.total)) return rc;
     const LaunchCtx ctx = begin(h, stream);
@@ -459,5 +561,50 @@ extern "C" int cmgan_scene(cmgan_handle* h, const float* clean, int B, int L, lo
     LAUNCH(ctx, "scene_vmax", scene_vmax<<<grid, MX_TPB, 0, s>>>(a));
     LAUNCH(ctx, "scene_scale", scene_scale<<<B, MX_TPB, 0, s>>>(a));
     LAUNCH(ctx, "scene_apply", scene_apply<<<grid, MX_TPB, 0, s>>>(a));
-    return check_launch(h, "scene");
+    return check_launch(h, api + 6);                         // "mix" / "scene": the name without its cmgan_
+}
+
+}  // namespace
+
+extern "C" int cmgan_mix_tile(void) { return MX_TILE; }
+
+extern "C" int cmgan_scene_max_sources(void) { return SC_MAX_S; }
+
+extern "C" size_t cmgan_scene_workspace_bytes(const cmgan_handle* h, int B, int L, int Kmax, int S) {
+    (void)h;
+    return sc_shape_ok(B, L, Kmax, S) ? sc_layout(B, L, S).total : 0;
+}
+
+extern "C" size_t cmgan_mix_workspace_bytes(const cmgan_handle* h, int B, int L, int Kmax) {
+    return cmgan_scene_workspace_bytes(h, B, L, Kmax, 0);
+}
+
+extern "C" int cmgan_scene(cmgan_handle* h, const float* clean, int B, int L, long long ld, const float* noise_bank,
+                           long long bank_len, const long long* noise_start, const long long* noise_len,
+                           const long long* noise_off, const float* snr_db, const float* src_bank, long long src_bank_len,
+                           int S, const int* n_src, const long long* src_start, const long long* src_len,
+                           const long long* src_off, const float* src_snr_db, const float* rir_bank, int R, int Kmax,
+                           const int* rir_index, const int* rir_len, const int* src_rir_index, const int* src_rir_len,
+                           float peak, int early, float* noisy, float* target, long long ld_out, double* g, double* p,
+                           double* ps, double* scale, void* ws, size_t ws_bytes, void* stream) {
+    return mix_scene("cmgan_scene", h, clean, B, L, ld, noise_bank, bank_len, noise_start, noise_len, noise_off, snr_db,
+                     src_bank, src_bank_len, S, n_src, src_start, src_len, src_off, src_snr_db, rir_bank, R, Kmax, rir_index,
+                     rir_len, src_rir_index, src_rir_len, peak, early, noisy, target, ld_out, g, p, ps, scale, ws, ws_bytes,
+                     stream);
+}
+
+// the scene without located sources whose dry noise and outputs must all be there; its [B, 1 + S] tables g and p are
+// this call's [B] vectors g and pn
+extern "C" int cmgan_mix(cmgan_handle* h, const float* clean, int B, int L, long long ld, const float* noise_bank,
+                         long long bank_len, const long long* noise_start, const long long* noise_len,
+                         const long long* noise_off, const float* rir_bank, int R, int Kmax, const int* rir_index,
+                         const int* rir_len, const float* snr_db, float peak, int early, float* noisy, float* target,
+                         long long ld_out, double* g, double* scale, double* ps, double* pn, void* ws, size_t ws_bytes,
+                         void* stream) {
+    if (!clean || !noise_bank || !noise_start || !noise_len || !noise_off || !snr_db || !noisy || !target || !g || !scale
+        || !ps || !pn)
+        return fail(h, CMGAN_E_BADARG, "cmgan_mix: null pointer");
+    return mix_scene("cmgan_mix", h, clean, B, L, ld, noise_bank, bank_len, noise_start, noise_len, noise_off, snr_db,
+                     nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, rir_bank, R, Kmax, rir_index, rir_len, nullptr,
+                     nullptr, peak, early, noisy, target, ld_out, g, pn, ps, scale, ws, ws_bytes, stream);
 }

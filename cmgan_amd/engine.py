@@ -93,39 +93,14 @@ MIX_MAX_TAPS = 65536          # longest RIR of cmgan_mix
 
 def check_mix_args(device, clean, noise_bank, noise_start, noise_len, noise_off, snr_db, rir_bank=None, rir_index=None,
                    rir_len=None, peak: float = 0.99, early: int = -1):
-    """Argument rules of Engine.mix (shapes, dtypes, devices and host scalars; pure host code).  Returns (B, L, R, Kmax)."""
-    tensor_arg(clean, "clean", torch.float32, device, "[B, L] with B, L >= 1",
-               lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) >= 1)
-    B, L = clean.shape
-    if B > 65535:
-        raise ValueError(f"clean: at most 65535 rows, got {B}")
-    tensor_arg(noise_bank, "noise_bank", torch.float32, device, "a flat bank of >= 1 samples",
-               lambda t: t.dim() == 1 and t.numel() >= 1)
-    row = lambda t: tuple(t.shape) == (B,)
-    tensor_arg(noise_start, "noise_start", torch.int64, device, f"[{B}]", row)
-    tensor_arg(noise_len, "noise_len", torch.int64, device, f"[{B}]", row)
-    tensor_arg(noise_off, "noise_off", torch.int64, device, f"[{B}]", row)
-    tensor_arg(snr_db, "snr_db", torch.float32, device, f"[{B}]", row)
-    R, Kmax = 0, 0
-    if rir_bank is None:
-        if rir_index is not None or rir_len is not None:
-            raise ValueError("rir_index / rir_len given without a rir_bank")
-    else:
-        tensor_arg(rir_bank, "rir_bank", torch.float32, device, "[R, Kmax] with R, Kmax >= 1",
-             lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) >= 1)
-        R, Kmax = rir_bank.shape
-        if Kmax > MIX_MAX_TAPS:
-            raise ValueError(f"rir_bank: RIRs of up to {MIX_MAX_TAPS} taps are supported, got Kmax = {Kmax}")
-        if rir_index is None or rir_len is None:
-            raise ValueError("a rir_bank needs rir_index and rir_len")
-        tensor_arg(rir_index, "rir_index", torch.int32, device, f"[{B}]", row)
-        tensor_arg(rir_len, "rir_len", torch.int32, device, f"[{B}]", row)
-    peak = float(peak)
-    if not (peak > 0.0 and peak < float("inf")):
-        raise ValueError(f"peak must be positive and finite, got {peak}")
-    if int(early) != early or early < -1:
-        raise ValueError(f"early must be -1 (dry target) or a sample count >= 0, got {early}")
-    return B, L, R, Kmax
+    """Argument rules of Engine.mix: those of Engine.scene (check_scene_args) without located sources and with a dry
+    noise that must be there.  Returns (B, L, R, Kmax)."""
+    for name, t in (("noise_bank", noise_bank), ("noise_start", noise_start), ("noise_len", noise_len),
+                    ("noise_off", noise_off), ("snr_db", snr_db)):
+        if t is None:
+            raise TypeError(f"{name}: expected a torch.Tensor, got NoneType")
+    return check_scene_args(device, clean, noise_bank, noise_start, noise_len, noise_off, snr_db, rir_bank=rir_bank,
+                            rir_index=rir_index, rir_len=rir_len, peak=peak, early=early)[:4]
 
 
 class SceneInfo(NamedTuple):
@@ -245,7 +220,7 @@ def check_rir_args(device, rooms, n_taps, K, n_images, fs=16000, c: float = 343.
     c = float(c)
     if not (c > 0.0 and c < float("inf")):
         raise ValueError(f"c must be positive and finite, got {c}")
-    if int(tw) != tw or not 1 <= tw <= RIR_MAX_TW:
+    if not _whole_in(tw, 1, RIR_MAX_TW, allow_bool=True):
         raise ValueError(f"tw must be a half-width in [1, {RIR_MAX_TW}] samples, got {tw}")
     if out is not None:
         try:
@@ -255,6 +230,46 @@ def check_rir_args(device, rooms, n_taps, K, n_images, fs=16000, c: float = 343.
         tensor_arg(rir, "out[0]", torch.float32, device, f"[{R}, {int(K)}]", lambda t: tuple(t.shape) == (R, int(K)))
         tensor_arg(length, "out[1]", torch.int32, device, f"[{R}]", lambda t: tuple(t.shape) == (R,))
     return R, int(K), N
+
+
+def _row_stride_ok(t, B: int, L: int) -> bool:
+    return t.stride(1) == 1 and (B == 1 or t.stride(0) >= L)
+
+
+def _row_batch(device, wav, max_L: Optional[int] = None):
+    """The rule for the batch of the augmentation calls: wav is a float32 [B, L] tensor of at most 65535 rows (of at most
+    max_L samples), each contiguous and at least L from the next.  Returns (B, L)."""
+    tensor_arg(wav, "wav", torch.float32, device, "[B, L] with B, L >= 1",
+               lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) >= 1, contiguous=False)     # (its own stride rule below)
+    B, L = wav.shape
+    if B > 65535:
+        raise ValueError(f"wav: at most 65535 rows, got {B}")
+    if max_L is not None and L > max_L:
+        raise ValueError(f"wav: rows of up to {max_L} samples are supported, got {L}")
+    if not _row_stride_ok(wav, B, L):
+        raise ValueError(f"wav: rows must be contiguous and at least L apart, got strides {tuple(wav.stride())}")
+    return B, L
+
+
+def _whole_in(v, lo: int, hi: int, allow_bool: bool = False) -> bool:
+    """Whether the host scalar v is a whole number in [lo, hi]; a bool is none unless allowed."""
+    return (allow_bool or not isinstance(v, bool)) and int(v) == v and lo <= v <= hi
+
+
+def _out_len(device, B: int, n_out, out):
+    """The n_out / out pair of Engine.warp and Engine.stretch: n_out a length or None, out a float32 [B, N] tensor of such
+    rows that agrees with it, or None.  Returns N, None when neither says it."""
+    if n_out is not None and not _whole_in(n_out, 1, 2 ** 31 - 1):
+        raise ValueError(f"n_out must be an output length in [1, 2^31 - 1] or None, got {n_out}")
+    N = None if n_out is None else int(n_out)
+    if out is not None:
+        tensor_arg(out, "out", torch.float32, device, f"[{B}, N]" if N is None else f"[{B}, {N}]",
+                   lambda t: t.dim() == 2 and t.size(0) == B and t.size(1) >= 1 and (N is None or t.size(1) == N),
+                   contiguous=False)
+        N = int(out.size(1))
+        if not _row_stride_ok(out, B, N):
+            raise ValueError(f"out: rows must be contiguous and at least N apart, got strides {tuple(out.stride())}")
+    return N
 
 
 class SpeechLevel(NamedTuple):
@@ -282,18 +297,10 @@ def level_workspace_bytes(B: int, L: int) -> int:
 
 def check_level_args(device, wav, lengths=None, fs=16000):
     """Argument rules of Engine.speech_level (shapes, dtypes, devices and host scalars; pure host code).  Returns (B, L)."""
-    tensor_arg(wav, "wav", torch.float32, device, "[B, L] with B, L >= 1",
-               lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) >= 1, contiguous=False)     # (its own stride rule below)
-    B, L = wav.shape
-    if B > 65535:
-        raise ValueError(f"wav: at most 65535 rows, got {B}")
-    if L > LEVEL_MAX_L:
-        raise ValueError(f"wav: rows of up to {LEVEL_MAX_L} samples are supported, got {L}")
-    if wav.stride(1) != 1 or (B > 1 and wav.stride(0) < L):
-        raise ValueError(f"wav: rows must be contiguous and at least L apart, got strides {tuple(wav.stride())}")
+    B, L = _row_batch(device, wav, LEVEL_MAX_L)
     if lengths is not None:
         tensor_arg(lengths, "lengths", torch.int32, device, f"[{B}]", lambda t: tuple(t.shape) == (B,))
-    if isinstance(fs, bool) or int(fs) != fs or not LEVEL_FS[0] <= fs <= LEVEL_FS[1]:
+    if not _whole_in(fs, *LEVEL_FS):
         raise ValueError(f"fs must be a sample rate in [{LEVEL_FS[0]}, {LEVEL_FS[1]}] Hz, got {fs}")
     return B, L
 
@@ -315,21 +322,9 @@ def channel_workspace_bytes(B: int, L: int, S: int) -> int:
     return up(B * 4) + up(B * 17 * N * N * 8) + 2 * up(B * nt * N * 8)
 
 
-def _row_stride_ok(t, B: int, L: int) -> bool:
-    return t.stride(1) == 1 and (B == 1 or t.stride(0) >= L)
-
-
 def check_channel_args(device, wav, sos, n_sections=None, clip=None, lengths=None, out=None):
     """Argument rules of Engine.channel (shapes, dtypes and devices; pure host code).  Returns (B, L, S)."""
-    tensor_arg(wav, "wav", torch.float32, device, "[B, L] with B, L >= 1",
-               lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) >= 1, contiguous=False)     # (its own stride rule below)
-    B, L = wav.shape
-    if B > 65535:
-        raise ValueError(f"wav: at most 65535 rows, got {B}")
-    if L > CHANNEL_MAX_L:
-        raise ValueError(f"wav: rows of up to {CHANNEL_MAX_L} samples are supported, got {L}")
-    if not _row_stride_ok(wav, B, L):
-        raise ValueError(f"wav: rows must be contiguous and at least L apart, got strides {tuple(wav.stride())}")
+    B, L = _row_batch(device, wav, CHANNEL_MAX_L)
     tensor_arg(sos, "sos", torch.float64, device, f"[{B}, S, 6] with 1 <= S <= {CHANNEL_MAX_SECTIONS}",
                lambda t: t.dim() == 3 and t.size(0) == B and 1 <= t.size(1) <= CHANNEL_MAX_SECTIONS and t.size(2) == 6)
     row = lambda t: tuple(t.shape) == (B,)
@@ -357,32 +352,16 @@ WARP_ROLLOFF = (0.5, 1.0)     # the cutoff as a fraction of the lower Nyquist ra
 def check_warp_args(device, wav, rate, n_out=None, lengths=None, zeros=24, rolloff=0.95, out=None):
     """Argument rules of Engine.warp (shapes, dtypes, devices and host scalars; pure host code).  Returns (B, L, N); N is
     None when neither n_out nor out says it (Engine.warp then takes cmgan_warp_out_len(L, 1 / 4))."""
-    tensor_arg(wav, "wav", torch.float32, device, "[B, L] with B, L >= 1",
-               lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) >= 1, contiguous=False)     # (its own stride rule below)
-    B, L = wav.shape
-    if B > 65535:
-        raise ValueError(f"wav: at most 65535 rows, got {B}")
-    if not _row_stride_ok(wav, B, L):
-        raise ValueError(f"wav: rows must be contiguous and at least L apart, got strides {tuple(wav.stride())}")
+    B, L = _row_batch(device, wav)
     row = lambda t: tuple(t.shape) == (B,)
     tensor_arg(rate, "rate", torch.float64, device, f"[{B}]", row)
     if lengths is not None:
         tensor_arg(lengths, "lengths", torch.int32, device, f"[{B}]", row)
-    if n_out is not None and (isinstance(n_out, bool) or int(n_out) != n_out or not 1 <= n_out <= 2 ** 31 - 1):
-        raise ValueError(f"n_out must be an output length in [1, 2^31 - 1] or None, got {n_out}")
-    if isinstance(zeros, bool) or int(zeros) != zeros or not WARP_ZEROS[0] <= zeros <= WARP_ZEROS[1]:
+    if not _whole_in(zeros, *WARP_ZEROS):
         raise ValueError(f"zeros must be a whole number in [{WARP_ZEROS[0]}, {WARP_ZEROS[1]}], got {zeros}")
     if isinstance(rolloff, bool) or not WARP_ROLLOFF[0] <= float(rolloff) <= WARP_ROLLOFF[1]:
         raise ValueError(f"rolloff must lie in [{WARP_ROLLOFF[0]}, {WARP_ROLLOFF[1]}], got {rolloff}")
-    N = None if n_out is None else int(n_out)
-    if out is not None:
-        tensor_arg(out, "out", torch.float32, device, f"[{B}, N]" if N is None else f"[{B}, {N}]",
-                   lambda t: t.dim() == 2 and t.size(0) == B and t.size(1) >= 1 and (N is None or t.size(1) == N),
-                   contiguous=False)
-        N = int(out.size(1))
-        if not _row_stride_ok(out, B, N):
-            raise ValueError(f"out: rows must be contiguous and at least N apart, got strides {tuple(out.stride())}")
-    return B, L, N
+    return B, L, _out_len(device, B, n_out, out)
 
 
 STRETCH_HOP = (16, 1024)      # samples per frame of cmgan_stretch (1024 = cmgan_stretch_max_hop())
@@ -393,45 +372,27 @@ PITCH_FACTOR = (0.5, 2.0)     # frequency ratios of Engine.pitch_shift: an octav
 def check_stretch_args(device, wav, rate, n_out=None, lengths=None, hop=256, search=160, out=None):
     """Argument rules of Engine.stretch (shapes, dtypes, devices and host scalars; pure host code).  Returns (B, L, N); N
     is None when neither n_out nor out says it (Engine.stretch then takes cmgan_warp_out_len(L, 1 / 4))."""
-    tensor_arg(wav, "wav", torch.float32, device, "[B, L] with B, L >= 1",
-               lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) >= 1, contiguous=False)     # (its own stride rule below)
-    B, L = wav.shape
-    if B > 65535:
-        raise ValueError(f"wav: at most 65535 rows, got {B}")
-    if not _row_stride_ok(wav, B, L):
-        raise ValueError(f"wav: rows must be contiguous and at least L apart, got strides {tuple(wav.stride())}")
+    B, L = _row_batch(device, wav)
     row = lambda t: tuple(t.shape) == (B,)
     tensor_arg(rate, "rate", torch.float64, device, f"[{B}]", row)
     if lengths is not None:
         tensor_arg(lengths, "lengths", torch.int32, device, f"[{B}]", row)
-    if n_out is not None and (isinstance(n_out, bool) or int(n_out) != n_out or not 1 <= n_out <= 2 ** 31 - 1):
-        raise ValueError(f"n_out must be an output length in [1, 2^31 - 1] or None, got {n_out}")
-    if isinstance(hop, bool) or int(hop) != hop or not STRETCH_HOP[0] <= hop <= STRETCH_HOP[1]:
+    if not _whole_in(hop, *STRETCH_HOP):
         raise ValueError(f"hop must be a whole number in [{STRETCH_HOP[0]}, {STRETCH_HOP[1]}], got {hop}")
-    if isinstance(search, bool) or int(search) != search or not STRETCH_SEARCH[0] <= search <= STRETCH_SEARCH[1]:
+    if not _whole_in(search, *STRETCH_SEARCH):
         raise ValueError(f"search must be a whole number in [{STRETCH_SEARCH[0]}, {STRETCH_SEARCH[1]}], got {search}")
-    N = None if n_out is None else int(n_out)
-    if out is not None:
-        tensor_arg(out, "out", torch.float32, device, f"[{B}, N]" if N is None else f"[{B}, {N}]",
-                   lambda t: t.dim() == 2 and t.size(0) == B and t.size(1) >= 1 and (N is None or t.size(1) == N),
-                   contiguous=False)
-        N = int(out.size(1))
-        if not _row_stride_ok(out, B, N):
-            raise ValueError(f"out: rows must be contiguous and at least N apart, got strides {tuple(out.stride())}")
-    return B, L, N
+    return B, L, _out_len(device, B, n_out, out)
 
 
 def check_pitch_args(device, wav, factor, n_out=None, hop=256, search=160, zeros=24, rolloff=0.95):
     """Argument rules of Engine.pitch_shift, all judged before its first launch: those of Engine.stretch and Engine.warp,
     with `factor` a float64 [B] device tensor (its VALUES are judged on the device: a row outside [1/2, 2] comes out as
     zeros).  Returns (B, L)."""
-    tensor_arg(wav, "wav", torch.float32, device, "[B, L] with B, L >= 1",
-               lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) >= 1, contiguous=False)
-    B = wav.size(0)
+    B, L = _row_batch(device, wav)
     tensor_arg(factor, "factor", torch.float64, device, f"[{B}]", lambda t: tuple(t.shape) == (B,))
     check_stretch_args(device, wav, factor, None, None, hop, search)
     check_warp_args(device, wav, factor, n_out, None, zeros, rolloff)
-    return B, int(wav.size(1))
+    return B, L
 
 
 def metric_frames(L: int, fs: int):
@@ -1218,6 +1179,13 @@ class Engine:
         return (out, st) if status else out
 
     # ---- speed perturbation ---------------------------------------------------------
+    def _default_out_len(self, L: int) -> int:
+        """The output length of warp and stretch when the caller gives none: room for the slowest valid rate."""
+        N = int(self.lib.cmgan_warp_out_len(L, 1.0 / WARP_MAX_RATE))
+        if N > 2 ** 31 - 1:
+            raise ValueError(f"wav: rows of {L} samples need n_out; the default, {N}, is beyond 2^31 - 1")
+        return N
+
     @_on_device
     def warp(self, wav: torch.Tensor, rate: torch.Tensor, n_out: Optional[int] = None, lengths: Optional[torch.Tensor] = None,
              zeros: int = 24, rolloff: float = 0.95, out: Optional[torch.Tensor] = None, info: bool = False):
@@ -1238,9 +1206,7 @@ class Engine:
         Bit-reproducible, row-independent, one launch, no workspace, no synchronisation, graph-capturable."""
         B, L, N = check_warp_args(self.device, wav, rate, n_out, lengths, zeros, rolloff, out)
         if N is None:
-            N = int(self.lib.cmgan_warp_out_len(L, 1.0 / WARP_MAX_RATE))
-            if N > 2 ** 31 - 1:
-                raise ValueError(f"wav: rows of {L} samples need n_out; the default, {N}, is beyond 2^31 - 1")
+            N = self._default_out_len(L)
         if out is None:
             out = torch.empty(B, N, dtype=torch.float32, device=self.device)
         n = torch.empty(B, dtype=torch.int32, device=self.device) if info else None
@@ -1274,9 +1240,7 @@ class Engine:
         graph-capturable."""
         B, L, N = check_stretch_args(self.device, wav, rate, n_out, lengths, hop, search, out)
         if N is None:
-            N = int(self.lib.cmgan_warp_out_len(L, 1.0 / WARP_MAX_RATE))
-            if N > 2 ** 31 - 1:
-                raise ValueError(f"wav: rows of {L} samples need n_out; the default, {N}, is beyond 2^31 - 1")
+            N = self._default_out_len(L)
         if out is None:
             out = torch.empty(B, N, dtype=torch.float32, device=self.device)
         n = st = pos = srch = None

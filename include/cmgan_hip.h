@@ -649,7 +649,8 @@ int cmgan_resample(cmgan_handle* h, const float* x_dev, int B, int n_buf, long l
  * [0, bank_len) counts as silence, rir_index is clamped to [0, R) and rir_len to [1, Kmax]; noise_off may be any int64.
  * Workspace: cmgan_mix_workspace_bytes (h may be NULL; 0 for an unsupported shape; non-decreasing in B, L and Kmax),
  * 256-byte aligned; it holds the float64 speech and target rows between the launches.  Six launches (five without a
- * bank), no synchronisation, no allocation; graph-capturable, and a replay reads the tables' current contents.          */
+ * bank), no synchronisation, no allocation; graph-capturable, and a replay reads the tables' current contents.  The call
+ * is cmgan_scene (below) without located sources: the same checks, kernels and workspace layout, under this name.       */
 int cmgan_mix_tile(void);
 size_t cmgan_mix_workspace_bytes(const cmgan_handle* h, int B, int L, int Kmax);
 int cmgan_mix(cmgan_handle* h, const float* clean_dev, int B, int L, long long ld, const float* noise_bank_dev,
@@ -680,7 +681,9 @@ int cmgan_mix(cmgan_handle* h, const float* clean_dev, int B, int L, long long l
  * Arithmetic, reductions and guarantees are those of cmgan_mix: float64 products and sums, taps in ascending k, one rounding
  * to float32; two-stage reductions in a fixed order that depends on L alone; no atomics.  Row b's outputs depend neither
  * on B, nor on the other rows or their n_src, nor on the table columns beyond S_b, which are never read.  With S == 0 and a
- * dry-noise bank every output has the bits of cmgan_mix.  Untrusted tables as there: a source segment that is empty or
+ * dry-noise bank every output has the bits of cmgan_mix: cmgan_mix IS that call (one implementation; it only insists on
+ * the dry noise and on all four of its [B] outputs, and cmgan_mix_workspace_bytes(h, B, L, Kmax) equals
+ * cmgan_scene_workspace_bytes(h, B, L, Kmax, 0)).  Untrusted tables as there: a source segment that is empty or
  * leaves [0, src_bank_len) is silence (c_j = 0, P_j = 0, g_j = 0), RIR indices are clamped to [0, R), lengths to [1, Kmax];
  * offsets may be any int64.
  * Method.  The source index is a grid axis of the convolution kernel: slice 0 is the talker's convolution of cmgan_mix,

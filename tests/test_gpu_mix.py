@@ -1,4 +1,4 @@
-"""Dynamic mixing on the GPU (cmgan_amd/csrc/mix.hip; include/cmgan_hip.h, "Dynamic mixing"): Engine.mix against the
+"""Dynamic mixing on the GPU (cmgan_amd/csrc/scene.hip; include/cmgan_hip.h, "Dynamic mixing"): Engine.mix against the
 float64 numpy model of tests/mix_model.py over the kernels' tile, chunk and length edges, the edge semantics of gain and
 peak guard, bit-reproducibility and row independence, hipGraph replay with the device-side draws changed in place, and
 the front end (DynamicMixer, MixingLoader) against the model fed with the same draws."""

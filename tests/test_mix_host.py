@@ -1,4 +1,4 @@
-"""CPU side of dynamic mixing (cmgan_amd/csrc/mix.hip; include/cmgan_hip.h, "Dynamic mixing"): the float64 model the GPU
+"""CPU side of dynamic mixing (cmgan_amd/csrc/scene.hip; include/cmgan_hip.h, "Dynamic mixing"): the float64 model the GPU
 tests compare the kernels with (tests/mix_model.py) against scipy and against its own definition, the workspace formula,
 and every argument error of cmgan_mix and Engine.mix, all of which are judged before a handle or a GPU is needed."""
 import ctypes
@@ -120,9 +120,14 @@ def test_workspace_bytes_monotone_and_rejects_unsupported_shapes():
         assert ws(4, 4000, K) >= max(prev, 1)
         prev = ws(4, 4000, K)
     assert ws(32, 32000, 8000) >= 2 * 32 * 32000 * 8             # the float64 speech and target rows
-    for B, L, K in [(0, 10, 1), (-1, 10, 1), (65536, 10, 1), (1, 0, 1), (1, -5, 1), (1, 10, 0), (1, 10, 65537),
-                    (1, 2 ** 31 - 1, 1)]:
+    rejected = [(0, 10, 1), (-1, 10, 1), (65536, 10, 1), (1, 0, 1), (1, -5, 1), (1, 10, 0), (1, 10, 65537), (1, 2 ** 31 - 1, 1)]
+    for B, L, K in rejected:
         assert ws(B, L, K) == 0, (B, L, K)
+    # a scene without located sources needs the same bytes, on every shape walked above and the rejected ones
+    walked = [(B, 4000, 100) for B in (1, 2, 5, 32, 65535)] + [(4, 4000, K) for K in (1, 2, 1000, 20000, 65536)] \
+        + [(4, L, 100) for L in (1, 2, tile - 1, tile, tile + 1, 2 * tile + 3, 32000, 10 ** 6)] + [(1, 1, 1), (32, 32000, 8000)]
+    for B, L, K in walked + rejected:
+        assert int(lib.cmgan_scene_workspace_bytes(None, B, L, K, 0)) == ws(B, L, K), (B, L, K)
 
 
 # ------------------------------------------------------------------ argument errors of the C ABI, without a handle
@@ -163,7 +168,7 @@ def _call(**over):
 def test_abi_argument_errors_without_gpu(over, code, text):
     rc, msg = _call(**over)
     assert rc == code, (rc, msg)
-    assert text in msg, msg
+    assert msg.startswith("cmgan_mix: ") and text in msg, msg
 
 
 # ------------------------------------------------------------------ argument errors of Engine.mix, on CPU tensors

@@ -12,7 +12,11 @@ Per case: device ms per Engine.scene call and per Engine.mix call on the same cl
 (HIP events around `iters` calls after a warm-up; the two are measured alternately, `repeats` times each, and the median
 and the spread are reported), their ratio, the seconds the host takes per clip for the same scene in float64 (fftconvolve
 of the clip and of each looped segment, powers, gains, sum and peak guard; timed on the first --host-clips clips), and the
-largest difference of those clips' noisy rows from the host's, in float32 ulps of the row's peak."""
+largest difference of those clips' noisy rows from the host's, in float32 ulps of the row's peak.
+
+cmgan_mix is the S = 0 case of cmgan_scene and runs the same kernels (cmgan_amd/csrc/scene.hip), so the S = 0 row times
+one code path twice and its `same_bits_as_mix` holds by construction; profiles/r15_scene_bench.json was measured when
+Engine.mix still had kernels of its own."""
 import argparse
 import json
 import os
