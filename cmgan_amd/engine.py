@@ -256,6 +256,17 @@ def _whole_in(v, lo: int, hi: int, allow_bool: bool = False) -> bool:
     return (allow_bool or not isinstance(v, bool)) and int(v) == v and lo <= v <= hi
 
 
+def _rate_batch(device, wav, rate, lengths):
+    """The arguments Engine.warp and Engine.stretch share: the row batch, a float64 [B] rate and int32 [B] lengths or None.
+    Returns (B, L)."""
+    B, L = _row_batch(device, wav)
+    row = lambda t: tuple(t.shape) == (B,)
+    tensor_arg(rate, "rate", torch.float64, device, f"[{B}]", row)
+    if lengths is not None:
+        tensor_arg(lengths, "lengths", torch.int32, device, f"[{B}]", row)
+    return B, L
+
+
 def _out_len(device, B: int, n_out, out):
     """The n_out / out pair of Engine.warp and Engine.stretch: n_out a length or None, out a float32 [B, N] tensor of such
     rows that agrees with it, or None.  Returns N, None when neither says it."""
@@ -352,11 +363,7 @@ WARP_ROLLOFF = (0.5, 1.0)     # the cutoff as a fraction of the lower Nyquist ra
 def check_warp_args(device, wav, rate, n_out=None, lengths=None, zeros=24, rolloff=0.95, out=None):
     """Argument rules of Engine.warp (shapes, dtypes, devices and host scalars; pure host code).  Returns (B, L, N); N is
     None when neither n_out nor out says it (Engine.warp then takes cmgan_warp_out_len(L, 1 / 4))."""
-    B, L = _row_batch(device, wav)
-    row = lambda t: tuple(t.shape) == (B,)
-    tensor_arg(rate, "rate", torch.float64, device, f"[{B}]", row)
-    if lengths is not None:
-        tensor_arg(lengths, "lengths", torch.int32, device, f"[{B}]", row)
+    B, L = _rate_batch(device, wav, rate, lengths)
     if not _whole_in(zeros, *WARP_ZEROS):
         raise ValueError(f"zeros must be a whole number in [{WARP_ZEROS[0]}, {WARP_ZEROS[1]}], got {zeros}")
     if isinstance(rolloff, bool) or not WARP_ROLLOFF[0] <= float(rolloff) <= WARP_ROLLOFF[1]:
@@ -372,11 +379,7 @@ PITCH_FACTOR = (0.5, 2.0)     # frequency ratios of Engine.pitch_shift: an octav
 def check_stretch_args(device, wav, rate, n_out=None, lengths=None, hop=256, search=160, out=None):
     """Argument rules of Engine.stretch (shapes, dtypes, devices and host scalars; pure host code).  Returns (B, L, N); N
     is None when neither n_out nor out says it (Engine.stretch then takes cmgan_warp_out_len(L, 1 / 4))."""
-    B, L = _row_batch(device, wav)
-    row = lambda t: tuple(t.shape) == (B,)
-    tensor_arg(rate, "rate", torch.float64, device, f"[{B}]", row)
-    if lengths is not None:
-        tensor_arg(lengths, "lengths", torch.int32, device, f"[{B}]", row)
+    B, L = _rate_batch(device, wav, rate, lengths)
     if not _whole_in(hop, *STRETCH_HOP):
         raise ValueError(f"hop must be a whole number in [{STRETCH_HOP[0]}, {STRETCH_HOP[1]}], got {hop}")
     if not _whole_in(search, *STRETCH_SEARCH):
@@ -1179,12 +1182,16 @@ class Engine:
         return (out, st) if status else out
 
     # ---- speed perturbation ---------------------------------------------------------
-    def _default_out_len(self, L: int) -> int:
-        """The output length of warp and stretch when the caller gives none: room for the slowest valid rate."""
-        N = int(self.lib.cmgan_warp_out_len(L, 1.0 / WARP_MAX_RATE))
-        if N > 2 ** 31 - 1:
-            raise ValueError(f"wav: rows of {L} samples need n_out; the default, {N}, is beyond 2^31 - 1")
-        return N
+    def _out_and_info(self, B: int, L: int, N: Optional[int], out: Optional[torch.Tensor], info: bool, n_info: int):
+        """What warp and stretch make of checked arguments: (N, out, n_info int32 [B] tensors - None without `info`).  N
+        defaults to room for the slowest valid rate, `out` to a new float32 [B, N] tensor."""
+        if N is None:
+            N = int(self.lib.cmgan_warp_out_len(L, 1.0 / WARP_MAX_RATE))
+            if N > 2 ** 31 - 1:
+                raise ValueError(f"wav: rows of {L} samples need n_out; the default, {N}, is beyond 2^31 - 1")
+        if out is None:
+            out = torch.empty(B, N, dtype=torch.float32, device=self.device)
+        return N, out, [torch.empty(B, dtype=torch.int32, device=self.device) if info else None for _ in range(n_info)]
 
     @_on_device
     def warp(self, wav: torch.Tensor, rate: torch.Tensor, n_out: Optional[int] = None, lengths: Optional[torch.Tensor] = None,
@@ -1205,12 +1212,7 @@ class Engine:
         not a finite number in [1 / 4, 4], a length outside [0, L]) and come out as zeros with out_len 0.
         Bit-reproducible, row-independent, one launch, no workspace, no synchronisation, graph-capturable."""
         B, L, N = check_warp_args(self.device, wav, rate, n_out, lengths, zeros, rolloff, out)
-        if N is None:
-            N = self._default_out_len(L)
-        if out is None:
-            out = torch.empty(B, N, dtype=torch.float32, device=self.device)
-        n = torch.empty(B, dtype=torch.int32, device=self.device) if info else None
-        st = torch.empty(B, dtype=torch.int32, device=self.device) if info else None
+        N, out, (n, st) = self._out_and_info(B, L, N, out, info, 2)
         self._call("cmgan_warp", wav, B, L, wav.stride(0) if B > 1 else L, lengths, rate, int(zeros), float(rolloff), out, N,
                    out.stride(0) if B > 1 else N, n, st)
         return (out, n, st) if info else out
@@ -1239,14 +1241,8 @@ class Engine:
         Bit-reproducible, row-independent, one launch (one block per row), no workspace, no synchronisation,
         graph-capturable."""
         B, L, N = check_stretch_args(self.device, wav, rate, n_out, lengths, hop, search, out)
-        if N is None:
-            N = self._default_out_len(L)
-        if out is None:
-            out = torch.empty(B, N, dtype=torch.float32, device=self.device)
-        n = st = pos = srch = None
-        if info:
-            n, st, srch = (torch.empty(B, dtype=torch.int32, device=self.device) for _ in range(3))
-            pos = torch.empty(B, -(-N // int(hop)), dtype=torch.int32, device=self.device)
+        N, out, (n, st, srch) = self._out_and_info(B, L, N, out, info, 3)
+        pos = torch.empty(B, -(-N // int(hop)), dtype=torch.int32, device=self.device) if info else None
         self._call("cmgan_stretch", wav, B, L, wav.stride(0) if B > 1 else L, lengths, rate, int(hop), int(search), out, N,
                    out.stride(0) if B > 1 else N, n, st, pos, srch)
         return (out, n, st, pos, srch) if info else out

@@ -38,6 +38,7 @@ import torch
 import torch.utils.data
 
 from .data import _natural_key, fit_length, read_wav
+from .engine import STRETCH_HOP, STRETCH_SEARCH, _whole_in
 
 __all__ = ["NoiseBank", "RirBank", "RoomSampler", "sabine_beta", "DynamicMixer", "MixingLoader", "CleanDataset",
            "clean_only", "Draw", "SceneDraw", "tile", "ChannelSampler", "biquad_peaking", "biquad_low_shelf", "biquad_high_shelf",
@@ -60,11 +61,38 @@ def warp_len(L: int, rate: float) -> int:
 PITCH_RANGE = 12.0            # semitones either way: the factors 1/2 .. 2 of Engine.pitch_shift
 
 
-def _pair(value, name: str, what: str):
+# ---- option parsing: every "(low, high)", probability and whole number of the samplers and the mixer goes through these
+def _pair(name: str, value, low, high, wording: str, form: Optional[str] = "(low, high)", closed: bool = True,
+          echo: bool = False, whole: bool = False):
+    """The option `name` = (low, high) as two floats with low <= lo <= hi <= high (closed=False: low < lo and hi < high);
+    whole=True: exactly two ints (no bool) instead.  What is no such pair is refused as "`name` must be `form`" - with
+    form=None by the conversion's own error - and a pair outside the bounds as "`name` must be `wording`", naming the
+    value as given or, with echo=True, as parsed."""
     try:
-        return float(value[0]), float(value[1])
+        lo, hi = value if whole else (float(value[0]), float(value[1]))
     except (TypeError, ValueError, IndexError):
-        raise ValueError(f"{name} must be None or (low, high){what}, got {value}") from None
+        if form is None:
+            raise
+        raise ValueError(f"{name} must be {form}, got {value}") from None
+    ok = not whole or not any(isinstance(v, bool) or not isinstance(v, int) for v in (lo, hi))
+    if not (ok and (low <= lo <= hi <= high if closed else low < lo <= hi < high)):
+        raise ValueError(f"{name} must be {wording}, got {(lo, hi) if echo else value}")
+    return (int(lo), int(hi)) if whole else (lo, hi)
+
+
+def _positive_pair(name: str, value, form: Optional[str] = "(low, high)"):
+    return _pair(name, value, 0.0, math.inf, "(low, high) with 0 < low <= high", form, closed=False)
+
+
+def _rate_pair(name: str, value):
+    lo, hi = SPEED_RANGE
+    return _pair(name, value, lo, hi, f"(low, high) with {lo} <= low <= high <= {hi}", "None or (low, high)", echo=True)
+
+
+def _probability(name: str, p, as_given: bool = False) -> float:
+    if not 0.0 <= (p if as_given else float(p)) <= 1.0:
+        raise ValueError(f"{name} must lie in [0, 1], got {p}")
+    return float(p)
 
 
 def _stretch_ranges(tempo=None, pitch=None, speed=None, p_tempo: float = 1.0, p_pitch: float = 1.0, p_speed: float = 1.0):
@@ -181,9 +209,7 @@ class RoomSampler:
             raise ValueError(f"dims must be ((Lx, Ly, Lz) low, (Lx, Ly, Lz) high), got {dims}") from None
         if len(lo) != 3 or len(hi) != 3 or not all(0.0 < a <= b < math.inf for a, b in zip(lo, hi)):
             raise ValueError(f"dims must be ((Lx, Ly, Lz) low, (Lx, Ly, Lz) high) with 0 < low <= high, got {dims}")
-        t_lo, t_hi = float(rt60[0]), float(rt60[1])
-        if not 0.0 < t_lo <= t_hi < math.inf:
-            raise ValueError(f"rt60 must be (low, high) with 0 < low <= high, got {rt60}")
+        t_lo, t_hi = _positive_pair("rt60", rt60, form=None)
         margin = float(margin)
         if not 0.0 <= margin < 0.5 * min(lo):
             raise ValueError(f"margin must lie in [0, {0.5 * min(lo)}): half the smallest room size of {dims}, got {margin}")
@@ -297,16 +323,6 @@ def butter_lowpass_sos(order: int, fc, fs) -> torch.Tensor:
                         for k in range(order // 2)], dim=-2)
 
 
-def _range(name: str, v, lo_min: float = 0.0, what: str = "0 < low <= high"):
-    try:
-        lo, hi = float(v[0]), float(v[1])
-    except (TypeError, ValueError, IndexError):
-        raise ValueError(f"{name} must be (low, high), got {v}") from None
-    if not lo_min < lo <= hi < math.inf:
-        raise ValueError(f"{name} must be (low, high) with {what}, got {v}")
-    return lo, hi
-
-
 class ChannelSampler:
     """Random recording channels for Engine.channel: `draw(B, fs, device)` -> `(sos float64 [B, S, 6], n_sections int32
     [B], n_shared int32 [B], clip_rel float64 [B])`.
@@ -326,15 +342,13 @@ class ChannelSampler:
     def __init__(self, p_highpass: float = 0.5, highpass_hz=(20.0, 120.0), max_eq: int = 3, eq_hz=None, eq_db: float = 6.0,
                  eq_q=(0.5, 2.0), p_bandlimit: float = 0.2, bandlimit_hz=(3400.0, 3800.0), bandlimit_order: int = 8,
                  p_clip: float = 0.1, clip_rel=(0.3, 0.9), generator: Optional[torch.Generator] = None):
-        for name, p in (("p_highpass", p_highpass), ("p_bandlimit", p_bandlimit), ("p_clip", p_clip)):
-            if not 0.0 <= float(p) <= 1.0:
-                raise ValueError(f"{name} must lie in [0, 1], got {p}")
-        self.p_highpass, self.p_bandlimit, self.p_clip = float(p_highpass), float(p_bandlimit), float(p_clip)
-        self.highpass_hz = _range("highpass_hz", highpass_hz)
-        self.eq_hz = None if eq_hz is None else _range("eq_hz", eq_hz)
-        self.eq_q = _range("eq_q", eq_q)
-        self.bandlimit_hz = _range("bandlimit_hz", bandlimit_hz)
-        self.clip_rel = _range("clip_rel", clip_rel)
+        self.p_highpass, self.p_bandlimit, self.p_clip = (
+            _probability(name, p) for name, p in (("p_highpass", p_highpass), ("p_bandlimit", p_bandlimit), ("p_clip", p_clip)))
+        self.highpass_hz = _positive_pair("highpass_hz", highpass_hz)
+        self.eq_hz = None if eq_hz is None else _positive_pair("eq_hz", eq_hz)
+        self.eq_q = _positive_pair("eq_q", eq_q)
+        self.bandlimit_hz = _positive_pair("bandlimit_hz", bandlimit_hz)
+        self.clip_rel = _positive_pair("clip_rel", clip_rel)
         if isinstance(max_eq, bool) or int(max_eq) != max_eq or max_eq < 0:
             raise ValueError(f"max_eq must be a section count >= 0, got {max_eq}")
         eq_db = float(eq_db)
@@ -464,27 +478,16 @@ class StretchDraw(NamedTuple):
     warp_rate: Optional[torch.Tensor]
 
 
-class SceneDraw(NamedTuple):
-    """What a DynamicMixer(sources=...) drew for a batch: the fields of Draw, then the per-source arguments of Engine.scene,
-    [B] and [B, S] device tensors with S = the upper end of `sources`."""
-    noise_start: torch.Tensor
-    noise_len: torch.Tensor
-    noise_off: torch.Tensor
-    snr_db: torch.Tensor
-    rir_index: Optional[torch.Tensor]
-    rir_len: Optional[torch.Tensor]
-    rooms: Optional[torch.Tensor] = None
-    level_db: Optional[torch.Tensor] = None
-    channel: Optional[tuple] = None
-    speed: Optional[torch.Tensor] = None
-    n_src: Optional[torch.Tensor] = None          # int32 [B]: how many of the S columns a row uses
-    src_start: Optional[torch.Tensor] = None
-    src_len: Optional[torch.Tensor] = None
-    src_off: Optional[torch.Tensor] = None
-    src_snr_db: Optional[torch.Tensor] = None
-    src_rir_index: Optional[torch.Tensor] = None  # None without a rir_bank or rooms: the sources are dry
-    src_rir_len: Optional[torch.Tensor] = None
-    src_rooms: Optional[torch.Tensor] = None      # with rooms=...: the float64 [B, S, 15] tables of RoomSampler.draw_sources
+_SOURCE_FIELDS = (
+    "n_src",                                      # int32 [B]: how many of the S columns a row uses
+    "src_start", "src_len", "src_off", "src_snr_db",
+    "src_rir_index", "src_rir_len",               # None without a rir_bank or rooms: the sources are dry
+    "src_rooms",                                  # with rooms=...: the float64 [B, S, 15] tables of RoomSampler.draw_sources
+)
+SceneDraw = collections.namedtuple("SceneDraw", Draw._fields + _SOURCE_FIELDS,
+                                   defaults=(None,) * (len(Draw._field_defaults) + len(_SOURCE_FIELDS)))
+SceneDraw.__doc__ = """What a DynamicMixer(sources=...) drew for a batch: the fields of Draw, then the per-source arguments of
+Engine.scene, [B] and [B, S] device tensors with S = the upper end of `sources`."""
 
 
 class DynamicMixer:
@@ -578,19 +581,11 @@ class DynamicMixer:
                  source_snr_db=(0.0, 20.0), dry_noise: bool = True, tempo=None, p_tempo: float = 1.0, pitch=None,
                  p_pitch: float = 1.0, stretch_hop: int = 256, stretch_search: int = 160):
         if sources is not None:
-            try:
-                lo_n, hi_n = sources
-            except (TypeError, ValueError):
-                raise ValueError(f"sources must be None or (low, high), got {sources}") from None
-            if any(isinstance(v, bool) or not isinstance(v, int) for v in (lo_n, hi_n)) or not (0 <= lo_n <= hi_n and 1 <= hi_n <= 4):
-                raise ValueError(f"sources must be (low, high) whole numbers with 0 <= low <= high and 1 <= high <= 4, got {sources}")
-            sources = (int(lo_n), int(hi_n))
-            try:
-                source_snr_db = (float(source_snr_db[0]), float(source_snr_db[1]))
-            except (TypeError, ValueError, IndexError):
-                raise ValueError(f"source_snr_db must be (low, high), got {source_snr_db}") from None
-            if not source_snr_db[0] <= source_snr_db[1]:
-                raise ValueError(f"source_snr_db must be (low, high) with low <= high, got {source_snr_db}")
+            given, counts = sources, "(low, high) whole numbers with 0 <= low <= high and 1 <= high <= 4"
+            sources = _pair("sources", given, 0, 4, counts, "None or (low, high)", whole=True)
+            if sources[1] < 1:
+                raise ValueError(f"sources must be {counts}, got {given}")
+            source_snr_db = _pair("source_snr_db", source_snr_db, -math.inf, math.inf, "(low, high) with low <= high", echo=True)
             if source_bank is not None and source_bank.device != engine.device:
                 raise RuntimeError(f"source_bank is on {source_bank.device} but the engine is bound to {engine.device}")
         elif source_bank is not None:
@@ -599,34 +594,17 @@ class DynamicMixer:
             raise ValueError("dry_noise=False needs sources: the batch would hold no noise at all")
         self.sources, self.source_snr_db, self.dry_noise = sources, source_snr_db, bool(dry_noise)
         self.source_bank = source_bank if source_bank is not None else noise_bank
-        if speed is not None:
-            try:
-                speed = (float(speed[0]), float(speed[1]))
-            except (TypeError, ValueError, IndexError):
-                raise ValueError(f"speed must be None or (low, high), got {speed}") from None
-            if not SPEED_RANGE[0] <= speed[0] <= speed[1] <= SPEED_RANGE[1]:
-                raise ValueError(f"speed must be (low, high) with {SPEED_RANGE[0]} <= low <= high <= {SPEED_RANGE[1]}, got {speed}")
-        if not 0.0 <= float(p_speed) <= 1.0:
-            raise ValueError(f"p_speed must lie in [0, 1], got {p_speed}")
-        self.speed, self.p_speed = speed, float(p_speed)
-        self.speed_zeros, self.speed_rolloff = int(speed_zeros), float(speed_rolloff)
-        if tempo is not None:
-            tempo = _pair(tempo, "tempo", "")
-            if not SPEED_RANGE[0] <= tempo[0] <= tempo[1] <= SPEED_RANGE[1]:
-                raise ValueError(f"tempo must be (low, high) with {SPEED_RANGE[0]} <= low <= high <= {SPEED_RANGE[1]}, got {tempo}")
+        self.speed = speed = None if speed is None else _rate_pair("speed", speed)
+        self.p_speed = _probability("p_speed", p_speed)
+        self.speed_zeros, self.speed_rolloff = int(speed_zeros), float(speed_rolloff)       # Engine.warp judges them
+        self.tempo = tempo = None if tempo is None else _rate_pair("tempo", tempo)
         if pitch is not None:
-            pitch = _pair(pitch, "pitch", " in semitones")
-            if not -PITCH_RANGE <= pitch[0] <= pitch[1] <= PITCH_RANGE:
-                raise ValueError(f"pitch must be (low, high) semitones with {-PITCH_RANGE} <= low <= high <= {PITCH_RANGE}, "
-                                 f"got {pitch}")
-        for name, p in (("p_tempo", p_tempo), ("p_pitch", p_pitch)):
-            if not 0.0 <= float(p) <= 1.0:
-                raise ValueError(f"{name} must lie in [0, 1], got {p}")
-        if isinstance(stretch_hop, bool) or int(stretch_hop) != stretch_hop or not 16 <= stretch_hop <= 1024:
-            raise ValueError(f"stretch_hop must be a whole number in [16, 1024], got {stretch_hop}")
-        if isinstance(stretch_search, bool) or int(stretch_search) != stretch_search or not 0 <= stretch_search <= 1024:
-            raise ValueError(f"stretch_search must be a whole number in [0, 1024], got {stretch_search}")
-        self.tempo, self.p_tempo, self.pitch, self.p_pitch = tempo, float(p_tempo), pitch, float(p_pitch)
+            pitch = _pair("pitch", pitch, -PITCH_RANGE, PITCH_RANGE, f"(low, high) semitones with {-PITCH_RANGE} <= low <= high "
+                          f"<= {PITCH_RANGE}", "None or (low, high) in semitones", echo=True)
+        self.pitch, self.p_tempo, self.p_pitch = pitch, _probability("p_tempo", p_tempo), _probability("p_pitch", p_pitch)
+        for name, v, limits in (("stretch_hop", stretch_hop, STRETCH_HOP), ("stretch_search", stretch_search, STRETCH_SEARCH)):
+            if not _whole_in(v, *limits):
+                raise ValueError(f"{name} must be a whole number in [{limits[0]}, {limits[1]}], got {v}")
         self.stretch_hop, self.stretch_search = int(stretch_hop), int(stretch_search)
         self.last_stretch: Optional[StretchDraw] = None
         if tempo is not None or pitch is not None:
@@ -645,27 +623,19 @@ class DynamicMixer:
         if snr_on not in ("rms", "active"):
             raise ValueError(f"snr_on must be 'rms' or 'active', got {snr_on!r}")
         if level_db is not None:
-            try:
-                level_db = (float(level_db[0]), float(level_db[1]))
-            except (TypeError, ValueError, IndexError):
-                raise ValueError(f"level_db must be None or (low, high) in dBFS, got {level_db}") from None
-            if not level_db[0] <= level_db[1] < math.inf or level_db[0] == -math.inf:
-                raise ValueError(f"level_db must be (low, high) with finite low <= high, got {level_db}")
+            level_db = _pair("level_db", level_db, -math.inf, math.inf, "(low, high) with finite low <= high",
+                             "None or (low, high) in dBFS", closed=False, echo=True)
         if (snr_on == "active" or level_db is not None) and not 8000 <= int(sample_rate) <= 192000:
             raise ValueError(f"the speech level is measured at 8000 .. 192000 Hz, got sample_rate = {sample_rate}")
         self.snr_on, self.level_db, self.last_level = snr_on, level_db, None
-        lo, hi = float(snr_db[0]), float(snr_db[1])
-        if not lo <= hi:
-            raise ValueError(f"snr_db must be (low, high) with low <= high, got {snr_db}")
-        if not 0.0 <= p_reverb <= 1.0:
-            raise ValueError(f"p_reverb must lie in [0, 1], got {p_reverb}")
+        self.snr_db = _pair("snr_db", snr_db, -math.inf, math.inf, "(low, high) with low <= high", form=None)
+        self.p_reverb = _probability("p_reverb", p_reverb, as_given=True)
         if early_ms is not None and early_ms < 0:
             raise ValueError(f"early_ms must be >= 0 or None, got {early_ms}")
         for name, bank in (("noise_bank", noise_bank), ("rir_bank", rir_bank)):
             if bank is not None and bank.device != engine.device:
                 raise RuntimeError(f"{name} is on {bank.device} but the engine is bound to {engine.device}")
-        self.engine, self.noise_bank, self.snr_db, self.peak = engine, noise_bank, (lo, hi), float(peak)
-        self.p_reverb, self.generator = float(p_reverb), generator
+        self.engine, self.noise_bank, self.peak, self.generator = engine, noise_bank, float(peak), generator
         self.n_rirs = len(rir_bank) if rir_bank is not None else 0
         self.rir_bank = rir_bank.with_identity() if rir_bank is not None and p_reverb < 1.0 else rir_bank
         self.early = -1 if early_ms is None else int(round(early_ms * sample_rate / 1000.0))
@@ -683,64 +653,84 @@ class DynamicMixer:
                 raise ValueError(f"responses of {rir_seconds} s in rooms as small as {rooms.lo} need image ranges "
                                  f"{self.n_images}; up to 255 are supported")
 
-    def draw(self, B: int):
-        dev, gen, nb = self.engine.device, self.generator, self.noise_bank
-        item = torch.randint(0, len(nb), (B,), generator=gen, device=dev)
-        start, length = nb.start[item], nb.length[item]
-        u = torch.rand(B, dtype=torch.float64, generator=gen, device=dev)
-        off = torch.minimum((u * length).to(torch.int64), length - 1)
-        lo, hi = self.snr_db
-        snr = (lo + (hi - lo) * torch.rand(B, dtype=torch.float32, generator=gen, device=dev)).contiguous()
-        idx = rlen = None
+    # ---- the draws: one helper per kind, each a fixed sequence of calls on the mixer's generator --------------------
+    def _rand(self, *shape, dtype=torch.float64) -> torch.Tensor:
+        return torch.rand(*shape, dtype=dtype, generator=self.generator, device=self.engine.device)
+
+    def _randint(self, low: int, high: int, *shape) -> torch.Tensor:
+        return torch.randint(low, high, shape, generator=self.generator, device=self.engine.device)
+
+    def _draw_uniform(self, rng, *shape, dtype=torch.float64) -> torch.Tensor:
+        """Uniform in rng = (lo, hi)."""
+        lo, hi = rng
+        return lo + (hi - lo) * self._rand(*shape, dtype=dtype)
+
+    def _draw_rate(self, B: int, rng, p: float, semitones: bool = False) -> torch.Tensor:
+        """Uniform in rng = (lo, hi), or exactly 1.0 with probability 1 - p, from ONE rand(B, 2); semitones=True: the
+        factor 2^(x / 12) of such a draw, clamped to the host's own 2^(lo / 12), 2^(hi / 12): the bounds the batch length
+        was worked out from."""
+        lo, hi = rng
+        u = self._rand(B, 2)
+        x = lo + (hi - lo) * u[:, 0]
+        if semitones:
+            x, lo, hi = torch.exp2(x / 12.0), 2.0 ** (lo / 12.0), 2.0 ** (hi / 12.0)
+        return torch.where(u[:, 1] < p, torch.clamp(x, lo, hi), torch.ones_like(x))       # (the sum may round past hi)
+
+    def _draw_item(self, bank: NoiseBank, *shape):
+        """An item of the bank and a uniform offset into it, per element: (start, length, offset), int64."""
+        item = self._randint(0, len(bank), *shape)
+        start, length = bank.start[item].contiguous(), bank.length[item].contiguous()
+        return start, length, torch.minimum((self._rand(*shape) * length).to(torch.int64), length - 1)
+
+    def _draw_dry(self, index: torch.Tensor, identity: int):
+        """With probability 1 - p_reverb a row is dry and its index becomes `identity`: (index, the mask of the wet rows);
+        at p_reverb = 1 nothing is drawn and the mask is None."""
+        if self.p_reverb >= 1.0:
+            return index, None
+        wet = self._rand(index.size(0), dtype=torch.float32) < self.p_reverb
+        return torch.where(wet, index, torch.full_like(index, identity)), wet
+
+    def _draw_responses(self, B: int):
+        """(rir_index, rir_len, the room table, the rooms' own n_taps) of the talkers; the rooms are the sampler's draw."""
+        dev = self.engine.device
         if self.rir_bank is not None:
-            idx = torch.randint(0, self.n_rirs, (B,), generator=gen, device=dev)
-            if self.p_reverb < 1.0:
-                wet = torch.rand(B, dtype=torch.float32, generator=gen, device=dev) < self.p_reverb
-                idx = torch.where(wet, idx, torch.full_like(idx, self.n_rirs))
-            rlen = self.rir_bank.length[idx].contiguous()
-            idx = idx.to(torch.int32)
-        table = None
+            index, _ = self._draw_dry(self._randint(0, self.n_rirs, B), self.n_rirs)
+            return index.to(torch.int32), self.rir_bank.length[index].contiguous(), None, None
         if self.rooms is not None:
-            table, rlen = self.rooms.draw(B, self.rir_taps, self.sample_rate, device=dev)
-            room_taps = rlen
-            idx = torch.arange(B, dtype=torch.int32, device=dev)
-            if self.p_reverb < 1.0:
-                wet = torch.rand(B, dtype=torch.float32, generator=gen, device=dev) < self.p_reverb
-                idx = torch.where(wet, idx, torch.full_like(idx, B))
-                rlen = torch.where(wet, rlen, torch.ones_like(rlen))
-        level = None
-        if self.level_db is not None:
-            lo, hi = self.level_db
-            level = lo + (hi - lo) * torch.rand(B, dtype=torch.float64, generator=gen, device=dev)
-        speed = None
-        if self.speed is not None:
-            lo, hi = self.speed
-            u = torch.rand(B, 2, dtype=torch.float64, generator=gen, device=dev)
-            speed = torch.clamp(lo + (hi - lo) * u[:, 0], lo, hi)          # (the sum may round past hi)
-            speed = torch.where(u[:, 1] < self.p_speed, speed, torch.ones_like(speed)).contiguous()
-        chan = self.channel.draw(B, self.sample_rate, device=dev) if self.channel is not None else None
-        drawn = Draw(start.contiguous(), length.contiguous(), off, snr, idx, rlen, table, level, chan, speed)
-        if self.sources is not None:
-            S, sb = self.sources[1], self.source_bank
-            n_src = torch.randint(self.sources[0], S + 1, (B,), generator=gen, device=dev).to(torch.int32)
-            s_item = torch.randint(0, len(sb), (B, S), generator=gen, device=dev)
-            s_start, s_len = sb.start[s_item].contiguous(), sb.length[s_item].contiguous()
-            u = torch.rand(B, S, dtype=torch.float64, generator=gen, device=dev)
-            s_off = torch.minimum((u * s_len).to(torch.int64), s_len - 1)
-            lo, hi = self.source_snr_db
-            s_snr = (lo + (hi - lo) * torch.rand(B, S, dtype=torch.float32, generator=gen, device=dev)).contiguous()
-            s_idx = s_rlen = s_rooms = None
-            if self.rir_bank is not None:
-                s_idx = torch.randint(0, self.n_rirs, (B, S), generator=gen, device=dev)
-                s_rlen = self.rir_bank.length[s_idx].contiguous()
-                s_idx = s_idx.to(torch.int32)
-            if self.rooms is not None:
-                s_rooms = self.rooms.draw_sources(table, S)
-                base = B + (1 if self.p_reverb < 1.0 else 0)               # behind the talkers' rows and the identity
-                s_idx = base + torch.arange(B * S, dtype=torch.int32, device=dev).reshape(B, S)
-                s_rlen = room_taps[:, None].expand(B, S).contiguous()
-            return SceneDraw(*drawn, n_src, s_start, s_len, s_off, s_snr, s_idx, s_rlen, s_rooms)
-        return drawn
+            table, taps = self.rooms.draw(B, self.rir_taps, self.sample_rate, device=dev)
+            index, wet = self._draw_dry(torch.arange(B, dtype=torch.int32, device=dev), B)
+            return index, taps if wet is None else torch.where(wet, taps, torch.ones_like(taps)), table, taps
+        return None, None, None, None
+
+    def _draw_sources(self, B: int, table: Optional[torch.Tensor], taps: Optional[torch.Tensor]):
+        """The trailing fields of a SceneDraw; `table` and `taps` are the rooms of _draw_responses."""
+        S = self.sources[1]
+        n_src = self._randint(self.sources[0], S + 1, B).to(torch.int32)
+        start, length, off = self._draw_item(self.source_bank, B, S)
+        snr = self._draw_uniform(self.source_snr_db, B, S, dtype=torch.float32)
+        index = rlen = rooms = None
+        if self.rir_bank is not None:
+            index = self._randint(0, self.n_rirs, B, S)
+            index, rlen = index.to(torch.int32), self.rir_bank.length[index].contiguous()
+        elif table is not None:
+            rooms = self.rooms.draw_sources(table, S)
+            index = self._bank_rows(B) + torch.arange(B * S, dtype=torch.int32, device=table.device).reshape(B, S)
+            rlen = taps[:, None].expand(B, S).contiguous()
+        return n_src, start, length, off, snr, index, rlen, rooms
+
+    def _bank_rows(self, B: int) -> int:
+        """The rows of the simulated bank in front of the sources' responses: the talkers' and, with dry rows, the identity."""
+        return B + (1 if self.p_reverb < 1.0 else 0)
+
+    def draw(self, B: int):
+        start, length, off = self._draw_item(self.noise_bank, B)
+        snr = self._draw_uniform(self.snr_db, B, dtype=torch.float32)
+        index, rlen, table, taps = self._draw_responses(B)
+        level = None if self.level_db is None else self._draw_uniform(self.level_db, B)
+        speed = None if self.speed is None else self._draw_rate(B, self.speed, self.p_speed)
+        chan = None if self.channel is None else self.channel.draw(B, self.sample_rate, device=self.engine.device)
+        drawn = Draw(start, length, off, snr, index, rlen, table, level, chan, speed)
+        return drawn if self.sources is None else SceneDraw(*drawn, *self._draw_sources(B, table, taps))
 
     def _ranges(self):
         return _stretch_ranges(self.tempo, self.pitch, self.speed, self.p_tempo, self.p_pitch, self.p_speed)
@@ -756,29 +746,18 @@ class DynamicMixer:
         """The tempo and pitch draws of a batch (None when both are off), made after `draw`; `speed` is its Draw.speed."""
         if self.tempo is None and self.pitch is None:
             return None
-        dev, gen = self.engine.device, self.generator
-        one = torch.ones(B, dtype=torch.float64, device=dev)
-        t = f = one
-        if self.tempo is not None:
-            lo, hi = self.tempo
-            u = torch.rand(B, 2, dtype=torch.float64, generator=gen, device=dev)
-            t = torch.clamp(lo + (hi - lo) * u[:, 0], lo, hi)              # (the sum may round past hi)
-            t = torch.where(u[:, 1] < self.p_tempo, t, one)
-        if self.pitch is not None:
-            lo, hi = self.pitch
-            u = torch.rand(B, 2, dtype=torch.float64, generator=gen, device=dev)
-            # clamped to the host's own 2^(lo / 12), 2^(hi / 12): the bounds the batch length was worked out from
-            f = torch.clamp(torch.exp2((lo + (hi - lo) * u[:, 0]) / 12.0), 2.0 ** (lo / 12.0), 2.0 ** (hi / 12.0))
-            f = torch.where(u[:, 1] < self.p_pitch, f, one)
+        one = torch.ones(B, dtype=torch.float64, device=self.engine.device)
+        t = one if self.tempo is None else self._draw_rate(B, self.tempo, self.p_tempo)
+        f = one if self.pitch is None else self._draw_rate(B, self.pitch, self.p_pitch, semitones=True)
         warp = None
         if self.pitch is not None or speed is not None:
             warp = (f if speed is None else speed * f).contiguous()
-        return StretchDraw(t.contiguous(), f.contiguous(), (t / f).contiguous(), warp)
+        return StretchDraw(t, f, (t / f).contiguous(), warp)
 
     def _simulate(self, d: Draw) -> RirBank:
         """The batch's responses, simulated into the persistent allocation (made anew only when B changes)."""
         B, K = d.rooms.size(0), self.rir_taps
-        base = B + (1 if self.p_reverb < 1.0 else 0)
+        base = self._bank_rows(B)
         n_s = self.sources[1] if self.sources is not None else 0
         rows = base + B * n_s
         if self.last_bank is None or self.last_bank.data.size(0) != rows:
@@ -805,48 +784,63 @@ class DynamicMixer:
         return torch.where(ok, gain, torch.ones_like(gain)).to(torch.float32)
 
     def __call__(self, clean: torch.Tensor):
-        d = self.last_draw = self.draw(clean.size(0))
+        B = clean.size(0)
+        d = self.last_draw = self.draw(B)
         rir = self.rir_bank if self.rooms is None else self._simulate(d)
-        snr = d.snr_db
-        s = self.last_stretch = self.draw_stretch(clean.size(0), d.speed)
-        if s is not None:
-            (_, t_hi), (f_lo, f_hi), (_, v_hi) = self._ranges()
-            N1 = warp_len(clean.size(1), t_hi / f_lo)
-            clean = self.engine.stretch(clean, s.stretch_rate, N1, hop=self.stretch_hop, search=self.stretch_search)
-            if s.warp_rate is not None:                               # the speed stage's warp is this one
-                clean = self.engine.warp(clean, s.warp_rate, warp_len(N1, v_hi * f_hi), zeros=self.speed_zeros,
-                                         rolloff=self.speed_rolloff)
-        elif d.speed is not None:
-            clean = self.engine.warp(clean, d.speed, warp_len(clean.size(1), self.speed[1]), zeros=self.speed_zeros,
-                                     rolloff=self.speed_rolloff)
-        if self.snr_on == "active" or d.level_db is not None:
-            lv = self.last_level = self.engine.speech_level(clean, fs=self.sample_rate)
-            if self.snr_on == "active":
-                ok = torch.isfinite(lv.activity) & (lv.activity > 0)
-                delta = torch.where(ok, -10.0 * torch.log10(torch.where(ok, lv.activity, torch.ones_like(lv.activity))),
-                                    torch.zeros_like(lv.activity))
-                snr = (d.snr_db.to(torch.float64) - delta).to(torch.float32).contiguous()
-            if d.level_db is not None:
-                clean = (clean * self.level_gain(lv, d.level_db)[:, None]).contiguous()
-        early = self.early if rir is not None else -1
-        if self.sources is None:
-            noisy, target, info = self.engine.mix(clean, self.noise_bank.data, d.noise_start, d.noise_len, d.noise_off,
-                                                  snr, rir.data if rir is not None else None, d.rir_index, d.rir_len,
-                                                  peak=self.peak, early=early)
-        else:
-            src_snr = d.src_snr_db
-            if self.snr_on == "active":
-                src_snr = (src_snr.to(torch.float64) - delta[:, None]).to(torch.float32).contiguous()
-            dry = (self.noise_bank.data, d.noise_start, d.noise_len, d.noise_off, snr) if self.dry_noise else (None,) * 5
-            noisy, target, info = self.engine.scene(clean, *dry, d.n_src, self.source_bank.data, d.src_start, d.src_len,
-                                                    d.src_off, src_snr, rir.data if rir is not None else None, d.rir_index,
-                                                    d.rir_len, d.src_rir_index, d.src_rir_len, peak=self.peak, early=early)
-        if d.channel is not None:
-            sos, n_sections, n_shared, clip_rel = d.channel
-            self.engine.channel(noisy, sos, n_sections, self.channel_clip(clip_rel, noisy), out=noisy)
-            if self.channel_on == "both":
-                self.engine.channel(target, sos, n_shared, out=target)
+        s = self.last_stretch = self.draw_stretch(B, d.speed)
+        clean = self._perturb(d, s, clean)
+        shift, clean = self._level(d, clean)
+        noisy, target, info = self._mix(d, clean, rir, shift)
+        self._channel(d, noisy, target)
         return target, noisy, info
+
+    # ---- the stages of a call, in its order -------------------------------------------------------------------------
+    def _perturb(self, d: Draw, s: Optional[StretchDraw], clean: torch.Tensor) -> torch.Tensor:
+        """Tempo, pitch and speed: Engine.stretch and / or the ONE Engine.warp."""
+        warp = lambda x, rate, N: self.engine.warp(x, rate, N, zeros=self.speed_zeros, rolloff=self.speed_rolloff)
+        if s is None:
+            return clean if d.speed is None else warp(clean, d.speed, warp_len(clean.size(1), self.speed[1]))
+        (_, t_hi), (f_lo, f_hi), (_, v_hi) = self._ranges()
+        N1 = warp_len(clean.size(1), t_hi / f_lo)
+        clean = self.engine.stretch(clean, s.stretch_rate, N1, hop=self.stretch_hop, search=self.stretch_search)
+        return clean if s.warp_rate is None else warp(clean, s.warp_rate, warp_len(N1, v_hi * f_hi))   # the speed stage's warp is this one
+
+    def _level(self, d: Draw, clean: torch.Tensor):
+        """The level measurement: (D, the batch at its drawn level), D the float64 [B] shift of snr_on="active" or None."""
+        if self.snr_on != "active" and d.level_db is None:
+            return None, clean
+        lv = self.last_level = self.engine.speech_level(clean, fs=self.sample_rate)
+        shift = None
+        if self.snr_on == "active":
+            ok = torch.isfinite(lv.activity) & (lv.activity > 0)
+            shift = torch.where(ok, -10.0 * torch.log10(torch.where(ok, lv.activity, torch.ones_like(lv.activity))),
+                                torch.zeros_like(lv.activity))
+        if d.level_db is not None:
+            clean = (clean * self.level_gain(lv, d.level_db)[:, None]).contiguous()
+        return shift, clean
+
+    def _mix(self, d: Draw, clean: torch.Tensor, rir: Optional[RirBank], shift: Optional[torch.Tensor]):
+        """Engine.mix, or Engine.scene with sources: (noisy, target, info)."""
+        def shifted(snr, by):
+            return snr if by is None else (snr.to(torch.float64) - by).to(torch.float32).contiguous()
+        snr = shifted(d.snr_db, shift)
+        bank, early = (None, -1) if rir is None else (rir.data, self.early)
+        if self.sources is None:
+            return self.engine.mix(clean, self.noise_bank.data, d.noise_start, d.noise_len, d.noise_off, snr, bank,
+                                   d.rir_index, d.rir_len, peak=self.peak, early=early)
+        src_snr = shifted(d.src_snr_db, None if shift is None else shift[:, None])
+        dry = (self.noise_bank.data, d.noise_start, d.noise_len, d.noise_off, snr) if self.dry_noise else (None,) * 5
+        return self.engine.scene(clean, *dry, d.n_src, self.source_bank.data, d.src_start, d.src_len, d.src_off, src_snr,
+                                 bank, d.rir_index, d.rir_len, d.src_rir_index, d.src_rir_len, peak=self.peak, early=early)
+
+    def _channel(self, d: Draw, noisy: torch.Tensor, target: torch.Tensor) -> None:
+        """The recording channel, in place: on noisy, and with channel_on="both" the shared sections on target."""
+        if d.channel is None:
+            return
+        sos, n_sections, n_shared, clip_rel = d.channel
+        self.engine.channel(noisy, sos, n_sections, self.channel_clip(clip_rel, noisy), out=noisy)
+        if self.channel_on == "both":
+            self.engine.channel(target, sos, n_shared, out=target)
 
     @staticmethod
     def channel_clip(clip_rel: torch.Tensor, noisy: torch.Tensor) -> torch.Tensor:

@@ -354,3 +354,26 @@ def test_mixing_loader_feeds_a_generator_train_step(eng):
         rows = _model_of_draw(clips[k * B:(k + 1) * B], nb, mixer.rir_bank, draws[k], mixer.peak, mixer.early)
         _assert_rows32(f"batch {k}", noisy.cpu().numpy(), rows, "noisy")
         _assert_rows32(f"batch {k}", target.cpu().numpy(), rows, "target")
+
+
+# ------------------------------------------------------------------ 6. the mixer's stages, against the recorded bits
+def test_mixer_gives_the_recorded_bits(eng):
+    """The 12 configurations of tests/mixer_cases.py - every stage alone, the usual pairs and everything at once, B = 3,
+    L = 1536 - give the bits DynamicMixer gave at the commit before its constructor, draws and call were taken apart into
+    helpers and stages (tests/golden/make_mixer_bits.py): target, noisy, every info vector, and every tensor of last_draw,
+    last_stretch and last_level; a field that was None is None."""
+    import os
+    import mixer_cases as C
+    want = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mixer_parent_bits.npz"))
+    names = []
+    for name, mixer, clean in C.bits_configs(eng):
+        fields = C.mixed_fields(mixer, clean)
+        assert sorted(f"{name}/{k}" for k, _ in fields) == sorted(k for k in want.files if k.startswith(name + "/")), name
+        for key, t in fields:
+            if want[f"{name}/{key}"].dtype.kind == "U":
+                assert t is None and str(want[f"{name}/{key}"]) == "None", f"{name} {key}: recorded as None, got {t}"
+            else:
+                assert t is not None, f"{name} {key}: None, recorded as a tensor"
+                C.assert_recorded_bits(name, {key: t}, want)
+        names.append(name)
+    assert len(names) == 12

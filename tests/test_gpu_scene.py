@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import scene_model as M
+from mixer_cases import assert_recorded_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -117,20 +118,6 @@ def parent_bits():
     return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mix_parent_bits.npz"))
 
 
-def _assert_recorded_bits(case, got, want):
-    """got: device tensors by name; want: the recorded unsigned views.  Names the first differing row and index."""
-    for key, t in got.items():
-        w = want[f"{case}/{key}"]
-        g = t.contiguous().cpu().numpy().view(w.dtype)
-        assert g.shape == w.shape, f"{case} {key}: shape {g.shape}, recorded {w.shape}"
-        if not np.array_equal(g, w):
-            at = np.argwhere(g != w)[0]
-            row, idx = int(at[0]), (int(at[1]) if len(at) > 1 else 0)
-            f = np.float32 if w.dtype == np.uint32 else np.float64
-            raise AssertionError(f"{case} {key}: row {row} differs first at index {idx}: got {g[tuple(at)]:#x} "
-                                 f"({g.view(f)[tuple(at)]!r}), recorded {w[tuple(at)]:#x} ({w.view(f)[tuple(at)]!r})")
-
-
 @pytest.mark.parametrize("name", [f"tile-{T0 - 1}", f"tile-{2 * T0 + T0 // 2 + 7}", "chunk", "peak"])
 def test_without_sources_the_bits_are_engine_mix(eng, batches, parent_bits, name):
     """Engine.mix and both source-free forms of Engine.scene give each other's bits - which one code path would do by
@@ -143,14 +130,14 @@ def test_without_sources_the_bits_are_engine_mix(eng, batches, parent_bits, name
                 a[12] = a[13] = a[14] = a[15] = a[16] = None
             case = f"{name}/early{early}/{'rir' if rir else 'dry'}"
             n1, t1, i1 = eng.mix(a[0], a[1], a[2], a[3], a[4], a[5], a[12], a[13], a[14], peak=bt.peak, early=early)
-            _assert_recorded_bits(case, dict(noisy=n1, target=t1, g=i1.g, scale=i1.scale, Ps=i1.Ps, Pn=i1.Pn), parent_bits)
+            assert_recorded_bits(case, dict(noisy=n1, target=t1, g=i1.g, scale=i1.scale, Ps=i1.Ps, Pn=i1.Pn), parent_bits)
             no_src = a[:6] + [None] * 6 + a[12:15] + [None, None]
             zero = list(a)
             zero[6] = torch.zeros_like(a[6])                                               # or: four columns, none used
             for args in (no_src, zero):
                 n2, t2, i2 = eng.scene(*args, peak=bt.peak, early=early)
-                _assert_recorded_bits(case, dict(noisy=n2, target=t2, g=i2.g[:, 0], scale=i2.scale, Ps=i2.Ps, Pn=i2.P[:, 0]),
-                                      parent_bits)
+                assert_recorded_bits(case, dict(noisy=n2, target=t2, g=i2.g[:, 0], scale=i2.scale, Ps=i2.Ps, Pn=i2.P[:, 0]),
+                                     parent_bits)
                 assert torch.equal(n1.view(torch.int32), n2.view(torch.int32)) and torch.equal(t1.view(torch.int32), t2.view(torch.int32))
                 assert torch.equal(i1.g, i2.g[:, 0]) and torch.equal(i1.Pn, i2.P[:, 0])
                 assert torch.equal(i1.scale, i2.scale) and torch.equal(i1.Ps, i2.Ps)

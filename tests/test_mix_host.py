@@ -249,3 +249,40 @@ def test_clean_only_dataset_follows_the_length_rule(tmp_path):
     full = long_.astype(np.float32) / 32768.0
     assert n == 200 and x.numel() == 64
     assert any(np.array_equal(x.numpy(), full[s:s + 64]) for s in range(200 - 64 + 1))
+
+
+# ------------------------------------------------------------------ DynamicMixer's draws and messages, as recorded
+def test_draws_and_messages_are_the_recorded_ones():
+    """DynamicMixer's contract is exact - draw order, generator state, bits, and the text of every refusal - so both are
+    pinned from outside (tests/golden/make_mixer_draws.py, recorded at the commit before the constructor and the draws
+    were rebuilt from shared helpers): for the 384 option combinations of tests/mixer_cases.py every field of draw(6) and
+    draw_stretch(6, d.speed) - dtype, shape, strides and bits, None where it was None - and the final state of the three
+    generators; for one bad option per parser path, and for pairs of them, the exception type and its full text."""
+    import json
+    import mixer_cases as C
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    z = np.load(os.path.join(golden, "mixer_parent_draws.npz"))
+    manifest, blob = json.loads(str(z["manifest"])), z["blob"]
+    redo = (f"; recorded at {str(z['provenance'])!r}, this is torch {torch.__version__}: if torch's generators moved, record "
+            f"again with tests/golden/make_mixer_draws.py AT THAT COMMIT, not at the one under test")
+    cases = list(C.draw_cases())
+    assert len(cases) == 384 and [name for name, _ in cases] == list(manifest)
+    at = 0
+    for name, opt in cases:
+        mixer, gens = C.draw_mixer(opt, C.NoEngine())
+        rows, raw = C.pack(C.drawn_fields(mixer, gens))
+        assert [r[0] for r in rows] == [w[0] for w in manifest[name]], f"{name}: fields {[r[0] for r in rows]}" + redo
+        mine = 0
+        for got, want in zip(rows, manifest[name]):
+            assert got == want, f"{name} {got[0]}: [name, dtype, shape, strides, bytes] = {got}, recorded {want}" + redo
+            n = 0 if want[1] is None else want[-1]
+            if not np.array_equal(raw[mine:mine + n], blob[at:at + n]):
+                k = int(np.argmax(raw[mine:mine + n] != blob[at:at + n]))
+                raise AssertionError(f"{name} {got[0]} ({got[1]} {got[2]}): differs first at byte {k}" + redo)
+            mine, at = mine + n, at + n
+    assert at == blob.size
+    with open(os.path.join(golden, "mixer_parent_messages.json")) as f:
+        recorded = json.load(f)["messages"]
+    assert list(recorded) == [name for name, _, _ in C.BAD_OPTIONS]
+    for name, make, kw in C.BAD_OPTIONS:
+        assert C.message_of(make, kw) == recorded[name], f"{name}: {make.__name__}({kw})"
