@@ -3,23 +3,23 @@ scipy.signal.sosfilt in float64 on one host thread; Engine.mix without a RIR).
 
     python tools/channel_bench.py [--batch 32] [--iters 100] [--repeats 7] [--host-clips 2] [--limit 120] [--out PATH]
 
-Prints one JSON line (and writes it to --out, default profiles/r13_channel_bench.json).  Six cases at 16 kHz: --batch
-clips of 2 s and of 10 s with S = 1, 4 and 8 sections per row (every row uses all S; S = 8 is a high-pass, three
-equaliser sections and an 8th-order Butterworth band limit, the others its first sections), half of the rows clipped.
-Every case runs in a process of its own under a time limit of --limit seconds; after a case that fails or runs out of
-time no further case is started.  Per case: device ms per Engine.channel call and per Engine.mix call without a RIR (HIP
-events around `iters` calls after a warm-up; the two are measured alternately, `repeats` times each, and the median and
-the spread are reported; a channel call is its four launches), the in-place call, the seconds the host takes per clip
+Prints one JSON line (and writes it to --out when one is given: profiles/r13_channel_bench.json was written by passing
+--out).  Six cases at 16 kHz: --batch clips of 2 s and of 10 s with S = 1, 4 and 8 sections per row (every row uses all
+S; S = 8 is a high-pass, three equaliser sections and an 8th-order Butterworth band limit, the others its first
+sections), half of the rows clipped.  Every case runs isolated under --limit seconds and the calls are timed alternately
+(tools/benchlib.py).  Per case: device ms per Engine.channel call and per Engine.mix call without a RIR (the median and
+the spread of `repeats` measurements of `iters` calls; a channel call is its four launches), the in-place call, the
+seconds the host takes per clip
 for sosfilt in float64 (timed on the first --host-clips clips), the worst |gpu - f32(host)| in float32 ulps, and the
 arithmetic: a sample costs 5 S fused multiply-adds in each of the two passes over the row, and every thread of both
 passes adds 8 (scan) + up to 8 (apply only) mat-vecs of N (N + 2) / 2 multiply-adds, N = 2 S."""
 import argparse
-import json
 import os
 import statistics
-import subprocess
 import sys
 import time
+
+import benchlib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -63,32 +63,11 @@ def run_case(B, seconds, S, iters, repeats, host_clips):
     clip = torch.from_numpy(clip_np).to(dev)
     out = torch.empty_like(wav)
     scratch = wav.clone()
-    bank = torch.from_numpy((0.1 * rng.standard_normal(10 * FS)).astype(np.float32)).to(dev)
-    start = torch.zeros(B, dtype=torch.int64, device=dev)
-    length = torch.full((B,), bank.numel(), dtype=torch.int64, device=dev)
-    off = torch.arange(B, dtype=torch.int64, device=dev) * 977
-    snr = torch.linspace(0.0, 20.0, B, dtype=torch.float32, device=dev)
+    beside = benchlib.mix_beside(rng, B, dev)
     calls = {"channel": lambda: eng.channel(wav, sos, None, clip, out=out),
              "in_place": lambda: eng.channel(scratch, sos, None, clip, out=scratch),
-             "mix": lambda: eng.mix(wav, bank, start, length, off, snr)}
-
-    def timed(call):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            call()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / iters
-
-    for _ in range(3):
-        for c in calls.values():
-            c()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in calls}
-    for _ in range(repeats):                                          # alternately: all see the same machine
-        for k, c in calls.items():
-            ms[k].append(timed(c))
+             "mix": lambda: eng.mix(wav, *beside)}
+    ms = benchlib.alternate(calls, iters, repeats, warmup=3)
     got = eng.channel(wav, sos, None, clip).cpu().numpy()
     n_host = max(1, min(host_clips, B))
     sosfilt(sos_np[0], x[0, :2000].astype(np.float64))                # (imports, first-use costs)
@@ -98,14 +77,14 @@ def run_case(B, seconds, S, iters, repeats, host_clips):
     ulps = max(float(np.max(np.abs(got[b].astype(np.float64) - want[b].astype(np.float32).astype(np.float64))
                             / np.spacing(np.abs(want[b]).astype(np.float32)))) for b in range(n_host))
     med = {k: statistics.median(v) for k, v in ms.items()}
+    ch, ip, mx = (benchlib.summary(ms[k]) for k in ("channel", "in_place", "mix"))
     N = 2 * next(p for p in (1, 2, 4, 8) if S <= p)
     nt = -(-L // tile)
     fma = B * (2 * 5 * S * L + nt * 256 * (8 + 8 + 8) * (N * (N + 2) // 2))
     return {"case": f"{B}x{seconds}s S={S}", "samples_per_clip": L, "tiles_per_clip": nt, "sections": S,
-            "channel_ms_per_call": round(med["channel"], 4), "channel_ms_min": round(min(ms["channel"]), 4),
-            "channel_ms_max": round(max(ms["channel"]), 4), "in_place_ms_per_call": round(med["in_place"], 4),
-            "mix_no_rir_ms_per_call": round(med["mix"], 4), "mix_ms_min": round(min(ms["mix"]), 4),
-            "mix_ms_max": round(max(ms["mix"]), 4), "channel_over_mix": round(med["channel"] / med["mix"], 3),
+            "channel_ms_per_call": ch[0], "channel_ms_min": ch[1], "channel_ms_max": ch[2], "in_place_ms_per_call": ip[0],
+            "mix_no_rir_ms_per_call": mx[0], "mix_ms_min": mx[1], "mix_ms_max": mx[2],
+            "channel_over_mix": round(med["channel"] / med["mix"], 3),
             "msamples_per_s": round(B * L / (med["channel"] * 1e-3) / 1e6, 1), "float64_fma_upper_bound": fma,
             "float64_gfma_per_s": round(fma / (med["channel"] * 1e-3) / 1e9, 1),
             "host_sosfilt_s_per_clip": round(host_s, 5), "host_clips_timed": n_host,
@@ -120,40 +99,17 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--host-clips", type=int, default=2)
     ap.add_argument("--limit", type=float, default=120.0)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r13_channel_bench.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--case", nargs=2, type=int, default=None, metavar=("SECONDS", "S"), help="(internal) run one case")
     a = ap.parse_args()
     if a.case is not None:
-        print("CASE " + json.dumps(run_case(a.batch, a.case[0], a.case[1], a.iters, a.repeats, a.host_clips)))
-        return
-    rows, stopped = [], None
-    for seconds in (2, 10):
-        for S in (1, 4, 8):
-            cmd = [sys.executable, os.path.abspath(__file__), "--batch", str(a.batch), "--iters", str(a.iters), "--repeats",
-                   str(a.repeats), "--host-clips", str(a.host_clips), "--case", str(seconds), str(S)]
-            try:
-                r = subprocess.run(cmd, capture_output=True, text=True, timeout=a.limit)
-            except subprocess.TimeoutExpired:
-                stopped = f"{seconds}s S={S}: no result within {a.limit} s"
-                break
-            line = next((l for l in r.stdout.splitlines() if l.startswith("CASE ")), None)
-            if r.returncode != 0 or line is None:
-                stopped = f"{seconds}s S={S}: exit status {r.returncode}: {r.stderr.strip()[-400:]}"
-                break
-            rows.append(json.loads(line[5:]))
-        if stopped:
-            break
-    cpus = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else os.cpu_count()
+        return benchlib.print_case(run_case(a.batch, a.case[0], a.case[1], a.iters, a.repeats, a.host_clips))
+    rows, stopped = benchlib.run_cases(__file__, benchlib.flags(a, "batch", "iters", "repeats", "host_clips"),
+                                       [(f"{sec}s S={S}", (sec, S)) for sec in (2, 10) for S in (1, 4, 8)], a.limit)
     line = {"metric": "channel", "batch": a.batch, "fs": FS, "launches_per_call": 4, "iters": a.iters, "repeats": a.repeats,
-            "limit_s_per_case": a.limit, "cases": rows, "stopped": stopped, "host_threads": 1, "host_cpus_available": cpus}
-    s = json.dumps(line)
-    print(s)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(s + "\n")
-    if stopped:
-        raise SystemExit(1)
+            "limit_s_per_case": a.limit, "cases": rows, "stopped": stopped, "host_threads": 1,
+            "host_cpus_available": benchlib.host_cpus()}
+    benchlib.emit(line, a.out, stopped)
 
 
 if __name__ == "__main__":

@@ -1,18 +1,17 @@
 """The active speech level on the GPU vs the host, and beside the call it now precedes (cmgan_speech_level /
 Engine.speech_level vs the same definition in float64 numpy + scipy.signal.lfilter; Engine.mix without a RIR).
 
-    python tools/level_bench.py [--batch 32] [--iters 200] [--repeats 7] [--host-clips 4] [--out PATH]
+    python tools/level_bench.py [--batch 32] [--iters 200] [--repeats 7] [--host-clips 4] [--limit 120] [--out PATH]
 
 Prints one JSON line (and writes it to --out).  Two cases at 16 kHz: --batch clips of 2 s and of 10 s, seeded bursts of
-noise with pauses.  Per case: device ms per Engine.speech_level call and per Engine.mix call without a RIR (HIP events
-around `iters` calls after a warm-up; the two are measured alternately, `repeats` times each, and the median and the
-spread are reported; a level call is its four launches), the fraction of the mix call that the measurement adds, the
+noise with pauses.  Every case runs isolated under --limit seconds and the two calls are timed alternately
+(tools/benchlib.py).  Per case: device ms per Engine.speech_level call and per Engine.mix call without a RIR (the median
+and the spread of `repeats` measurements of `iters` calls; a level call is its four launches), the fraction of the mix call that the measurement adds, the
 seconds the host takes per clip for the same definition (two lfilter passes and fifteen threshold scans in float64 on one
 thread, timed on the first --host-clips clips), whether the integer counts are equal and the worst relative difference
 of the three levels, and the bytes the kernels move: the clips are read twice (4 bytes a sample each time); the per-tile
 states are 56 + 64 bytes per 1024 samples written and read once."""
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -22,7 +21,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
-import torch  # noqa: E402
+
+import benchlib  # noqa: E402
 
 FS = 16000
 MARGIN_DB = 15.9
@@ -74,24 +74,8 @@ def clips(B, L, seed):
     return x
 
 
-def timed(call, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        call()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--batch", type=int, default=32)
-    ap.add_argument("--iters", type=int, default=200)
-    ap.add_argument("--repeats", type=int, default=7)
-    ap.add_argument("--host-clips", type=int, default=4)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+def run_case(B, seconds, iters, repeats, host_clips):
+    import torch
     from cmgan_amd import _lib
     from cmgan_amd.engine import Engine
 
@@ -100,58 +84,56 @@ def main():
     eng = Engine()
     dev = eng.device
     tile = int(_lib.load().cmgan_speech_level_tile())
-    B = a.batch
-    rng = np.random.default_rng(1)
-    bank = torch.from_numpy((0.1 * rng.standard_normal(10 * FS)).astype(np.float32)).to(dev)
-    rows = []
-    for seconds in (2, 10):
-        L = seconds * FS
-        x = clips(B, L, seed=seconds)
-        wav = torch.from_numpy(x).to(dev)
-        start = torch.zeros(B, dtype=torch.int64, device=dev)
-        length = torch.full((B,), bank.numel(), dtype=torch.int64, device=dev)
-        off = torch.arange(B, dtype=torch.int64, device=dev) * 977
-        snr = torch.linspace(0.0, 20.0, B, dtype=torch.float32, device=dev)
-        level_call = lambda: eng.speech_level(wav, fs=FS, counts=True)
-        mix_call = lambda: eng.mix(wav, bank, start, length, off, snr)
-        for _ in range(3):
-            (lv, cnt), _ = level_call(), mix_call()
-        torch.cuda.synchronize()
-        level_ms, mix_ms = [], []
-        for _ in range(a.repeats):                                    # alternately: both see the same machine
-            level_ms.append(timed(level_call, a.iters))
-            mix_ms.append(timed(mix_call, a.iters))
-        got = torch.stack(list(lv), dim=1).cpu().numpy()
-        got_cnt = cnt.cpu().numpy()
-        n_host = max(1, min(a.host_clips, B))
-        host_level(x[0, :2000], FS)                                   # (imports, first-use costs)
-        t0 = time.perf_counter()
-        want = [host_level(x[b], FS) for b in range(n_host)]
-        host_s = (time.perf_counter() - t0) / n_host
-        counts_equal = all(np.array_equal(got_cnt[b, :15], want[b][3]) for b in range(n_host))
-        rel = max(abs(got[b, k] - want[b][k]) / abs(want[b][k]) for b in range(n_host) for k in range(3) if want[b][k] != 0.0)
-        lm, mm = statistics.median(level_ms), statistics.median(mix_ms)
-        nt = -(-L // tile)
-        moved = B * (2 * 4 * L + nt * (56 + 64) * 2)
-        rows.append({"case": f"{B}x{seconds}s", "samples_per_clip": L, "tiles_per_clip": nt,
-                     "level_ms_per_call": round(lm, 4), "level_ms_min": round(min(level_ms), 4), "level_ms_max": round(max(level_ms), 4),
-                     "mix_no_rir_ms_per_call": round(mm, 4), "mix_ms_min": round(min(mix_ms), 4), "mix_ms_max": round(max(mix_ms), 4),
-                     "level_over_mix": round(lm / mm, 3), "bytes_moved": moved,
-                     "level_gb_per_s": round(moved / (lm * 1e-3) / 1e9, 1),
-                     "host_float64_s_per_clip": round(host_s, 5), "host_clips_timed": n_host,
-                     "speedup_vs_host": round(host_s * B * 1000.0 / lm, 1),
-                     "counts_equal_host": bool(counts_equal), "max_rel_diff_levels_vs_host": float(rel),
-                     "mean_activity": float(np.mean(got[:, 2]))})
-    cpus = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else os.cpu_count()
-    line = {"metric": "speech_level", "batch": B, "fs": FS, "tile": tile, "launches_per_call": 4, "iters": a.iters,
-            "repeats": a.repeats, "cases": rows, "host_threads": 1, "host_cpus_available": cpus,
-            "mix_no_rir_ms_r09": 0.046, "device": torch.cuda.get_device_name(0)}
-    s = json.dumps(line)
-    print(s)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(s + "\n")
+    beside = benchlib.mix_beside(np.random.default_rng(1), B, dev)
+    L = seconds * FS
+    x = clips(B, L, seed=seconds)
+    wav = torch.from_numpy(x).to(dev)
+    calls = {"level": lambda: eng.speech_level(wav, fs=FS, counts=True), "mix": lambda: eng.mix(wav, *beside)}
+    ms = benchlib.alternate(calls, iters, repeats, warmup=3)
+    lv, cnt = calls["level"]()
+    got = torch.stack(list(lv), dim=1).cpu().numpy()
+    got_cnt = cnt.cpu().numpy()
+    n_host = max(1, min(host_clips, B))
+    host_level(x[0, :2000], FS)                                       # (imports, first-use costs)
+    t0 = time.perf_counter()
+    want = [host_level(x[b], FS) for b in range(n_host)]
+    host_s = (time.perf_counter() - t0) / n_host
+    counts_equal = all(np.array_equal(got_cnt[b, :15], want[b][3]) for b in range(n_host))
+    rel = max(abs(got[b, k] - want[b][k]) / abs(want[b][k]) for b in range(n_host) for k in range(3) if want[b][k] != 0.0)
+    lm, mm = statistics.median(ms["level"]), statistics.median(ms["mix"])
+    lvl, mix = benchlib.summary(ms["level"]), benchlib.summary(ms["mix"])
+    nt = -(-L // tile)
+    moved = B * (2 * 4 * L + nt * (56 + 64) * 2)
+    return {"case": f"{B}x{seconds}s", "samples_per_clip": L, "tiles_per_clip": nt,
+            "level_ms_per_call": lvl[0], "level_ms_min": lvl[1], "level_ms_max": lvl[2],
+            "mix_no_rir_ms_per_call": mix[0], "mix_ms_min": mix[1], "mix_ms_max": mix[2],
+            "level_over_mix": round(lm / mm, 3), "bytes_moved": moved,
+            "level_gb_per_s": round(moved / (lm * 1e-3) / 1e9, 1),
+            "host_float64_s_per_clip": round(host_s, 5), "host_clips_timed": n_host,
+            "speedup_vs_host": round(host_s * B * 1000.0 / lm, 1),
+            "counts_equal_host": bool(counts_equal), "max_rel_diff_levels_vs_host": float(rel),
+            "mean_activity": float(np.mean(got[:, 2])), "device": torch.cuda.get_device_name(0), "tile": tile}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--host-clips", type=int, default=4)
+    ap.add_argument("--limit", type=float, default=120.0)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--case", type=int, default=None, metavar="SECONDS", help="(internal) run one case")
+    a = ap.parse_args()
+    if a.case is not None:
+        return benchlib.print_case(run_case(a.batch, a.case, a.iters, a.repeats, a.host_clips))
+    rows, stopped = benchlib.run_cases(__file__, benchlib.flags(a, "batch", "iters", "repeats", "host_clips"),
+                                       [(f"{sec}s", (sec,)) for sec in (2, 10)], a.limit)
+    device, tile = benchlib.lift(rows, "device", "tile")
+    line = {"metric": "speech_level", "batch": a.batch, "fs": FS, "tile": tile, "launches_per_call": 4, "iters": a.iters,
+            "repeats": a.repeats, "limit_s_per_case": a.limit, "cases": rows, "stopped": stopped, "host_threads": 1,
+            "host_cpus_available": benchlib.host_cpus(), "mix_no_rir_ms_r09": 0.046, "device": device}
+    benchlib.emit(line, a.out, stopped)
 
 
 if __name__ == "__main__":

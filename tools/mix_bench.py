@@ -1,15 +1,15 @@
 """Dynamic mixing on the GPU vs the host (cmgan_mix / Engine.mix vs a float64 numpy / scipy mixer).
 
-    python tools/mix_bench.py [--batch 32] [--seconds 2] [--rir-seconds 0.5] [--iters 50] [--repeats 5] [--out PATH]
+    python tools/mix_bench.py [--batch 32] [--seconds 2] [--rir-seconds 0.5] [--iters 50] [--repeats 5] [--limit 120]
+                              [--out PATH]
 
 Prints one JSON line (and writes it to --out).  For B clips of the given length at 16 kHz, without a RIR and with RIRs of
---rir-seconds: device ms per Engine.mix call (HIP events around `iters` calls after a warm-up, the median and the spread
-of `repeats` such measurements; a call is all of its launches), and the seconds the host takes to mix the same batch with
+--rir-seconds, each of the two an isolated case under --limit seconds (tools/benchlib.py): device ms per Engine.mix call
+(the median and the spread of `repeats` measurements of `iters` calls; a call is all of its launches), and the seconds the host takes to mix the same batch with
 the same draws in float64 - scipy.signal.fftconvolve for the reverberation, numpy for the rest - at numpy's and scipy's
 default threading (one thread: scipy.fft workers = 1, the other operations are element-wise), plus the worst difference
 between the two results over the batch's peak."""
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -19,7 +19,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
-import torch  # noqa: E402
+
+import benchlib  # noqa: E402
 
 FS = 16000
 
@@ -58,15 +59,8 @@ def host_mix(clean, bank, start, length, off, snr, rir, idx, rlen, peak, early):
     return noisy, target
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--batch", type=int, default=32)
-    ap.add_argument("--seconds", type=float, default=2.0)
-    ap.add_argument("--rir-seconds", type=float, default=0.5)
-    ap.add_argument("--iters", type=int, default=50)
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+def run_case(a, name):
+    import torch
     from cmgan_amd.engine import Engine
 
     if not torch.cuda.is_available():
@@ -92,47 +86,47 @@ def main():
     t = lambda v: torch.from_numpy(v).to(dev)
     d_clean, d_bank, d_start, d_len, d_off, d_snr = t(clean), t(bank), t(start), t(length), t(off), t(snr)
     d_rir, d_idx, d_rlen = t(rir), t(idx), t(rlen)
-    rows = []
-    for name, with_rir in (("no_rir", False), ("rir", True)):
-        call = (lambda: eng.mix(d_clean, d_bank, d_start, d_len, d_off, d_snr, d_rir, d_idx, d_rlen, peak=peak, early=early)) \
-            if with_rir else (lambda: eng.mix(d_clean, d_bank, d_start, d_len, d_off, d_snr, peak=peak))
-        for _ in range(5):
-            noisy, target, info = call()
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(a.repeats):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(a.iters):
-                noisy, target, info = call()
-            e1.record()
-            torch.cuda.synchronize()
-            ms.append(e0.elapsed_time(e1) / a.iters)
-        host_args = (clean, bank, start, length, off, snr) + ((rir, idx, rlen, peak, early) if with_rir
-                                                              else (None, None, None, peak, -1))
-        host_mix(*[v[:1] if i in (0,) else v for i, v in enumerate(host_args)])           # (imports, FFT plans)
-        t0 = time.perf_counter()
-        want_n, want_t = host_mix(*host_args)
-        host_s = time.perf_counter() - t0
-        pk = float(np.max(np.abs(want_n)))
-        err = max(float(np.max(np.abs(noisy.cpu().numpy() - want_n))), float(np.max(np.abs(target.cpu().numpy() - want_t)))) / pk
-        dev_ms = statistics.median(ms)
-        rows.append({"case": name, "rir_taps": K if with_rir else 0, "early_samples": early if with_rir else -1,
-                     "device_ms_per_call": round(dev_ms, 4), "device_ms_min": round(min(ms), 4),
-                     "device_ms_max": round(max(ms), 4),
-                     "fma_per_call": int(B) * L * (K if with_rir else 1),
-                     "host_float64_s": round(host_s, 4), "speedup_vs_host": round(host_s * 1000.0 / dev_ms, 1),
-                     "max_err_over_peak_vs_host": err})
-    cpus = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else os.cpu_count()
-    line = {"metric": "mix", "batch": B, "clip_s": a.seconds, "rir_s": a.rir_seconds, "fs": FS, "iters": a.iters,
-            "repeats": a.repeats, "cases": rows, "host_threads": 1, "host_cpus_available": cpus,
-            "train_step_ms_batch32": 157.0, "device": torch.cuda.get_device_name(0)}
-    s = json.dumps(line)
-    print(s)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(s + "\n")
+    with_rir = name == "rir"
+    call = (lambda: eng.mix(d_clean, d_bank, d_start, d_len, d_off, d_snr, d_rir, d_idx, d_rlen, peak=peak, early=early)) \
+        if with_rir else (lambda: eng.mix(d_clean, d_bank, d_start, d_len, d_off, d_snr, peak=peak))
+    ms = benchlib.alternate({name: call}, a.iters, a.repeats, warmup=5)[name]
+    noisy, target, info = call()
+    host_args = (clean, bank, start, length, off, snr) + ((rir, idx, rlen, peak, early) if with_rir
+                                                          else (None, None, None, peak, -1))
+    host_mix(*[v[:1] if i in (0,) else v for i, v in enumerate(host_args)])           # (imports, FFT plans)
+    t0 = time.perf_counter()
+    want_n, want_t = host_mix(*host_args)
+    host_s = time.perf_counter() - t0
+    pk = float(np.max(np.abs(want_n)))
+    err = max(float(np.max(np.abs(noisy.cpu().numpy() - want_n))), float(np.max(np.abs(target.cpu().numpy() - want_t)))) / pk
+    dev_ms, (med, lo, hi) = statistics.median(ms), benchlib.summary(ms)
+    return {"case": name, "rir_taps": K if with_rir else 0, "early_samples": early if with_rir else -1,
+            "device_ms_per_call": med, "device_ms_min": lo, "device_ms_max": hi,
+            "fma_per_call": int(B) * L * (K if with_rir else 1),
+            "host_float64_s": round(host_s, 4), "speedup_vs_host": round(host_s * 1000.0 / dev_ms, 1),
+            "max_err_over_peak_vs_host": err, "device": torch.cuda.get_device_name(0)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--seconds", type=float, default=2.0)
+    ap.add_argument("--rir-seconds", type=float, default=0.5)
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--limit", type=float, default=120.0)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--case", choices=("no_rir", "rir"), default=None, help="(internal) run one case")
+    a = ap.parse_args()
+    if a.case is not None:
+        return benchlib.print_case(run_case(a, a.case))
+    rows, stopped = benchlib.run_cases(__file__, benchlib.flags(a, "batch", "seconds", "rir_seconds", "iters", "repeats"),
+                                       [(name, (name,)) for name in ("no_rir", "rir")], a.limit)
+    device, = benchlib.lift(rows, "device")
+    line = {"metric": "mix", "batch": a.batch, "clip_s": a.seconds, "rir_s": a.rir_seconds, "fs": FS, "iters": a.iters,
+            "repeats": a.repeats, "limit_s_per_case": a.limit, "cases": rows, "stopped": stopped, "host_threads": 1,
+            "host_cpus_available": benchlib.host_cpus(), "train_step_ms_batch32": 157.0, "device": device}
+    benchlib.emit(line, a.out, stopped)
 
 
 if __name__ == "__main__":

@@ -7,14 +7,15 @@ The mixer is host-bound Python around small launches, so what a change to cmgan_
 call, not the kernels.  For configuration 1 (defaults) and configuration 12 (every stage at once: rooms, levels, channel,
 speed, tempo, pitch, sources) of tests/mixer_cases.py at the given shape, prints one JSON line (and writes it to --out):
 the wall clock around `calls` calls after a warm-up with one torch.cuda.synchronize() at the end, per call, as the median
-and the spread of `repeats` such measurements.  --root names the tree whose cmgan_amd package is timed (default: this
+and the spread of `repeats` such measurements (the loop is tools/benchlib.py's; the tool stays in one process: it times
+the host).  --root names the tree whose cmgan_amd package is timed (default: this
 one); set CMGAN_HIP_LIB to time two trees' Python against one built library in the same session."""
 import argparse
-import json
 import os
-import statistics
 import sys
 import time
+
+import benchlib
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FS = 16000
@@ -56,30 +57,24 @@ def main():
             speed=(0.9, 1.1), p_speed=0.5, tempo=(0.9, 1.1), p_tempo=0.5, pitch=(-2, 2), sources=(0, 2), source_bank=talkers,
             source_snr_db=(0, 10)),
     }
+
+    def wall_ms(call, calls):
+        t0 = time.perf_counter()
+        for _ in range(calls):
+            call()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1000.0 / calls
+
     rows = []
     for name, make in configs.items():
         mixer = make()
-        for _ in range(10):
-            mixer(clean)
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(a.repeats):
-            t0 = time.perf_counter()
-            for _ in range(a.calls):
-                mixer(clean)
-            torch.cuda.synchronize()
-            ms.append((time.perf_counter() - t0) * 1000.0 / a.calls)
-        rows.append({"case": name, "ms_per_call": round(statistics.median(ms), 4), "ms_min": round(min(ms), 4),
-                     "ms_max": round(max(ms), 4), "repeats_ms": [round(v, 4) for v in ms]})
+        ms = benchlib.alternate({name: lambda: mixer(clean)}, a.calls, a.repeats, warmup=10, timer=wall_ms)[name]
+        med, lo, hi = benchlib.summary(ms)
+        rows.append({"case": name, "ms_per_call": med, "ms_min": lo, "ms_max": hi, "repeats_ms": [round(v, 4) for v in ms]})
     line = {"metric": "mixer_call", "label": a.label, "package": os.path.relpath(os.path.dirname(os.path.abspath(cmgan_amd.__file__)), HERE),
             "batch": B, "clip_s": a.seconds, "rir_s": a.rir_seconds, "fs": FS, "calls": a.calls, "repeats": a.repeats,
             "cases": rows, "device": torch.cuda.get_device_name(0)}
-    s = json.dumps(line)
-    print(s)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(s + "\n")
+    benchlib.emit(line, a.out)
 
 
 if __name__ == "__main__":

@@ -1,17 +1,18 @@
 """Room impulse responses on the GPU vs the host (cmgan_rir / Engine.rir vs the image-source method in float64 numpy).
 
-    python tools/rir_bench.py [--rooms 32] [--seconds 0.5] [--iters 10] [--repeats 5] [--host-rooms 2] [--out PATH]
+    python tools/rir_bench.py [--rooms 32] [--seconds 0.5] [--iters 10] [--repeats 5] [--host-rooms 2] [--limit 120]
+                              [--out PATH]
 
 Prints one JSON line (and writes it to --out).  Two cases at 16 kHz, c = 343 m/s, tw = 40: `fixed`, --rooms copies of a
 6 x 5 x 3 m room at rt60 0.5 s with their own source / receiver positions, and `sampled`, --rooms rooms drawn by the
-default RoomSampler, both with the image ranges RoomSampler.n_images gives.  Per case: device ms per Engine.rir call
-(HIP events around `iters` calls after a warm-up, the median and the spread of `repeats` such measurements; a call is
+default RoomSampler, both with the image ranges RoomSampler.n_images gives and both drawn from one generator in that
+order, each an isolated case under --limit seconds (tools/benchlib.py; the second case replays the first one's draw).
+Per case: device ms per Engine.rir call (the median and the spread of `repeats` measurements of `iters` calls; a call is
 both of its launches), the seconds the host takes per room for the same sum, vectorised over images in float64 numpy on
 one thread (measured on the first --host-rooms rooms), the worst difference between the two over the response's peak,
 and the work: the images that reach the responses, the (image, tap) pairs inside a window - 9 float64 operations each
 as the kernel writes them - and the list entries the threads visit, one add + compare each."""
 import argparse
-import json
 import math
 import os
 import statistics
@@ -22,10 +23,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
-import torch  # noqa: E402
+
+import benchlib  # noqa: E402
 
 FS, C, TW, DMIN = 16000, 343.0, 40, 0.01
 FP64_VECTOR_PEAK_TFLOPS = 78.6                                   # MI355X data sheet
+CASES = ("fixed_6x5x3_rt60_0.5", "default_room_sampler")
 
 
 def host_images(room, N):
@@ -77,15 +80,8 @@ def work(rooms, n_taps, K, N, tile):
     return images, pairs, visits
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--rooms", type=int, default=32)
-    ap.add_argument("--seconds", type=float, default=0.5)
-    ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--host-rooms", type=int, default=2)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+def run_case(a, name):
+    import torch
     from cmgan_amd import _lib
     from cmgan_amd.engine import Engine
     from cmgan_amd.mixing import RoomSampler
@@ -99,55 +95,55 @@ def main():
     gen = torch.Generator(device=dev)
     gen.manual_seed(0)
     size = (6.0, 5.0, 3.0)
-    fixed = RoomSampler(dims=(size, size), rt60=(0.5, 0.5), generator=gen)
-    sampled = RoomSampler(generator=gen)
-    rows = []
-    for name, sampler in (("fixed_6x5x3_rt60_0.5", fixed), ("default_room_sampler", sampled)):
+    samplers = (RoomSampler(dims=(size, size), rt60=(0.5, 0.5), generator=gen), RoomSampler(generator=gen))
+    for sampler in samplers[:CASES.index(name) + 1]:             # (the draws before this case's move the generator)
         rooms, n_taps = sampler.draw(R, K, FS, device=dev)
-        N = sampler.n_images(K, FS, C, TW)
-        call = lambda: eng.rir(rooms, n_taps, K, N, fs=FS, c=C, tw=TW)
-        for _ in range(2):
-            rir, length = call()
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(a.repeats):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(a.iters):
-                rir, length = call()
-            e1.record()
-            torch.cuda.synchronize()
-            ms.append(e0.elapsed_time(e1) / a.iters)
-        rooms_h, taps_h, got = rooms.cpu().numpy(), n_taps.cpu().numpy(), rir.cpu().numpy()
-        n_host = max(1, min(a.host_rooms, R))
-        host_rir(rooms_h[0], 64, K, (1, 1, 1))                   # (imports, first-use costs)
-        t0 = time.perf_counter()
-        want = [host_rir(rooms_h[r], int(taps_h[r]), K, N) for r in range(n_host)]
-        host_s = (time.perf_counter() - t0) / n_host
-        err = max(float(np.max(np.abs(got[r] - want[r]))) / float(np.max(np.abs(want[r]))) for r in range(n_host))
-        images, pairs, visits = work(rooms_h, taps_h, K, N, tile)
-        dev_ms = statistics.median(ms)
-        flop = 9 * pairs + 2 * visits
-        rows.append({"case": name, "taps": K, "n_images": list(N), "images_enumerated_per_room": 8 * math.prod(2 * n + 1 for n in N),
-                     "images_reaching": images, "pairs_in_window": pairs, "list_entries_visited": visits,
-                     "device_ms_per_call": round(dev_ms, 4), "device_ms_min": round(min(ms), 4), "device_ms_max": round(max(ms), 4),
-                     "device_ms_per_room": round(dev_ms / R, 5), "float64_flop": flop,
-                     "float64_tflops": round(flop / (dev_ms * 1e-3) / 1e12, 3),
-                     "frac_of_fp64_vector_peak": round(flop / (dev_ms * 1e-3) / 1e12 / FP64_VECTOR_PEAK_TFLOPS, 4),
-                     "host_float64_s_per_room": round(host_s, 4), "host_rooms_timed": n_host,
-                     "speedup_vs_host": round(host_s * R * 1000.0 / dev_ms, 1), "max_err_over_peak_vs_host": err,
-                     "mean_n_taps": float(np.mean(taps_h))})
-    cpus = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else os.cpu_count()
-    line = {"metric": "rir", "rooms": R, "rir_s": a.seconds, "fs": FS, "c": C, "tw": TW, "tile": tile, "iters": a.iters,
-            "repeats": a.repeats, "cases": rows, "host_threads": 1, "host_cpus_available": cpus,
-            "fp64_vector_peak_tflops": FP64_VECTOR_PEAK_TFLOPS, "train_step_ms_batch32": 157.0,
-            "device": torch.cuda.get_device_name(0)}
-    s = json.dumps(line)
-    print(s)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(s + "\n")
+    N = sampler.n_images(K, FS, C, TW)
+    call = lambda: eng.rir(rooms, n_taps, K, N, fs=FS, c=C, tw=TW)
+    ms = benchlib.alternate({name: call}, a.iters, a.repeats, warmup=2)[name]
+    rir, length = call()
+    rooms_h, taps_h, got = rooms.cpu().numpy(), n_taps.cpu().numpy(), rir.cpu().numpy()
+    n_host = max(1, min(a.host_rooms, R))
+    host_rir(rooms_h[0], 64, K, (1, 1, 1))                       # (imports, first-use costs)
+    t0 = time.perf_counter()
+    want = [host_rir(rooms_h[r], int(taps_h[r]), K, N) for r in range(n_host)]
+    host_s = (time.perf_counter() - t0) / n_host
+    err = max(float(np.max(np.abs(got[r] - want[r]))) / float(np.max(np.abs(want[r]))) for r in range(n_host))
+    images, pairs, visits = work(rooms_h, taps_h, K, N, tile)
+    dev_ms, (med, lo, hi) = statistics.median(ms), benchlib.summary(ms)
+    flop = 9 * pairs + 2 * visits
+    return {"case": name, "taps": K, "n_images": list(N), "images_enumerated_per_room": 8 * math.prod(2 * n + 1 for n in N),
+            "images_reaching": images, "pairs_in_window": pairs, "list_entries_visited": visits,
+            "device_ms_per_call": med, "device_ms_min": lo, "device_ms_max": hi,
+            "device_ms_per_room": round(dev_ms / R, 5), "float64_flop": flop,
+            "float64_tflops": round(flop / (dev_ms * 1e-3) / 1e12, 3),
+            "frac_of_fp64_vector_peak": round(flop / (dev_ms * 1e-3) / 1e12 / FP64_VECTOR_PEAK_TFLOPS, 4),
+            "host_float64_s_per_room": round(host_s, 4), "host_rooms_timed": n_host,
+            "speedup_vs_host": round(host_s * R * 1000.0 / dev_ms, 1), "max_err_over_peak_vs_host": err,
+            "mean_n_taps": float(np.mean(taps_h)), "device": torch.cuda.get_device_name(0), "tile": tile}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rooms", type=int, default=32)
+    ap.add_argument("--seconds", type=float, default=0.5)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--host-rooms", type=int, default=2)
+    ap.add_argument("--limit", type=float, default=120.0)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--case", choices=CASES, default=None, help="(internal) run one case")
+    a = ap.parse_args()
+    if a.case is not None:
+        return benchlib.print_case(run_case(a, a.case))
+    rows, stopped = benchlib.run_cases(__file__, benchlib.flags(a, "rooms", "seconds", "iters", "repeats", "host_rooms"),
+                                       [(name, (name,)) for name in CASES], a.limit)
+    device, tile = benchlib.lift(rows, "device", "tile")
+    line = {"metric": "rir", "rooms": a.rooms, "rir_s": a.seconds, "fs": FS, "c": C, "tw": TW, "tile": tile, "iters": a.iters,
+            "repeats": a.repeats, "limit_s_per_case": a.limit, "cases": rows, "stopped": stopped, "host_threads": 1,
+            "host_cpus_available": benchlib.host_cpus(), "fp64_vector_peak_tflops": FP64_VECTOR_PEAK_TFLOPS,
+            "train_step_ms_batch32": 157.0, "device": device}
+    benchlib.emit(line, a.out, stopped)
 
 
 if __name__ == "__main__":

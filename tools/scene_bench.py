@@ -4,26 +4,26 @@ talker response; a float64 scipy.signal.fftconvolve chain on one host thread).
     python tools/scene_bench.py [--batch 32] [--seconds 2] [--rir-seconds 0.5] [--iters 20] [--repeats 7]
                                 [--host-clips 2] [--limit 180] [--out PATH]
 
-Prints one JSON line (and writes it to --out, default profiles/r15_scene_bench.json).  One case per source count S = 0, 1,
-2, 4 at 16 kHz: --batch clips of --seconds, every response (the talker's and each source's) --rir-seconds long, every row
-with all S sources, segments of 3 s looping from a random offset, a dry noise as well.  Every case runs in a process of
-its own under a time limit of --limit seconds; after a case that fails or runs out of time no further case is started.
+Prints one JSON line (and writes it to --out when one is given: profiles/r15_scene_bench.json was written by passing
+--out).  One case per source count S = 0, 1, 2, 4 at 16 kHz: --batch clips of --seconds, every response (the talker's and
+each source's) --rir-seconds long, every row with all S sources, segments of 3 s looping from a random offset, a dry noise
+as well.  Every case runs isolated under --limit seconds and the two calls are timed alternately (tools/benchlib.py).
 Per case: device ms per Engine.scene call and per Engine.mix call on the same clean batch, dry noise and talker responses
-(HIP events around `iters` calls after a warm-up; the two are measured alternately, `repeats` times each, and the median
-and the spread are reported), their ratio, the seconds the host takes per clip for the same scene in float64 (fftconvolve
-of the clip and of each looped segment, powers, gains, sum and peak guard; timed on the first --host-clips clips), and the
-largest difference of those clips' noisy rows from the host's, in float32 ulps of the row's peak.
+(the median and the spread of `repeats` measurements of `iters` calls), their ratio, the seconds the host takes per clip
+for the same scene in float64 (fftconvolve of the clip and of each looped segment, powers, gains, sum and peak guard;
+timed on the first --host-clips clips), and the largest difference of those clips' noisy rows from the host's, in float32
+ulps of the row's peak.
 
 cmgan_mix is the S = 0 case of cmgan_scene and runs the same kernels (cmgan_amd/csrc/scene.hip), so the S = 0 row times
 one code path twice and its `same_bits_as_mix` holds by construction; profiles/r15_scene_bench.json was measured when
 Engine.mix still had kernels of its own."""
 import argparse
-import json
 import os
 import statistics
-import subprocess
 import sys
 import time
+
+import benchlib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -89,24 +89,7 @@ def run_case(B, seconds, rir_seconds, S, iters, repeats, host_clips):
     calls = {"scene": lambda: eng.scene(clean, bank, n_start, n_len, n_off, snr, *src, rir, idx, rlen, s_idx, s_rlen, peak=PEAK,
                                         early=EARLY),
              "mix": lambda: eng.mix(clean, bank, n_start, n_len, n_off, snr, rir, idx, rlen, peak=PEAK, early=EARLY)}
-
-    def timed(call):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            call()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / iters
-
-    for _ in range(2):
-        for c in calls.values():
-            c()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in calls}
-    for _ in range(repeats):                                              # alternately: both see the same machine
-        for k, c in calls.items():
-            ms[k].append(timed(c))
+    ms = benchlib.alternate(calls, iters, repeats, warmup=2)
     got = calls["scene"]()[0].cpu().numpy()
     same_as_mix = bool(torch.equal(calls["scene"]()[0], calls["mix"]()[0])) if S == 0 else None
     n_host = max(1, min(host_clips, B))
@@ -119,11 +102,11 @@ def run_case(B, seconds, rir_seconds, S, iters, repeats, host_clips):
         host_s.append(s)
         ulps = max(ulps, float(np.max(np.abs(got[b] - want)) / np.spacing(np.float32(np.max(np.abs(want))))))
     med = {k: statistics.median(v) for k, v in ms.items()}
+    sc, mx = benchlib.summary(ms["scene"]), benchlib.summary(ms["mix"])
     macs = B * L * K * (1 + S)                                            # (the talker's taps beyond the clip's start are fewer)
     return {"case": f"S={S}", "sources": S, "samples_per_clip": L, "taps": K,
-            "scene_ms_per_call": round(med["scene"], 4), "scene_ms_min": round(min(ms["scene"]), 4),
-            "scene_ms_max": round(max(ms["scene"]), 4), "mix_ms_per_call": round(med["mix"], 4),
-            "mix_ms_min": round(min(ms["mix"]), 4), "mix_ms_max": round(max(ms["mix"]), 4),
+            "scene_ms_per_call": sc[0], "scene_ms_min": sc[1], "scene_ms_max": sc[2],
+            "mix_ms_per_call": mx[0], "mix_ms_min": mx[1], "mix_ms_max": mx[2],
             "scene_over_mix": round(med["scene"] / med["mix"], 3), "gmac_per_s": round(macs / (med["scene"] * 1e-3) / 1e9, 1),
             "same_bits_as_mix": same_as_mix, "host_fftconvolve_s_per_clip": round(statistics.median(host_s), 5),
             "host_clips_timed": n_host, "host_ms_per_batch": round(statistics.median(host_s) * B * 1000.0, 2),
@@ -140,39 +123,17 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--host-clips", type=int, default=2)
     ap.add_argument("--limit", type=float, default=180.0)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r15_scene_bench.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--case", type=int, default=None, metavar="S", help="(internal) run one case")
     a = ap.parse_args()
     if a.case is not None:
-        print("CASE " + json.dumps(run_case(a.batch, a.seconds, a.rir_seconds, a.case, a.iters, a.repeats, a.host_clips)))
-        return
-    rows, stopped = [], None
-    for S in SOURCES:
-        cmd = [sys.executable, os.path.abspath(__file__), "--batch", str(a.batch), "--seconds", str(a.seconds), "--rir-seconds",
-               str(a.rir_seconds), "--iters", str(a.iters), "--repeats", str(a.repeats), "--host-clips", str(a.host_clips),
-               "--case", str(S)]
-        try:
-            r = subprocess.run(cmd, capture_output=True, text=True, timeout=a.limit)
-        except subprocess.TimeoutExpired:
-            stopped = f"S={S}: no result within {a.limit} s"
-            break
-        line = next((l for l in r.stdout.splitlines() if l.startswith("CASE ")), None)
-        if r.returncode != 0 or line is None:
-            stopped = f"S={S}: exit status {r.returncode}: {r.stderr.strip()[-400:]}"
-            break
-        rows.append(json.loads(line[5:]))
-    cpus = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else os.cpu_count()
+        return benchlib.print_case(run_case(a.batch, a.seconds, a.rir_seconds, a.case, a.iters, a.repeats, a.host_clips))
+    common = benchlib.flags(a, "batch", "seconds", "rir_seconds", "iters", "repeats", "host_clips")
+    rows, stopped = benchlib.run_cases(__file__, common, [(f"S={S}", (S,)) for S in SOURCES], a.limit)
     line = {"metric": "scene", "batch": a.batch, "fs": FS, "seconds": a.seconds, "rir_seconds": a.rir_seconds, "peak": PEAK,
             "early": EARLY, "launches_per_call": 6, "iters": a.iters, "repeats": a.repeats, "limit_s_per_case": a.limit,
-            "cases": rows, "stopped": stopped, "host_threads": 1, "host_cpus_available": cpus}
-    s = json.dumps(line)
-    print(s)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(s + "\n")
-    if stopped:
-        raise SystemExit(1)
+            "cases": rows, "stopped": stopped, "host_threads": 1, "host_cpus_available": benchlib.host_cpus()}
+    benchlib.emit(line, a.out, stopped)
 
 
 if __name__ == "__main__":

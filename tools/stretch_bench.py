@@ -3,25 +3,24 @@ model of tests/stretch_model.py on one host thread; Engine.warp; Engine.mix with
 
     python tools/stretch_bench.py [--batch 32] [--iters 100] [--repeats 7] [--host-clips 2] [--limit 240] [--out PATH]
 
-Prints one JSON line (and writes it to --out, default profiles/r16_stretch_bench.json).  Two cases at 16 kHz: --batch clips
-of ceil(32000 x 1.1) samples stretched to 32000 (2 s batches) and of ceil(160000 x 1.1) stretched to 160000 (10 s), one
-rate per row, uniform in 0.9 .. 1.1, hop = 256, search = 160; the clips are a harmonic tone with a gliding pitch under an
-envelope, plus noise.  Every case runs in a process of its own under a time limit of --limit seconds; after a case that
-fails or runs out of time no further case is started.  Per case: device ms per Engine.stretch call (one launch, one
+Prints one JSON line (and writes it to --out when one is given: profiles/r16_stretch_bench.json was written by passing
+--out).  Two cases at 16 kHz: --batch clips of ceil(32000 x 1.1) samples stretched to 32000 (2 s batches) and of
+ceil(160000 x 1.1) stretched to 160000 (10 s), one rate per row, uniform in 0.9 .. 1.1, hop = 256, search = 160; the clips
+are a harmonic tone with a gliding pitch under an envelope, plus noise.  Every case runs isolated under --limit seconds
+and the calls are timed alternately (tools/benchlib.py).  Per case: device ms per Engine.stretch call (one launch, one
 block per row), the same call with every rate at 1.0 (no frame is searched) and at 1.1, Engine.warp on the same batch at
-the same rates, and Engine.mix without a RIR on the stretched batch (HIP events around `iters` calls after a warm-up; the
-calls are measured alternately, `repeats` times each, and the median and the spread are reported), the frames and the
-searched frames per clip, the seconds the host takes per clip for the numpy model (positions and cross-fade, timed on the
-first --host-clips clips), and a check of those clips against the model: every position equal, the samples in float32
-ulps."""
+the same rates, and Engine.mix without a RIR on the stretched batch (the median and the spread of `repeats` measurements
+of `iters` calls), the frames and the searched frames per clip, the seconds the host takes per clip for the numpy model
+(positions and cross-fade, timed on the first --host-clips clips), and a check of those clips against the model: every
+position equal, the samples in float32 ulps."""
 import argparse
-import json
 import math
 import os
 import statistics
-import subprocess
 import sys
 import time
+
+import benchlib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -68,34 +67,13 @@ def run_case(B, seconds, iters, repeats, host_clips):
     fast = torch.full((B,), HI, dtype=torch.float64, device=dev)
     out = torch.empty(B, N, dtype=torch.float32, device=dev)
     scratch = torch.empty_like(out)
-    bank = torch.from_numpy((0.1 * rng.standard_normal(10 * FS)).astype(np.float32)).to(dev)
-    start = torch.zeros(B, dtype=torch.int64, device=dev)
-    length = torch.full((B,), bank.numel(), dtype=torch.int64, device=dev)
-    off = torch.arange(B, dtype=torch.int64, device=dev) * 977
-    snr = torch.linspace(0.0, 20.0, B, dtype=torch.float32, device=dev)
+    beside = benchlib.mix_beside(rng, B, dev)
     calls = {"stretch": lambda: eng.stretch(wav, rate, N, hop=HOP, search=SEARCH, out=out),
              "stretch_rate_1": lambda: eng.stretch(wav, ones, N, hop=HOP, search=SEARCH, out=scratch),
              "stretch_rate_1p1": lambda: eng.stretch(wav, fast, N, hop=HOP, search=SEARCH, out=scratch),
              "warp": lambda: eng.warp(wav, rate, N, out=scratch),
-             "mix": lambda: eng.mix(out, bank, start, length, off, snr)}
-
-    def timed(call):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            call()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / iters
-
-    for _ in range(3):
-        for c in calls.values():
-            c()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in calls}
-    for _ in range(repeats):                                          # alternately: all see the same machine
-        for k, c in calls.items():
-            ms[k].append(timed(c))
+             "mix": lambda: eng.mix(out, *beside)}
+    ms = benchlib.alternate(calls, iters, repeats, warmup=3)
     got, n_out, status, pos, searched = (t.cpu().numpy() for t in eng.stretch(wav, rate, N, hop=HOP, search=SEARCH, info=True))
     _, _, _, _, searched_fast = (t.cpu().numpy() for t in eng.stretch(wav, fast, N, hop=HOP, search=SEARCH, info=True))
     n_host = max(1, min(host_clips, B))
@@ -110,16 +88,17 @@ def run_case(B, seconds, iters, repeats, host_clips):
         err = np.abs(got[b, :len(want)].astype(np.float64) - want.astype(np.float64)) / np.spacing(np.maximum(np.abs(want), 1e-30))
         ulps = max(ulps, float(np.max(err)))
     med = {k: statistics.median(v) for k, v in ms.items()}
+    st, wp, mx = (benchlib.summary(ms[k]) for k in ("stretch", "warp", "mix"))
     K = -(-N // HOP)
     return {"case": f"{B}x{seconds}s", "samples_in_per_clip": L, "samples_out_per_clip": N, "frames_per_clip": K,
             "searched_frames_per_clip_mean": round(float(searched.mean()), 1), "searched_frames_per_clip_max": int(searched.max()),
             "searched_frames_per_clip_rate_1p1": round(float(searched_fast.mean()), 1),
-            "stretch_ms_per_call": round(med["stretch"], 4), "stretch_ms_min": round(min(ms["stretch"]), 4),
-            "stretch_ms_max": round(max(ms["stretch"]), 4), "stretch_rate_1_ms_per_call": round(med["stretch_rate_1"], 4),
-            "stretch_rate_1p1_ms_per_call": round(med["stretch_rate_1p1"], 4),
-            "warp_ms_per_call": round(med["warp"], 4), "warp_ms_min": round(min(ms["warp"]), 4), "warp_ms_max": round(max(ms["warp"]), 4),
-            "mix_no_rir_ms_per_call": round(med["mix"], 4), "mix_ms_min": round(min(ms["mix"]), 4),
-            "mix_ms_max": round(max(ms["mix"]), 4), "stretch_over_warp": round(med["stretch"] / med["warp"], 3),
+            "stretch_ms_per_call": st[0], "stretch_ms_min": st[1], "stretch_ms_max": st[2],
+            "stretch_rate_1_ms_per_call": benchlib.summary(ms["stretch_rate_1"])[0],
+            "stretch_rate_1p1_ms_per_call": benchlib.summary(ms["stretch_rate_1p1"])[0],
+            "warp_ms_per_call": wp[0], "warp_ms_min": wp[1], "warp_ms_max": wp[2],
+            "mix_no_rir_ms_per_call": mx[0], "mix_ms_min": mx[1], "mix_ms_max": mx[2],
+            "stretch_over_warp": round(med["stretch"] / med["warp"], 3),
             "stretch_over_mix": round(med["stretch"] / med["mix"], 3),
             "msamples_out_per_s": round(B * N / (med["stretch"] * 1e-3) / 1e6, 1),
             "us_per_searched_frame_of_the_slowest_row": round((med["stretch"] - med["stretch_rate_1"]) * 1e3 / max(int(searched.max()), 1), 3),
@@ -137,38 +116,17 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--host-clips", type=int, default=2)
     ap.add_argument("--limit", type=float, default=240.0)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r16_stretch_bench.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--case", type=int, default=None, metavar="SECONDS", help="(internal) run one case")
     a = ap.parse_args()
     if a.case is not None:
-        print("CASE " + json.dumps(run_case(a.batch, a.case, a.iters, a.repeats, a.host_clips)))
-        return
-    rows, stopped = [], None
-    for seconds in (2, 10):
-        cmd = [sys.executable, os.path.abspath(__file__), "--batch", str(a.batch), "--iters", str(a.iters), "--repeats",
-               str(a.repeats), "--host-clips", str(a.host_clips), "--case", str(seconds)]
-        try:
-            r = subprocess.run(cmd, capture_output=True, text=True, timeout=a.limit)
-        except subprocess.TimeoutExpired:
-            stopped = f"{seconds}s: no result within {a.limit} s"
-            break
-        line = next((l for l in r.stdout.splitlines() if l.startswith("CASE ")), None)
-        if r.returncode != 0 or line is None:
-            stopped = f"{seconds}s: exit status {r.returncode}: {r.stderr.strip()[-400:]}"
-            break
-        rows.append(json.loads(line[5:]))
-    cpus = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else os.cpu_count()
+        return benchlib.print_case(run_case(a.batch, a.case, a.iters, a.repeats, a.host_clips))
+    rows, stopped = benchlib.run_cases(__file__, benchlib.flags(a, "batch", "iters", "repeats", "host_clips"),
+                                       [(f"{sec}s", (sec,)) for sec in (2, 10)], a.limit)
     line = {"metric": "stretch", "batch": a.batch, "fs": FS, "rates": [0.9, 1.1], "hop": HOP, "search": SEARCH,
             "launches_per_call": 1, "iters": a.iters, "repeats": a.repeats, "limit_s_per_case": a.limit, "cases": rows,
-            "stopped": stopped, "host_threads": 1, "host_cpus_available": cpus}
-    s = json.dumps(line)
-    print(s)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(s + "\n")
-    if stopped:
-        raise SystemExit(1)
+            "stopped": stopped, "host_threads": 1, "host_cpus_available": benchlib.host_cpus()}
+    benchlib.emit(line, a.out, stopped)
 
 
 if __name__ == "__main__":

@@ -3,28 +3,27 @@ scipy.signal.resample_poly on one host thread; Engine.mix without a RIR).
 
     python tools/warp_bench.py [--batch 32] [--iters 100] [--repeats 7] [--host-clips 4] [--limit 120] [--out PATH]
 
-Prints one JSON line (and writes it to --out, default profiles/r14_warp_bench.json).  Two cases at 16 kHz: --batch clips
-of ceil(32000 x 1.1) samples warped to 32000 (2 s batches) and of ceil(160000 x 1.1) warped to 160000 (10 s), one rate
-per row, uniform in 0.9 .. 1.1, zeros = 24, rolloff = 0.95.  Every case runs in a process of its own under a time limit
-of --limit seconds; after a case that fails or runs out of time no further case is started.  Per case: device ms per
-Engine.warp call (one launch) and per Engine.mix call without a RIR on the warped batch (HIP events around `iters` calls
-after a warm-up; the two are measured alternately, `repeats` times each, and the median and the spread are reported), the
-same warp with every rate at 1.0 and at 1.1 (the tap count follows the rate), the seconds the host takes per clip for
-scipy.signal.resample_poly(x, 10, 11) in float64 - ONE fixed ratio, the nearest thing the host has (timed on the first
---host-clips clips) -, the taps per output, and a check of 256 outputs of one row against the definition written out in
-float64 numpy (np.sinc, np.cos), in float32 ulps.
+Prints one JSON line (and writes it to --out when one is given: profiles/r14_warp_bench.json was written by passing
+--out).  Two cases at 16 kHz: --batch clips of ceil(32000 x 1.1) samples warped to 32000 (2 s batches) and of
+ceil(160000 x 1.1) warped to 160000 (10 s), one rate per row, uniform in 0.9 .. 1.1, zeros = 24, rolloff = 0.95.  Every
+case runs isolated under --limit seconds and the calls are timed alternately (tools/benchlib.py).  Per case: device ms
+per Engine.warp call (one launch) and per Engine.mix call without a RIR on the warped batch (the median and the spread of
+`repeats` measurements of `iters` calls), the same warp with every rate at 1.0 and at 1.1 (the tap count follows the
+rate), the seconds the host takes per clip for scipy.signal.resample_poly(x, 10, 11) in float64 - ONE fixed ratio, the
+nearest thing the host has (timed on the first --host-clips clips) -, the taps per output, and a check of 256 outputs of
+one row against the definition written out in float64 numpy (np.sinc, np.cos), in float32 ulps.
 
 A/B of the tap recurrence against sinpi / cospi at every tap: build the other form side by side,
 `cmgan_amd.build.build(variant="direct", extra_flags=["-DWARP_DIRECT_TRIG"])`, and run this tool alternately with and
 without `CMGAN_HIP_LIB=cmgan_amd/lib/variants/direct/libcmgan_hip.so` in one session."""
 import argparse
-import json
 import math
 import os
 import statistics
-import subprocess
 import sys
 import time
+
+import benchlib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -73,33 +72,12 @@ def run_case(B, seconds, iters, repeats, host_clips):
     fast = torch.full((B,), HI, dtype=torch.float64, device=dev)
     out = torch.empty(B, N, dtype=torch.float32, device=dev)
     scratch = torch.empty_like(out)
-    bank = torch.from_numpy((0.1 * rng.standard_normal(10 * FS)).astype(np.float32)).to(dev)
-    start = torch.zeros(B, dtype=torch.int64, device=dev)
-    length = torch.full((B,), bank.numel(), dtype=torch.int64, device=dev)
-    off = torch.arange(B, dtype=torch.int64, device=dev) * 977
-    snr = torch.linspace(0.0, 20.0, B, dtype=torch.float32, device=dev)
+    beside = benchlib.mix_beside(rng, B, dev)
     calls = {"warp": lambda: eng.warp(wav, rate, N, zeros=ZEROS, rolloff=ROLLOFF, out=out),
              "warp_rate_1": lambda: eng.warp(wav, ones, N, zeros=ZEROS, rolloff=ROLLOFF, out=scratch),
              "warp_rate_1p1": lambda: eng.warp(wav, fast, N, zeros=ZEROS, rolloff=ROLLOFF, out=scratch),
-             "mix": lambda: eng.mix(out, bank, start, length, off, snr)}
-
-    def timed(call):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            call()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / iters
-
-    for _ in range(3):
-        for c in calls.values():
-            c()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in calls}
-    for _ in range(repeats):                                          # alternately: all see the same machine
-        for k, c in calls.items():
-            ms[k].append(timed(c))
+             "mix": lambda: eng.mix(out, *beside)}
+    ms = benchlib.alternate(calls, iters, repeats, warmup=3)
     got, n_out, status = (t.cpu().numpy() for t in eng.warp(wav, rate, N, zeros=ZEROS, rolloff=ROLLOFF, info=True))
     n_host = max(1, min(host_clips, B))
     resample_poly(x[0, :2000].astype(np.float64), 10, 11)             # (imports, first-use costs)
@@ -111,14 +89,15 @@ def run_case(B, seconds, iters, repeats, host_clips):
     want = host_outputs(x[0], float(rate_np[0]), ns).astype(np.float32)
     ulps = float(np.max(np.abs(got[0, ns].astype(np.float64) - want.astype(np.float64)) / np.spacing(np.abs(want))))
     med = {k: statistics.median(v) for k, v in ms.items()}
+    wp, mx = benchlib.summary(ms["warp"]), benchlib.summary(ms["mix"])
     fc = ROLLOFF / np.maximum(rate_np, 1.0)
     taps = float(np.mean(2.0 * ZEROS / fc))
     return {"case": f"{B}x{seconds}s", "samples_in_per_clip": L, "samples_out_per_clip": N, "tiles_per_clip": -(-N // tile),
-            "warp_ms_per_call": round(med["warp"], 4), "warp_ms_min": round(min(ms["warp"]), 4),
-            "warp_ms_max": round(max(ms["warp"]), 4), "warp_rate_1_ms_per_call": round(med["warp_rate_1"], 4),
-            "warp_rate_1p1_ms_per_call": round(med["warp_rate_1p1"], 4),
-            "mix_no_rir_ms_per_call": round(med["mix"], 4), "mix_ms_min": round(min(ms["mix"]), 4),
-            "mix_ms_max": round(max(ms["mix"]), 4), "warp_over_mix": round(med["warp"] / med["mix"], 3),
+            "warp_ms_per_call": wp[0], "warp_ms_min": wp[1], "warp_ms_max": wp[2],
+            "warp_rate_1_ms_per_call": benchlib.summary(ms["warp_rate_1"])[0],
+            "warp_rate_1p1_ms_per_call": benchlib.summary(ms["warp_rate_1p1"])[0],
+            "mix_no_rir_ms_per_call": mx[0], "mix_ms_min": mx[1], "mix_ms_max": mx[2],
+            "warp_over_mix": round(med["warp"] / med["mix"], 3),
             "msamples_out_per_s": round(B * N / (med["warp"] * 1e-3) / 1e6, 1), "mean_taps_per_output": round(taps, 1),
             "gtaps_per_s": round(B * N * taps / (med["warp"] * 1e-3) / 1e9, 1),
             "host_resample_poly_s_per_clip": round(host_s, 5), "host_clips_timed": n_host,
@@ -134,38 +113,17 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--host-clips", type=int, default=4)
     ap.add_argument("--limit", type=float, default=120.0)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r14_warp_bench.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--case", type=int, default=None, metavar="SECONDS", help="(internal) run one case")
     a = ap.parse_args()
     if a.case is not None:
-        print("CASE " + json.dumps(run_case(a.batch, a.case, a.iters, a.repeats, a.host_clips)))
-        return
-    rows, stopped = [], None
-    for seconds in (2, 10):
-        cmd = [sys.executable, os.path.abspath(__file__), "--batch", str(a.batch), "--iters", str(a.iters), "--repeats",
-               str(a.repeats), "--host-clips", str(a.host_clips), "--case", str(seconds)]
-        try:
-            r = subprocess.run(cmd, capture_output=True, text=True, timeout=a.limit)
-        except subprocess.TimeoutExpired:
-            stopped = f"{seconds}s: no result within {a.limit} s"
-            break
-        line = next((l for l in r.stdout.splitlines() if l.startswith("CASE ")), None)
-        if r.returncode != 0 or line is None:
-            stopped = f"{seconds}s: exit status {r.returncode}: {r.stderr.strip()[-400:]}"
-            break
-        rows.append(json.loads(line[5:]))
-    cpus = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else os.cpu_count()
+        return benchlib.print_case(run_case(a.batch, a.case, a.iters, a.repeats, a.host_clips))
+    rows, stopped = benchlib.run_cases(__file__, benchlib.flags(a, "batch", "iters", "repeats", "host_clips"),
+                                       [(f"{sec}s", (sec,)) for sec in (2, 10)], a.limit)
     line = {"metric": "warp", "batch": a.batch, "fs": FS, "rates": [0.9, 1.1], "zeros": ZEROS, "rolloff": ROLLOFF,
             "launches_per_call": 1, "iters": a.iters, "repeats": a.repeats, "limit_s_per_case": a.limit, "cases": rows,
-            "stopped": stopped, "host_threads": 1, "host_cpus_available": cpus}
-    s = json.dumps(line)
-    print(s)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(s + "\n")
-    if stopped:
-        raise SystemExit(1)
+            "stopped": stopped, "host_threads": 1, "host_cpus_available": benchlib.host_cpus()}
+    benchlib.emit(line, a.out, stopped)
 
 
 if __name__ == "__main__":
