@@ -34,20 +34,12 @@
 #include <stdint.h>
 
 #include "api_internal.h"
+#include "rir_common.hip.h"
 
 namespace {
 
-constexpr int RR_TPB = 256;                 // threads of both kernels
-constexpr int RR_TILE = RR_TPB;             // taps per block of rir_taps: one per thread
-constexpr int RR_CAP = 512;                 // images per LDS list chunk: 5 float64 planes, 20 KiB
-constexpr int RR_UNR = 8;                   // list entries whose t0 a thread fetches at once (RR_CAP is a multiple)
-constexpr int RR_MAX_K = 65536;             // longest response (the limit of cmgan_mix)
-constexpr int RR_MAX_N = 255;               // largest image index per axis
-constexpr int RR_MAX_TW = 64;               // largest half-width of the fractional-delay filter
-constexpr int RR_PW = RR_MAX_N + 2;         // powers b^0 .. b^(N + 1) of one coefficient
 constexpr int RR_HEAD = 16;                 // record: 15 room numbers, k_r
 constexpr int RR_REC = RR_HEAD + 6 * RR_PW; // float64 words of a row's record in the workspace
-constexpr double RR_PI = 3.14159265358979323846;
 
 struct RirArgs {
     const double* rooms;
@@ -83,25 +75,6 @@ __global__ __launch_bounds__(RR_TPB) void rir_prep(RirArgs a) {
     }
 }
 
-// exclusive prefix sum of one int per thread in thread order; `total` is the block's sum
-__device__ inline int rr_scan(int v, int (*s)[RR_TPB], int& total) {
-    const int t = threadIdx.x;
-    int cur = 0;
-    s[0][t] = v;
-    __syncthreads();
-    for (int off = 1; off < RR_TPB; off <<= 1) {
-        int x = s[cur][t];
-        if (t >= off) x += s[cur][t - off];
-        s[cur ^ 1][t] = x;
-        cur ^= 1;
-        __syncthreads();
-    }
-    total = s[cur][RR_TPB - 1];
-    const int incl = s[cur][t];
-    __syncthreads();
-    return incl - v;
-}
-
 // one list entry for the tap at t = tt (its window test included); `sgn` = (-1)^j, cj / sj = cos / sin(pi j / tw)
 __device__ inline double rr_tap(double acc, double tt, double twd, double sgn, double cj, double sj, double sp, double ha,
                                 double hc, double hs) {
@@ -109,9 +82,6 @@ __device__ inline double rr_tap(double acc, double tt, double twd, double sgn, d
     const double sc = tt == 0.0 ? 1.0 : sgn * sp / tt;
     return fma(wa, sc, acc);
 }
-
-// a double bound of an nz range as an int in [-Nz - 1, Nz + 1] (NaN included: fmax / fmin drop it)
-__device__ inline int rr_bound(double v, int Nz) { return (int)fmin(fmax(v, (double)(-Nz - 1)), (double)(Nz + 1)); }
 
 __global__ __launch_bounds__(RR_TPB) void rir_taps(RirArgs a) {
     __shared__ double s_pw[6 * RR_PW];
@@ -240,8 +210,6 @@ __global__ __launch_bounds__(RR_TPB) void rir_taps(RirArgs a) {
     }
     if (k < a.K) out[k] = k < kr ? (float)acc : 0.f;
 }
-
-inline size_t rr_up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 inline bool rr_shape_ok(int R, int K, int tw) {
     return R >= 1 && R <= 65535 && K >= 1 && K <= RR_MAX_K && tw >= 1 && tw <= RR_MAX_TW;

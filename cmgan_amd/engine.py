@@ -232,6 +232,23 @@ def check_rir_args(device, rooms, n_taps, K, n_images, fs=16000, c: float = 343.
     return R, int(K), N
 
 
+RIR_MAX_BANDS = 8             # most frequency bands of cmgan_rir_bands
+RIR_MAX_FILTER = 1023         # longest filter of its filterbank (odd)
+
+
+def check_rir_bands_args(device, rooms, bands, n_taps, K, filters, n_images, fs=16000, c: float = 343.0, tw: int = 40,
+                         out=None):
+    """Argument rules of Engine.rir_bands (shapes, dtypes, devices and host scalars; pure host code).  Returns
+    (R, K, (Nx, Ny, Nz), NB, NF)."""
+    R, K, N = check_rir_args(device, rooms, n_taps, K, n_images, fs, c, tw, out)
+    tensor_arg(bands, "bands", torch.float64, device, f"[{R}, NB, 7] with 1 <= NB <= {RIR_MAX_BANDS}",
+               lambda t: t.dim() == 3 and t.size(0) == R and 1 <= t.size(1) <= RIR_MAX_BANDS and t.size(2) == 7)
+    NB = bands.size(1)
+    tensor_arg(filters, "filters", torch.float64, device, f"[{NB}, NF] with NF odd in [1, {RIR_MAX_FILTER}]",
+               lambda t: t.dim() == 2 and t.size(0) == NB and 1 <= t.size(1) <= RIR_MAX_FILTER and t.size(1) % 2 == 1)
+    return R, K, N, NB, filters.size(1)
+
+
 def _row_stride_ok(t, B: int, L: int) -> bool:
     return t.stride(1) == 1 and (B == 1 or t.stride(0) >= L)
 
@@ -460,7 +477,7 @@ class Engine:
             msg = self.lib.cmgan_last_error(None)
             raise _lib.CmganError(rc, msg.decode() if msg else "?")
         #: grow-only uint8 workspaces by name (_grow): "main", "branched" (enhance_graphed(branches > 1)), "conformer",
-        #: "metrics", "mix", "scene", "rir", "level", "channel" and ("resample", fs_in, fs_out), the rate pair's tap table
+        #: "metrics", "mix", "scene", "rir", "rir_bands", "level", "channel" and ("resample", fs_in, fs_out), the rate pair's tap table
         self._wss: dict = {}
         self._graphs: dict = {}          # enhance_graphed: input shape -> (graph, in, out, token)
         self._row_graphs: dict = {}      # streaming.enhance_windows: row shape -> (graph, in, out, token)
@@ -1128,6 +1145,32 @@ class Engine:
         rir, length = out
         self._call("cmgan_rir", rooms, n_taps, R, K, int(fs), float(c), int(tw), N[0], N[1], N[2], rir, K, length, ws,
                    ws.numel())
+        return rir, length
+
+    @_on_device
+    def rir_bands(self, rooms: torch.Tensor, bands: torch.Tensor, n_taps: torch.Tensor, K: int, filters: torch.Tensor,
+                  n_images, fs: int = 16000, c: float = 343.0, tw: int = 40, out=None):
+        """Room impulse responses with frequency-dependent walls and air absorption (cmgan_rir_bands, include/cmgan_hip.h):
+        Engine.rir simulated in NB frequency bands at once - one image list, one accumulator per band - and joined by a
+        filterbank.
+
+        rooms float64 [R, 15] as for Engine.rir (its six coefficients are not read); bands float64 [R, NB, 7], per band
+        the six reflection coefficients and the air attenuation m >= 0 in nepers per metre; n_taps int32 [R]; filters
+        float64 [NB, NF], NF odd, one FIR per band (`mixing.octave_filterbank`), whose delay (NF - 1) / 2 is taken out;
+        all on this Engine's device and read by the kernels only.  n_images must cover K + (NF - 1) / 2 taps.  `out` =
+        (float32 [R, K], int32 [R]) is written in place.  Returns (rir float32 [R, K], length int32 [R]), as Engine.rir
+        does.  An invalid row (a non-finite entry in columns 0 - 8 or in its band table, a size <= 0, a coefficient
+        outside [0, 1], a negative m) is zeros with length 1.  Float64 arithmetic, one rounding to float32;
+        bit-reproducible, row-independent, no synchronisation, graph-capturable after one call at the shape."""
+        R, K, N, NB, NF = check_rir_bands_args(self.device, rooms, bands, n_taps, K, filters, n_images, fs, c, tw, out)
+        ws = self._grow("rir_bands", int(self.lib.cmgan_rir_bands_workspace_bytes(self._h, R, K, int(tw), NB, NF)),
+                        f"[{R}, {K}] with tw = {tw}, {NB} bands and {NF} filter taps is outside what cmgan_rir_bands supports")
+        if out is None:
+            out = (torch.empty(R, K, dtype=torch.float32, device=self.device),
+                   torch.empty(R, dtype=torch.int32, device=self.device))
+        rir, length = out
+        self._call("cmgan_rir_bands", rooms, bands, n_taps, R, K, NB, filters, NF, int(fs), float(c), int(tw), N[0], N[1],
+                   N[2], rir, K, length, ws, ws.numel())
         return rir, length
 
     # ---- active speech level -------------------------------------------------------

@@ -13,6 +13,9 @@ takes - with `clean` the training target (the dry clip, or the clip with its ear
     # either a fixed bank       rirs = RirBank.simulate(engine, RoomSampler(), 256)
     # or a fresh room per row of every batch
     mixer = DynamicMixer(engine, noise, rooms=RoomSampler(rt60=(0.2, 0.8)), snr_db=(0, 20), early_ms=50)
+    # rooms whose reverberation time falls with frequency: walls that absorb more per octave (tilt) and air absorption
+    # (air: the caller's ranges of nepers per metre, one per band), in 7 octave bands (Engine.rir_bands / cmgan_rir_bands)
+    mixer = DynamicMixer(engine, noise, rooms=RoomSampler(bands=7, tilt=(0.0, 0.5), air=my_air_ranges), snr_db=(0, 20))
     # the recording channel: a random equaliser, a band limit and clipping per row (Engine.channel / cmgan_channel)
     mixer = DynamicMixer(engine, noise, rirs, channel=ChannelSampler(p_bandlimit=0.2, p_clip=0.1))
     clean = torch.utils.data.DataLoader(clean_only("data/train", 32000), batch_size=32, pin_memory=True, drop_last=True)
@@ -40,7 +43,7 @@ import torch.utils.data
 from .data import _natural_key, fit_length, read_wav
 from .engine import STRETCH_HOP, STRETCH_SEARCH, _whole_in
 
-__all__ = ["NoiseBank", "RirBank", "RoomSampler", "sabine_beta", "DynamicMixer", "MixingLoader", "CleanDataset",
+__all__ = ["NoiseBank", "RirBank", "RoomSampler", "sabine_beta", "octave_filterbank", "DynamicMixer", "MixingLoader", "CleanDataset",
            "clean_only", "Draw", "SceneDraw", "tile", "ChannelSampler", "biquad_peaking", "biquad_low_shelf", "biquad_high_shelf",
            "biquad_lowpass", "biquad_highpass", "butter_lowpass_sos", "warp_len", "stretch_len", "StretchDraw"]
 
@@ -193,16 +196,78 @@ def sabine_beta(rt60, dims) -> torch.Tensor:
     return torch.sqrt(1.0 - alpha)
 
 
+def octave_filterbank(fs, n_bands: int = 7, n_taps: int = 511, f0: float = 125.0) -> torch.Tensor:
+    """The FIR filterbank of Engine.rir_bands: float64 [n_bands, n_taps] on the host, n_taps odd, D = (n_taps - 1) / 2.
+
+    Band i is centred at f0 2^i.  On u = log2(f / f0) it has the gain 0.5 (1 + cos(pi (u - i))) for |u - i| < 1, the lowest
+    band flat down to DC and the highest flat up to Nyquist, so neighbouring bands sum to one.  The gains are sampled on M
+    points, M the smallest power of two >= 8 n_taps; the zero-phase inverse real FFT is centred at D, cut to n_taps taps
+    and multiplied by 0.5 (1 - cos(2 pi (j + 1) / (n_taps + 1))).  The last band is then replaced by delta_D minus the sum
+    of the others: the bank sums to a pure delay of D samples by construction (n_bands = 1 is delta).  A bank whose
+    second-highest centre is not below fs / 2 is rejected."""
+    if isinstance(n_bands, bool) or int(n_bands) != n_bands or not 1 <= n_bands <= 8:
+        raise ValueError(f"n_bands must be a whole number in [1, 8], got {n_bands}")
+    if isinstance(n_taps, bool) or int(n_taps) != n_taps or not 1 <= n_taps <= 1023 or int(n_taps) % 2 != 1:
+        raise ValueError(f"n_taps must be an odd whole number in [1, 1023], got {n_taps}")
+    fs, f0, NB, NF = float(fs), float(f0), int(n_bands), int(n_taps)
+    if not (0.0 < fs < math.inf and 0.0 < f0 < math.inf):
+        raise ValueError(f"fs and f0 must be positive and finite, got fs = {fs}, f0 = {f0}")
+    if NB >= 2 and not f0 * 2.0 ** (NB - 2) < 0.5 * fs:
+        raise ValueError(f"{NB} octave bands from {f0} Hz need the centre {f0 * 2.0 ** (NB - 2)} Hz of the second-highest band "
+                         f"below fs / 2 = {0.5 * fs} Hz")
+    D = (NF - 1) // 2
+    M = 1 << max(0, math.ceil(math.log2(8 * NF)))
+    f = np.arange(M // 2 + 1, dtype=np.float64) * (fs / M)
+    with np.errstate(divide="ignore"):
+        u = np.log2(f / f0)                                          # (-inf at DC: the lowest band's flat side)
+    bank = np.zeros((NB, NF))
+    j = np.arange(NF)
+    window = 0.5 * (1.0 - np.cos(2.0 * np.pi * (j + 1) / (NF + 1)))
+    for i in range(NB - 1):
+        x = np.clip(u - i, -1.0, 1.0)
+        gain = 0.5 * (1.0 + np.cos(np.pi * x))
+        if i == 0:
+            gain = np.where(u <= 0.0, 1.0, gain)
+        bank[i] = np.fft.irfft(gain, M)[(j - D) % M] * window
+    bank[NB - 1] = -bank[:NB - 1].sum(axis=0)
+    bank[NB - 1, D] += 1.0
+    return torch.from_numpy(bank)
+
+
+def _band_ranges(name: str, value, n: int):
+    """`n` (low, high) pairs with 0 <= low <= high < inf."""
+    try:
+        pairs = tuple((float(lo), float(hi)) for lo, hi in value)
+    except (TypeError, ValueError):
+        pairs = ()
+    if len(pairs) != n or not all(0.0 <= lo <= hi < math.inf for lo, hi in pairs):
+        raise ValueError(f"{name} must be None or {n} (low, high) pairs, one per band, with 0 <= low <= high, got {value}")
+    return pairs
+
+
 class RoomSampler:
     """Random shoe-box rooms for Engine.rir: `draw(R, K, fs)` -> `(rooms float64 [R, 15], n_taps int32 [R])`.
 
     Per row: the size uniform per axis between `dims` = (low, high) (metres), source and receiver uniform and independent
     in the room shrunk by `margin` on every side, rt60 uniform in `rt60` = (low, high) seconds; the six reflection
     coefficients are `sabine_beta(rt60, size)` and n_taps = min(K, ceil(rt60 fs)).  Everything is drawn from `generator`
-    (None: the device's default one) on the device with tensor arithmetic: no host synchronisation."""
+    (None: the device's default one) on the device with tensor arithmetic: no host synchronisation.
+
+    `bands` = n (1 .. 8) turns on the band model of Engine.rir_bands: walls whose absorption depends on frequency, and air
+    absorption, in n octave bands from 125 Hz joined by `octave_filterbank(fs, n, filter_taps)`.  `draw_bands(rooms)`,
+    called after `draw`, gives the float64 [R, n, 7] band table.  `tilt` = (low, high) is drawn per room, in octaves of
+    absorption growth per octave of frequency: alpha_b = clamp(alpha 2^(tilt (b - b_ref)), 0, 1) with alpha = 1 - beta^2 of
+    the table and b_ref the band nearest 1 kHz, so by Sabine's formula band b has the reverberation time rt60 2^(-tilt (b -
+    b_ref)) while its alpha_b stays below 1, and at 1 kHz the room is the one `draw` made.  `air` is None (no air
+    absorption) or n (low, high) ranges of the amplitude attenuation m_b in nepers per metre, drawn per room; there is no
+    default table of a "standard atmosphere": the values are the caller's.  Without `bands` (the default) the sampler is
+    what it was: the same draws from the generator, and `draw_bands` is an error."""
+
+    BAND_F0 = 125.0               # Hz: the centre of band 0
 
     def __init__(self, dims=((3.0, 3.0, 2.5), (10.0, 8.0, 4.0)), rt60=(0.2, 0.8), margin: float = 0.5,
-                 generator: Optional[torch.Generator] = None):
+                 generator: Optional[torch.Generator] = None, bands: Optional[int] = None, tilt=(0.0, 0.0), air=None,
+                 filter_taps: int = 511):
         try:
             lo, hi = (tuple(float(v) for v in d) for d in dims)
         except (TypeError, ValueError):
@@ -214,11 +279,64 @@ class RoomSampler:
         if not 0.0 <= margin < 0.5 * min(lo):
             raise ValueError(f"margin must lie in [0, {0.5 * min(lo)}): half the smallest room size of {dims}, got {margin}")
         self.lo, self.hi, self.rt60, self.margin, self.generator = lo, hi, (t_lo, t_hi), margin, generator
+        if bands is None:
+            if tuple(tilt) != (0.0, 0.0) or air is not None:
+                raise ValueError("tilt and air belong to the band model: give bands=n with them")
+            self.bands, self.tilt, self.air, self.filter_taps, self.band_ref = None, (0.0, 0.0), None, int(filter_taps), 0
+        else:
+            if isinstance(bands, bool) or int(bands) != bands or not 1 <= bands <= 8:
+                raise ValueError(f"bands must be None or a band count in [1, 8], got {bands}")
+            if isinstance(filter_taps, bool) or int(filter_taps) != filter_taps or not 1 <= filter_taps <= 1023 \
+                    or int(filter_taps) % 2 != 1:
+                raise ValueError(f"filter_taps must be an odd whole number in [1, 1023], got {filter_taps}")
+            self.bands, self.filter_taps = int(bands), int(filter_taps)
+            self.tilt = _pair("tilt", tilt, -math.inf, math.inf, "(low, high) with finite low <= high", closed=False, echo=True)
+            self.air = None if air is None else _band_ranges("air", air, self.bands)
+            # the band nearest 1 kHz on the octave scale
+            self.band_ref = min(max(int(round(math.log2(1000.0 / self.BAND_F0))), 0), self.bands - 1)
+        self._filters = {}
 
     def n_images(self, K: int, fs: int, c: float = SPEED_OF_SOUND, tw: int = RIR_TW):
         """(Nx, Ny, Nz) that leaves out no image of a K-tap response in any room this sampler draws: host arithmetic on
-        the LOWER size bound, ceil((K + tw) c / fs / (2 Lmin_axis)) + 1."""
+        the LOWER size bound, ceil((K + tw) c / fs / (2 Lmin_axis)) + 1.  With `bands` the ranges cover K + D taps, D the
+        filterbank's delay: Engine.rir_bands simulates the bands that far."""
+        if self.bands is not None:
+            K = K + (self.filter_taps - 1) // 2
         return tuple(int(math.ceil((K + tw) * c / fs / (2.0 * l))) + 1 for l in self.lo)
+
+    def filters(self, fs: int, device=None) -> torch.Tensor:
+        """`octave_filterbank(fs, bands, filter_taps)` on `device`: computed once per (fs, device) and kept."""
+        if self.bands is None:
+            raise ValueError("this RoomSampler has no bands")
+        key = (int(fs), str(device))
+        if key not in self._filters:
+            self._filters[key] = octave_filterbank(fs, self.bands, self.filter_taps, self.BAND_F0).to(device or "cpu")
+        return self._filters[key]
+
+    def draw_bands(self, rooms: torch.Tensor) -> torch.Tensor:
+        """The band table of rooms that `draw` made: float64 [R, bands, 7] for a drawn [R, 15] one, per band the six
+        reflection coefficients and m.  One rand(R, 1 + bands) from `generator` on the device of `rooms`, after the
+        room draws: column 0 is the room's tilt, column 1 + b the place of m_b in its range.  Per wall beta_b =
+        sqrt(1 - alpha_b); a band whose factor 2^(tilt (b - b_ref)) is exactly 1 keeps the table's beta itself."""
+        if self.bands is None:
+            raise ValueError("this RoomSampler has no bands")
+        if not isinstance(rooms, torch.Tensor) or rooms.dtype != torch.float64 or rooms.dim() != 2 or rooms.size(1) != 15:
+            raise ValueError("rooms must be a float64 [R, 15] table of RoomSampler.draw")
+        R, n = rooms.size(0), self.bands
+        u = torch.rand(R, 1 + n, dtype=torch.float64, generator=self.generator, device=rooms.device)
+        tilt = self.tilt[0] + (self.tilt[1] - self.tilt[0]) * u[:, 0]
+        step = torch.arange(n, dtype=torch.float64).to(rooms.device, non_blocking=True) - float(self.band_ref)
+        octaves = tilt[:, None] * step[None, :]                                        # [R, n]
+        beta = rooms[:, None, 9:15]                                                   # [R, 1, 6]
+        alpha = ((1.0 - beta * beta) * torch.exp2(octaves)[:, :, None]).clamp(0.0, 1.0)
+        walls = torch.where((octaves == 0.0)[:, :, None], beta.expand(R, n, 6), torch.sqrt(1.0 - alpha))
+        if self.air is None:
+            m = torch.zeros(R, n, dtype=torch.float64, device=rooms.device)
+        else:
+            lo = torch.tensor([p[0] for p in self.air], dtype=torch.float64).to(rooms.device, non_blocking=True)
+            hi = torch.tensor([p[1] for p in self.air], dtype=torch.float64).to(rooms.device, non_blocking=True)
+            m = lo + (hi - lo) * u[:, 1:]
+        return torch.cat([walls, m[:, :, None]], dim=2).contiguous()
 
     def draw(self, R: int, K: int, fs: int, device=None):
         gen = self.generator
@@ -412,10 +530,12 @@ class ChannelSampler:
 class RirBank:
     """Room impulse responses as one float32 [R, Kmax] device allocation, rows zero-padded, plus `length` (int32 [R]).
     Recorded responses come from `from_dir` / `from_arrays`; `simulate` makes the bank on the device from random shoe-box
-    rooms (Engine.rir, the image-source method) and keeps their table as `rooms` (float64 [R, 15], else None)."""
+    rooms (Engine.rir, the image-source method) and keeps their table as `rooms` (float64 [R, 15], else None); with a
+    banded sampler (RoomSampler(bands=n): Engine.rir_bands) also their band table as `bands` (float64 [R, n, 7])."""
 
-    def __init__(self, data: torch.Tensor, length: torch.Tensor, rooms: Optional[torch.Tensor] = None):
-        self.data, self.length, self.rooms = data, length, rooms
+    def __init__(self, data: torch.Tensor, length: torch.Tensor, rooms: Optional[torch.Tensor] = None,
+                 bands: Optional[torch.Tensor] = None):
+        self.data, self.length, self.rooms, self.bands = data, length, rooms, bands
 
     def __len__(self) -> int:
         return self.data.size(0)
@@ -443,8 +563,13 @@ class RirBank:
         """R rooms drawn by `sampler`, each simulated for up to `seconds` (a row's own length is its rt60, if shorter)."""
         K = int(round(seconds * sample_rate))
         rooms, n_taps = sampler.draw(R, K, sample_rate, device=engine.device)
-        data, length = engine.rir(rooms, n_taps, K, sampler.n_images(K, sample_rate), fs=sample_rate)
-        return cls(data, length, rooms)
+        N = sampler.n_images(K, sample_rate)
+        if sampler.bands is None:
+            data, length = engine.rir(rooms, n_taps, K, N, fs=sample_rate)
+            return cls(data, length, rooms)
+        bands = sampler.draw_bands(rooms)
+        data, length = engine.rir_bands(rooms, bands, n_taps, K, sampler.filters(sample_rate, engine.device), N, fs=sample_rate)
+        return cls(data, length, rooms, bands)
 
     def with_identity(self) -> "RirBank":
         """The bank with a one-tap identity response appended as its last row (rows that get no reverberation)."""
@@ -642,6 +767,7 @@ class DynamicMixer:
         self.last_draw: Optional[Draw] = None
         self.rooms, self.sample_rate = rooms, int(sample_rate)
         self.rir_taps, self.n_images, self.last_bank = 0, None, None
+        self.last_bands: Optional[torch.Tensor] = None      # rooms=RoomSampler(bands=n): the float64 [B, n, 7] table of the batch
         if rooms is not None:
             if rir_bank is not None:
                 raise ValueError("give either a rir_bank or rooms, not both")
@@ -754,8 +880,17 @@ class DynamicMixer:
             warp = (f if speed is None else speed * f).contiguous()
         return StretchDraw(t, f, (t / f).contiguous(), warp)
 
-    def _simulate(self, d: Draw) -> RirBank:
-        """The batch's responses, simulated into the persistent allocation (made anew only when B changes)."""
+    def draw_bands(self, d: Draw) -> Optional[torch.Tensor]:
+        """The band table of a batch's rooms (None unless rooms=RoomSampler(bands=n)): RoomSampler.draw_bands of d.rooms,
+        made after `draw` - the sources' draws included - so every other draw is what it is without bands.  Draw and
+        SceneDraw keep their fields: the table of the last call stays readable as `mixer.last_bands`."""
+        if self.rooms is None or self.rooms.bands is None:
+            return None
+        return self.rooms.draw_bands(d.rooms)
+
+    def _simulate(self, d: Draw, bands: Optional[torch.Tensor] = None) -> RirBank:
+        """The batch's responses, simulated into the persistent allocation (made anew only when B changes); with `bands`
+        by Engine.rir_bands, a source using its room's band table."""
         B, K = d.rooms.size(0), self.rir_taps
         base = self._bank_rows(B)
         n_s = self.sources[1] if self.sources is not None else 0
@@ -768,10 +903,18 @@ class DynamicMixer:
             self.last_bank = RirBank(data, length)
         sim = self.last_bank
         # rir_len is the sampler's n_taps, or 1 for a dry row (whose response is then one tap that no row uses)
-        self.engine.rir(d.rooms, d.rir_len, K, self.n_images, fs=self.sample_rate, out=(sim.data[:B], sim.length[:B]))
+        filt = None if bands is None else self.rooms.filters(self.sample_rate, self.engine.device)
+
+        def simulate(rooms, taps, out, table):
+            if table is None:
+                self.engine.rir(rooms, taps, K, self.n_images, fs=self.sample_rate, out=out)
+            else:
+                self.engine.rir_bands(rooms, table, taps, K, filt, self.n_images, fs=self.sample_rate, out=out)
+
+        simulate(d.rooms, d.rir_len, (sim.data[:B], sim.length[:B]), bands)
         if n_s:                                                   # the sources' responses: one call of B S rows
-            self.engine.rir(d.src_rooms.reshape(B * n_s, 15), d.src_rir_len.reshape(B * n_s), K, self.n_images,
-                            fs=self.sample_rate, out=(sim.data[base:], sim.length[base:]))
+            simulate(d.src_rooms.reshape(B * n_s, 15), d.src_rir_len.reshape(B * n_s), (sim.data[base:], sim.length[base:]),
+                     None if bands is None else bands.repeat_interleave(n_s, dim=0))
         return sim
 
     @staticmethod
@@ -786,7 +929,8 @@ class DynamicMixer:
     def __call__(self, clean: torch.Tensor):
         B = clean.size(0)
         d = self.last_draw = self.draw(B)
-        rir = self.rir_bank if self.rooms is None else self._simulate(d)
+        bands = self.last_bands = self.draw_bands(d)
+        rir = self.rir_bank if self.rooms is None else self._simulate(d, bands)
         s = self.last_stretch = self.draw_stretch(B, d.speed)
         clean = self._perturb(d, s, clean)
         shift, clean = self._level(d, clean)

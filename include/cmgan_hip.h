@@ -39,7 +39,7 @@ extern "C" {
 #define CMGAN_E_WORKSPACE   -5   /* workspace too small or misaligned              */
 #define CMGAN_E_HIP         -6   /* a HIP runtime call failed (see last_error)     */
 
-#define CMGAN_ABI_VERSION 14
+#define CMGAN_ABI_VERSION 15
 
 typedef struct cmgan_handle cmgan_handle;
 
@@ -723,7 +723,8 @@ int cmgan_scene(cmgan_handle* h, const float* clean_dev, int B, int L, long long
  *   taps     h[k] = sum_images a w(k - tau) sinc(k - tau), 0 <= k < k_r, with w(t) = (1 + cos(pi t / tw)) / 2 for
  *            |t| < tw, else 0, and sinc(t) = sin(pi t) / (pi t), sinc(0) = 1; images with tau - tw >= K add nothing
  *   outputs  rir_dev[r * ld + k] = f32(h[k]) for k < k_r and exactly 0.0f for k_r <= k < K;  len_dev[r] = k_r
- * Not modelled: a high-pass filter, air absorption, directivity.  All arithmetic is float64 and each tap is rounded to
+ * Not modelled: a high-pass filter, directivity; air absorption and frequency-dependent walls are cmgan_rir_bands, below.
+ * All arithmetic is float64 and each tap is rounded to
  * float32 exactly once.  A block owns cmgan_rir_tile() consecutive taps of one row and adds the images that reach them in
  * one fixed enumeration order (nx, ny, p, nz ascending), staged cmgan_rir_list_capacity() at a time in an on-chip list by
  * an order-preserving compaction: no atomics, the same bits from run to run, row r's bits depend neither on R nor on the
@@ -743,6 +744,43 @@ size_t cmgan_rir_workspace_bytes(const cmgan_handle* h, int R, int K, int tw);
 int cmgan_rir(cmgan_handle* h, const double* rooms_dev, const int* n_taps_dev, int R, int K, int fs, double c, int tw,
               int Nx, int Ny, int Nz, float* rir_dev, long long ld, int* len_dev, void* workspace_dev,
               size_t workspace_bytes, void* stream);
+
+/* ---- Room impulse responses in frequency bands: walls whose absorption depends on frequency, and air absorption ------
+ * cmgan_rir simulated in NB frequency bands at once and joined by a caller-supplied FIR filterbank.  An image's position,
+ * delay, window and sinc are the same in every band and only its amplitude differs, so the image list is built once and
+ * every tap carries one accumulator per band; NB calls of cmgan_rir would walk the list NB times.
+ *   rooms_dev   float64 [R, 15], the table of cmgan_rir: columns 0 - 8 (size, source, receiver) are used, columns 9 - 14
+ *               are never read
+ *   bands_dev   float64 [R, NB, 7]: per band the six reflection coefficients in cmgan_rir's order, then m, the amplitude
+ *               attenuation of air in nepers per metre (m >= 0)
+ *   n_taps_dev  int32 [R], the length of row r's response
+ *   filt_dev    float64 [NB, NF], NF odd, D = (NF - 1) / 2: one FIR per band, shared by all rows.  A caller-supplied
+ *               table whose values are not judged: a NaN in it propagates to the taps and is never an address
+ * For row r, with k_r = clamp(n_taps[r], 1, K) and the images (n, p), d, tau, w and sinc of cmgan_rir:
+ *   a_b      prod_axis b_{b,axis0}^|n - p| b_{b,axis1}^|n| exp(-m_b d) / (4 pi max(d, CMGAN_RIR_DMIN))          (0^0 = 1)
+ *   bands    h_b[q] = sum_images a_b w(q - tau) sinc(q - tau) for 0 <= q < k_r + D, and 0 outside that range
+ *   join     h[k] = sum_{b ascending} sum_{j ascending} g_b[j] h_b[k + D - j], one fused multiply-add per term in that
+ *            order: the filterbank's delay D is taken out, and the bands are simulated D taps past the row's end, so the
+ *            join truncates nothing there.  The caller's image ranges must cover K + D taps
+ *   outputs  rir_dev[r * ld + k] = f32(h[k]) for k < k_r and exactly 0.0f for k_r <= k < K;  len_dev[r] = k_r
+ * Still not modelled: directivity, and a material per wall beyond what the caller writes into the band table.  The
+ * guarantees are those of cmgan_rir: float64 throughout and one rounding to float32; per (tap, band) the images are added
+ * in the one fixed enumeration order of cmgan_rir; no atomics; the same bits from run to run; row r's bits depend neither
+ * on R nor on the other rows, and an N larger than needed changes no bit; nothing read from a table becomes an address.
+ * A row with a non-finite entry in columns 0 - 8 or in its band table, a size <= 0, a coefficient outside [0, 1] or a
+ * negative m is written as all zeros with len = 1.  Checked before any launch and before the handle is looked at (the
+ * message of a call with h == NULL is read with cmgan_last_error(NULL)): everything cmgan_rir checks, 1 <= NB <=
+ * cmgan_rir_max_bands() (8), NF odd in [1, cmgan_rir_max_filter()] (1023), 8-byte alignment of the band and filter
+ * tables; otherwise CMGAN_E_BADARG / CMGAN_E_UNSUPPORTED.  Workspace: cmgan_rir_bands_workspace_bytes (h may be NULL; 0
+ * when unsupported; non-decreasing in every argument), 256-byte aligned; it holds the row records (verdict, m_b, powers
+ * of the 6 NB coefficients) and the float64 band responses [R, NB, K + D] between the three launches.  No
+ * synchronisation, no allocation; graph-capturable, and a replay reads the tables' current contents. */
+int cmgan_rir_max_bands(void);
+int cmgan_rir_max_filter(void);
+size_t cmgan_rir_bands_workspace_bytes(const cmgan_handle* h, int R, int K, int tw, int NB, int NF);
+int cmgan_rir_bands(cmgan_handle* h, const double* rooms_dev, const double* bands_dev, const int* n_taps_dev, int R, int K,
+                    int NB, const double* filt_dev, int NF, int fs, double c, int tw, int Nx, int Ny, int Nz,
+                    float* rir_dev, long long ld, int* len_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---- Active speech level (the reference has no level handling: src/data/dataloader.py:13-50 replays pairs mixed
  * beforehand) ---------------------------------------------------------------------------------------------------------
