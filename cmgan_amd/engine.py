@@ -1123,6 +1123,11 @@ class Engine:
         return noisy, target, SceneInfo(gp[0], info[1], info[0], gp[1])
 
     # ---- room impulse responses ----------------------------------------------------
+    def _rir_out(self, R, K):
+        """The (rir float32 [R, K], length int32 [R]) pair that Engine.rir and Engine.rir_bands return."""
+        return (torch.empty(R, K, dtype=torch.float32, device=self.device),
+                torch.empty(R, dtype=torch.int32, device=self.device))
+
     @_on_device
     def rir(self, rooms: torch.Tensor, n_taps: torch.Tensor, K: int, n_images, fs: int = 16000, c: float = 343.0,
             tw: int = 40, out=None):
@@ -1139,10 +1144,7 @@ class Engine:
         R, K, N = check_rir_args(self.device, rooms, n_taps, K, n_images, fs, c, tw, out)
         ws = self._grow("rir", int(self.lib.cmgan_rir_workspace_bytes(self._h, R, K, int(tw))),
                         f"[{R}, {K}] with tw = {tw} is outside what cmgan_rir supports")
-        if out is None:
-            out = (torch.empty(R, K, dtype=torch.float32, device=self.device),
-                   torch.empty(R, dtype=torch.int32, device=self.device))
-        rir, length = out
+        rir, length = out if out is not None else self._rir_out(R, K)
         self._call("cmgan_rir", rooms, n_taps, R, K, int(fs), float(c), int(tw), N[0], N[1], N[2], rir, K, length, ws,
                    ws.numel())
         return rir, length
@@ -1165,10 +1167,7 @@ class Engine:
         R, K, N, NB, NF = check_rir_bands_args(self.device, rooms, bands, n_taps, K, filters, n_images, fs, c, tw, out)
         ws = self._grow("rir_bands", int(self.lib.cmgan_rir_bands_workspace_bytes(self._h, R, K, int(tw), NB, NF)),
                         f"[{R}, {K}] with tw = {tw}, {NB} bands and {NF} filter taps is outside what cmgan_rir_bands supports")
-        if out is None:
-            out = (torch.empty(R, K, dtype=torch.float32, device=self.device),
-                   torch.empty(R, dtype=torch.int32, device=self.device))
-        rir, length = out
+        rir, length = out if out is not None else self._rir_out(R, K)
         self._call("cmgan_rir_bands", rooms, bands, n_taps, R, K, NB, filters, NF, int(fs), float(c), int(tw), N[0], N[1],
                    N[2], rir, K, length, ws, ws.numel())
         return rir, length

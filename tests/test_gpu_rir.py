@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import mix_model as MM
+import rir_cases as RC
 import rir_model as M
 
 pytestmark = pytest.mark.gpu
@@ -339,3 +340,14 @@ def test_mixing_loader_with_rooms_feeds_a_generator_train_step(eng):
     opt = AdamW(eng, net.param_bucket, net.grad_bucket, lr=5e-4)
     loss, terms = generator_train_step(net, opt, target, noisy)
     assert np.isfinite(float(loss)) and bool(torch.isfinite(terms).all())
+
+
+# ------------------------------------------------------------------ 4. the recorded bits
+@pytest.mark.parametrize("name", RC.RIR_NAMES)
+def test_the_bits_are_the_recorded_ones(eng, TILE, name):
+    """Engine.rir on the cases of tests/rir_cases.py against tests/golden/rir_parent_bits.npz (make_rir_bits.py): the
+    model-based tests above bound the error, this one sees a changed rounding or a changed enumeration order."""
+    import os
+    from mixer_cases import assert_recorded_bits
+    want = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "rir_parent_bits.npz"))
+    assert_recorded_bits(f"rir/{name}", RC.run(eng, RC.rir_cases(TILE)[name], DEV), want)

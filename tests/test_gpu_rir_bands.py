@@ -1,4 +1,4 @@
-"""The banded room simulator on the GPU (cmgan_amd/csrc/rir_bands.hip; include/cmgan_hip.h, "Room impulse responses in
+"""The banded room simulator on the GPU (cmgan_amd/csrc/rir.hip; include/cmgan_hip.h, "Room impulse responses in
 frequency bands"): Engine.rir_bands against the float64 numpy model of tests/rir_bands_model.py over the kernels' tile
 and list edges, band counts and filter lengths, oversized image ranges, invalid rows, bit-reproducibility and row
 independence, hipGraph replay with the tables changed in place, and the front end (RirBank.simulate and
@@ -18,6 +18,7 @@ import torch
 
 import mix_model as MM
 import rir_bands_model as BM
+import rir_cases as RC
 import rir_model as M
 from test_gpu_rir import _check_mix
 
@@ -367,3 +368,14 @@ def test_dynamic_mixer_with_banded_rooms_and_sources(eng):
         x, y = getattr(d, name), getattr(plain.last_draw, name)
         assert (x is None and y is None) or all(torch.equal(a, b) for a, b in zip(*[v if isinstance(v, tuple) else (v,) for v in (x, y)])), name
     assert plain.last_bands is None and not torch.equal(plain.last_bank.data, sim.data)
+
+
+# ------------------------------------------------------------------ 4. the recorded bits
+@pytest.mark.parametrize("name", RC.RIR_BANDS_NAMES)
+def test_the_bits_are_the_recorded_ones(eng, TILE, name):
+    """Engine.rir_bands on the cases of tests/rir_cases.py against tests/golden/rir_parent_bits.npz (make_rir_bits.py): the
+    model-based tests above bound the error, this one sees a changed rounding or a changed enumeration order."""
+    import os
+    from mixer_cases import assert_recorded_bits
+    want = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "rir_parent_bits.npz"))
+    assert_recorded_bits(f"rir_bands/{name}", RC.run(eng, RC.rir_bands_cases(TILE)[name], DEV), want)

@@ -1,4 +1,4 @@
-"""CPU side of the banded room simulator (cmgan_amd/csrc/rir_bands.hip; include/cmgan_hip.h, "Room impulse responses in
+"""CPU side of the banded room simulator (cmgan_amd/csrc/rir.hip; include/cmgan_hip.h, "Room impulse responses in
 frequency bands"): the float64 model the GPU tests compare the kernels with (tests/rir_bands_model.py) against its own
 definition as a naive loop and against known answers, the octave filterbank, RoomSampler's band draws, the workspace
 formula, and every argument error of cmgan_rir_bands and Engine.rir_bands, all judged before a handle or a GPU is needed."""
@@ -397,3 +397,16 @@ def test_engine_rir_bands_argument_rules_without_gpu():
             check_rir_bands_args(cpu, **a)
     with pytest.raises(RuntimeError, match="bound to"):
         check_rir_bands_args(torch.device("meta"), **_args())
+
+
+# ------------------------------------------------------------------ the cases whose bits are recorded
+def test_the_recorded_cases_are_not_trivial():
+    """tests/rir_cases.py through the float64 model: what tests/golden/make_rir_bits.py asserts of the GPU's output."""
+    import rir_cases as RC
+    lib = _lib.load()
+    T, cap = int(lib.cmgan_rir_tile()), int(lib.cmgan_rir_list_capacity())
+    cases = RC.rir_bands_cases(T)
+    assert tuple(cases) == RC.RIR_BANDS_NAMES
+    for name, case in cases.items():
+        h, length = RC.model(case)
+        RC.nontrivial(name, case, h, length, T, cap)

@@ -307,3 +307,16 @@ def test_dynamic_mixer_rooms_argument_rules_without_gpu():
     assert bool((d.rir_len[dry] == 1).all()) and bool((d.rir_len[~dry] >= 3200).all()) and int(d.rir_len.max()) <= 4000
     # without rooms the draw has no table and the new field defaults to None
     assert DynamicMixer(_NoEngine(), noise).draw(4).rooms is None
+
+
+# ------------------------------------------------------------------ the cases whose bits are recorded
+def test_the_recorded_cases_are_not_trivial():
+    """tests/rir_cases.py through the float64 model: what tests/golden/make_rir_bits.py asserts of the GPU's output."""
+    import rir_cases as RC
+    lib = _lib.load()
+    T, cap = int(lib.cmgan_rir_tile()), int(lib.cmgan_rir_list_capacity())
+    cases = RC.rir_cases(T)
+    assert tuple(cases) == RC.RIR_NAMES
+    for name, case in cases.items():
+        h, length = RC.model(case)
+        RC.nontrivial(name, case, h, length, T, cap)
