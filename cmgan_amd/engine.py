@@ -249,22 +249,64 @@ def check_rir_bands_args(device, rooms, bands, n_taps, K, filters, n_images, fs=
     return R, K, N, NB, filters.size(1)
 
 
+RIR_STATS_COLUMNS = 10        # = cmgan_rir_stats_columns()
+RIR_STATS_NONFINITE, RIR_STATS_ZERO, RIR_STATS_NO_EDT, RIR_STATS_NO_T20, RIR_STATS_NO_T30 = 1, 2, 4, 8, 16    # status bits
+
+
+class RirStats(NamedTuple):
+    """Engine.rir_stats: float64 [R, NB + 1] device tensors (column 0 broad-band, column 1 + b band b) - the response's
+    energy, the index of its direct arrival, the direct-to-reverberant ratio, C50, C80 (dB), D50, the centre time Ts,
+    EDT, T20 and T30 (seconds) - and the int32 status bits (RIR_STATS_*: 0 where everything could be measured)."""
+    energy: torch.Tensor
+    direct: torch.Tensor
+    drr_db: torch.Tensor
+    c50_db: torch.Tensor
+    c80_db: torch.Tensor
+    d50: torch.Tensor
+    ts: torch.Tensor
+    edt: torch.Tensor
+    t20: torch.Tensor
+    t30: torch.Tensor
+    status: torch.Tensor
+
+
+def check_rir_stats_args(device, rir, length=None, filters=None, fs=16000, direct_ms=2.5):
+    """Argument rules of Engine.rir_stats (shapes, dtypes, devices and host scalars; pure host code).  Returns
+    (R, K, NB, NF), NF = 1 without filters."""
+    R, K = _row_batch(device, rir, RIR_MAX_TAPS, name="rir")
+    if length is not None:
+        tensor_arg(length, "length", torch.int32, device, f"[{R}]", lambda t: tuple(t.shape) == (R,))
+    NB, NF = 0, 1
+    if filters is not None:
+        tensor_arg(filters, "filters", torch.float64, device,
+                   f"[NB, NF] with 1 <= NB <= {RIR_MAX_BANDS} and NF odd in [1, {RIR_MAX_FILTER}]",
+                   lambda t: t.dim() == 2 and 1 <= t.size(0) <= RIR_MAX_BANDS and 1 <= t.size(1) <= RIR_MAX_FILTER
+                   and t.size(1) % 2 == 1)
+        NB, NF = filters.shape
+    if isinstance(fs, bool) or int(fs) != fs or not 1 <= fs <= 2 ** 31 - 1:
+        raise ValueError(f"fs must be a positive sample rate, got {fs}")
+    direct_ms = float(direct_ms)
+    if not 0.0 <= direct_ms < float("inf"):
+        raise ValueError(f"direct_ms must be finite and >= 0, got {direct_ms}")
+    return R, K, NB, NF
+
+
 def _row_stride_ok(t, B: int, L: int) -> bool:
     return t.stride(1) == 1 and (B == 1 or t.stride(0) >= L)
 
 
-def _row_batch(device, wav, max_L: Optional[int] = None):
+def _row_batch(device, wav, max_L: Optional[int] = None, name: str = "wav"):
     """The rule for the batch of the augmentation calls: wav is a float32 [B, L] tensor of at most 65535 rows (of at most
     max_L samples), each contiguous and at least L from the next.  Returns (B, L)."""
-    tensor_arg(wav, "wav", torch.float32, device, "[B, L] with B, L >= 1",
+    tensor_arg(wav, name, torch.float32, device, "[B, L] with B, L >= 1",
                lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) >= 1, contiguous=False)     # (its own stride rule below)
     B, L = wav.shape
     if B > 65535:
-        raise ValueError(f"wav: at most 65535 rows, got {B}")
+        raise ValueError(f"{name}: at most 65535 rows, got {B}")
     if max_L is not None and L > max_L:
-        raise ValueError(f"wav: rows of up to {max_L} samples are supported, got {L}")
+        raise ValueError(f"{name}: rows of up to {max_L} samples are supported, got {L}")
     if not _row_stride_ok(wav, B, L):
-        raise ValueError(f"wav: rows must be contiguous and at least L apart, got strides {tuple(wav.stride())}")
+        raise ValueError(f"{name}: rows must be contiguous and at least L apart, got strides {tuple(wav.stride())}")
     return B, L
 
 
@@ -1171,6 +1213,34 @@ class Engine:
         self._call("cmgan_rir_bands", rooms, bands, n_taps, R, K, NB, filters, NF, int(fs), float(c), int(tw), N[0], N[1],
                    N[2], rir, K, length, ws, ws.numel())
         return rir, length
+
+    @_on_device
+    def rir_stats(self, rir: torch.Tensor, length: Optional[torch.Tensor] = None, filters: Optional[torch.Tensor] = None,
+                  fs: int = 16000, direct_ms: float = 2.5, edc: bool = False):
+        """What every response of a bank measures as (cmgan_rir_stats, include/cmgan_hip.h): the Schroeder decay curve and
+        the room-acoustic parameters of ISO 3382-1 as its published description gives them, on the GPU.
+
+        rir float32 [R, K] (rows contiguous, any row stride >= K, K <= 65536) and length int32 [R] (None: every row has K
+        samples; clamped to [1, K]; samples from a row's length on are never read), as Engine.rir returns them; filters
+        float64 [NB, NF], NF odd, the filterbank of Engine.rir_bands (`mixing.octave_filterbank`) or None for the
+        broad-band analysis alone; all on this Engine's device and read by the kernels only.  direct_ms is the half-width
+        of the window around the strongest sample that counts as the direct sound.  Returns RirStats of float64 [R, NB +
+        1] tensors, column 0 broad-band and column 1 + b band b: energy, direct (the index of the strongest sample),
+        drr_db, c50_db, c80_db, d50, ts, edt, t20, t30, and the int32 status.  A time that cannot be fitted - the curve
+        does not fall far enough within the row (no noise-floor compensation is done) - is NaN with its status bit set;
+        a row with a non-finite sample is NaN throughout, a silent one NaN but for energy = 0.  edc=True returns
+        (RirStats, the decay curve float64 [R, NB + 1, K], zeros from a row's length on).  Float64 arithmetic;
+        bit-reproducible, row-independent, no synchronisation, graph-capturable after one call at the shape."""
+        R, K, NB, NF = check_rir_stats_args(self.device, rir, length, filters, fs, direct_ms)
+        ws = self._grow("rir_stats", int(self.lib.cmgan_rir_stats_workspace_bytes(self._h, R, K, NB, NF)),
+                        f"[{R}, {K}] with {NB} bands and {NF} filter taps is outside what cmgan_rir_stats supports")
+        stats = torch.empty(R, NB + 1, RIR_STATS_COLUMNS, dtype=torch.float64, device=self.device)
+        status = torch.empty(R, NB + 1, dtype=torch.int32, device=self.device)
+        curve = torch.empty(R, NB + 1, K, dtype=torch.float64, device=self.device) if edc else None
+        self._call("cmgan_rir_stats", rir, R, K, rir.stride(0) if R > 1 else K, length, filters, NB, NF, int(fs),
+                   float(direct_ms), stats, status, curve, ws, ws.numel())
+        out = RirStats(*stats.unbind(dim=2), status)
+        return (out, curve) if edc else out
 
     # ---- active speech level -------------------------------------------------------
     @_on_device

@@ -13,6 +13,10 @@ takes - with `clean` the training target (the dry clip, or the clip with its ear
     # either a fixed bank       rirs = RirBank.simulate(engine, RoomSampler(), 256)
     # or a fresh room per row of every batch
     mixer = DynamicMixer(engine, noise, rooms=RoomSampler(rt60=(0.2, 0.8)), snr_db=(0, 20), early_ms=50)
+    # what the rooms came out as (Engine.rir_stats / cmgan_rir_stats: T30, DRR, C50, ... per response, on the device):
+    # a bank measured and selected by it, or every batch labelled with the acoustics it was mixed with
+    rirs = RirBank.simulate(engine, RoomSampler(), 256, measure=True).where(t30=(0.3, 0.6), drr_db=(-5.0, 10.0))
+    mixer = DynamicMixer(engine, noise, rooms=RoomSampler(), room_stats=True)      # -> mixer.last_room_stats
     # rooms whose reverberation time falls with frequency: walls that absorb more per octave (tilt) and air absorption
     # (air: the caller's ranges of nepers per metre, one per band), in 7 octave bands (Engine.rir_bands / cmgan_rir_bands)
     mixer = DynamicMixer(engine, noise, rooms=RoomSampler(bands=7, tilt=(0.0, 0.5), air=my_air_ranges), snr_db=(0, 20))
@@ -41,7 +45,7 @@ import torch
 import torch.utils.data
 
 from .data import _natural_key, fit_length, read_wav
-from .engine import STRETCH_HOP, STRETCH_SEARCH, _whole_in
+from .engine import STRETCH_HOP, STRETCH_SEARCH, RirStats, _whole_in
 
 __all__ = ["NoiseBank", "RirBank", "RoomSampler", "sabine_beta", "octave_filterbank", "DynamicMixer", "MixingLoader", "CleanDataset",
            "clean_only", "Draw", "SceneDraw", "tile", "ChannelSampler", "biquad_peaking", "biquad_low_shelf", "biquad_high_shelf",
@@ -531,11 +535,13 @@ class RirBank:
     """Room impulse responses as one float32 [R, Kmax] device allocation, rows zero-padded, plus `length` (int32 [R]).
     Recorded responses come from `from_dir` / `from_arrays`; `simulate` makes the bank on the device from random shoe-box
     rooms (Engine.rir, the image-source method) and keeps their table as `rooms` (float64 [R, 15], else None); with a
-    banded sampler (RoomSampler(bands=n): Engine.rir_bands) also their band table as `bands` (float64 [R, n, 7])."""
+    banded sampler (RoomSampler(bands=n): Engine.rir_bands) also their band table as `bands` (float64 [R, n, 7]).
+    `measure` leaves what the responses measure as in `stats` (a RirStats of [R, NB + 1] tensors, else None), and `where`
+    selects rows by it."""
 
     def __init__(self, data: torch.Tensor, length: torch.Tensor, rooms: Optional[torch.Tensor] = None,
-                 bands: Optional[torch.Tensor] = None):
-        self.data, self.length, self.rooms, self.bands = data, length, rooms, bands
+                 bands: Optional[torch.Tensor] = None, stats: Optional[RirStats] = None):
+        self.data, self.length, self.rooms, self.bands, self.stats = data, length, rooms, bands, stats
 
     def __len__(self) -> int:
         return self.data.size(0)
@@ -559,24 +565,65 @@ class RirBank:
         return cls.from_arrays(_read_dir(path, sample_rate, engine), device=engine.device)
 
     @classmethod
-    def simulate(cls, engine, sampler: RoomSampler, R: int, seconds: float = 0.5, sample_rate: int = 16000) -> "RirBank":
-        """R rooms drawn by `sampler`, each simulated for up to `seconds` (a row's own length is its rt60, if shorter)."""
+    def simulate(cls, engine, sampler: RoomSampler, R: int, seconds: float = 0.5, sample_rate: int = 16000,
+                 measure: bool = False) -> "RirBank":
+        """R rooms drawn by `sampler`, each simulated for up to `seconds` (a row's own length is its rt60, if shorter).
+        measure=True then measures the bank (`measure`), in the sampler's bands if it has any."""
         K = int(round(seconds * sample_rate))
         rooms, n_taps = sampler.draw(R, K, sample_rate, device=engine.device)
         N = sampler.n_images(K, sample_rate)
-        if sampler.bands is None:
-            data, length = engine.rir(rooms, n_taps, K, N, fs=sample_rate)
-            return cls(data, length, rooms)
-        bands = sampler.draw_bands(rooms)
-        data, length = engine.rir_bands(rooms, bands, n_taps, K, sampler.filters(sample_rate, engine.device), N, fs=sample_rate)
-        return cls(data, length, rooms, bands)
+        filters = None if sampler.bands is None else sampler.filters(sample_rate, engine.device)
+        if filters is None:
+            bank = cls(*engine.rir(rooms, n_taps, K, N, fs=sample_rate), rooms)
+        else:
+            bands = sampler.draw_bands(rooms)
+            bank = cls(*engine.rir_bands(rooms, bands, n_taps, K, filters, N, fs=sample_rate), rooms, bands)
+        if measure:
+            bank.measure(engine, sample_rate, filters)
+        return bank
+
+    def measure(self, engine, fs: int = 16000, filters: Optional[torch.Tensor] = None) -> RirStats:
+        """What every response measures as (Engine.rir_stats: EDT, T20, T30, DRR, C50, ... broad-band and, with `filters`
+        = float64 [NB, NF] on the device, per band), kept as `self.stats` and returned.  No host synchronisation."""
+        self.stats = engine.rir_stats(self.data, self.length, filters, fs=fs)
+        return self.stats
+
+    def where(self, t30=None, drr_db=None, c50_db=None, band: int = 0) -> "RirBank":
+        """The sub-bank of the rows whose measured T30, DRR and C50 of column `band` (0: broad-band, 1 + b: band b) lie in
+        the given closed (low, high) ranges (None: not asked): `data`, `length`, `rooms`, `bands` and `stats`
+        index-selected on the device, in their order.  A NaN never lies in a range, so a row whose T30 could not be
+        fitted is dropped when `t30` is asked.  The bank must have been measured.  This is a bank-building step: the row
+        count of the result is read back from the device, ONE host synchronisation; an empty selection is an error."""
+        if self.stats is None:
+            raise ValueError("where() needs a measured bank: call measure() first, or simulate(..., measure=True)")
+        columns = self.stats.t30.size(1)
+        if isinstance(band, bool) or int(band) != band or not 0 <= band < columns:
+            raise ValueError(f"band must be a column in [0, {columns - 1}] of the measured stats, got {band}")
+        keep = torch.ones(len(self), dtype=torch.bool, device=self.device)
+        for name, rng, field in (("t30", t30, self.stats.t30), ("drr_db", drr_db, self.stats.drr_db),
+                                 ("c50_db", c50_db, self.stats.c50_db)):
+            if rng is not None:
+                lo, hi = _pair(name, rng, -math.inf, math.inf, "(low, high) with low <= high", "None or (low, high)")
+                keep &= (field[:, int(band)] >= lo) & (field[:, int(band)] <= hi)
+        index = torch.nonzero(keep).squeeze(1)                    # (the synchronisation)
+        if index.numel() == 0:
+            raise ValueError(f"where(t30={t30}, drr_db={drr_db}, c50_db={c50_db}, band={band}) selects no row of {len(self)}")
+        pick = lambda t: None if t is None else t.index_select(0, index).contiguous()
+        return RirBank(pick(self.data), pick(self.length), pick(self.rooms), pick(self.bands), RirStats(*map(pick, self.stats)))
 
     def with_identity(self) -> "RirBank":
-        """The bank with a one-tap identity response appended as its last row (rows that get no reverberation)."""
+        """The bank with a one-tap identity response appended as its last row (rows that get no reverberation).  A
+        measured bank stays one: the row measures as cmgan_rir_stats defines a lone unit sample - energy 1, direct 0, no
+        reverberant part (DRR, C50, C80 +inf; D50 1; Ts 0) and no decay to fit (NaN, the three bits) - in every column."""
         row = torch.zeros(1, self.data.size(1), dtype=torch.float32, device=self.device)
         row[0, 0] = 1.0
         one = torch.ones(1, dtype=torch.int32, device=self.device)
-        return RirBank(torch.cat([self.data, row]).contiguous(), torch.cat([self.length, one]))
+        stats = self.stats
+        if stats is not None:
+            inf, nan = math.inf, math.nan
+            lone = RirStats(1.0, 0.0, inf, inf, inf, 1.0, 0.0, nan, nan, nan, 4 | 8 | 16)
+            stats = RirStats(*(torch.cat([t, torch.full_like(t[:1], v)]) for t, v in zip(stats, lone)))
+        return RirBank(torch.cat([self.data, row]).contiguous(), torch.cat([self.length, one]), stats=stats)
 
 
 class Draw(NamedTuple):
@@ -695,7 +742,16 @@ class DynamicMixer:
     persistent bank; with neither the sources are dry.  A source keeps its room's own response length whether or not the
     talker's row was drawn dry, and its delay: it is not aligned with the talker.  The mixer then returns a SceneInfo.
     `dry_noise=False` (only with sources) drops the noise that is added without a room, so every noise is located; the
-    noise draws are made as before and not used."""
+    noise draws are made as before and not used.
+
+    `room_stats=True`: the batch is labelled with the acoustics it was mixed with (Engine.rir_stats / cmgan_rir_stats: T30,
+    DRR, C50, ... of ISO 3382-1).  With `rooms` the talkers' B simulated responses are measured once per call, on the
+    device, in the sampler's bands if it has any; with a `rir_bank` that has been measured (`RirBank.measure`) its `stats`
+    are gathered by the drawn index (a dry row shows the identity's).  Either way `mixer.last_room_stats` is a RirStats
+    of [B, NB + 1] tensors for the rows of the batch, a dry row of `rooms` showing its one-tap response.  Nothing is
+    drawn for it: with False (the default) `last_room_stats` is None and the outputs, draws and generator states are
+    what they are without the argument, and with True they are the same too.  An unmeasured bank, or neither a bank nor
+    rooms, is refused."""
 
     def __init__(self, engine, noise_bank: NoiseBank, rir_bank: Optional[RirBank] = None, snr_db=(0.0, 20.0),
                  early_ms: Optional[float] = 50.0, p_reverb: float = 1.0, peak: float = 0.99,
@@ -704,7 +760,7 @@ class DynamicMixer:
                  channel: Optional[ChannelSampler] = None, channel_on: str = "noisy", speed=None, p_speed: float = 1.0,
                  speed_zeros: int = 24, speed_rolloff: float = 0.95, sources=None, source_bank: Optional[NoiseBank] = None,
                  source_snr_db=(0.0, 20.0), dry_noise: bool = True, tempo=None, p_tempo: float = 1.0, pitch=None,
-                 p_pitch: float = 1.0, stretch_hop: int = 256, stretch_search: int = 160):
+                 p_pitch: float = 1.0, stretch_hop: int = 256, stretch_search: int = 160, room_stats: bool = False):
         if sources is not None:
             given, counts = sources, "(low, high) whole numbers with 0 <= low <= high and 1 <= high <= 4"
             sources = _pair("sources", given, 0, 4, counts, "None or (low, high)", whole=True)
@@ -766,6 +822,11 @@ class DynamicMixer:
         self.early = -1 if early_ms is None else int(round(early_ms * sample_rate / 1000.0))
         self.last_draw: Optional[Draw] = None
         self.rooms, self.sample_rate = rooms, int(sample_rate)
+        if not isinstance(room_stats, bool):
+            raise TypeError(f"room_stats must be a bool, got {type(room_stats).__name__}")
+        if room_stats and rooms is None and (rir_bank is None or rir_bank.stats is None):
+            raise ValueError("room_stats=True needs rooms, or a rir_bank that has been measured (RirBank.measure)")
+        self.room_stats, self.last_room_stats = room_stats, None
         self.rir_taps, self.n_images, self.last_bank = 0, None, None
         self.last_bands: Optional[torch.Tensor] = None      # rooms=RoomSampler(bands=n): the float64 [B, n, 7] table of the batch
         if rooms is not None:
@@ -931,6 +992,7 @@ class DynamicMixer:
         d = self.last_draw = self.draw(B)
         bands = self.last_bands = self.draw_bands(d)
         rir = self.rir_bank if self.rooms is None else self._simulate(d, bands)
+        self.last_room_stats = self._room_stats(d, rir, bands)
         s = self.last_stretch = self.draw_stretch(B, d.speed)
         clean = self._perturb(d, s, clean)
         shift, clean = self._level(d, clean)
@@ -939,6 +1001,17 @@ class DynamicMixer:
         return target, noisy, info
 
     # ---- the stages of a call, in its order -------------------------------------------------------------------------
+    def _room_stats(self, d: Draw, rir: Optional[RirBank], bands: Optional[torch.Tensor]) -> Optional[RirStats]:
+        """What the talkers' responses of the batch measure as: measured (rooms) or gathered from the measured bank."""
+        if not self.room_stats:
+            return None
+        if self.rooms is None:
+            index = d.rir_index.to(torch.int64)
+            return RirStats(*(t.index_select(0, index) for t in rir.stats))
+        B = d.rooms.size(0)
+        filt = None if bands is None else self.rooms.filters(self.sample_rate, self.engine.device)
+        return self.engine.rir_stats(rir.data[:B], rir.length[:B], filt, fs=self.sample_rate)
+
     def _perturb(self, d: Draw, s: Optional[StretchDraw], clean: torch.Tensor) -> torch.Tensor:
         """Tempo, pitch and speed: Engine.stretch and / or the ONE Engine.warp."""
         warp = lambda x, rate, N: self.engine.warp(x, rate, N, zeros=self.speed_zeros, rolloff=self.speed_rolloff)

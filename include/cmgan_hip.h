@@ -39,7 +39,7 @@ extern "C" {
 #define CMGAN_E_WORKSPACE   -5   /* workspace too small or misaligned              */
 #define CMGAN_E_HIP         -6   /* a HIP runtime call failed (see last_error)     */
 
-#define CMGAN_ABI_VERSION 15
+#define CMGAN_ABI_VERSION 16
 
 typedef struct cmgan_handle cmgan_handle;
 
@@ -781,6 +781,79 @@ size_t cmgan_rir_bands_workspace_bytes(const cmgan_handle* h, int R, int K, int 
 int cmgan_rir_bands(cmgan_handle* h, const double* rooms_dev, const double* bands_dev, const int* n_taps_dev, int R, int K,
                     int NB, const double* filt_dev, int NF, int fs, double c, int tw, int Nx, int Ny, int Nz,
                     float* rir_dev, long long ld, int* len_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- What a room impulse response measures as: decay curve, EDT / T20 / T30, DRR, C50 / C80, D50, Ts ------------------
+ * (the reference ships no impulse responses and no meter: src/data/dataloader.py:13-50 replays pairs mixed beforehand)
+ * The room-acoustic parameters of ISO 3382-1 as its published description gives them, broad-band and in the bands of a
+ * caller-supplied FIR filterbank, for the R rows rir_dev[r * ld + k] of a float32 [R, K] bank such as cmgan_rir makes.  No
+ * other program is claimed as the yardstick: the definition below is the contract.
+ *   len_dev     int32 [R] in DEVICE memory, read by the kernels only, or NULL for n = K; n = clamp(len[r], 1, K).  Samples at
+ *               k >= n and the padding between rows are never read
+ *   filt_dev    float64 [NB, NF], the layout and limits of cmgan_rir_bands: NF odd, D = (NF - 1) / 2, one FIR per band, shared
+ *               by all rows; its values are not judged (a NaN propagates to that band's columns and is never an address).
+ *               NULL with NB = 0: the broad-band analysis only (NF must still be odd; 1 will do)
+ *   stats_dev   float64 [R, NB + 1, P], P = cmgan_rir_stats_columns() = 10.  Slice 0 is broad-band, slice 1 + b is band b
+ *   status_dev  int32 [R, NB + 1], may be NULL: the CMGAN_RIR_STATS_* bits below
+ *   edc_dev     float64 [R, NB + 1, K], may be NULL: the decay curve EDC[k] for k < n and zeros from n on
+ * fs (Hz) and direct_ms are host numbers.  round(x) is floor(x + 1/2).  For row r and slice s:
+ *   band signal   s >= 1, b = s - 1:  y_s[k] = sum_j filt[b][j] h[k + D - j] for 0 <= k < n, with h = 0 outside [0, n); float64,
+ *                 j ascending, one fused multiply-add per term, from 0.  y_0[k] = h[k]
+ *   energy        e[k] = y_s[k]^2
+ *   direct        k0 = the smallest k < n that maximises |h[k]| of the BROAD-BAND row: the same for every slice.
+ *                 w = round(direct_ms fs / 1000),  k50 = min(k0 + round(0.050 fs), n),  k80 = min(k0 + round(0.080 fs), n)
+ *   decay curve   EDC[k] = sum_{j >= k} e[j] (Schroeder's backward integral),  E = EDC[0]
+ *   thresholds    ka(x) = the smallest k < n with EDC[k] <= c_x E, compared in the linear domain with the float64 constants
+ *                 CMGAN_RIR_STATS_DOWN_x below (c_x = 10^(-x/10), x = 5, 10, 25, 35).  Without such a k, ka(x) does not exist
+ *   decay times   T30 on [ka(5), ka(35)), T20 on [ka(5), ka(25)), EDT on [0, ka(10)).  With L[k] = 10 log10(EDC[k] / E), m the
+ *                 number of samples in the range and kbar their mean index:
+ *                     slope = fs sum_k (k - kbar) L[k] / (m (m^2 - 1) / 12)  dB/s,      time = -60 / slope  seconds
+ *                 (the least-squares line through the curve, extrapolated to 60 dB).  If the range's end does not exist,
+ *                 m < 2 or the slope is not negative, the time is NaN and its status bit is set
+ *   ratios        A = sum e[k] over max(k0 - w, 0) <= k <= min(k0 + w, n - 1);  DRR = 10 log10(A / (before + after)), the
+ *                 denominator the sum of the energies before and after that window, added as such and not E - A
+ *                 C50 = 10 log10(sum_{k < k50} e / EDC[k50]),  C80 alike with k80;  D50 = sum_{k < k50} e / E
+ *                 Ts = sum_k max(k - k0, 0) e[k] / (fs E)  seconds
+ *                 an empty denominator (nothing outside the window; k50 = n or nothing after it) gives +inf dB
+ *   columns       0 E, 1 k0 (as a double), 2 DRR dB, 3 C50 dB, 4 C80 dB, 5 D50, 6 Ts s, 7 EDT s, 8 T20 s, 9 T30 s
+ *   status        CMGAN_RIR_STATS_NONFINITE: a sample within n is NaN or inf; every column of every slice of the row is NaN
+ *                 (and its curve is NaN below n).  CMGAN_RIR_STATS_ZERO: E == 0; the slice's columns are NaN except E = 0.
+ *                 CMGAN_RIR_STATS_NO_EDT / _NO_T20 / _NO_T30: that time is NaN (always set with the two bits before)
+ * Not done: noise-floor compensation (Lundeby's truncation and correction) - a response with less than 35 dB of decay range
+ * above its floor gets a T30 that includes the floor, the curve of a response cut at n bends down towards n (the integral
+ * stops there) and a range that reaches into that bend shortens the time, and a response whose curve never falls 35 dB
+ * below E gets NaN rather than a guess; ISO's own octave filters are not supplied - the caller's filterbank is used,
+ * typically mixing.octave_filterbank, whose bands are wider than ISO's.
+ * All arithmetic is float64 on the VALU.  A block of the first launch owns cmgan_rir_stats_tile() consecutive samples of one
+ * (row, slice): it runs the band filter from on-chip copies of the span and the taps and leaves e[k] and the tile's total
+ * (a fixed tree) in the workspace.  One block per (row, slice) of the second launch folds the totals in descending tile
+ * order into entry sums, suffix-scans tile after tile from them, finds every ka as an integer minimum and k0 by a
+ * max-reduction under a total order (larger |h|, then smaller index), and adds the ratio and regression sums per thread in
+ * ascending k and then by the same fixed tree.  No atomics; every reduction runs in an order that depends on n and the tile
+ * grid alone: the same bits from run to run, row r's bits depend neither on R nor on the other rows, nor on ld, nor on K
+ * beyond n, and slice 0 does not depend on NB.  No value read from device memory is turned into an address except k0, which
+ * the kernel computed itself as an index below n.
+ * Checked before any launch and before the handle is looked at (the message of a call with h == NULL is read with
+ * cmgan_last_error(NULL)): null rir_dev / stats_dev, misaligned pointers (4 bytes for rir, len and status, 8 for filt, stats
+ * and edc), 1 <= R <= 65535, 1 <= K <= 65536, ld >= K, 0 <= NB <= cmgan_rir_max_bands(), filt_dev NULL exactly when NB = 0,
+ * NF odd in [1, cmgan_rir_max_filter()], fs > 0, direct_ms finite and >= 0, a workspace that is null, not 256-byte aligned
+ * or smaller than cmgan_rir_stats_workspace_bytes (h may be NULL; 0 for unsupported arguments; non-decreasing in each);
+ * otherwise CMGAN_E_BADARG / CMGAN_E_UNSUPPORTED.  Two launches, no synchronisation, no allocation; graph-capturable, and a
+ * replay reads the current contents of rir_dev, len_dev and filt_dev. */
+#define CMGAN_RIR_STATS_NONFINITE 1
+#define CMGAN_RIR_STATS_ZERO 2
+#define CMGAN_RIR_STATS_NO_EDT 4
+#define CMGAN_RIR_STATS_NO_T20 8
+#define CMGAN_RIR_STATS_NO_T30 16
+#define CMGAN_RIR_STATS_DOWN_5 0.31622776601683794     /* 10^-0.5 */
+#define CMGAN_RIR_STATS_DOWN_10 0.1                     /* 10^-1   */
+#define CMGAN_RIR_STATS_DOWN_25 0.0031622776601683794   /* 10^-2.5 */
+#define CMGAN_RIR_STATS_DOWN_35 0.00031622776601683794  /* 10^-3.5 */
+int cmgan_rir_stats_tile(void);
+int cmgan_rir_stats_columns(void);
+size_t cmgan_rir_stats_workspace_bytes(const cmgan_handle* h, int R, int K, int NB, int NF);
+int cmgan_rir_stats(cmgan_handle* h, const float* rir_dev, int R, int K, long long ld, const int* len_dev,
+                    const double* filt_dev, int NB, int NF, int fs, double direct_ms, double* stats_dev, int* status_dev,
+                    double* edc_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---- Active speech level (the reference has no level handling: src/data/dataloader.py:13-50 replays pairs mixed
  * beforehand) ---------------------------------------------------------------------------------------------------------
