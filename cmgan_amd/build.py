@@ -18,14 +18,14 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libcmgan_hip.so")
 SOURCES = ["api.hip", "api_train.hip", "conformer.hip", "conformer_x3.hip", "attn32_x3.hip", "ffn32_x3.hip", "conv.hip", "conv_x3.hip",
            "in_running.hip", "stft.hip", "stft_fft.hip", "train.hip", "train_x3.hip", "disc.hip", "metrics.hip", "resample.hip", "rir.hip",
-           "level.hip", "channel.hip", "warp.hip", "scene.hip", "stretch.hip", "rir_stats.hip"]
+           "level.hip", "channel.hip", "warp.hip", "scene.hip", "stretch.hip", "rir_stats.hip", "rir_tail.hip"]
 # pure-VALU kernels that WANT packed fp32 instructions (complex arithmetic of the FFT front / back end): built without
 # the "-packed-fp32-ops" feature removal below
 PACKED_FP32_SOURCES = {"stft_fft.hip"}
 # the F16X1 (single fp16 product) twins of the x3 kernels: the same sources compiled a second time with X1_FLAGS
 X1_SOURCES = ["conformer_x3.hip", "attn32_x3.hip", "ffn32_x3.hip", "conv_x3.hip"]
 X1_FLAGS = ["-DX3_SINGLE", "-DX3_TERMS=1"]
-HEADERS = ["common.hip.h", "kernels.h", "weights.h", "api_internal.h", "train.h", "stft_fft_tables.h", "warp_common.hip.h",
+HEADERS = ["common.hip.h", "kernels.h", "weights.h", "api_internal.h", "train.h", "stft_fft_tables.h", "warp_common.hip.h", "philox.hip.h",
            os.path.join("..", "..", "include", "cmgan_hip.h")]
 # the generator FORWARD path: what bench.py measures and what the PMC evidence under profiles/ was collected on.  The
 # training-step slices (train.hip, api_train.hip, train.h) and the public header (which grows with them) are left

@@ -2,6 +2,7 @@
 // generator forward path: the non-adversarial loss terms of Trainer.calculate_generator_loss (train.py:124-151)
 // as deterministic reductions (the scalars the data-parallel step all-reduces over RCCL).
 #include "train.h"
+#include "philox.hip.h"
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -2090,18 +2091,8 @@ __global__ __launch_bounds__(256) void swap_axes_kernel(const float* __restrict_
 // round(keep * 65536).  The offset is advanced by a one-thread kernel after the draw, so a captured graph replays with
 // fresh masks and nothing in the launches changes from step to step.  (torch's bernoulli_ on the 5.8 GB of masks of a
 // 32-clip step took 4.7 ms; this writes them at the HBM rate.)   state = {seed, offset} as two 64-bit words.
+// (philox4x32_10: philox.hip.h)
 // ---------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-        const unsigned n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
 __global__ __launch_bounds__(256) void dropout_mask_kernel(unsigned char* __restrict__ out, long ngroups, unsigned thresh,
                                                            const unsigned long long* __restrict__ state) {
     const unsigned long long seed = state[0], offset = state[1];

@@ -291,6 +291,42 @@ def check_rir_stats_args(device, rir, length=None, filters=None, fs=16000, direc
     return R, K, NB, NF
 
 
+RIR_TAIL_MAX_WINDOW = 4096    # = cmgan_rir_tail_max_window(): the longest fit window in samples
+RIR_TAIL_NOTHING, RIR_TAIL_WINDOW, RIR_TAIL_DECAY, RIR_TAIL_NONFINITE = 1, 2, 4, 8    # status bits
+
+
+class RirTail(NamedTuple):
+    """Engine.rir_tail: the fitted level A_b of every band (float64 [R, max(NB, 1)], 0 for a row left untouched) and the
+    int32 [R] status (0, or the RIR_TAIL_* bits of the reasons a row was left untouched)."""
+    gain: torch.Tensor
+    status: torch.Tensor
+
+
+def check_rir_tail_args(device, rir, length, n_taps, decay, seed, filters=None, fs=16000, window_ms=30.0):
+    """Argument rules of Engine.rir_tail (shapes, dtypes, devices and host scalars; pure host code).  Returns
+    (R, K, NB, NF, W): NB = 0 and NF = 1 without filters, W the window in samples."""
+    R, K = _row_batch(device, rir, RIR_MAX_TAPS, name="rir")
+    tensor_arg(length, "length", torch.int32, device, f"[{R}]", lambda t: tuple(t.shape) == (R,))
+    tensor_arg(n_taps, "n_taps", torch.int32, device, f"[{R}]", lambda t: tuple(t.shape) == (R,))
+    NB, NF = 0, 1
+    if filters is not None:
+        tensor_arg(filters, "filters", torch.float64, device,
+                   f"[NB, NF] with 1 <= NB <= {RIR_MAX_BANDS} and NF odd in [1, {RIR_MAX_FILTER}]",
+                   lambda t: t.dim() == 2 and 1 <= t.size(0) <= RIR_MAX_BANDS and 1 <= t.size(1) <= RIR_MAX_FILTER
+                   and t.size(1) % 2 == 1)
+        NB, NF = filters.shape
+    NBp = max(NB, 1)
+    tensor_arg(decay, "decay", torch.float64, device, f"[{R}, {NBp}]", lambda t: tuple(t.shape) == (R, NBp))
+    tensor_arg(seed, "seed", torch.int64, device, f"[{R}]", lambda t: tuple(t.shape) == (R,))
+    if isinstance(fs, bool) or int(fs) != fs or not 1 <= fs <= 2 ** 31 - 1:
+        raise ValueError(f"fs must be a positive sample rate, got {fs}")
+    window_ms = float(window_ms)
+    W = int(window_ms * float(fs) / 1000.0 + 0.5) if 0.0 <= window_ms < float("inf") else 0      # round to nearest, halves up
+    if not 1 <= W <= RIR_TAIL_MAX_WINDOW:
+        raise ValueError(f"window_ms must give a window of 1 .. {RIR_TAIL_MAX_WINDOW} samples at fs = {fs}, got {window_ms}")
+    return R, K, NB, NF, W
+
+
 def _row_stride_ok(t, B: int, L: int) -> bool:
     return t.stride(1) == 1 and (B == 1 or t.stride(0) >= L)
 
@@ -1241,6 +1277,32 @@ class Engine:
                    float(direct_ms), stats, status, curve, ws, ws.numel())
         out = RirStats(*stats.unbind(dim=2), status)
         return (out, curve) if edc else out
+
+    @_on_device
+    def rir_tail(self, rir: torch.Tensor, length: torch.Tensor, n_taps: torch.Tensor, decay: torch.Tensor, seed: torch.Tensor,
+                 filters: Optional[torch.Tensor] = None, fs: int = 16000, window_ms: float = 30.0):
+        """The diffuse reverberant tail behind the early part of every response of a bank (cmgan_rir_tail,
+        include/cmgan_hip.h): from its junction on, a row is extended IN PLACE by decaying noise that follows the given
+        60 dB decay time band by band, its level fitted to the `window_ms` in front of the junction.
+
+        rir float32 [R, K] (rows contiguous, any row stride >= K) and length int32 [R], as Engine.rir / Engine.rir_bands
+        return them for a SHORT n_taps: length is the junction (clamped to [1, K]), below which the row is never written;
+        n_taps int32 [R], the wanted total length; decay float64 [R, max(NB, 1)] seconds; seed int64 [R], one noise key per
+        row; filters float64 [NB, NF], NF odd, the filterbank of Engine.rir_bands, or None for one broad band; all on this
+        Engine's device and read by the kernels only.  Returns (rir, length, RirTail(gain, status)): the bank and its
+        lengths updated in place, the fitted level per band and the int32 status.  A row with nothing to add, with a
+        window that does not fit in front of its junction ((NF - 1) / 2 more with filters), with a decay time that is not
+        finite and > 0 or with a non-finite sample in the fit's reach keeps its taps and length and gets gain 0 and the
+        RIR_TAIL_* bits of the reasons.  Float64 arithmetic, one rounding to float32; bit-reproducible, row-independent,
+        no synchronisation, graph-capturable after one call at the shape."""
+        R, K, NB, NF, W = check_rir_tail_args(self.device, rir, length, n_taps, decay, seed, filters, fs, window_ms)
+        ws = self._grow("rir_tail", int(self.lib.cmgan_rir_tail_workspace_bytes(self._h, R, K, NB, NF)),
+                        f"[{R}, {K}] with {NB} bands and {NF} filter taps is outside what cmgan_rir_tail supports")
+        gain = torch.empty(R, max(NB, 1), dtype=torch.float64, device=self.device)
+        status = torch.empty(R, dtype=torch.int32, device=self.device)
+        self._call("cmgan_rir_tail", rir, R, K, rir.stride(0) if R > 1 else K, length, n_taps, decay, seed, filters, NB, NF, W,
+                   int(fs), status, gain, ws, ws.numel())
+        return rir, length, RirTail(gain, status)
 
     # ---- active speech level -------------------------------------------------------
     @_on_device

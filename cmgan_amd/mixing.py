@@ -20,6 +20,9 @@ takes - with `clean` the training target (the dry clip, or the clip with its ear
     # rooms whose reverberation time falls with frequency: walls that absorb more per octave (tilt) and air absorption
     # (air: the caller's ranges of nepers per metre, one per band), in 7 octave bands (Engine.rir_bands / cmgan_rir_bands)
     mixer = DynamicMixer(engine, noise, rooms=RoomSampler(bands=7, tilt=(0.0, 0.5), air=my_air_ranges), snr_db=(0, 20))
+    # long responses - halls, stairwells: the image-source method only to 80 ms after the direct sound, a diffuse tail of
+    # decaying noise at the room's decay time from there on (Engine.rir_tail / cmgan_rir_tail)
+    mixer = DynamicMixer(engine, noise, rooms=RoomSampler(rt60=(0.4, 1.2), tail_ms=80.0), rir_seconds=1.0)
     # the recording channel: a random equaliser, a band limit and clipping per row (Engine.channel / cmgan_channel)
     mixer = DynamicMixer(engine, noise, rirs, channel=ChannelSampler(p_bandlimit=0.2, p_clip=0.1))
     clean = torch.utils.data.DataLoader(clean_only("data/train", 32000), batch_size=32, pin_memory=True, drop_last=True)
@@ -45,15 +48,16 @@ import torch
 import torch.utils.data
 
 from .data import _natural_key, fit_length, read_wav
-from .engine import STRETCH_HOP, STRETCH_SEARCH, RirStats, _whole_in
+from .engine import RIR_TAIL_MAX_WINDOW, STRETCH_HOP, STRETCH_SEARCH, RirStats, RirTail, _whole_in
 
 __all__ = ["NoiseBank", "RirBank", "RoomSampler", "sabine_beta", "octave_filterbank", "DynamicMixer", "MixingLoader", "CleanDataset",
            "clean_only", "Draw", "SceneDraw", "tile", "ChannelSampler", "biquad_peaking", "biquad_low_shelf", "biquad_high_shelf",
-           "biquad_lowpass", "biquad_highpass", "butter_lowpass_sos", "warp_len", "stretch_len", "StretchDraw"]
+           "biquad_lowpass", "biquad_highpass", "butter_lowpass_sos", "warp_len", "stretch_len", "StretchDraw", "TailDraw"]
 
 SPEED_OF_SOUND = 343.0        # m/s, the default `c` of Engine.rir
 RIR_TW = 40                   # the default half-width of its fractional-delay filter, in samples
 SPEED_RANGE = (0.25, 4.0)     # the rates Engine.warp takes (cmgan_warp_max_rate)
+THREE_LN10 = 3.0 * math.log(10.0)    # a 60 dB decay over T seconds is 3 ln 10 / T amplitude nepers per second
 
 
 def warp_len(L: int, rate: float) -> int:
@@ -249,6 +253,18 @@ def _band_ranges(name: str, value, n: int):
     return pairs
 
 
+class TailDraw(NamedTuple):
+    """RoomSampler.draw_tail: what Engine.rir_tail needs beyond the responses `draw` was simulated to.  n_full int32 [R],
+    the responses' whole lengths; decay float64 [R, max(bands, 1)], the 60 dB decay time per band; seed int64 [R]; with
+    `sources` also src_junction int32 [R, n], every located source's own junction, and src_seed int64 [R, n] (a source uses
+    its room's n_full and decay)."""
+    n_full: torch.Tensor
+    decay: torch.Tensor
+    seed: torch.Tensor
+    src_junction: Optional[torch.Tensor] = None
+    src_seed: Optional[torch.Tensor] = None
+
+
 class RoomSampler:
     """Random shoe-box rooms for Engine.rir: `draw(R, K, fs)` -> `(rooms float64 [R, 15], n_taps int32 [R])`.
 
@@ -265,13 +281,24 @@ class RoomSampler:
     b_ref)) while its alpha_b stays below 1, and at 1 kHz the room is the one `draw` made.  `air` is None (no air
     absorption) or n (low, high) ranges of the amplitude attenuation m_b in nepers per metre, drawn per room; there is no
     default table of a "standard atmosphere": the values are the caller's.  Without `bands` (the default) the sampler is
-    what it was: the same draws from the generator, and `draw_bands` is an error."""
+    what it was: the same draws from the generator, and `draw_bands` is an error.
+
+    `tail_ms` = a float turns on the hybrid of Engine.rir_tail: the image-source method only up to a JUNCTION `tail_ms`
+    milliseconds after the direct sound, a diffuse tail of decaying noise from there on.  `draw` then returns as n_taps the
+    junction min(n_full, ceil((|source - receiver| / c + tail_ms / 1000) fs)), n_full the n_taps above, and `n_images`
+    covers only the largest junction the sampler can draw - that is where the saving comes from.  `draw_tail(rooms, fs)`,
+    called after `draw` (and `draw_bands`, and `draw_sources`), gives a TailDraw: n_full, the decay times - the drawn rt60
+    itself, or with `bands` 1 / decay_b = 1 / (rt60 2^(-tilt (b - b_ref))) + m_b c / (3 ln 10), walls and air, from the rt60
+    and tilt that were drawn and not from the table's coefficients - and int64 noise seeds, a torch.randint from
+    `generator` on the device after every other draw.  The tail's level is fitted to the `tail_window_ms` in front of the
+    junction, so tail_ms must exceed that window (with `bands`, by the filterbank's delay too).  With None (the default)
+    the sampler draws the same numbers as before and `draw_tail` is an error."""
 
     BAND_F0 = 125.0               # Hz: the centre of band 0
 
     def __init__(self, dims=((3.0, 3.0, 2.5), (10.0, 8.0, 4.0)), rt60=(0.2, 0.8), margin: float = 0.5,
                  generator: Optional[torch.Generator] = None, bands: Optional[int] = None, tilt=(0.0, 0.0), air=None,
-                 filter_taps: int = 511):
+                 filter_taps: int = 511, tail_ms: Optional[float] = None, tail_window_ms: float = 30.0):
         try:
             lo, hi = (tuple(float(v) for v in d) for d in dims)
         except (TypeError, ValueError):
@@ -299,11 +326,29 @@ class RoomSampler:
             # the band nearest 1 kHz on the octave scale
             self.band_ref = min(max(int(round(math.log2(1000.0 / self.BAND_F0))), 0), self.bands - 1)
         self._filters = {}
+        if tail_ms is not None:
+            if isinstance(tail_ms, bool) or not isinstance(tail_ms, (int, float)) or not 0.0 < tail_ms < math.inf:
+                raise ValueError(f"tail_ms must be None or a positive, finite number of milliseconds, got {tail_ms}")
+            tail_ms = float(tail_ms)
+        if isinstance(tail_window_ms, bool) or not isinstance(tail_window_ms, (int, float)) or not 0.0 < tail_window_ms < math.inf:
+            raise ValueError(f"tail_window_ms must be a positive, finite number of milliseconds, got {tail_window_ms}")
+        self.tail_ms, self.tail_window_ms = tail_ms, float(tail_window_ms)
+        self._drawn = {}              # tail_ms: the rt60, n_full (draw), tilt and m (draw_bands) of the last draw, for draw_tail
+
+    def max_junction(self, K: int, fs: int, c: float = SPEED_OF_SOUND) -> int:
+        """The largest n_taps `draw` can return: K, or with `tail_ms` min(K, ceil((d / c + tail_ms / 1000) fs)) with d the
+        diagonal of the UPPER size bound shrunk by the margin, the farthest a source can be from a receiver."""
+        if self.tail_ms is None:
+            return K
+        d = math.sqrt(sum((l - 2.0 * self.margin) ** 2 for l in self.hi))
+        return min(K, int(math.ceil((d / c + self.tail_ms / 1000.0) * fs)))
 
     def n_images(self, K: int, fs: int, c: float = SPEED_OF_SOUND, tw: int = RIR_TW):
         """(Nx, Ny, Nz) that leaves out no image of a K-tap response in any room this sampler draws: host arithmetic on
         the LOWER size bound, ceil((K + tw) c / fs / (2 Lmin_axis)) + 1.  With `bands` the ranges cover K + D taps, D the
-        filterbank's delay: Engine.rir_bands simulates the bands that far."""
+        filterbank's delay: Engine.rir_bands simulates the bands that far.  With `tail_ms` K is `max_junction(K, fs)`:
+        the images stop at the junction."""
+        K = self.max_junction(K, fs, c)
         if self.bands is not None:
             K = K + (self.filter_taps - 1) // 2
         return tuple(int(math.ceil((K + tw) * c / fs / (2.0 * l))) + 1 for l in self.lo)
@@ -340,7 +385,49 @@ class RoomSampler:
             lo = torch.tensor([p[0] for p in self.air], dtype=torch.float64).to(rooms.device, non_blocking=True)
             hi = torch.tensor([p[1] for p in self.air], dtype=torch.float64).to(rooms.device, non_blocking=True)
             m = lo + (hi - lo) * u[:, 1:]
+        if self.tail_ms is not None:
+            self._drawn.update(tilt=tilt, m=m)
         return torch.cat([walls, m[:, :, None]], dim=2).contiguous()
+
+    def _junction(self, tables: torch.Tensor, n_full: torch.Tensor, fs: int) -> torch.Tensor:
+        """min(n_full, ceil((|source - receiver| / c + tail_ms / 1000) fs)) of [..., 15] tables, int32."""
+        direct = torch.linalg.vector_norm(tables[..., 3:6] - tables[..., 6:9], dim=-1) / SPEED_OF_SOUND
+        return torch.minimum(torch.ceil((direct + self.tail_ms / 1000.0) * fs).to(torch.int32), n_full)
+
+    def draw_tail(self, rooms: torch.Tensor, fs: int, sources: Optional[torch.Tensor] = None) -> TailDraw:
+        """The TailDraw of rooms that `draw` made last (and `draw_bands`, with bands; `sources`: the [R, n, 15] tables of
+        `draw_sources`).  Only the seeds are drawn: torch.randint(R) and, with sources, torch.randint(R, n) from
+        `generator` on the device of `rooms`; the rest is arithmetic on what the earlier draws kept."""
+        if self.tail_ms is None:
+            raise ValueError("this RoomSampler has no tail_ms")
+        if not isinstance(rooms, torch.Tensor) or rooms.dtype != torch.float64 or rooms.dim() != 2 or rooms.size(1) != 15:
+            raise ValueError("rooms must be a float64 [R, 15] table of RoomSampler.draw")
+        R, kept = rooms.size(0), self._drawn
+        need = ("rt", "n_full") if self.bands is None else ("rt", "n_full", "tilt", "m")
+        if any(k not in kept or kept[k].size(0) != R or kept[k].device != rooms.device for k in need):
+            raise ValueError("draw_tail follows draw (and draw_bands, with bands) of the same rooms")
+        W = int(self.tail_window_ms * float(fs) / 1000.0 + 0.5)
+        D = 0 if self.bands is None else (self.filter_taps - 1) // 2
+        if not 1 <= W <= RIR_TAIL_MAX_WINDOW or math.ceil(self.tail_ms / 1000.0 * fs) < W + D:
+            raise ValueError(f"tail_ms = {self.tail_ms} at fs = {fs} must leave room for the fit window of tail_window_ms = "
+                             f"{self.tail_window_ms} (1 .. {RIR_TAIL_MAX_WINDOW} samples) and the filterbank's delay of {D} samples")
+        rt = kept["rt"]
+        if self.bands is None:
+            decay = rt[:, None].contiguous()
+        else:
+            step = torch.arange(self.bands, dtype=torch.float64).to(rooms.device, non_blocking=True) - float(self.band_ref)
+            walls = rt[:, None] * torch.exp2(-kept["tilt"][:, None] * step[None, :])
+            decay = (1.0 / (1.0 / walls + kept["m"] * (SPEED_OF_SOUND / THREE_LN10))).contiguous()
+        draw = lambda *shape: torch.randint(0, 2 ** 63 - 1, shape, dtype=torch.int64, generator=self.generator,
+                                            device=rooms.device)
+        seed = draw(R)
+        if sources is None:
+            return TailDraw(kept["n_full"], decay, seed)
+        if not isinstance(sources, torch.Tensor) or sources.dtype != torch.float64 or sources.dim() != 3 \
+                or sources.size(0) != R or sources.size(2) != 15:
+            raise ValueError(f"sources must be the float64 [{R}, n, 15] tables of RoomSampler.draw_sources")
+        junction = self._junction(sources, kept["n_full"][:, None], fs).contiguous()
+        return TailDraw(kept["n_full"], decay, seed, junction, draw(R, sources.size(1)))
 
     def draw(self, R: int, K: int, fs: int, device=None):
         gen = self.generator
@@ -356,6 +443,9 @@ class RoomSampler:
         beta = sabine_beta(rt, size)
         rooms = torch.cat([size, source, receiver, beta[:, None].expand(R, 6)], dim=1).contiguous()
         n_taps = torch.ceil(rt * fs).clamp(1, K).to(torch.int32)
+        if self.tail_ms is not None:
+            self._drawn = dict(rt=rt, n_full=n_taps)
+            n_taps = self._junction(rooms, n_taps, fs)
         return rooms, n_taps
 
     def draw_sources(self, rooms: torch.Tensor, n: int) -> torch.Tensor:
@@ -542,6 +632,7 @@ class RirBank:
     def __init__(self, data: torch.Tensor, length: torch.Tensor, rooms: Optional[torch.Tensor] = None,
                  bands: Optional[torch.Tensor] = None, stats: Optional[RirStats] = None):
         self.data, self.length, self.rooms, self.bands, self.stats = data, length, rooms, bands, stats
+        self.tail: Optional[RirTail] = None      # simulate with RoomSampler(tail_ms=...): the fitted levels and the status
 
     def __len__(self) -> int:
         return self.data.size(0)
@@ -568,7 +659,9 @@ class RirBank:
     def simulate(cls, engine, sampler: RoomSampler, R: int, seconds: float = 0.5, sample_rate: int = 16000,
                  measure: bool = False) -> "RirBank":
         """R rooms drawn by `sampler`, each simulated for up to `seconds` (a row's own length is its rt60, if shorter).
-        measure=True then measures the bank (`measure`), in the sampler's bands if it has any."""
+        With RoomSampler(tail_ms=...) the image-source call stops at each row's junction and Engine.rir_tail adds the
+        rest (`tail` keeps its RirTail).  measure=True then measures the bank (`measure`), in the sampler's bands if it
+        has any."""
         K = int(round(seconds * sample_rate))
         rooms, n_taps = sampler.draw(R, K, sample_rate, device=engine.device)
         N = sampler.n_images(K, sample_rate)
@@ -578,6 +671,10 @@ class RirBank:
         else:
             bands = sampler.draw_bands(rooms)
             bank = cls(*engine.rir_bands(rooms, bands, n_taps, K, filters, N, fs=sample_rate), rooms, bands)
+        if sampler.tail_ms is not None:                           # the responses end at their junctions: the diffuse tail
+            t = sampler.draw_tail(rooms, sample_rate)
+            bank.tail = engine.rir_tail(bank.data, bank.length, t.n_full, t.decay, t.seed, filters, fs=sample_rate,
+                                        window_ms=sampler.tail_window_ms)[2]
         if measure:
             bank.measure(engine, sample_rate, filters)
         return bank
@@ -751,7 +848,14 @@ class DynamicMixer:
     of [B, NB + 1] tensors for the rows of the batch, a dry row of `rooms` showing its one-tap response.  Nothing is
     drawn for it: with False (the default) `last_room_stats` is None and the outputs, draws and generator states are
     what they are without the argument, and with True they are the same too.  An unmeasured bank, or neither a bank nor
-    rooms, is refused."""
+    rooms, is refused.
+
+    `rooms=RoomSampler(tail_ms=...)`: the hybrid room simulator.  The image-source calls stop at every response's junction
+    (the talkers' and each located source's own) and Engine.rir_tail / cmgan_rir_tail adds a diffuse tail up to the
+    response's whole length, so `rir_seconds` of a second or two stay affordable.  The tail draw (`mixer.last_tail`, a
+    TailDraw) follows `draw` and `draw_bands`; `last_draw.rir_len` and `src_rir_len` then hold the EXTENDED lengths the batch
+    was mixed with, and `room_stats=True` measures the extended responses.  Without `tail_ms` nothing of this is drawn or
+    run."""
 
     def __init__(self, engine, noise_bank: NoiseBank, rir_bank: Optional[RirBank] = None, snr_db=(0.0, 20.0),
                  early_ms: Optional[float] = 50.0, p_reverb: float = 1.0, peak: float = 0.99,
@@ -829,6 +933,7 @@ class DynamicMixer:
         self.room_stats, self.last_room_stats = room_stats, None
         self.rir_taps, self.n_images, self.last_bank = 0, None, None
         self.last_bands: Optional[torch.Tensor] = None      # rooms=RoomSampler(bands=n): the float64 [B, n, 7] table of the batch
+        self.last_tail: Optional[TailDraw] = None           # rooms=RoomSampler(tail_ms=...): the batch's tail draw
         if rooms is not None:
             if rir_bank is not None:
                 raise ValueError("give either a rir_bank or rooms, not both")
@@ -949,9 +1054,25 @@ class DynamicMixer:
             return None
         return self.rooms.draw_bands(d.rooms)
 
-    def _simulate(self, d: Draw, bands: Optional[torch.Tensor] = None) -> RirBank:
+    def draw_tail(self, d: Draw) -> Optional[TailDraw]:
+        """The diffuse tails of a batch's rooms (None unless rooms=RoomSampler(tail_ms=...)): RoomSampler.draw_tail of
+        d.rooms and, with sources, d.src_rooms, made after `draw` and `draw_bands`; kept as `mixer.last_tail`."""
+        if self.rooms is None or self.rooms.tail_ms is None:
+            return None
+        return self.rooms.draw_tail(d.rooms, self.sample_rate, getattr(d, "src_rooms", None))
+
+    def _extended(self, d: Draw, sim: RirBank) -> Draw:
+        """`d` with the lengths Engine.rir_tail left in the simulated bank in place of the junctions that were drawn."""
+        B = d.rooms.size(0)
+        d = d._replace(rir_len=sim.length[:B].clone())
+        if self.sources is None:
+            return d
+        return d._replace(src_rir_len=sim.length[self._bank_rows(B):].reshape(B, self.sources[1]).clone())
+
+    def _simulate(self, d: Draw, bands: Optional[torch.Tensor] = None, tail: Optional[TailDraw] = None) -> RirBank:
         """The batch's responses, simulated into the persistent allocation (made anew only when B changes); with `bands`
-        by Engine.rir_bands, a source using its room's band table."""
+        by Engine.rir_bands, a source using its room's band table; with `tail` each call stops at the rows' junctions and
+        Engine.rir_tail adds the rest, a source from its own junction with its room's decay and a seed of its own."""
         B, K = d.rooms.size(0), self.rir_taps
         base = self._bank_rows(B)
         n_s = self.sources[1] if self.sources is not None else 0
@@ -972,10 +1093,21 @@ class DynamicMixer:
             else:
                 self.engine.rir_bands(rooms, table, taps, K, filt, self.n_images, fs=self.sample_rate, out=out)
 
-        simulate(d.rooms, d.rir_len, (sim.data[:B], sim.length[:B]), bands)
+        def extend(out, n_full, decay, seed):                     # (a dry row's junction is 1: no window fits, it stays)
+            self.engine.rir_tail(*out, n_full, decay, seed, filt, fs=self.sample_rate, window_ms=self.rooms.tail_window_ms)
+
+        out = (sim.data[:B], sim.length[:B])
+        simulate(d.rooms, d.rir_len, out, bands)
+        if tail is not None:
+            extend(out, tail.n_full, tail.decay, tail.seed)
         if n_s:                                                   # the sources' responses: one call of B S rows
-            simulate(d.src_rooms.reshape(B * n_s, 15), d.src_rir_len.reshape(B * n_s), (sim.data[base:], sim.length[base:]),
+            out = (sim.data[base:], sim.length[base:])
+            taps = d.src_rir_len if tail is None else tail.src_junction
+            simulate(d.src_rooms.reshape(B * n_s, 15), taps.reshape(B * n_s), out,
                      None if bands is None else bands.repeat_interleave(n_s, dim=0))
+            if tail is not None:
+                extend(out, tail.n_full.repeat_interleave(n_s), tail.decay.repeat_interleave(n_s, dim=0),
+                       tail.src_seed.reshape(B * n_s))
         return sim
 
     @staticmethod
@@ -991,7 +1123,10 @@ class DynamicMixer:
         B = clean.size(0)
         d = self.last_draw = self.draw(B)
         bands = self.last_bands = self.draw_bands(d)
-        rir = self.rir_bank if self.rooms is None else self._simulate(d, bands)
+        tail = self.last_tail = self.draw_tail(d)
+        rir = self.rir_bank if self.rooms is None else self._simulate(d, bands, tail)
+        if tail is not None:                                      # the batch is mixed with the extended responses
+            d = self.last_draw = self._extended(d, rir)
         self.last_room_stats = self._room_stats(d, rir, bands)
         s = self.last_stretch = self.draw_stretch(B, d.speed)
         clean = self._perturb(d, s, clean)

@@ -39,7 +39,7 @@ extern "C" {
 #define CMGAN_E_WORKSPACE   -5   /* workspace too small or misaligned              */
 #define CMGAN_E_HIP         -6   /* a HIP runtime call failed (see last_error)     */
 
-#define CMGAN_ABI_VERSION 16
+#define CMGAN_ABI_VERSION 17
 
 typedef struct cmgan_handle cmgan_handle;
 
@@ -854,6 +854,73 @@ size_t cmgan_rir_stats_workspace_bytes(const cmgan_handle* h, int R, int K, int 
 int cmgan_rir_stats(cmgan_handle* h, const float* rir_dev, int R, int K, long long ld, const int* len_dev,
                     const double* filt_dev, int NB, int NF, int fs, double direct_ms, double* stats_dev, int* status_dev,
                     double* edc_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- The diffuse reverberant tail behind the early part of a room impulse response ------------------------------------
+ * (the reference ships no impulse responses and no simulator: src/data/dataloader.py:13-50 replays pairs mixed beforehand)
+ * The image-source method costs the cube of the response length; after the mixing time the reflections are dense and
+ * indistinguishable from decaying noise.  As gpuRIR does after its Tdiff, this call extends every row of a float32 [R, K]
+ * bank IN PLACE from its junction with noise under an exponential envelope that follows a GIVEN 60 dB decay time, band by
+ * band, the level fitted to one window in front of the junction.  It reads no room geometry: a recorded bank will do.
+ * All tables are in DEVICE memory and read by the kernels only:
+ *   rir_dev     float32 [R, K], row stride ld: row r holds valid taps below k_x; taps below k_x are never written
+ *   len_dev     int32 [R], in / out.  In: the junction, k_x = clamp(len[r], 1, K).  Out: max(k_x, k_end)
+ *   n_taps_dev  int32 [R]: the wanted total length, k_end = clamp(n_taps[r], 1, K)
+ *   decay_dev   float64 [R, NB'], NB' = max(NB, 1): the 60 dB decay time of band b in seconds
+ *   seed_dev    int64 [R]: one Philox key per row
+ *   filt_dev    float64 [NB, NF], NF odd, D = (NF - 1) / 2: the filterbank cmgan_rir_bands joins with (its values are not
+ *               judged), or NULL with NB = 0: broad-band, one band with g = {1}, NF = 1, D = 0 (the NF given is then only
+ *               checked to be odd)
+ *   status_dev  int32 [R], out: 0, or the CMGAN_RIR_TAIL_* bits of the reasons the row was left untouched
+ *   gain_dev    float64 [R, NB'], out: A_b below; 0 for an untouched row
+ * window (W samples) and fs (Hz) are host numbers.  For row r:
+ *   noise    nu[q] = (w0 + w1 + w2 + w3 - 2 (2^32 - 1)) / CMGAN_RIR_TAIL_NOISE_DIV for q >= 0 and 0 for q < 0, with (w0 .. w3) the
+ *            four 32-bit words of Philox4x32-10 at the counter words (q, 0, 0, 0) under the key (low, high 32 bits of
+ *            seed[r]).  The numerator is an integer below 2^34, exact in float64; the divisor is sqrt((2^64 - 1) / 3), the
+ *            standard deviation of the sum; the division is IEEE's.  Mean 0, variance 1, kurtosis 2.7 (four uniforms)
+ *   rate     delta_b = CMGAN_RIR_TAIL_3LN10 / (decay[r][b] fs): amplitude nepers per sample
+ *   band     z_b[k] = sum_j g_b[j] h[k + D - j] for k_x - D - W <= k < k_x - D: j ascending, one fused multiply-add per term
+ *            from 0, h the row's float32 values widened and 0 outside [0, k_x)
+ *   fit      E_b = sum_k z_b[k]^2,  G_b = sum_j g_b[j]^2,  S_b = sum_k exp(-2 delta_b (k - k_x)) over that window;
+ *            A_b = sqrt(E_b / (G_b S_b)), and 0 where E_b = 0 (a silent band is no error).  Each sum: thread t of 256 adds its
+ *            terms t, t + 256, ... in ascending order (squares by one fma each), thread 0 adds the 256 partials in ascending t
+ *   tail     y[k] = sum_b sum_j g_b[j] e_b[k + D - j],  e_b[q] = (A_b exp(-delta_b (q - k_x))) nu[q] rounded in that bracketing,
+ *            for k_x <= k < k_end: b ascending, then j ascending, one fused multiply-add per term into one accumulator
+ *            from 0, as the join of cmgan_rir_bands sums
+ *   outputs  rir_dev[r * ld + k] = f32(y[k]) for k_x <= k < k_end and exactly 0.0f for k_end <= k < K;  len[r] = k_end
+ * A row is left untouched - its taps and its len unchanged, gain 0 - with one status bit per reason:
+ *   CMGAN_RIR_TAIL_NOTHING    k_end <= k_x: nothing to add
+ *   CMGAN_RIR_TAIL_WINDOW     k_x - D - W < 0: the window does not fit
+ *   CMGAN_RIR_TAIL_DECAY      a decay time of the row is NaN, infinite or <= 0
+ *   CMGAN_RIR_TAIL_NONFINITE  a sample the fit reads - h[k], max(k_x - W - 2 D, 0) <= k < k_x - is NaN or infinite (judged
+ *                             only where the window fits)
+ * Not done: no fit of the decay rate (the early part of a shoe-box response is too sparse for one: the time is an input),
+ * no cross-fade (a hard switch at k_x), no Gaussian noise (kurtosis 2.7), nothing correlated between rows or channels.  A
+ * decay time so short that exp overflows within the window (far below a sample) gives non-finite taps, never an address.
+ * All arithmetic is float64 on the VALU and each tap is rounded to float32 exactly once.  The first launch has one block
+ * per (band, row) for the fit; a block of the second owns cmgan_rir_tail_tile() consecutive taps of one row, computes nu
+ * once for the span they reach and then, band after band, stages e_b on chip with one exp per element.  No atomics; the
+ * same bits from run to run; row r's bits depend neither on R nor on the other rows (their samples, band tables or
+ * seeds), nor on ld, nor on K beyond k_end.  Nothing read from a table becomes an address without a clamp.
+ * Checked before any launch and before the handle is looked at (the message of a call with h == NULL is read with
+ * cmgan_last_error(NULL)): null pointers (only filt_dev may be NULL), misaligned pointers (4 bytes for rir, len, n_taps and
+ * status, 8 for decay, seed, filt and gain), 1 <= R <= 65535, 1 <= K <= 65536, ld >= K, 0 <= NB <= cmgan_rir_max_bands(),
+ * filt_dev NULL exactly when NB = 0, NF odd in [1, cmgan_rir_max_filter()], 1 <= window <= cmgan_rir_tail_max_window()
+ * (4096), fs > 0, a workspace that is null, not 256-byte aligned or smaller than cmgan_rir_tail_workspace_bytes (h may be
+ * NULL; 0 for unsupported arguments; non-decreasing in each); otherwise CMGAN_E_BADARG / CMGAN_E_UNSUPPORTED.  The
+ * workspace holds each row's junction between the two launches.  No synchronisation, no allocation; graph-capturable, and
+ * a replay reads the tables' current contents - len_dev among them, which the call before it has rewritten. */
+#define CMGAN_RIR_TAIL_NOTHING 1
+#define CMGAN_RIR_TAIL_WINDOW 2
+#define CMGAN_RIR_TAIL_DECAY 4
+#define CMGAN_RIR_TAIL_NONFINITE 8
+#define CMGAN_RIR_TAIL_3LN10 6.907755278982137       /* 3 ln 10 */
+#define CMGAN_RIR_TAIL_NOISE_DIV 2479700524.506239   /* sqrt((2^64 - 1) / 3) */
+int cmgan_rir_tail_tile(void);
+int cmgan_rir_tail_max_window(void);
+size_t cmgan_rir_tail_workspace_bytes(const cmgan_handle* h, int R, int K, int NB, int NF);
+int cmgan_rir_tail(cmgan_handle* h, float* rir_dev, int R, int K, long long ld, int* len_dev, const int* n_taps_dev,
+                   const double* decay_dev, const long long* seed_dev, const double* filt_dev, int NB, int NF, int window,
+                   int fs, int* status_dev, double* gain_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---- Active speech level (the reference has no level handling: src/data/dataloader.py:13-50 replays pairs mixed
  * beforehand) ---------------------------------------------------------------------------------------------------------
