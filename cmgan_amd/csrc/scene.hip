@@ -43,6 +43,13 @@
 //   scene_vmax    per tile: max |v| -> one partial slot
 //   scene_scale   one block per row: the partial maxima -> s
 //   scene_apply   noisy = f32(v s), target = f32(target s) or clean's bits
+// cmgan_scene_path is cmgan_scene for a talker and sources that MOVE: P waypoint columns in the RIR tables, waypoint p at
+// input sample p H weighting the samples around it by u_p[m] = (H - |m - p H|) / H (held at the path's ends), so that
+//   speech[i] = sum_p sum_k h_p[k] (u_p[m] clean[b, m]),  m = i + d_p - k     every waypoint's OWN direct index d_p removed
+//   c_j[i]    = sum_p sum_k h_jp[k] (u_p[m] seg_j[m]),    m = i - k
+// in ONE accumulator over (p, k) ascending.  scene_direct_path and scene_conv_path take the places of scene_direct and
+// scene_conv; the inner tap loop, the store and every later kernel are shared, and a row with one waypoint has the static
+// call's bits.  Doppler is not modelled.
 // The per-row tables are read on the device only.  An entry that would make a kernel read outside its bank is not
 // trusted: a segment that leaves its bank or has no sample counts as silence (c_j = 0, P_j = 0, g_j = 0), a RIR index is
 // clamped to [0, R), a RIR length to [1, Kmax], offsets may be any int64.
@@ -218,6 +225,75 @@ __device__ inline void scene_gains(const SceneArgs& a, int b, int sb, double* g)
     for (int j = 1; j <= SC_MAX_S; ++j) g[j] = j <= sb ? a.g[(size_t)b * (1 + a.S) + j] : 0.0;
 }
 
+// one staged chunk of kc taps, ascending, into a thread's MX_OPT accumulators; the first nb taps also feed the target.
+// xs = s_x + t + kc - 1: output t + 256 r of the tile meets tap j of the chunk at xs[256 r - j]
+__device__ inline void mx_chunk_taps(const double* s_h, const double* xs, int kc, int nb, double* acc_s, double* acc_t) {
+    int j = 0;
+    for (; j < nb; ++j) {
+        const double hv = s_h[j];
+#pragma unroll
+        for (int r = 0; r < MX_OPT; ++r) {
+            const double xv = xs[r * MX_TPB - j];
+            acc_s[r] = fma(hv, xv, acc_s[r]);
+            acc_t[r] = fma(hv, xv, acc_t[r]);
+        }
+    }
+    for (; j + 1 < kc; j += 2) {
+        const double h0 = s_h[j], h1 = s_h[j + 1];
+#pragma unroll
+        for (int r = 0; r < MX_OPT; ++r) {
+            acc_s[r] = fma(h0, xs[r * MX_TPB - j], acc_s[r]);
+            acc_s[r] = fma(h1, xs[r * MX_TPB - j - 1], acc_s[r]);
+        }
+    }
+    for (; j < kc; ++j) {
+        const double hv = s_h[j];
+#pragma unroll
+        for (int r = 0; r < MX_OPT; ++r) acc_s[r] = fma(hv, xs[r * MX_TPB - j], acc_s[r]);
+    }
+}
+
+// the end of a convolution block, static or along a path: the float64 rows to the workspace, the block's sums of squares
+// to its partial slots; every thread calls
+__device__ inline void scene_conv_store(const SceneArgs& a, int src, int b, int i0, int cnt, size_t es, const double* acc_s,
+                                        const double* acc_t, double* s_red) {
+    const int t = threadIdx.x;
+    if (src == 0) {
+        const NoiseRow nr = scene_noise_row(a, b);
+        double ps = 0.0, pn = 0.0;
+#pragma unroll
+        for (int r = 0; r < MX_OPT; ++r) {
+            const int o = t + r * MX_TPB;
+            if (o < cnt) {
+                const size_t e = (size_t)b * a.L + i0 + o;
+                a.speech[e] = acc_s[r];
+                if (a.early >= 0) a.tgt[e] = acc_t[r];
+                ps = fma(acc_s[r], acc_s[r], ps);
+                const double n = mix_noise(nr, i0 + o);
+                pn = fma(n, n, pn);
+            }
+        }
+        ps = block_sum(ps, s_red);
+        pn = block_sum(pn, s_red);
+        if (t == 0) {
+            a.part_ps[(size_t)b * a.nt + blockIdx.x] = ps;
+            a.part_pn[(size_t)b * a.nt + blockIdx.x] = pn;
+        }
+    } else {
+        double pc = 0.0;
+#pragma unroll
+        for (int r = 0; r < MX_OPT; ++r) {
+            const int o = t + r * MX_TPB;
+            if (o < cnt) {
+                a.c[es * a.L + i0 + o] = acc_s[r];
+                pc = fma(acc_s[r], acc_s[r], pc);
+            }
+        }
+        pc = block_sum(pc, s_red);
+        if (t == 0) a.part_pc[es * a.nt + blockIdx.x] = pc;
+    }
+}
+
 // ------------------------------------------------------------------------------------------ kernels
 __global__ __launch_bounds__(MX_TPB) void scene_direct(SceneArgs a) {
     __shared__ float s_v[MX_TPB];
@@ -289,66 +365,139 @@ __global__ __launch_bounds__(MX_TPB) void scene_conv(SceneArgs a) {
         __syncthreads();
         long long nb_ll = kt - k0 + 1;                       // taps of the chunk that also feed the target
         const int nb = nb_ll < 0 ? 0 : (nb_ll > kc ? kc : (int)nb_ll);
-        const double* xs = s_x + t + kc - 1;
-        int j = 0;
-        for (; j < nb; ++j) {
-            const double hv = s_h[j];
-#pragma unroll
-            for (int r = 0; r < MX_OPT; ++r) {
-                const double xv = xs[r * MX_TPB - j];
-                acc_s[r] = fma(hv, xv, acc_s[r]);
-                acc_t[r] = fma(hv, xv, acc_t[r]);
-            }
-        }
-        for (; j + 1 < kc; j += 2) {
-            const double h0 = s_h[j], h1 = s_h[j + 1];
-#pragma unroll
-            for (int r = 0; r < MX_OPT; ++r) {
-                acc_s[r] = fma(h0, xs[r * MX_TPB - j], acc_s[r]);
-                acc_s[r] = fma(h1, xs[r * MX_TPB - j - 1], acc_s[r]);
-            }
-        }
-        for (; j < kc; ++j) {
-            const double hv = s_h[j];
-#pragma unroll
-            for (int r = 0; r < MX_OPT; ++r) acc_s[r] = fma(hv, xs[r * MX_TPB - j], acc_s[r]);
-        }
+        mx_chunk_taps(s_h, s_x + t + kc - 1, kc, nb, acc_s, acc_t);
         __syncthreads();
     }
+    scene_conv_store(a, src, b, i0, cnt, es, acc_s, acc_t, s_red);
+}
+
+// ---- cmgan_scene_path: the talker and the sources move along a path of responses.  In `a` the four RIR tables are the
+// [B, P] / [B, S, P] ones and `d` is not used: the direct indices, one per waypoint, are in `dp`.
+struct ScenePathArgs {
+    SceneArgs a;
+    const int* n_path;               // [B]
+    const int* s_n_path;             // [B, S]
+    int* dp;                         // workspace: [B][P]
+    long long H;                     // input samples between waypoints
+    int P;
+};
+
+constexpr int SP_MAX_P = 64;                    // waypoint columns
+constexpr long long SP_MAX_H = 1LL << 30;       // so p H and the weights' numerators stay far inside an int64 / a double
+constexpr long long SP_FAR = 1LL << 40;         // beyond every sample index and every p H
+
+__device__ inline int path_count(const int* n_path, size_t row, int P) {
+    const int n = n_path[row];
+    return n < 1 ? 1 : (n > P ? P : n);
+}
+
+// u_p[m]: the triangle of half-width H around p H - an exact integer numerator, one IEEE division - that the first
+// waypoint holds at 1 for m <= 0 and the last one for m >= (Pb - 1) H
+__device__ inline double path_weight(long long m, int p, int Pb, long long H) {
+    long long a = m - (long long)p * H;
+    if (a <= 0 && p == 0) return 1.0;
+    if (a >= 0 && p == Pb - 1) return 1.0;
+    if (a < 0) a = -a;
+    return a < H ? (double)(H - a) / (double)H : 0.0;
+}
+
+__global__ __launch_bounds__(MX_TPB) void scene_direct_path(ScenePathArgs pa) {
+    __shared__ float s_v[MX_TPB];
+    __shared__ int s_i[MX_TPB];
+    const SceneArgs& a = pa.a;
+    const int p = blockIdx.x, b = blockIdx.y;
+    if (p >= path_count(pa.n_path, b, pa.P)) return;         // (the whole block) a column beyond the row's path is not read
+    const size_t e = (size_t)b * pa.P + p;
+    const float* h;
+    int K;
+    mx_rir_row(a.rir, a.R, a.Kmax, a.rir_index[e], a.rir_len[e], h, K);
+    const int d = mx_direct_index(h, K, s_v, s_i);
+    if (threadIdx.x == 0) pa.dp[e] = d;
+}
+
+// scene_conv along a path: the same tile, chunks, inner loop and accumulators, once per waypoint p in ascending order.
+// Waypoint p weights the input samples m in (p H - H, p H + H) - the first one everything before, the last one everything
+// after - so from a tile of cnt outputs it walks only the taps k = i + d_p - m that meet such a sample: at most
+// cnt + 2 H - 2 of them, inside [0, K_p) and, for the talker, inside the clip.  The span is staged ALREADY weighted (one
+// product per staged sample, rounded once), so the tap loop is scene_conv's.
+__global__ __launch_bounds__(MX_TPB) void scene_conv_path(ScenePathArgs pa) {
+    __shared__ double s_x[MX_TILE + MX_KC];
+    __shared__ double s_h[MX_KC];
+    __shared__ double s_red[MX_TPB];
+    const SceneArgs& a = pa.a;
+    const int t = threadIdx.x, src = blockIdx.y, b = blockIdx.z;
+    if (src > scene_count(a, b)) return;                     // (the whole block: src and b are its own)
+    const int i0 = blockIdx.x * MX_TILE;
+    const int cnt = a.L - i0 < MX_TILE ? a.L - i0 : MX_TILE;
+    const float* row = a.clean + (size_t)b * a.ld;
+    const long long H = pa.H;
+    NoiseRow seg = mx_segment(nullptr, 0, 0, 0, 0);
+    size_t es = 0, pe;                                       // the source's slot b S + src - 1; its row of the path tables
+    int Pb;
     if (src == 0) {
-        const NoiseRow nr = scene_noise_row(a, b);
-        double ps = 0.0, pn = 0.0;
-#pragma unroll
-        for (int r = 0; r < MX_OPT; ++r) {
-            const int o = t + r * MX_TPB;
-            if (o < cnt) {
-                const size_t e = (size_t)b * a.L + i0 + o;
-                a.speech[e] = acc_s[r];
-                if (a.early >= 0) a.tgt[e] = acc_t[r];
-                ps = fma(acc_s[r], acc_s[r], ps);
-                const double n = mix_noise(nr, i0 + o);
-                pn = fma(n, n, pn);
-            }
-        }
-        ps = block_sum(ps, s_red);
-        pn = block_sum(pn, s_red);
-        if (t == 0) {
-            a.part_ps[(size_t)b * a.nt + blockIdx.x] = ps;
-            a.part_pn[(size_t)b * a.nt + blockIdx.x] = pn;
-        }
+        pe = (size_t)b * pa.P;
+        Pb = path_count(pa.n_path, b, pa.P);
     } else {
-        double pc = 0.0;
-#pragma unroll
-        for (int r = 0; r < MX_OPT; ++r) {
-            const int o = t + r * MX_TPB;
-            if (o < cnt) {
-                a.c[es * a.L + i0 + o] = acc_s[r];
-                pc = fma(acc_s[r], acc_s[r], pc);
-            }
-        }
-        pc = block_sum(pc, s_red);
-        if (t == 0) a.part_pc[es * a.nt + blockIdx.x] = pc;
+        es = (size_t)b * a.S + (src - 1);
+        seg = mx_segment(a.src_bank, a.src_bank_len, a.s_start[es], a.s_len[es], a.s_off[es]);
+        pe = es * pa.P;
+        Pb = seg.p ? path_count(pa.s_n_path, es, pa.P) : 0;  // silence: no waypoint, c = 0
     }
+    double acc_s[MX_OPT], acc_t[MX_OPT];
+#pragma unroll
+    for (int r = 0; r < MX_OPT; ++r) acc_s[r] = acc_t[r] = 0.0;
+    for (int p = 0; p < Pb; ++p) {
+        // the input samples this waypoint weights
+        long long m_lo = p == 0 ? -SP_FAR : (long long)p * H - H + 1;
+        long long m_hi = p == Pb - 1 ? SP_FAR : (long long)p * H + H - 1;
+        const float* h;
+        int K, d = 0;
+        long long kt = -1;
+        if (src == 0) {
+            if (m_lo < 0) m_lo = 0;
+            if (m_hi > a.L - 1) m_hi = a.L - 1;
+            if (m_lo > m_hi) continue;                       // (p, Pb, H and L are the block's own: no thread skips a barrier)
+            mx_rir_row(a.rir, a.R, a.Kmax, a.rir_index[pe + p], a.rir_len[pe + p], h, K);
+            d = pa.dp[pe + p];
+            if (a.early >= 0) {
+                kt = (long long)d + a.early;
+                if (kt > K - 1) kt = K - 1;
+            }
+        } else {
+            mx_rir_row(a.rir, a.R, a.Kmax, a.s_rir_index[pe + p], a.s_rir_len[pe + p], h, K);
+        }
+        long long k_lo = (long long)i0 + d - m_hi;
+        if (k_lo < 0) k_lo = 0;
+        long long k_hi = (long long)i0 + cnt - 1 + d - m_lo;
+        if (k_hi > K - 1) k_hi = K - 1;
+        for (long long k0 = k_lo; k0 <= k_hi; k0 += MX_KC) {
+            const int kc = k_hi - k0 + 1 < MX_KC ? (int)(k_hi - k0 + 1) : MX_KC;
+            for (int j = t; j < kc; j += MX_TPB) s_h[j] = (double)h[k0 + j];
+            // s_x[q] = u_p[x0 + q] signal[x0 + q]: output o of the tile meets tap k0 + j at s_x[o + kc - 1 - j]
+            const long long x0 = (long long)i0 + d - (k0 + kc - 1);
+            if (src == 0) {
+                for (int q = t; q < MX_TILE + kc - 1; q += MX_TPB) {
+                    const long long x = x0 + q;
+                    s_x[q] = (x >= 0 && x < a.L) ? path_weight(x, p, Pb, H) * (double)row[x] : 0.0;
+                }
+            } else {
+                long long pos = (seg.off + x0 + t) % seg.len;    // the one modulo of this thread and chunk; x0 may be < 0
+                if (pos < 0) pos += seg.len;
+                const long long step = MX_TPB % seg.len;
+                for (int q = t; q < MX_TILE + kc - 1; q += MX_TPB) {
+                    s_x[q] = path_weight(x0 + q, p, Pb, H) * (double)seg.p[pos];
+                    pos += step;
+                    if (pos >= seg.len) pos -= seg.len;
+                }
+            }
+            __syncthreads();
+            long long nb_ll = kt - k0 + 1;                   // taps of the chunk that also feed the target
+            const int nb = nb_ll < 0 ? 0 : (nb_ll > kc ? kc : (int)nb_ll);
+            mx_chunk_taps(s_h, s_x + t + kc - 1, kc, nb, acc_s, acc_t);
+            __syncthreads();
+        }
+    }
+    scene_conv_store(a, src, b, i0, cnt, es, acc_s, acc_t, s_red);
 }
 
 __global__ __launch_bounds__(MX_TPB) void scene_gain(SceneArgs a) {
@@ -458,16 +607,27 @@ inline bool sc_shape_ok(int B, int L, int Kmax, int S) {
     return B >= 1 && B <= 65535 && L >= 1 && L <= MX_MAX_L && Kmax >= 1 && Kmax <= MX_MAX_K && S >= 0 && S <= SC_MAX_S;
 }
 
+// what cmgan_scene_path has beyond cmgan_scene; its workspace is that call's with the plane d [B, P] behind it
+struct PathSpec {
+    int P;
+    long long H;
+    const int* n_path;
+    const int* src_n_path;
+};
+
+inline size_t sp_total(int B, int L, int S, int P) { return sc_layout(B, L, S).total + mx_up256((size_t)B * P * sizeof(int)); }
+
 // cmgan_scene, and cmgan_mix as its S = 0 case: `api` is the name of the entry point that was called, for the messages.
 // Every argument is judged before the handle is, so that the errors below need no GPU (the message of a call without a
-// handle is read with cmgan_last_error(NULL)).
+// handle is read with cmgan_last_error(NULL)).  With a `path` the call is cmgan_scene_path: the RIR tables have P columns
+// per row and per source, and scene_direct_path / scene_conv_path take the places of scene_direct / scene_conv.
 int mix_scene(const char* api, cmgan_handle* h, const float* clean, int B, int L, long long ld, const float* noise_bank,
               long long bank_len, const long long* noise_start, const long long* noise_len, const long long* noise_off,
               const float* snr_db, const float* src_bank, long long src_bank_len, int S, const int* n_src,
               const long long* src_start, const long long* src_len, const long long* src_off, const float* src_snr_db,
               const float* rir_bank, int R, int Kmax, const int* rir_index, const int* rir_len, const int* src_rir_index,
               const int* src_rir_len, float peak, int early, float* noisy, float* target, long long ld_out, double* g,
-              double* p, double* ps, double* scale, void* ws, size_t ws_bytes, void* stream) {
+              double* p, double* ps, double* scale, void* ws, size_t ws_bytes, void* stream, const PathSpec* path = nullptr) {
     if (!clean || !noisy || !target || !g || !p || !ps || !scale) return fail(h, CMGAN_E_BADARG, "%s: null pointer", api);
     if (noise_bank && (!noise_start || !noise_len || !noise_off || !snr_db))
         return fail(h, CMGAN_E_BADARG, "%s: a dry-noise bank needs noise_start, noise_len, noise_off and snr_db", api);
@@ -504,9 +664,24 @@ int mix_scene(const char* api, cmgan_handle* h, const float* clean, int B, int L
         return fail(h, CMGAN_E_UNSUPPORTED, "%s: RIRs of up to %d taps are supported (Kmax=%d)", api, MX_MAX_K, Kmax);
     if (L > MX_MAX_L)
         return fail(h, CMGAN_E_UNSUPPORTED, "%s: rows of up to %d samples are supported (L=%d)", api, MX_MAX_L, L);
-    if (!h) return fail(nullptr, CMGAN_E_BADARG, "%s: null handle", api);
     const SceneLayout l = sc_layout(B, L, S);
-    if (int rc = check_ws(h, ws, ws_bytes, l.total)) return rc;
+    if (path) {
+        if (path->P < 1 || path->P > SP_MAX_P || path->H < 1 || path->H > SP_MAX_H)
+            return fail(h, CMGAN_E_BADARG, "%s: need 1 <= P <= %d waypoints and a hop 1 <= H <= 2^30 (P=%d H=%lld)", api,
+                        SP_MAX_P, path->P, path->H);
+        if (!rir_bank) return fail(h, CMGAN_E_BADARG, "%s: a path needs a RIR bank", api);
+        if (!path->n_path || (S > 0 && !path->src_n_path))
+            return fail(h, CMGAN_E_BADARG, "%s: a path needs n_path and, with S > 0, src_n_path", api);
+        if (((uintptr_t)path->n_path | (uintptr_t)path->src_n_path) & 3)
+            return fail(h, CMGAN_E_BADARG, "%s: float32 / int32 buffers must be 4-byte aligned", api);
+        const size_t need = sp_total(B, L, S, path->P);
+        if (!ws || ((uintptr_t)ws & 255) != 0 || ws_bytes < need)
+            return fail(h, CMGAN_E_BADARG, "%s: the workspace must be 256-byte aligned and hold %zu bytes (%zu given)", api,
+                        need, ws ? ws_bytes : (size_t)0);
+    }
+    if (!h) return fail(nullptr, CMGAN_E_BADARG, "%s: null handle", api);
+    if (!path)
+        if (int rc = check_ws(h, ws, ws_bytes, l.total)) return rc;
     const LaunchCtx ctx = begin(h, stream);
     hipStream_t s = ctx.stream;
     char* w = (char*)ws;
@@ -555,13 +730,19 @@ int mix_scene(const char* api, cmgan_handle* h, const float* clean, int B, int L
     a.nt = mx_tiles(L);
     a.S = S;
     const dim3 grid(a.nt, B);
-    if (rir_bank) LAUNCH(ctx, "scene_direct", scene_direct<<<B, MX_TPB, 0, s>>>(a));
-    LAUNCH(ctx, "scene_conv", scene_conv<<<dim3(a.nt, 1 + S, B), MX_TPB, 0, s>>>(a));
+    if (path) {
+        const ScenePathArgs pa{a, path->n_path, path->src_n_path, (int*)(w + l.total), path->H, path->P};
+        LAUNCH(ctx, "scene_direct_path", scene_direct_path<<<dim3(path->P, B), MX_TPB, 0, s>>>(pa));
+        LAUNCH(ctx, "scene_conv_path", scene_conv_path<<<dim3(a.nt, 1 + S, B), MX_TPB, 0, s>>>(pa));
+    } else {
+        if (rir_bank) LAUNCH(ctx, "scene_direct", scene_direct<<<B, MX_TPB, 0, s>>>(a));
+        LAUNCH(ctx, "scene_conv", scene_conv<<<dim3(a.nt, 1 + S, B), MX_TPB, 0, s>>>(a));
+    }
     LAUNCH(ctx, "scene_gain", scene_gain<<<B, MX_TPB, 0, s>>>(a));
     LAUNCH(ctx, "scene_vmax", scene_vmax<<<grid, MX_TPB, 0, s>>>(a));
     LAUNCH(ctx, "scene_scale", scene_scale<<<B, MX_TPB, 0, s>>>(a));
     LAUNCH(ctx, "scene_apply", scene_apply<<<grid, MX_TPB, 0, s>>>(a));
-    return check_launch(h, api + 6);                         // "mix" / "scene": the name without its cmgan_
+    return check_launch(h, api + 6);                         // "mix" / "scene" / "scene_path": the name without its cmgan_
 }
 
 }  // namespace
@@ -591,6 +772,29 @@ extern "C" int cmgan_scene(cmgan_handle* h, const float* clean, int B, int L, lo
                      src_bank, src_bank_len, S, n_src, src_start, src_len, src_off, src_snr_db, rir_bank, R, Kmax, rir_index,
                      rir_len, src_rir_index, src_rir_len, peak, early, noisy, target, ld_out, g, p, ps, scale, ws, ws_bytes,
                      stream);
+}
+
+extern "C" int cmgan_scene_max_waypoints(void) { return SP_MAX_P; }
+
+extern "C" size_t cmgan_scene_path_workspace_bytes(const cmgan_handle* h, int B, int L, int Kmax, int S, int P) {
+    (void)h;
+    return sc_shape_ok(B, L, Kmax, S) && P >= 1 && P <= SP_MAX_P ? sp_total(B, L, S, P) : 0;
+}
+
+extern "C" int cmgan_scene_path(cmgan_handle* h, const float* clean, int B, int L, long long ld, const float* noise_bank,
+                                long long bank_len, const long long* noise_start, const long long* noise_len,
+                                const long long* noise_off, const float* snr_db, const float* src_bank, long long src_bank_len,
+                                int S, const int* n_src, const long long* src_start, const long long* src_len,
+                                const long long* src_off, const float* src_snr_db, const float* rir_bank, int R, int Kmax,
+                                int P, int H, const int* n_path, const int* rir_index, const int* rir_len,
+                                const int* src_n_path, const int* src_rir_index, const int* src_rir_len, float peak, int early,
+                                float* noisy, float* target, long long ld_out, double* g, double* p, double* ps, double* scale,
+                                void* ws, size_t ws_bytes, void* stream) {
+    const PathSpec path{P, H, n_path, src_n_path};
+    return mix_scene("cmgan_scene_path", h, clean, B, L, ld, noise_bank, bank_len, noise_start, noise_len, noise_off, snr_db,
+                     src_bank, src_bank_len, S, n_src, src_start, src_len, src_off, src_snr_db, rir_bank, R, Kmax, rir_index,
+                     rir_len, src_rir_index, src_rir_len, peak, early, noisy, target, ld_out, g, p, ps, scale, ws, ws_bytes,
+                     stream, &path);
 }
 
 // the scene without located sources whose dry noise and outputs must all be there; its [B, 1 + S] tables g and p are

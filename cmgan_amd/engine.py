@@ -191,6 +191,47 @@ def check_scene_args(device, clean, noise_bank=None, noise_start=None, noise_len
     return B, L, R, Kmax, S
 
 
+SCENE_MAX_WAYPOINTS = 64      # waypoint columns of a path (= cmgan_scene_max_waypoints())
+SCENE_MAX_HOP = 2 ** 30       # largest hop between waypoints, in samples
+
+
+def check_scene_path_args(device, clean, hop, n_path, rir_bank, rir_index, rir_len, noise_bank=None, noise_start=None,
+                          noise_len=None, noise_off=None, snr_db=None, n_src=None, src_bank=None, src_start=None, src_len=None,
+                          src_off=None, src_snr_db=None, src_n_path=None, src_rir_index=None, src_rir_len=None,
+                          peak: float = 0.99, early: int = -1):
+    """Argument rules of Engine.scene_path: those of Engine.scene (check_scene_args) for everything but the responses, a
+    rir_bank that must be there, and the path tables.  Pure host code.  Returns (B, L, R, Kmax, S, P)."""
+    # everything but the responses by the static rules
+    B, L, _, _, S = check_scene_args(device, clean, noise_bank, noise_start, noise_len, noise_off, snr_db, n_src, src_bank,
+                                     src_start, src_len, src_off, src_snr_db, peak=peak, early=early)
+    if rir_bank is None:
+        raise ValueError("a path needs a rir_bank")
+    tensor_arg(rir_bank, "rir_bank", torch.float32, device, "[R, Kmax] with R, Kmax >= 1",
+               lambda t: t.dim() == 2 and t.size(0) >= 1 and t.size(1) >= 1)
+    R, Kmax = rir_bank.shape
+    if Kmax > MIX_MAX_TAPS:
+        raise ValueError(f"rir_bank: RIRs of up to {MIX_MAX_TAPS} taps are supported, got Kmax = {Kmax}")
+    tensor_arg(rir_index, "rir_index", torch.int32, device, f"[{B}, P] with 1 <= P <= {SCENE_MAX_WAYPOINTS}",
+               lambda t: t.dim() == 2 and t.size(0) == B and 1 <= t.size(1) <= SCENE_MAX_WAYPOINTS)
+    P = int(rir_index.size(1))
+    tensor_arg(rir_len, "rir_len", torch.int32, device, f"[{B}, {P}]", lambda t: tuple(t.shape) == (B, P))
+    tensor_arg(n_path, "n_path", torch.int32, device, f"[{B}]", lambda t: tuple(t.shape) == (B,))
+    if not _whole_in(hop, 1, SCENE_MAX_HOP):
+        raise ValueError(f"hop must be a whole number of samples in [1, 2^30], got {hop}")
+    if S:
+        for name, t, shape in (("src_n_path", src_n_path, (B, S)), ("src_rir_index", src_rir_index, (B, S, P)),
+                               ("src_rir_len", src_rir_len, (B, S, P))):
+            if t is None:
+                raise ValueError(f"a path with sources needs {name}")
+            tensor_arg(t, name, torch.int32, device, f"{list(shape)}", lambda t, shape=shape: tuple(t.shape) == shape)
+    else:
+        given = [name for name, t in (("src_n_path", src_n_path), ("src_rir_index", src_rir_index), ("src_rir_len", src_rir_len))
+                 if t is not None]
+        if given:
+            raise ValueError(f"{' / '.join(given)} given without n_src")
+    return B, L, R, Kmax, S, P
+
+
 RIR_MAX_TAPS = 65536          # longest response of cmgan_rir (= MIX_MAX_TAPS: its output is a bank of cmgan_mix)
 RIR_MAX_IMAGES = 255          # largest image index per axis
 RIR_MAX_TW = 64               # largest half-width of the fractional-delay filter
@@ -1198,6 +1239,45 @@ class Engine:
                    noise_start, noise_len, noise_off, snr_db, src_bank, src_bank.numel() if src_bank is not None else 0, S,
                    n_src, src_start, src_len, src_off, src_snr_db, rir_bank, R, Kmax, rir_index, rir_len, src_rir_index,
                    src_rir_len, float(peak), int(early), noisy, target, L, gp[0], gp[1], info[0], info[1], ws, ws.numel())
+        return noisy, target, SceneInfo(gp[0], info[1], info[0], gp[1])
+
+    # ---- paths: a talker and sources that move ---------------------------------------
+    @_on_device
+    def scene_path(self, clean: torch.Tensor, hop: int, n_path: torch.Tensor, rir_bank: torch.Tensor, rir_index: torch.Tensor,
+                   rir_len: torch.Tensor, noise_bank: Optional[torch.Tensor] = None, noise_start: Optional[torch.Tensor] = None,
+                   noise_len: Optional[torch.Tensor] = None, noise_off: Optional[torch.Tensor] = None,
+                   snr_db: Optional[torch.Tensor] = None, n_src: Optional[torch.Tensor] = None,
+                   src_bank: Optional[torch.Tensor] = None, src_start: Optional[torch.Tensor] = None,
+                   src_len: Optional[torch.Tensor] = None, src_off: Optional[torch.Tensor] = None,
+                   src_snr_db: Optional[torch.Tensor] = None, src_n_path: Optional[torch.Tensor] = None,
+                   src_rir_index: Optional[torch.Tensor] = None, src_rir_len: Optional[torch.Tensor] = None,
+                   peak: float = 0.99, early: int = -1):
+        """Engine.scene for a talker and sources that MOVE: a path of responses each (cmgan_scene_path, include/cmgan_hip.h).
+
+        rir_index / rir_len are int32 [B, P], 1 <= P <= 64: waypoint p of row b is that row of rir_bank and sits at input
+        sample p * hop; n_path int32 [B] is how many of the P columns the row uses (clamped to [1, P]; 1: it stands
+        still).  The responses of neighbouring waypoints are cross-faded linearly by emission time, each with its OWN
+        direct-path delay removed, so the speech stays aligned with the dry clip; Doppler is not modelled.  With n_src the
+        sources take src_n_path int32 [B, S] and src_rir_index / src_rir_len int32 [B, S, P] the same way (their delay
+        stays).  Everything else is Engine.scene's, and so is what comes back: (noisy [B, L], target [B, L], SceneInfo).
+        A row whose n_path and src_n_path are 1 has the bits of Engine.scene with column 0 of the tables.  Float64
+        arithmetic, one rounding to float32; bit-reproducible, row-independent, no synchronisation, graph-capturable
+        after one call at the shape; the columns beyond a row's own count are never read."""
+        B, L, R, Kmax, S, P = check_scene_path_args(self.device, clean, hop, n_path, rir_bank, rir_index, rir_len, noise_bank,
+                                                    noise_start, noise_len, noise_off, snr_db, n_src, src_bank, src_start,
+                                                    src_len, src_off, src_snr_db, src_n_path, src_rir_index, src_rir_len, peak,
+                                                    early)
+        ws = self._grow("scene_path", int(self.lib.cmgan_scene_path_workspace_bytes(self._h, B, L, Kmax, S, P)),
+                        f"[{B}, {L}] with {Kmax} taps, {S} sources and {P} waypoints is outside what cmgan_scene_path supports")
+        noisy = torch.empty(B, L, dtype=torch.float32, device=self.device)
+        target = torch.empty(B, L, dtype=torch.float32, device=self.device)
+        gp = torch.empty(2, B, 1 + S, dtype=torch.float64, device=self.device)
+        info = torch.empty(2, B, dtype=torch.float64, device=self.device)
+        self._call("cmgan_scene_path", clean, B, L, L, noise_bank, noise_bank.numel() if noise_bank is not None else 0,
+                   noise_start, noise_len, noise_off, snr_db, src_bank, src_bank.numel() if src_bank is not None else 0, S,
+                   n_src, src_start, src_len, src_off, src_snr_db, rir_bank, R, Kmax, P, int(hop), n_path, rir_index, rir_len,
+                   src_n_path, src_rir_index, src_rir_len, float(peak), int(early), noisy, target, L, gp[0], gp[1], info[0],
+                   info[1], ws, ws.numel())
         return noisy, target, SceneInfo(gp[0], info[1], info[0], gp[1])
 
     # ---- room impulse responses ----------------------------------------------------

@@ -23,6 +23,9 @@ takes - with `clean` the training target (the dry clip, or the clip with its ear
     # long responses - halls, stairwells: the image-source method only to 80 ms after the direct sound, a diffuse tail of
     # decaying noise at the room's decay time from there on (Engine.rir_tail / cmgan_rir_tail)
     mixer = DynamicMixer(engine, noise, rooms=RoomSampler(rt60=(0.4, 1.2), tail_ms=80.0), rir_seconds=1.0)
+    # talkers that walk: a path of responses per row, cross-faded by emission time (Engine.scene_path / cmgan_scene_path);
+    # with tail_ms the 9 responses per row of a 2 s batch cost little beside the mix itself
+    mixer = DynamicMixer(engine, noise, rooms=RoomSampler(tail_ms=80.0), rir_seconds=1.0, motion=(0.5, 1.5), p_motion=0.5)
     # the recording channel: a random equaliser, a band limit and clipping per row (Engine.channel / cmgan_channel)
     mixer = DynamicMixer(engine, noise, rirs, channel=ChannelSampler(p_bandlimit=0.2, p_clip=0.1))
     clean = torch.utils.data.DataLoader(clean_only("data/train", 32000), batch_size=32, pin_memory=True, drop_last=True)
@@ -48,11 +51,11 @@ import torch
 import torch.utils.data
 
 from .data import _natural_key, fit_length, read_wav
-from .engine import RIR_TAIL_MAX_WINDOW, STRETCH_HOP, STRETCH_SEARCH, RirStats, RirTail, _whole_in
+from .engine import RIR_TAIL_MAX_WINDOW, SCENE_MAX_HOP, SCENE_MAX_WAYPOINTS, STRETCH_HOP, STRETCH_SEARCH, RirStats, RirTail, _whole_in
 
 __all__ = ["NoiseBank", "RirBank", "RoomSampler", "sabine_beta", "octave_filterbank", "DynamicMixer", "MixingLoader", "CleanDataset",
            "clean_only", "Draw", "SceneDraw", "tile", "ChannelSampler", "biquad_peaking", "biquad_low_shelf", "biquad_high_shelf",
-           "biquad_lowpass", "biquad_highpass", "butter_lowpass_sos", "warp_len", "stretch_len", "StretchDraw", "TailDraw"]
+           "biquad_lowpass", "biquad_highpass", "butter_lowpass_sos", "warp_len", "stretch_len", "StretchDraw", "TailDraw", "PathDraw"]
 
 SPEED_OF_SOUND = 343.0        # m/s, the default `c` of Engine.rir
 RIR_TW = 40                   # the default half-width of its fractional-delay filter, in samples
@@ -98,6 +101,15 @@ def _positive_pair(name: str, value, form: Optional[str] = "(low, high)"):
 def _rate_pair(name: str, value):
     lo, hi = SPEED_RANGE
     return _pair(name, value, lo, hi, f"(low, high) with {lo} <= low <= high <= {hi}", "None or (low, high)", echo=True)
+
+
+def _speed_pair(name: str, value):
+    """(low, high) metres per second with 0 <= low <= high < inf."""
+    wording = "(low, high) metres per second with 0 <= low <= high"
+    lo, hi = _pair(name, value, 0.0, math.inf, wording, "None or (low, high)")
+    if hi == math.inf:
+        raise ValueError(f"{name} must be {wording}, got {value}")
+    return lo, hi
 
 
 def _probability(name: str, p, as_given: bool = False) -> float:
@@ -464,6 +476,34 @@ class RoomSampler:
         out[:, :, 3:6] = self.margin + inner * u
         return out
 
+    def draw_path(self, rooms: torch.Tensor, P: int, seconds: float, speed=(0.5, 1.5)) -> torch.Tensor:
+        """A straight walk per source for Engine.scene_path: float64 [R, P, 15] tables for the [R, 15] one `draw` made, or
+        [R, n, P, 15] for the [R, n, 15] ones of `draw_sources`.  Every waypoint keeps the room's size, receiver and
+        reflection coefficients.  Waypoint 0 is the drawn source position; an end point is drawn uniform in the room
+        shrunk by `margin` and a speed uniform in `speed` = (low, high) metres per second; a segment longer than
+        speed x `seconds` is shortened to that (the room is convex, so it stays inside), and the P waypoints are spaced
+        linearly on it, `seconds` apart from first to last.  ONE rand(R, 4) (rand(R, n, 4)) from `generator` on the device
+        of `rooms`: the end point, then the speed - so: after every other draw of the sampler.
+        `tables.reshape(-1, 15)` with each room's n_taps repeated is one Engine.rir / Engine.rir_bands call."""
+        if not isinstance(rooms, torch.Tensor) or rooms.dtype != torch.float64 or rooms.dim() not in (2, 3) or rooms.size(-1) != 15:
+            raise ValueError("rooms must be a float64 [R, 15] table of RoomSampler.draw or the [R, n, 15] ones of draw_sources")
+        if not _whole_in(P, 1, SCENE_MAX_WAYPOINTS):
+            raise ValueError(f"P must be a waypoint count in [1, {SCENE_MAX_WAYPOINTS}], got {P}")
+        if isinstance(seconds, bool) or not isinstance(seconds, (int, float)) or not 0.0 < seconds < math.inf:
+            raise ValueError(f"seconds must be positive and finite, got {seconds}")
+        lo, hi = _speed_pair("speed", speed)
+        P, lead = int(P), tuple(rooms.shape[:-1])
+        u = torch.rand(*lead, 4, dtype=torch.float64, generator=self.generator, device=rooms.device)
+        start = rooms[..., 3:6]
+        step = self.margin + (rooms[..., 0:3] - 2.0 * self.margin) * u[..., 0:3] - start
+        far = torch.linalg.vector_norm(step, dim=-1, keepdim=True)
+        reach = (lo + (hi - lo) * u[..., 3:4]) * float(seconds)
+        step = step * torch.where(far > reach, reach / torch.where(far > reach, far, torch.ones_like(far)), torch.ones_like(far))
+        along = torch.arange(P, dtype=torch.float64).to(rooms.device, non_blocking=True) / float(max(P - 1, 1))
+        out = rooms[..., None, :].expand(*lead, P, 15).clone()
+        out[..., 3:6] = start[..., None, :] + step[..., None, :] * along[:, None]
+        return out
+
 
 # ---- biquad designs: R. Bristow-Johnson's audio-EQ-cookbook formulas, normalised to a0 = 1 --------------------------
 def _f64(v, like=None) -> torch.Tensor:
@@ -759,6 +799,27 @@ SceneDraw.__doc__ = """What a DynamicMixer(sources=...) drew for a batch: the fi
 Engine.scene, [B] and [B, S] device tensors with S = the upper end of `sources`."""
 
 
+_PATH_FIELDS = (
+    "path",                                       # float64 [B, P, 15]: RoomSampler.draw_path of the batch's rooms (None: the talkers stand still)
+    "n_path",                                     # int32 [B]: P for a row that moves, 1 for one drawn static
+    "src_path", "src_n_path",                     # float64 [B, S, P, 15] and int32 [B, S] (None without sources; src_path None: they stand still)
+)
+PathDraw = collections.namedtuple("PathDraw", SceneDraw._fields + _PATH_FIELDS,
+                                  defaults=(None,) * (len(SceneDraw._field_defaults) + len(_PATH_FIELDS)))
+PathDraw.__doc__ = """What a DynamicMixer(motion=... / source_motion=...) drew for a batch: the fields of SceneDraw (the sources' None
+without `sources`), then the paths.  rir_index / rir_len are the [B, P] and src_rir_index / src_rir_len the [B, S, P] tables
+of Engine.scene_path.  Draw and SceneDraw keep their fields: a mixer without motion never makes a PathDraw."""
+
+
+class _Paths(NamedTuple):
+    """The sampler's part of a PathDraw, before the responses are simulated: the tables and every waypoint's n_taps."""
+    P: int
+    path: Optional[torch.Tensor]
+    taps: Optional[torch.Tensor]                  # int32 [B, P]
+    src_path: Optional[torch.Tensor]
+    src_taps: Optional[torch.Tensor]              # int32 [B, S, P]
+
+
 class DynamicMixer:
     """`mixer(clean_dev)` -> `(target, noisy, MixInfo)` for a float32 [B, L] device batch of clean speech.
 
@@ -855,7 +916,21 @@ class DynamicMixer:
     response's whole length, so `rir_seconds` of a second or two stay affordable.  The tail draw (`mixer.last_tail`, a
     TailDraw) follows `draw` and `draw_bands`; `last_draw.rir_len` and `src_rir_len` then hold the EXTENDED lengths the batch
     was mixed with, and `room_stats=True` measures the extended responses.  Without `tail_ms` nothing of this is drawn or
-    run."""
+    run.
+
+    `motion=(lo, hi)` metres per second (needs `rooms`; a `rir_bank` of fixed responses cannot move): talkers that walk
+    (Engine.scene_path / cmgan_scene_path).  A waypoint every `motion_hop_ms` (H samples, `motion_hop`), P = 1 + ceil((N -
+    1) / H) of them for the batch length N that reaches the mix, at most 64 (`waypoints(N)`).  Every row gets a path,
+    `RoomSampler.draw_path` from its drawn source position over (P - 1) H samples, made from the sampler's generator
+    after all its other draws, and all B P responses are simulated into the persistent bank by the calls a static batch
+    makes (with `bands` the waypoints share their room's band table; with `tail_ms` every waypoint has a junction of its
+    own, and all waypoints of a path share ONE tail seed and decay: their tails are the same noise at fitted levels, so
+    the cross-fade does not dip by 3 dB between uncorrelated tails).  A row then moves with probability `p_motion`
+    (n_path = P) or stands at waypoint 0 (n_path = 1): one rand(B) from the mixer's generator after every other draw,
+    the stretch draws included.  `source_motion=(lo, hi)` (needs `sources` and `rooms`) walks every located source the
+    same way, a path per source drawn after the talkers'.  `last_draw` is then a PathDraw and the mixer returns a
+    SceneInfo.  `room_stats=True` measures waypoint 0 of every talker.  Doppler is not modelled.  With both None (the
+    default) nothing is drawn or run: outputs, `last_draw` and every generator state are what they are without them."""
 
     def __init__(self, engine, noise_bank: NoiseBank, rir_bank: Optional[RirBank] = None, snr_db=(0.0, 20.0),
                  early_ms: Optional[float] = 50.0, p_reverb: float = 1.0, peak: float = 0.99,
@@ -864,7 +939,8 @@ class DynamicMixer:
                  channel: Optional[ChannelSampler] = None, channel_on: str = "noisy", speed=None, p_speed: float = 1.0,
                  speed_zeros: int = 24, speed_rolloff: float = 0.95, sources=None, source_bank: Optional[NoiseBank] = None,
                  source_snr_db=(0.0, 20.0), dry_noise: bool = True, tempo=None, p_tempo: float = 1.0, pitch=None,
-                 p_pitch: float = 1.0, stretch_hop: int = 256, stretch_search: int = 160, room_stats: bool = False):
+                 p_pitch: float = 1.0, stretch_hop: int = 256, stretch_search: int = 160, room_stats: bool = False,
+                 motion=None, p_motion: float = 1.0, motion_hop_ms: float = 250.0, source_motion=None):
         if sources is not None:
             given, counts = sources, "(low, high) whole numbers with 0 <= low <= high and 1 <= high <= 4"
             sources = _pair("sources", given, 0, 4, counts, "None or (low, high)", whole=True)
@@ -944,6 +1020,28 @@ class DynamicMixer:
             if max(self.n_images) > 255:
                 raise ValueError(f"responses of {rir_seconds} s in rooms as small as {rooms.lo} need image ranges "
                                  f"{self.n_images}; up to 255 are supported")
+        # ---- motion: judged last, so that every earlier error is what it was
+        self.motion = None if motion is None else _speed_pair("motion", motion)
+        self.source_motion = None if source_motion is None else _speed_pair("source_motion", source_motion)
+        self.p_motion = _probability("p_motion", p_motion)
+        if (self.motion is not None or self.source_motion is not None) and rooms is None:
+            raise ValueError("motion / source_motion need rooms: a path is simulated, a rir_bank of fixed responses cannot move")
+        if self.source_motion is not None and sources is None:
+            raise ValueError("source_motion given without sources")
+        self.motion_hop = 0                                 # H, the samples between waypoints
+        if self.motion is not None or self.source_motion is not None:
+            if isinstance(motion_hop_ms, bool) or not isinstance(motion_hop_ms, (int, float)) or not 0.0 < motion_hop_ms < math.inf \
+                    or not 1 <= round(motion_hop_ms * sample_rate / 1000.0) <= SCENE_MAX_HOP:
+                raise ValueError(f"motion_hop_ms must give a hop of 1 .. 2^30 samples, got {motion_hop_ms} ms at {sample_rate} Hz")
+            self.motion_hop = int(round(motion_hop_ms * sample_rate / 1000.0))
+
+    def waypoints(self, N: int) -> int:
+        """P = 1 + ceil((N - 1) / H): the waypoints a batch of N samples needs; more than 64 is refused."""
+        P = 1 + -(-(int(N) - 1) // self.motion_hop)
+        if P > SCENE_MAX_WAYPOINTS:
+            raise ValueError(f"a batch of {N} samples with a waypoint every {self.motion_hop} needs {P} waypoints; up to "
+                             f"{SCENE_MAX_WAYPOINTS} are supported: raise motion_hop_ms")
+        return P
 
     # ---- the draws: one helper per kind, each a fixed sequence of calls on the mixer's generator --------------------
     def _rand(self, *shape, dtype=torch.float64) -> torch.Tensor:
@@ -1010,9 +1108,10 @@ class DynamicMixer:
             rlen = taps[:, None].expand(B, S).contiguous()
         return n_src, start, length, off, snr, index, rlen, rooms
 
-    def _bank_rows(self, B: int) -> int:
-        """The rows of the simulated bank in front of the sources' responses: the talkers' and, with dry rows, the identity."""
-        return B + (1 if self.p_reverb < 1.0 else 0)
+    def _bank_rows(self, B: int, P: int = 1) -> int:
+        """The rows of the simulated bank in front of the sources' responses: the talkers' (P per row when they move) and,
+        with dry rows, the identity."""
+        return B * P + (1 if self.p_reverb < 1.0 else 0)
 
     def draw(self, B: int):
         start, length, off = self._draw_item(self.noise_bank, B)
@@ -1061,6 +1160,55 @@ class DynamicMixer:
             return None
         return self.rooms.draw_tail(d.rooms, self.sample_rate, getattr(d, "src_rooms", None))
 
+    def draw_paths(self, d: Draw, N: int, tail: Optional[TailDraw] = None) -> Optional[_Paths]:
+        """The walks of a batch of N samples (None unless `motion` or `source_motion`): RoomSampler.draw_path of d.rooms
+        and then of d.src_rooms, made after `draw`, `draw_bands` and `draw_tail`, over the (P - 1) H samples the waypoints
+        span.  A waypoint's n_taps is its row's - with `tail` its OWN junction - and 1 on a row drawn dry."""
+        if self.motion is None and self.source_motion is None:
+            return None
+        P, fs = self.waypoints(N), self.sample_rate
+        seconds = max(P - 1, 1) * self.motion_hop / float(fs)
+        path = taps = src_path = src_taps = None
+        if self.motion is not None:
+            path = self.rooms.draw_path(d.rooms, P, seconds, speed=self.motion)
+            taps = d.rir_len[:, None].expand(-1, P)
+            if tail is not None:                                  # (d.rir_len is 1 on a dry row, else waypoint 0's junction)
+                taps = torch.where(taps > 1, self.rooms._junction(path, tail.n_full[:, None], fs), taps)
+            taps = taps.contiguous()
+        if self.source_motion is not None:
+            src_path = self.rooms.draw_path(d.src_rooms, P, seconds, speed=self.source_motion)
+            src_taps = (d.src_rir_len[:, :, None].expand(-1, -1, P) if tail is None
+                        else self.rooms._junction(src_path, tail.n_full[:, None, None], fs)).contiguous()
+        return _Paths(P, path, taps, src_path, src_taps)
+
+    def _draw_moving(self, B: int, paths: _Paths) -> torch.Tensor:
+        """n_path: P with probability p_motion, else 1 - one rand(B) of the mixer's generator; all 1 without `motion`."""
+        one = torch.ones(B, dtype=torch.int32, device=self.engine.device)
+        if paths.path is None:
+            return one
+        return torch.where(self._rand(B, dtype=torch.float32) < self.p_motion, one * paths.P, one)
+
+    def _path_draw(self, d: Draw, sim: RirBank, paths: _Paths, extended: bool) -> PathDraw:
+        """`d` as a PathDraw: the [B, P] / [B, S, P] tables of Engine.scene_path over the simulated bank, a dry row on the
+        identity in every column, whoever stands still on its one response in every column; extended: the lengths are
+        those Engine.rir_tail left in the bank."""
+        B, P, dev = d.rooms.size(0), paths.P, self.engine.device
+        Pt = 1 if paths.path is None else P
+        base = self._bank_rows(B, Pt)
+        index = torch.arange(B * Pt, dtype=torch.int32, device=dev).reshape(B, Pt)
+        if self.p_reverb < 1.0:
+            index = torch.where((d.rir_index != B)[:, None], index, torch.full_like(index, B * Pt))
+        rlen = sim.length[:B * Pt].reshape(B, Pt) if extended else (d.rir_len[:, None] if paths.path is None else paths.taps)
+        out = PathDraw(*d)._replace(rir_index=index.expand(B, P).contiguous(), rir_len=rlen.expand(B, P).contiguous(), path=paths.path)
+        if self.sources is None:
+            return out
+        S = self.sources[1]
+        Ps = 1 if paths.src_path is None else P
+        index = base + torch.arange(B * S * Ps, dtype=torch.int32, device=dev).reshape(B, S, Ps)
+        rlen = sim.length[base:].reshape(B, S, Ps) if extended else (d.src_rir_len[:, :, None] if paths.src_path is None else paths.src_taps)
+        return out._replace(src_rir_index=index.expand(B, S, P).contiguous(), src_rir_len=rlen.expand(B, S, P).contiguous(),
+                            src_path=paths.src_path, src_n_path=torch.full((B, S), Ps, dtype=torch.int32, device=dev))
+
     def _extended(self, d: Draw, sim: RirBank) -> Draw:
         """`d` with the lengths Engine.rir_tail left in the simulated bank in place of the junctions that were drawn."""
         B = d.rooms.size(0)
@@ -1069,19 +1217,26 @@ class DynamicMixer:
             return d
         return d._replace(src_rir_len=sim.length[self._bank_rows(B):].reshape(B, self.sources[1]).clone())
 
-    def _simulate(self, d: Draw, bands: Optional[torch.Tensor] = None, tail: Optional[TailDraw] = None) -> RirBank:
-        """The batch's responses, simulated into the persistent allocation (made anew only when B changes); with `bands`
-        by Engine.rir_bands, a source using its room's band table; with `tail` each call stops at the rows' junctions and
-        Engine.rir_tail adds the rest, a source from its own junction with its room's decay and a seed of its own."""
+    def _simulate(self, d: Draw, bands: Optional[torch.Tensor] = None, tail: Optional[TailDraw] = None,
+                  paths: Optional[_Paths] = None) -> RirBank:
+        """The batch's responses, simulated into the persistent allocation (made anew only when its row count changes);
+        with `bands` by Engine.rir_bands, a source using its room's band table; with `tail` each call stops at the rows'
+        junctions and Engine.rir_tail adds the rest, a source from its own junction with its room's decay and a seed of
+        its own.  With `paths` the same calls simulate every waypoint: Pt rows per talker, Ps per source, each with its
+        room's bands, decay and whole length and its PATH's seed."""
         B, K = d.rooms.size(0), self.rir_taps
-        base = self._bank_rows(B)
+        Pt = 1 if paths is None or paths.path is None else paths.P
+        Ps = 1 if paths is None or paths.src_path is None else paths.P
+        talkers = B * Pt
+        base = self._bank_rows(B, Pt)
         n_s = self.sources[1] if self.sources is not None else 0
-        rows = base + B * n_s
+        rows = base + B * n_s * Ps
+        each = lambda t, n: t if n == 1 else t.repeat_interleave(n, dim=0)        # a row's value for each of its n responses
         if self.last_bank is None or self.last_bank.data.size(0) != rows:
             data = torch.zeros(rows, K, dtype=torch.float32, device=self.engine.device)
             length = torch.ones(rows, dtype=torch.int32, device=self.engine.device)
-            if base > B:
-                data[B, 0] = 1.0                                  # the identity of the dry rows
+            if base > talkers:
+                data[talkers, 0] = 1.0                            # the identity of the dry rows
             self.last_bank = RirBank(data, length)
         sim = self.last_bank
         # rir_len is the sampler's n_taps, or 1 for a dry row (whose response is then one tap that no row uses)
@@ -1096,18 +1251,24 @@ class DynamicMixer:
         def extend(out, n_full, decay, seed):                     # (a dry row's junction is 1: no window fits, it stays)
             self.engine.rir_tail(*out, n_full, decay, seed, filt, fs=self.sample_rate, window_ms=self.rooms.tail_window_ms)
 
-        out = (sim.data[:B], sim.length[:B])
-        simulate(d.rooms, d.rir_len, out, bands)
+        out = (sim.data[:talkers], sim.length[:talkers])
+        if Pt == 1:
+            simulate(d.rooms, d.rir_len, out, bands)
+        else:
+            simulate(paths.path.reshape(talkers, 15), paths.taps.reshape(talkers), out, None if bands is None else each(bands, Pt))
         if tail is not None:
-            extend(out, tail.n_full, tail.decay, tail.seed)
-        if n_s:                                                   # the sources' responses: one call of B S rows
+            extend(out, each(tail.n_full, Pt), each(tail.decay, Pt), each(tail.seed, Pt))
+        if n_s:                                                   # the sources' responses: one call of B S (Ps) rows
             out = (sim.data[base:], sim.length[base:])
-            taps = d.src_rir_len if tail is None else tail.src_junction
-            simulate(d.src_rooms.reshape(B * n_s, 15), taps.reshape(B * n_s), out,
-                     None if bands is None else bands.repeat_interleave(n_s, dim=0))
+            if Ps == 1:
+                rooms, taps = d.src_rooms, d.src_rir_len if tail is None else tail.src_junction
+            else:
+                rooms, taps = paths.src_path, paths.src_taps
+            simulate(rooms.reshape(B * n_s * Ps, 15), taps.reshape(B * n_s * Ps), out,
+                     None if bands is None else bands.repeat_interleave(n_s * Ps, dim=0))
             if tail is not None:
-                extend(out, tail.n_full.repeat_interleave(n_s), tail.decay.repeat_interleave(n_s, dim=0),
-                       tail.src_seed.reshape(B * n_s))
+                extend(out, tail.n_full.repeat_interleave(n_s * Ps), tail.decay.repeat_interleave(n_s * Ps, dim=0),
+                       each(tail.src_seed.reshape(B * n_s), Ps))
         return sim
 
     @staticmethod
@@ -1124,11 +1285,17 @@ class DynamicMixer:
         d = self.last_draw = self.draw(B)
         bands = self.last_bands = self.draw_bands(d)
         tail = self.last_tail = self.draw_tail(d)
-        rir = self.rir_bank if self.rooms is None else self._simulate(d, bands, tail)
-        if tail is not None:                                      # the batch is mixed with the extended responses
+        moving = self.motion is not None or self.source_motion is not None
+        paths = self.draw_paths(d, self.stretch_len(clean.size(1)), tail) if moving else None
+        rir = self.rir_bank if self.rooms is None else self._simulate(d, bands, tail, paths)
+        if paths is not None:                                     # the [B, P] tables over the simulated waypoints
+            d = self.last_draw = self._path_draw(d, rir, paths, tail is not None)
+        elif tail is not None:                                    # the batch is mixed with the extended responses
             d = self.last_draw = self._extended(d, rir)
         self.last_room_stats = self._room_stats(d, rir, bands)
         s = self.last_stretch = self.draw_stretch(B, d.speed)
+        if paths is not None:                                     # who moves: the last draw of all
+            d = self.last_draw = d._replace(n_path=self._draw_moving(B, paths))
         clean = self._perturb(d, s, clean)
         shift, clean = self._level(d, clean)
         noisy, target, info = self._mix(d, clean, rir, shift)
@@ -1145,6 +1312,9 @@ class DynamicMixer:
             return RirStats(*(t.index_select(0, index) for t in rir.stats))
         B = d.rooms.size(0)
         filt = None if bands is None else self.rooms.filters(self.sample_rate, self.engine.device)
+        if isinstance(d, PathDraw):                               # a talker that moves is measured where it starts
+            first = d.rir_index[:, 0].to(torch.int64)
+            return self.engine.rir_stats(rir.data.index_select(0, first), d.rir_len[:, 0].contiguous(), filt, fs=self.sample_rate)
         return self.engine.rir_stats(rir.data[:B], rir.length[:B], filt, fs=self.sample_rate)
 
     def _perturb(self, d: Draw, s: Optional[StretchDraw], clean: torch.Tensor) -> torch.Tensor:
@@ -1177,6 +1347,13 @@ class DynamicMixer:
             return snr if by is None else (snr.to(torch.float64) - by).to(torch.float32).contiguous()
         snr = shifted(d.snr_db, shift)
         bank, early = (None, -1) if rir is None else (rir.data, self.early)
+        if isinstance(d, PathDraw):
+            src = (None,) * 9 if self.sources is None else (
+                d.n_src, self.source_bank.data, d.src_start, d.src_len, d.src_off,
+                shifted(d.src_snr_db, None if shift is None else shift[:, None]), d.src_n_path, d.src_rir_index, d.src_rir_len)
+            dry = (self.noise_bank.data, d.noise_start, d.noise_len, d.noise_off, snr) if self.dry_noise else (None,) * 5
+            return self.engine.scene_path(clean, self.motion_hop, d.n_path, bank, d.rir_index, d.rir_len, *dry, *src,
+                                          peak=self.peak, early=early)
         if self.sources is None:
             return self.engine.mix(clean, self.noise_bank.data, d.noise_start, d.noise_len, d.noise_off, snr, bank,
                                    d.rir_index, d.rir_len, peak=self.peak, early=early)

@@ -39,7 +39,7 @@ extern "C" {
 #define CMGAN_E_WORKSPACE   -5   /* workspace too small or misaligned              */
 #define CMGAN_E_HIP         -6   /* a HIP runtime call failed (see last_error)     */
 
-#define CMGAN_ABI_VERSION 17
+#define CMGAN_ABI_VERSION 18
 
 typedef struct cmgan_handle cmgan_handle;
 
@@ -705,6 +705,58 @@ int cmgan_scene(cmgan_handle* h, const float* clean_dev, int B, int L, long long
                 const int* rir_index_dev, const int* rir_len_dev, const int* src_rir_index_dev, const int* src_rir_len_dev,
                 float peak, int early, float* noisy_dev, float* target_dev, long long ld_out, double* g_dev, double* p_dev,
                 double* ps_dev, double* scale_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- Paths: a talker and sources that MOVE through the room (no counterpart in the reference, see "Scenes") ------------
+ * cmgan_scene with a path of responses instead of one: P waypoint columns per row and per source, waypoint p at input
+ * sample p H (host ints, 1 <= P <= cmgan_scene_max_waypoints() = 64, 1 <= H <= 2^30).  rir_index_dev / rir_len_dev are
+ * int32 [B, P], src_rir_index_dev / src_rir_len_dev int32 [B, S, P], n_path_dev int32 [B] and src_n_path_dev int32 [B, S]
+ * say how many of the columns a row / a source uses: Pb = the entry clamped to [1, P], read on the device; the columns
+ * beyond Pb are never read.  A RIR bank is required (without one there is nothing to move through: CMGAN_E_BADARG).  All
+ * other arguments, the outputs and the untrusted-table rules (indices clamped to [0, R), lengths to [1, Kmax]) are
+ * cmgan_scene's.
+ *   weights  for any integer input index m:  u_p[m] = (double)(H - |m - p H|) / (double)H where that is positive, else 0 -
+ *            an exact integer numerator and one IEEE division; u_0[m] = 1 for m <= 0, u_{Pb-1}[m] = 1 for m >= (Pb - 1) H
+ *            (Pb = 1: u_0 = 1 everywhere).  Neighbouring waypoints cross-fade linearly by EMISSION time.
+ *   talker   h_p the response of waypoint p, d_p ITS OWN first-argmax direct index.
+ *            speech[i] = sum over p ascending, then k ascending, of h_p[k] xw,  xw = u_p[m] (double)clean[b, m] rounded
+ *            once to float64,  m = i + d_p - k; only the terms with 0 <= m < L and u_p[m] > 0 count.  One fused
+ *            multiply-add per term into ONE accumulator from 0, across the waypoints.  Every waypoint's own delay is
+ *            removed: the speech stays aligned with the dry clip wherever the talker is, and the direct peaks of
+ *            neighbouring responses coincide, so the cross-fade does not comb them.
+ *   target   early >= 0: the same sum over the taps k <= d_p + early of each waypoint, from the same loads; early == -1:
+ *            the clean row's bits, as in cmgan_mix.
+ *   sources  c_j[i] = the same sum with m = i - k (the delay stays) over seg_j[m], which loops both ways; EVERY integer m
+ *            is weighted by u_p[m], m < 0 included.  Silence rules as in cmgan_scene.
+ *   the rest powers, gains, the fma chain over the sources, the peak guard, the stores and the outputs g, p, ps, scale
+ *            are cmgan_scene's, by the same kernels.
+ * NOT modelled: Doppler shift.  The responses are cross-faded at the emitted sample; no sample is resampled in time, so a
+ * fast source changes colour and level but not pitch.
+ * Contract: a row with Pb = 1 whose sources all have one waypoint has the bits of cmgan_scene called with column 0 of the
+ * tables.  Guarantees as there: no atomics, reductions in an order that depends on L alone, the same bits from run to
+ * run; a row's bits depend neither on B, nor on the other rows or their n_path, nor on padding, nor on unread columns.
+ * Whether a zero-weight term of a non-finite tap shows in the output is unspecified.
+ * Method.  scene_direct_path, grid (P, B), finds d_p.  scene_conv_path has scene_conv's grid: a block owns
+ * cmgan_mix_tile() outputs of one (row, source) slice and, for every waypoint whose window can reach the tile, walks only
+ * the taps that meet a non-zero weight - at most cnt + 2 H - 2, inside [0, K_p) and, for the talker, inside the clip - in
+ * the chunks of scene_conv, with the span staged on chip ALREADY weighted (one product per staged sample, not per term).
+ * Expected cost: about 2 + cmgan_mix_tile() / H times cmgan_scene's convolution.
+ * Every argument is checked before the handle is (cmgan_last_error(NULL) reads the message of a call with h == NULL):
+ * CMGAN_E_BADARG / CMGAN_E_UNSUPPORTED before any launch, a short or misaligned workspace included.
+ * Workspace: cmgan_scene_path_workspace_bytes (h may be NULL; 0 for an unsupported shape; non-decreasing in every
+ * argument): cmgan_scene's plus d [B, P].  Six launches, no synchronisation, no allocation; graph-capturable, and a replay
+ * reads the tables' current contents.                                                                                  */
+int cmgan_scene_max_waypoints(void);
+size_t cmgan_scene_path_workspace_bytes(const cmgan_handle* h, int B, int L, int Kmax, int S, int P);
+int cmgan_scene_path(cmgan_handle* h, const float* clean_dev, int B, int L, long long ld, const float* noise_bank_dev,
+                     long long bank_len, const long long* noise_start_dev, const long long* noise_len_dev,
+                     const long long* noise_off_dev, const float* snr_db_dev, const float* src_bank_dev,
+                     long long src_bank_len, int S, const int* n_src_dev, const long long* src_start_dev,
+                     const long long* src_len_dev, const long long* src_off_dev, const float* src_snr_db_dev,
+                     const float* rir_bank_dev, int R, int Kmax, int P, int H, const int* n_path_dev,
+                     const int* rir_index_dev, const int* rir_len_dev, const int* src_n_path_dev,
+                     const int* src_rir_index_dev, const int* src_rir_len_dev, float peak, int early, float* noisy_dev,
+                     float* target_dev, long long ld_out, double* g_dev, double* p_dev, double* ps_dev, double* scale_dev,
+                     void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---- Room impulse responses (the reference ships no impulse responses and no simulator; its --cut_len help names
  * "denoise and dereverberation", src/data/dataloader.py:13-50 replays pairs mixed beforehand) --------------------------
