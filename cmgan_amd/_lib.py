@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CMGAN_HIP_LIB") or os.path.join(HERE, "lib", "libcmgan_hip.so")
 
 OK = 0
-ABI_VERSION = 18
+ABI_VERSION = 19
 MFMA_F32, MFMA_F16X3, MFMA_F16X1, MFMA_F16MIX = 0, 1, 2, 3
 # CMGAN_MIX_* bits of Config.single_mask (include/cmgan_hip.h)
 MIX = {"conv": 1, "ff1": 2, "ff2": 4, "qkv": 8, "attn": 16, "pw1": 32, "dwpw2": 64}
@@ -221,6 +221,13 @@ SIGNATURES = {
     "cmgan_rir_bands_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int, c_int]),
     "cmgan_rir_bands": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_double,
                                 c_int, c_int, c_int, c_int, c_void_p, c_longlong, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "cmgan_rir_dir_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "cmgan_rir_dir": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_int, c_int,
+                              c_int, c_void_p, c_longlong, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "cmgan_rir_bands_dir_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int, c_int]),
+    "cmgan_rir_bands_dir": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                    c_int, c_int, c_double, c_int, c_int, c_int, c_int, c_void_p, c_longlong, c_void_p, c_void_p,
+                                    c_size_t, c_void_p]),
     "cmgan_rir_stats_tile": (c_int, []),
     "cmgan_rir_stats_columns": (c_int, []),
     "cmgan_rir_stats_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),

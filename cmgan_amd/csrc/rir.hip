@@ -46,6 +46,15 @@
 //                       RR_TILE + NF - 1 samples (zeros outside [0, k_r + D)), and the band's NF filter taps in LDS; every
 //                       thread runs its double sum in the stated order into ONE accumulator, rounds once and writes the
 //                       zeros beyond k_r.  Consecutive threads read consecutive float64, the filter tap is a broadcast.
+//
+// DIRECTIVITY (cmgan_rir_dir, cmgan_rir_bands_dir): first-order patterns at both ends, per band.  The gain of an image,
+//   g_b = fma(1 - alpha_s,b, cos_s, alpha_s,b) fma(1 - alpha_m,b, cos_m, alpha_m,b),  cos_m = (o . v) / d,  cos_s = -(o . u_p) / d,
+// with u_p the source's unit facing vector mirrored with the image ((1 - 2 p) u per axis) and v the receiver's, depends
+// on the image and not on the tap: it is one more factor of the amplitude an entry already stores.  The tap kernels are
+// templates on DIR; the DIR forms read the unit vectors and the alphas from a longer record (the prep kernels of the
+// DIR calls judge and normalise the two tables), and their entry lambdas multiply g_b in.  The list layout, rr_consume
+// and the DIR = false instantiations are what they were.  A pattern of all ones gives g_b = fma(0, cos, 1)^2 = 1.0
+// exactly, so such a row has the bits of the plain call.
 #include <math.h>
 #include <stdint.h>
 
@@ -72,6 +81,14 @@ constexpr int RB_AIR = 16;
 constexpr int RB_HEAD = 24;                 // cmgan_rir_bands: 9 room numbers, (unused), k_r, m_b at RB_AIR .. 23
 constexpr int RR_REC = RR_HEAD + 6 * RR_PW;
 __host__ __device__ inline size_t rb_rec(int NB) { return (size_t)RB_HEAD + (size_t)6 * NB * RR_PW; }
+// the records of the directional calls are longer: behind the powers the unit vectors u, v and (alpha_s, alpha_m) per band
+constexpr int RD_ALPHA = 6;
+constexpr double RD_MAX_COMPONENT = 1.0e100;   // of a facing vector: its square stays finite
+__host__ __device__ inline size_t rd_words(int NB) { return (size_t)RD_ALPHA + (size_t)2 * NB; }
+template <bool DIR>
+__host__ __device__ inline size_t rr_rec_words() { return (size_t)RR_REC + (DIR ? rd_words(1) : 0); }
+template <bool DIR>
+__host__ __device__ inline size_t rb_rec_words(int NB) { return rb_rec(NB) + (DIR ? rd_words(NB) : 0); }
 
 // Between the 8-byte LDS stores of a list entry: merged into one 16-byte store (ds_write2_b64), the later data dwords are
 // still being read by the LDS path when the next VALU instruction overwrites them (tools/isa_lint.py).
@@ -95,6 +112,11 @@ struct BandArgs : RirArgs {
     int NB, NF;
 };
 
+struct DirArgs {             // the prep kernels of the directional calls only: the tap kernels read the record
+    const double* orient;    // [R][6]
+    const double* pattern;   // [R][NB][2]
+};
+
 // ---------------------------------------------------------------- the prep kernels
 __device__ inline bool rr_finite(double v) { return v - v == 0.0; }
 __device__ inline int rr_clamp_taps(int n_taps, int K, bool ok) { return !ok || n_taps < 1 ? 1 : (n_taps > K ? K : n_taps); }
@@ -115,11 +137,37 @@ __device__ inline void rr_powers(double* pw, int ncoef, bool ok, Coef coef) {
     }
 }
 
-__global__ __launch_bounds__(RR_TPB) void rir_prep(RirArgs a) {
+// Row r of the two tables of a directional call, judged (a non-finite entry, an alpha outside [0, 1], a component beyond
+// RD_MAX_COMPONENT, a zero vector at an end that has some alpha < 1); `out` gets the unit vectors u, v (zeros for a zero
+// vector: every alpha of that end is then 1 and the cosine is multiplied by 0) and the nb (alpha_s, alpha_m) pairs.
+__device__ inline bool rd_prep(const DirArgs& d, int r, int nb, double* out) {
+    const int t = threadIdx.x;
+    const double* o = d.orient + (size_t)r * 6;
+    const double* p = d.pattern + (size_t)r * nb * 2;
+    bool ok = true, aimed_s = false, aimed_m = false;
+    for (int i = 0; i < 6; ++i) ok = ok && rr_finite(o[i]) && fabs(o[i]) <= RD_MAX_COMPONENT;
+    for (int i = 0; i < 2 * nb; ++i) {
+        ok = ok && p[i] >= 0.0 && p[i] <= 1.0;                    // (a NaN fails both)
+        if (i & 1) aimed_m = aimed_m || p[i] < 1.0;
+        else aimed_s = aimed_s || p[i] < 1.0;
+    }
+    const double nu = sqrt(fma(o[2], o[2], fma(o[1], o[1], o[0] * o[0])));
+    const double nv = sqrt(fma(o[5], o[5], fma(o[4], o[4], o[3] * o[3])));
+    ok = ok && (!aimed_s || nu > 0.0) && (!aimed_m || nv > 0.0);
+    if (t < RD_ALPHA) {
+        const double n = t < 3 ? nu : nv;
+        out[t] = (ok && n > 0.0) ? o[t] / n : 0.0;
+    } else if (t < RD_ALPHA + 2 * nb) {
+        out[t] = ok ? p[t - RD_ALPHA] : 1.0;
+    }
+    return ok;
+}
+
+// `ok`: what the caller has judged of the row already; `rec` the row's record
+__device__ inline void rir_prep_row(const RirArgs& a, double* rec, bool ok) {
     const int t = threadIdx.x, r = blockIdx.x;
     const double* room = a.rooms + (size_t)r * 15;
-    double* rec = a.rec + (size_t)r * RR_REC;
-    bool ok = rr_geometry_ok(room);
+    ok = ok && rr_geometry_ok(room);
     for (int i = 9; i < 15; ++i) ok = ok && rr_finite(room[i]) && room[i] >= 0.0 && room[i] <= 1.0;
     const int kr = rr_clamp_taps(a.n_taps[r], a.K, ok);
     if (t < 15) rec[t] = room[t];
@@ -128,12 +176,22 @@ __global__ __launch_bounds__(RR_TPB) void rir_prep(RirArgs a) {
     rr_powers(rec + RR_HEAD, 6, ok, [&](int w) { return room[9 + w]; });
 }
 
-__global__ __launch_bounds__(RR_TPB) void rir_bands_prep(BandArgs a) {
+__global__ __launch_bounds__(RR_TPB) void rir_prep(RirArgs a) {
+    const int r = blockIdx.x;
+    rir_prep_row(a, a.rec + (size_t)r * rr_rec_words<false>(), true);
+}
+
+__global__ __launch_bounds__(RR_TPB) void rir_dir_prep(RirArgs a, DirArgs d) {
+    const int r = blockIdx.x;
+    double* rec = a.rec + (size_t)r * rr_rec_words<true>();
+    rir_prep_row(a, rec, rd_prep(d, r, 1, rec + RR_REC));
+}
+
+__device__ inline void rir_bands_prep_row(const BandArgs& a, double* rec, bool ok) {
     const int t = threadIdx.x, r = blockIdx.x;
     const double* room = a.rooms + (size_t)r * 15;
     const double* band = a.bands + (size_t)r * a.NB * 7;
-    double* rec = a.rec + (size_t)r * rb_rec(a.NB);
-    bool ok = rr_geometry_ok(room);
+    ok = ok && rr_geometry_ok(room);
     for (int i = 0; i < a.NB * 7; ++i) ok = ok && rr_finite(band[i]) && band[i] >= 0.0 && (i % 7 == 6 || band[i] <= 1.0);
     const int kr = rr_clamp_taps(a.n_taps[r], a.K, ok);
     if (t < 9) rec[t] = room[t];
@@ -142,6 +200,17 @@ __global__ __launch_bounds__(RR_TPB) void rir_bands_prep(BandArgs a) {
     if (t >= RB_AIR && t < RB_HEAD) rec[t] = (ok && t - RB_AIR < a.NB) ? band[(t - RB_AIR) * 7 + 6] : 0.0;
     if (t == 0) a.len[r] = kr;
     rr_powers(rec + RB_HEAD, 6 * a.NB, ok, [&](int w) { return band[w / 6 * 7 + w % 6]; });      // w = 6 b + wall
+}
+
+__global__ __launch_bounds__(RR_TPB) void rir_bands_prep(BandArgs a) {
+    const int r = blockIdx.x;
+    rir_bands_prep_row(a, a.rec + (size_t)r * rb_rec_words<false>(a.NB), true);
+}
+
+__global__ __launch_bounds__(RR_TPB) void rir_bands_dir_prep(BandArgs a, DirArgs d) {
+    const int r = blockIdx.x;
+    double* rec = a.rec + (size_t)r * rb_rec_words<true>(a.NB);
+    rir_bands_prep_row(a, rec, rd_prep(d, r, a.NB, rec + rb_rec(a.NB)));
 }
 
 // ---------------------------------------------------------------- the enumeration
@@ -175,13 +244,24 @@ __device__ inline int rr_bound(double v, int Nz) { return (int)fmin(fmax(v, (dou
 // a column (nx, ny, p): its nz candidates [lo1, hi1] then [lo2, hi2] (ascending, disjoint; n1 in the first, ncand in
 // all), dx^2 + dy^2, the z offset of nz = 0, and the places w RR_PW + exponent of its four x / y powers in a [6][RR_PW]
 // table (exponents <= N + 1 < RR_PW: indices, not table values).  A column past the last has no candidates and places 0.
-struct RrColumn {
+// A directional column (RrColumn<true>) also carries px, py, dx and dy - the mirror signs and the offset; the plain one
+// is the struct it was.
+template <bool DIR>
+struct RrAim {};
+template <>
+struct RrAim<true> {
+    int px, py;
+    double dx, dy;
+};
+template <bool DIR>
+struct RrColumn : RrAim<DIR> {
     int lo1, lo2, n1, ncand, pz, ax, bx, ay, by;
     double q, zo;
 };
 
-__device__ inline RrColumn rr_column(const RrTile& g, int col) {
-    RrColumn c = {};
+template <bool DIR>
+__device__ inline RrColumn<DIR> rr_column(const RrTile& g, int col) {
+    RrColumn<DIR> c = {};
     int hi1 = -1, hi2 = -1;
     if (col < g.ncols) {
         const int p = col & 7, xy = col >> 3;
@@ -191,6 +271,7 @@ __device__ inline RrColumn rr_column(const RrTile& g, int col) {
         c.pz = p & 1;
         const double dx = fma((double)(2 * nx), g.Lx, (px ? -g.sx : g.sx) - g.mx);
         const double dy = fma((double)(2 * ny), g.Ly, (py ? -g.sy : g.sy) - g.my);
+        if constexpr (DIR) c.px = px, c.py = py, c.dx = dx, c.dy = dy;
         c.q = fma(dy, dy, dx * dx);
         c.zo = (c.pz ? -g.sz : g.sz) - g.mz;
         c.ax = 0 * RR_PW + abs(nx - px), c.bx = 1 * RR_PW + abs(nx), c.ay = 2 * RR_PW + abs(ny - py), c.by = 3 * RR_PW + abs(ny);
@@ -217,15 +298,18 @@ __device__ inline RrColumn rr_column(const RrTile& g, int col) {
 }
 
 // candidate i of a column: its nz, its distance, and whether its delay reaches the tile
-__device__ inline int rr_nz(const RrColumn& c, int i) { return i < c.n1 ? c.lo1 + i : c.lo2 + (i - c.n1); }
+template <class Column>
+__device__ inline int rr_nz(const Column& c, int i) { return i < c.n1 ? c.lo1 + i : c.lo2 + (i - c.n1); }
 __device__ inline bool rr_reaches(const RrTile& g, double tau) { return tau > g.t_lo && tau < g.t_hi; }
-__device__ inline double rr_distance(const RrTile& g, const RrColumn& c, int nz) {
+template <class Column>
+__device__ inline double rr_distance(const RrTile& g, const Column& c, int nz) {
     const double dz = fma((double)(2 * nz), g.Lz, c.zo);
     return sqrt(fma(dz, dz, c.q));
 }
 
 // the candidates that reach the tile, with the delay the entries are made from
-__device__ inline int rr_count(const RrTile& g, const RrColumn& c) {
+template <class Column>
+__device__ inline int rr_count(const RrTile& g, const Column& c) {
     int cnt = 0;
     for (int i = 0; i < c.ncand; ++i) cnt += rr_reaches(g, rr_distance(g, c, rr_nz(c, i)) * g.spm) ? 1 : 0;
     return cnt;
@@ -253,8 +337,8 @@ __device__ inline int rr_scan(int v, int (*s)[RR_TPB], int& total) {
 // The round's list, RR_CAP entries at a time: this thread's `cnt` images take the places base .. base + cnt - 1 of `total`.
 // entry(e, nz, d, tau) writes entry e of the chunk (s_t0[e] = k0 - tau among it); consume(n), called by the whole
 // block between two barriers, adds the chunk's n entries to the taps.
-template <class Entry, class Consume>
-__device__ inline void rr_list(const RrTile& g, const RrColumn& c, int cnt, int base, int total, double* s_t0, Entry entry,
+template <class Column, class Entry, class Consume>
+__device__ inline void rr_list(const RrTile& g, const Column& c, int cnt, int base, int total, double* s_t0, Entry entry,
                                Consume consume) {
     int cursor = 0, pos = base;
     for (int cs = 0; cs < total; cs += RR_CAP) {
@@ -294,14 +378,40 @@ __device__ inline void rr_consume(const double* s_t0, int n, double jd, double t
     }
 }
 
+// ---------------------------------------------------------------- directivity: what an entry lambda of a DIR form adds
+// the unit facing vectors of the row, from the words `w` of its record (uniform over the block)
+struct RrFacing {
+    double ux, uy, uz, vx, vy, vz;
+};
+__device__ inline RrFacing rr_facing(const double* w) { return RrFacing{w[0], w[1], w[2], w[3], w[4], w[5]}; }
+
+// The cosines of image nz of the column at distance d: between the source image's mirrored facing vector and the ray to
+// the receiver, and between the receiver's vector and the ray back to the image.  dz is rr_distance's; both 0 at d == 0.
+// One reciprocal of d serves both (measured: a per cent off the single-band call against two divisions).
+__device__ inline void rr_cosines(const RrFacing& f, const RrTile& g, const RrColumn<true>& c, int nz, double d, double& cos_s,
+                                  double& cos_m) {
+    const double dz = fma((double)(2 * nz), g.Lz, c.zo);
+    const double om = fma(dz, f.vz, fma(c.dy, f.vy, c.dx * f.vx));
+    const double os = fma(dz, c.pz ? -f.uz : f.uz, fma(c.dy, c.py ? -f.uy : f.uy, c.dx * (c.px ? -f.ux : f.ux)));
+    const double rd = d > 0.0 ? 1.0 / d : 0.0;
+    cos_m = om * rd;
+    cos_s = -os * rd;
+}
+
+// signed: the rear lobe of a pattern with alpha < 1/2 is negative
+__device__ inline double rr_gain(double alpha_s, double alpha_m, double cos_s, double cos_m) {
+    return fma(1.0 - alpha_s, cos_s, alpha_s) * fma(1.0 - alpha_m, cos_m, alpha_m);
+}
+
 // ---------------------------------------------------------------- cmgan_rir's tap kernel
+template <bool DIR>
 __global__ __launch_bounds__(RR_TPB) void rir_taps(RirArgs a) {
     __shared__ double s_pw[6 * RR_PW];
     __shared__ double s_t0[RR_CAP + RR_UNR], s_sp[RR_CAP], s_ha[RR_CAP], s_hc[RR_CAP], s_hs[RR_CAP];
     __shared__ int s_scan[2][RR_TPB];
     const int t = threadIdx.x, r = blockIdx.y;
     const int k0 = blockIdx.x * RR_TILE, k = k0 + t;
-    const double* rec = a.rec + (size_t)r * RR_REC;
+    const double* rec = a.rec + (size_t)r * rr_rec_words<DIR>();
     float* out = a.rir + (size_t)r * a.ld;
     const int kr = (int)rec[RR_KR];                              // 0: an invalid row
     if (k0 >= kr) {                                              // (the whole block: nothing of this tile is a tap)
@@ -310,6 +420,8 @@ __global__ __launch_bounds__(RR_TPB) void rir_taps(RirArgs a) {
     }
     for (int i = t; i < 6 * RR_PW; i += RR_TPB) s_pw[i] = rec[RR_HEAD + i];
     const RrTile g = rr_tile(a, rec, k0, (k0 + RR_TILE < kr ? k0 + RR_TILE : kr) - 1);
+    const RrFacing f = DIR ? rr_facing(rec + RR_REC) : RrFacing{};
+    const double alpha_s = DIR ? rec[RR_REC + RD_ALPHA] : 1.0, alpha_m = DIR ? rec[RR_REC + RD_ALPHA + 1] : 1.0;
     __syncthreads();
     // this thread's tap: j = t
     const double twd = (double)a.tw, jd = (double)t;
@@ -317,7 +429,7 @@ __global__ __launch_bounds__(RR_TPB) void rir_taps(RirArgs a) {
     double acc = 0.0;
 
     for (int c0 = 0; c0 < g.ncols; c0 += RR_TPB) {
-        const RrColumn c = rr_column(g, c0 + t);
+        const RrColumn<DIR> c = rr_column<DIR>(g, c0 + t);
         const double cxy = s_pw[c.ax] * s_pw[c.bx] * s_pw[c.ay] * s_pw[c.by];
         const int cnt = rr_count(g, c);
         int total;
@@ -325,8 +437,13 @@ __global__ __launch_bounds__(RR_TPB) void rir_taps(RirArgs a) {
         rr_list(g, c, cnt, base, total, s_t0,
                 [=](int e, int nz, double d, double tau) {
                     const int ez = nz - c.pz;
-                    const double amp = cxy * s_pw[4 * RR_PW + (ez < 0 ? -ez : ez)] * s_pw[5 * RR_PW + (nz < 0 ? -nz : nz)]
-                                     / (4.0 * RR_PI * fmax(d, CMGAN_RIR_DMIN));
+                    double amp = cxy * s_pw[4 * RR_PW + (ez < 0 ? -ez : ez)] * s_pw[5 * RR_PW + (nz < 0 ? -nz : nz)]
+                               / (4.0 * RR_PI * fmax(d, CMGAN_RIR_DMIN));
+                    if constexpr (DIR) {
+                        double cos_s, cos_m;
+                        rr_cosines(f, g, c, nz, d, cos_s, cos_m);
+                        amp *= rr_gain(alpha_s, alpha_m, cos_s, cos_m);
+                    }
                     const double t0 = (double)k0 - tau, ha = 0.5 * amp, ang = t0 / twd;
                     s_t0[e] = t0;
                     s_sp[e] = sinpi(t0) / RR_PI;
@@ -348,7 +465,7 @@ __global__ __launch_bounds__(RR_TPB) void rir_taps(RirArgs a) {
 }
 
 // ---------------------------------------------------------------- cmgan_rir_bands' tap and join kernels
-template <int NB>
+template <int NB, bool DIR>
 __global__ __launch_bounds__(RR_TPB) void rir_bands_taps(BandArgs a) {
     __shared__ double s_t0[RR_CAP + RR_UNR], s_sp[RR_CAP], s_hc[RR_CAP], s_hs[RR_CAP];
     __shared__ double s_amp[NB][RR_CAP];
@@ -356,12 +473,14 @@ __global__ __launch_bounds__(RR_TPB) void rir_bands_taps(BandArgs a) {
     const int t = threadIdx.x, r = blockIdx.y;
     const int k0 = blockIdx.x * RR_TILE, k = k0 + t;
     const int D = (a.NF - 1) / 2, KD = a.K + D;
-    const double* rec = a.rec + (size_t)r * rb_rec(NB);
+    const double* rec = a.rec + (size_t)r * rb_rec_words<DIR>(NB);
     const double* pw = rec + RB_HEAD;                            // [NB][6][RR_PW]
+    const double* facing = rec + rb_rec(NB);                     // (DIR) u, v, then [NB][2] alphas, read per image like the powers
     const int kr = (int)rec[RR_KR];                              // 0: an invalid row
     const int kq = kr > 0 ? kr + D : 0;                          // the band responses hold taps [0, kq)
     if (k0 >= kq) return;                                        // (the whole block; nothing from kq on is ever read)
     const RrTile g = rr_tile(a, rec, k0, (k0 + RR_TILE < kq ? k0 + RR_TILE : kq) - 1);
+    const RrFacing f = DIR ? rr_facing(facing) : RrFacing{};
     double air[NB];
 #pragma unroll
     for (int b = 0; b < NB; ++b) air[b] = rec[RB_AIR + b];
@@ -373,7 +492,7 @@ __global__ __launch_bounds__(RR_TPB) void rir_bands_taps(BandArgs a) {
     for (int b = 0; b < NB; ++b) acc[b] = 0.0;
 
     for (int c0 = 0; c0 < g.ncols; c0 += RR_TPB) {
-        const RrColumn c = rr_column(g, c0 + t);
+        const RrColumn<DIR> c = rr_column<DIR>(g, c0 + t);
         const int cnt = rr_count(g, c);
         int total;
         const int base = rr_scan(cnt, s_scan, total);
@@ -393,11 +512,15 @@ __global__ __launch_bounds__(RR_TPB) void rir_bands_taps(BandArgs a) {
                     const int ez = nz - c.pz;
                     const int az = ez < 0 ? -ez : ez, bz = nz < 0 ? -nz : nz;
                     const double spread = 4.0 * RR_PI * fmax(d, CMGAN_RIR_DMIN);
+                    double cos_s = 0.0, cos_m = 0.0;
+                    if constexpr (DIR) rr_cosines(f, g, c, nz, d, cos_s, cos_m);
 #pragma unroll
                     for (int b = 0; b < NB; ++b) {
                         const double* pb = pw + (size_t)b * 6 * RR_PW;
                         const double att = air[b] == 0.0 ? 1.0 : exp(-air[b] * d);
-                        s_amp[b][e] = cxy[b] * pb[4 * RR_PW + az] * pb[5 * RR_PW + bz] * att / spread;
+                        double amp = cxy[b] * pb[4 * RR_PW + az] * pb[5 * RR_PW + bz] * att / spread;
+                        if constexpr (DIR) amp *= rr_gain(facing[RD_ALPHA + 2 * b], facing[RD_ALPHA + 2 * b + 1], cos_s, cos_m);
+                        s_amp[b][e] = amp;
                         RB_KEEP_APART();
                     }
                     const double t0 = (double)k0 - tau, ang = t0 / twd;
@@ -429,12 +552,13 @@ __global__ __launch_bounds__(RR_TPB) void rir_bands_taps(BandArgs a) {
     }
 }
 
+template <bool DIR>                                              // (the record's length is all that differs)
 __global__ __launch_bounds__(RR_TPB) void rir_bands_join(BandArgs a) {
     __shared__ double s_h[RB_SPAN], s_g[RB_MAX_FILTER];
     const int t = threadIdx.x, r = blockIdx.y;
     const int k0 = blockIdx.x * RR_TILE, k = k0 + t;
     const int NF = a.NF, D = (NF - 1) / 2, KD = a.K + D;
-    const int kr = (int)a.rec[(size_t)r * rb_rec(a.NB) + RR_KR]; // 0: an invalid row
+    const int kr = (int)a.rec[(size_t)r * rb_rec_words<DIR>(a.NB) + RR_KR];   // 0: an invalid row
     float* out = a.rir + (size_t)r * a.ld;
     if (k0 >= kr) {                                              // (the whole block: nothing of this tile is a tap)
         if (k < a.K) out[k] = 0.f;
@@ -471,18 +595,28 @@ inline bool rb_shape_ok(int R, int K, int tw, int NB, int NF) {
     return rr_shape_ok(R, K, tw) && NB >= 1 && NB <= RB_MAX_BANDS && NF >= 1 && NF <= RB_MAX_FILTER && (NF & 1);
 }
 
-inline size_t rb_rec_bytes(int R, int NB) { return rr_up256((size_t)R * rb_rec(NB) * sizeof(double)); }
+template <bool DIR>
+inline size_t rr_rec_bytes(int R) { return rr_up256((size_t)R * rr_rec_words<DIR>() * sizeof(double)); }
+template <bool DIR>
+inline size_t rb_rec_bytes(int R, int NB) { return rr_up256((size_t)R * rb_rec_words<DIR>(NB) * sizeof(double)); }
+inline size_t rb_hb_bytes(int R, int K, int NB, int NF) {
+    return rr_up256((size_t)R * NB * (size_t)(K + (NF - 1) / 2) * sizeof(double));
+}
 
 // Judges every argument but the workspace and fills `a`; `bt` is null for cmgan_rir and holds bands, filt, NB and NF for
-// cmgan_rir_bands (it may be the object `a` is the base of: only the base is assigned, after the last read of `bt`).  The
-// handle is judged last: the errors before it need no GPU (without a handle the message is cmgan_last_error(NULL)'s).
-int rr_judge(cmgan_handle* h, const char* name, const BandArgs* bt, const double* rooms, const int* n_taps, int R, int K,
-             int fs, double c, int tw, int Nx, int Ny, int Nz, float* rir, long long ld, int* len, void* ws, RirArgs& a) {
-    if (!rooms || !n_taps || !rir || !len || (bt && (!bt->bands || !bt->filt)))
+// cmgan_rir_bands (it may be the object `a` is the base of: only the base is assigned, after the last read of `bt`); `dt`
+// is null for the plain calls and holds the two tables of a directional one.  The handle is judged last: the errors
+// before it need no GPU (without a handle the message is cmgan_last_error(NULL)'s).
+int rr_judge(cmgan_handle* h, const char* name, const BandArgs* bt, const DirArgs* dt, const double* rooms, const int* n_taps,
+             int R, int K, int fs, double c, int tw, int Nx, int Ny, int Nz, float* rir, long long ld, int* len, void* ws,
+             RirArgs& a) {
+    if (!rooms || !n_taps || !rir || !len || (bt && (!bt->bands || !bt->filt)) || (dt && (!dt->orient || !dt->pattern)))
         return fail(h, CMGAN_E_BADARG, "%s: null pointer", name);
     if (((uintptr_t)rooms | (bt ? (uintptr_t)bt->bands | (uintptr_t)bt->filt : 0)) & 7)
         return fail(h, CMGAN_E_BADARG, "%s: the float64 %s must be 8-byte aligned", name,
                     bt ? "room, band and filter tables" : "room table");
+    if (dt && (((uintptr_t)dt->orient | (uintptr_t)dt->pattern) & 7))
+        return fail(h, CMGAN_E_BADARG, "%s: the float64 orient and pattern tables must be 8-byte aligned", name);
     if (((uintptr_t)n_taps | (uintptr_t)rir | (uintptr_t)len) & 3)
         return fail(h, CMGAN_E_BADARG, "%s: float32 / int32 buffers must be 4-byte aligned", name);
     if (R < 1 || R > 65535 || K < 1 || ld < K)
@@ -515,6 +649,53 @@ int rr_judge(cmgan_handle* h, const char* name, const BandArgs* bt, const double
     return CMGAN_OK;
 }
 
+// the workspace of the two call families: the records, and for the banded ones the band responses behind them
+template <bool DIR>
+inline size_t rr_ws_bytes(int R, int K, int tw) { return rr_shape_ok(R, K, tw) ? rr_rec_bytes<DIR>(R) : 0; }
+template <bool DIR>
+inline size_t rb_ws_bytes(int R, int K, int tw, int NB, int NF) {
+    return rb_shape_ok(R, K, tw, NB, NF) ? rb_rec_bytes<DIR>(R, NB) + rb_hb_bytes(R, K, NB, NF) : 0;
+}
+
+// cmgan_rir (`dt` null) and cmgan_rir_dir: the same judgement, the same grid; the prep kernel and the record differ
+template <bool DIR>
+int rr_run(cmgan_handle* h, const char* name, const DirArgs* dt, const double* rooms, const int* n_taps, int R, int K, int fs,
+           double c, int tw, int Nx, int Ny, int Nz, float* rir, long long ld, int* len, void* ws, size_t ws_bytes, void* stream) {
+    RirArgs a;
+    if (int rc = rr_judge(h, name, nullptr, dt, rooms, n_taps, R, K, fs, c, tw, Nx, Ny, Nz, rir, ld, len, ws, a)) return rc;
+    if (int rc = check_ws(h, ws, ws_bytes, rr_ws_bytes<DIR>(R, K, tw))) return rc;
+    const LaunchCtx ctx = begin(h, stream);
+    hipStream_t s = ctx.stream;
+    const dim3 grid((K + RR_TILE - 1) / RR_TILE, R);
+    if constexpr (DIR) LAUNCH(ctx, "rir_dir_prep", rir_dir_prep<<<R, RR_TPB, 0, s>>>(a, *dt));
+    else LAUNCH(ctx, "rir_prep", rir_prep<<<R, RR_TPB, 0, s>>>(a));
+    LAUNCH(ctx, DIR ? "rir_dir_taps" : "rir_taps", rir_taps<DIR><<<grid, RR_TPB, 0, s>>>(a));
+    return check_launch(h, "rir");
+}
+
+template <bool DIR>
+int rb_run(cmgan_handle* h, const char* name, const DirArgs* dt, const double* rooms, const double* bands, const int* n_taps,
+           int R, int K, int NB, const double* filt, int NF, int fs, double c, int tw, int Nx, int Ny, int Nz, float* rir,
+           long long ld, int* len, void* ws, size_t ws_bytes, void* stream) {
+    BandArgs a;
+    a.bands = bands, a.filt = filt;
+    a.NB = NB, a.NF = NF;
+    if (int rc = rr_judge(h, name, &a, dt, rooms, n_taps, R, K, fs, c, tw, Nx, Ny, Nz, rir, ld, len, ws, a)) return rc;
+    if (int rc = check_ws(h, ws, ws_bytes, rb_ws_bytes<DIR>(R, K, tw, NB, NF))) return rc;
+    const LaunchCtx ctx = begin(h, stream);
+    hipStream_t s = ctx.stream;
+    a.hb = (double*)((char*)ws + rb_rec_bytes<DIR>(R, NB));
+    const dim3 grid_taps((K + (NF - 1) / 2 + RR_TILE - 1) / RR_TILE, R), grid_join((K + RR_TILE - 1) / RR_TILE, R);
+    if constexpr (DIR) LAUNCH(ctx, "rir_bands_dir_prep", rir_bands_dir_prep<<<R, RR_TPB, 0, s>>>(a, *dt));
+    else LAUNCH(ctx, "rir_bands_prep", rir_bands_prep<<<R, RR_TPB, 0, s>>>(a));
+    void (*const taps[RB_MAX_BANDS])(BandArgs) = {rir_bands_taps<1, DIR>, rir_bands_taps<2, DIR>, rir_bands_taps<3, DIR>,
+                                                  rir_bands_taps<4, DIR>, rir_bands_taps<5, DIR>, rir_bands_taps<6, DIR>,
+                                                  rir_bands_taps<7, DIR>, rir_bands_taps<8, DIR>};
+    LAUNCH(ctx, DIR ? "rir_bands_dir_taps" : "rir_bands_taps", taps[NB - 1]<<<grid_taps, RR_TPB, 0, s>>>(a));
+    LAUNCH(ctx, "rir_bands_join", rir_bands_join<DIR><<<grid_join, RR_TPB, 0, s>>>(a));
+    return check_launch(h, "rir_bands");
+}
+
 }  // namespace
 
 extern "C" int cmgan_rir_tile(void) { return RR_TILE; }
@@ -522,45 +703,42 @@ extern "C" int cmgan_rir_list_capacity(void) { return RR_CAP; }
 extern "C" int cmgan_rir_max_bands(void) { return RB_MAX_BANDS; }
 extern "C" int cmgan_rir_max_filter(void) { return RB_MAX_FILTER; }
 
-extern "C" size_t cmgan_rir_workspace_bytes(const cmgan_handle*, int R, int K, int tw) {
-    return rr_shape_ok(R, K, tw) ? rr_up256((size_t)R * RR_REC * sizeof(double)) : 0;
-}
+extern "C" size_t cmgan_rir_workspace_bytes(const cmgan_handle*, int R, int K, int tw) { return rr_ws_bytes<false>(R, K, tw); }
+extern "C" size_t cmgan_rir_dir_workspace_bytes(const cmgan_handle*, int R, int K, int tw) { return rr_ws_bytes<true>(R, K, tw); }
 
 extern "C" size_t cmgan_rir_bands_workspace_bytes(const cmgan_handle*, int R, int K, int tw, int NB, int NF) {
-    if (!rb_shape_ok(R, K, tw, NB, NF)) return 0;
-    return rb_rec_bytes(R, NB) + rr_up256((size_t)R * NB * (size_t)(K + (NF - 1) / 2) * sizeof(double));
+    return rb_ws_bytes<false>(R, K, tw, NB, NF);
+}
+
+extern "C" size_t cmgan_rir_bands_dir_workspace_bytes(const cmgan_handle*, int R, int K, int tw, int NB, int NF) {
+    return rb_ws_bytes<true>(R, K, tw, NB, NF);
 }
 
 extern "C" int cmgan_rir(cmgan_handle* h, const double* rooms, const int* n_taps, int R, int K, int fs, double c, int tw,
                          int Nx, int Ny, int Nz, float* rir, long long ld, int* len, void* ws, size_t ws_bytes,
                          void* stream) {
-    RirArgs a;
-    if (int rc = rr_judge(h, "cmgan_rir", nullptr, rooms, n_taps, R, K, fs, c, tw, Nx, Ny, Nz, rir, ld, len, ws, a)) return rc;
-    if (int rc = check_ws(h, ws, ws_bytes, cmgan_rir_workspace_bytes(h, R, K, tw))) return rc;
-    const LaunchCtx ctx = begin(h, stream);
-    hipStream_t s = ctx.stream;
-    const dim3 grid((K + RR_TILE - 1) / RR_TILE, R);
-    LAUNCH(ctx, "rir_prep", rir_prep<<<R, RR_TPB, 0, s>>>(a));
-    LAUNCH(ctx, "rir_taps", rir_taps<<<grid, RR_TPB, 0, s>>>(a));
-    return check_launch(h, "rir");
+    return rr_run<false>(h, "cmgan_rir", nullptr, rooms, n_taps, R, K, fs, c, tw, Nx, Ny, Nz, rir, ld, len, ws, ws_bytes, stream);
+}
+
+extern "C" int cmgan_rir_dir(cmgan_handle* h, const double* rooms, const double* orient, const double* pattern,
+                             const int* n_taps, int R, int K, int fs, double c, int tw, int Nx, int Ny, int Nz, float* rir,
+                             long long ld, int* len, void* ws, size_t ws_bytes, void* stream) {
+    const DirArgs dt{orient, pattern};
+    return rr_run<true>(h, "cmgan_rir_dir", &dt, rooms, n_taps, R, K, fs, c, tw, Nx, Ny, Nz, rir, ld, len, ws, ws_bytes, stream);
 }
 
 extern "C" int cmgan_rir_bands(cmgan_handle* h, const double* rooms, const double* bands, const int* n_taps, int R, int K,
                                int NB, const double* filt, int NF, int fs, double c, int tw, int Nx, int Ny, int Nz,
                                float* rir, long long ld, int* len, void* ws, size_t ws_bytes, void* stream) {
-    BandArgs a;
-    a.bands = bands, a.filt = filt;
-    a.NB = NB, a.NF = NF;
-    if (int rc = rr_judge(h, "cmgan_rir_bands", &a, rooms, n_taps, R, K, fs, c, tw, Nx, Ny, Nz, rir, ld, len, ws, a)) return rc;
-    if (int rc = check_ws(h, ws, ws_bytes, cmgan_rir_bands_workspace_bytes(h, R, K, tw, NB, NF))) return rc;
-    const LaunchCtx ctx = begin(h, stream);
-    hipStream_t s = ctx.stream;
-    a.hb = (double*)((char*)ws + rb_rec_bytes(R, NB));
-    const dim3 grid_taps((K + (NF - 1) / 2 + RR_TILE - 1) / RR_TILE, R), grid_join((K + RR_TILE - 1) / RR_TILE, R);
-    LAUNCH(ctx, "rir_bands_prep", rir_bands_prep<<<R, RR_TPB, 0, s>>>(a));
-    void (*const taps[RB_MAX_BANDS])(BandArgs) = {rir_bands_taps<1>, rir_bands_taps<2>, rir_bands_taps<3>, rir_bands_taps<4>,
-                                                  rir_bands_taps<5>, rir_bands_taps<6>, rir_bands_taps<7>, rir_bands_taps<8>};
-    LAUNCH(ctx, "rir_bands_taps", taps[NB - 1]<<<grid_taps, RR_TPB, 0, s>>>(a));
-    LAUNCH(ctx, "rir_bands_join", rir_bands_join<<<grid_join, RR_TPB, 0, s>>>(a));
-    return check_launch(h, "rir_bands");
+    return rb_run<false>(h, "cmgan_rir_bands", nullptr, rooms, bands, n_taps, R, K, NB, filt, NF, fs, c, tw, Nx, Ny, Nz, rir, ld,
+                         len, ws, ws_bytes, stream);
+}
+
+extern "C" int cmgan_rir_bands_dir(cmgan_handle* h, const double* rooms, const double* bands, const double* orient,
+                                   const double* pattern, const int* n_taps, int R, int K, int NB, const double* filt, int NF,
+                                   int fs, double c, int tw, int Nx, int Ny, int Nz, float* rir, long long ld, int* len,
+                                   void* ws, size_t ws_bytes, void* stream) {
+    const DirArgs dt{orient, pattern};
+    return rb_run<true>(h, "cmgan_rir_bands_dir", &dt, rooms, bands, n_taps, R, K, NB, filt, NF, fs, c, tw, Nx, Ny, Nz, rir, ld,
+                        len, ws, ws_bytes, stream);
 }

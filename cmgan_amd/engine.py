@@ -290,6 +290,20 @@ def check_rir_bands_args(device, rooms, bands, n_taps, K, filters, n_images, fs=
     return R, K, N, NB, filters.size(1)
 
 
+def check_rir_dir_args(device, R: int, NB: int, orient, pattern):
+    """Argument rules of the directivity tables of Engine.rir (NB = 1) and Engine.rir_bands (pure host code): both or
+    neither; orient float64 [R, 6], pattern float64 [R, NB, 2] ([R, 2] is accepted for [R, 1, 2]).  Returns (orient,
+    pattern as [R, NB, 2]), or (None, None)."""
+    if orient is None and pattern is None:
+        return None, None
+    if orient is None or pattern is None:
+        raise ValueError(f"orient and pattern go together: {'orient' if orient is None else 'pattern'} is missing")
+    tensor_arg(orient, "orient", torch.float64, device, f"[{R}, 6]", lambda t: tuple(t.shape) == (R, 6))
+    tensor_arg(pattern, "pattern", torch.float64, device, f"[{R}, {NB}, 2]" + (f" or [{R}, 2]" if NB == 1 else ""),
+               lambda t: tuple(t.shape) == (R, NB, 2) or (NB == 1 and tuple(t.shape) == (R, 2)))
+    return orient, pattern.reshape(R, NB, 2)
+
+
 RIR_STATS_COLUMNS = 10        # = cmgan_rir_stats_columns()
 RIR_STATS_NONFINITE, RIR_STATS_ZERO, RIR_STATS_NO_EDT, RIR_STATS_NO_T20, RIR_STATS_NO_T30 = 1, 2, 4, 8, 16    # status bits
 
@@ -596,7 +610,8 @@ class Engine:
             msg = self.lib.cmgan_last_error(None)
             raise _lib.CmganError(rc, msg.decode() if msg else "?")
         #: grow-only uint8 workspaces by name (_grow): "main", "branched" (enhance_graphed(branches > 1)), "conformer",
-        #: "metrics", "mix", "scene", "rir", "rir_bands", "level", "channel" and ("resample", fs_in, fs_out), the rate pair's tap table
+        #: "metrics", "mix", "scene", "rir", "rir_bands", "rir_dir", "rir_bands_dir", "level", "channel" and ("resample", fs_in,
+        #: fs_out), the rate pair's tap table
         self._wss: dict = {}
         self._graphs: dict = {}          # enhance_graphed: input shape -> (graph, in, out, token)
         self._row_graphs: dict = {}      # streaming.enhance_windows: row shape -> (graph, in, out, token)
@@ -1288,7 +1303,7 @@ class Engine:
 
     @_on_device
     def rir(self, rooms: torch.Tensor, n_taps: torch.Tensor, K: int, n_images, fs: int = 16000, c: float = 343.0,
-            tw: int = 40, out=None):
+            tw: int = 40, out=None, orient: Optional[torch.Tensor] = None, pattern: Optional[torch.Tensor] = None):
         """Room impulse responses of shoe-box rooms by the image-source method (cmgan_rir, include/cmgan_hip.h).
 
         rooms float64 [R, 15] (size Lx Ly Lz in metres, source, receiver, reflection coefficients bx0 bx1 by0 by1 bz0
@@ -1298,18 +1313,33 @@ class Engine:
         written in place.  Returns (rir float32 [R, K], length int32 [R]): exactly the `rir_bank` / `rir_len` source of
         Engine.mix.  Row r holds clamp(n_taps[r], 1, K) taps and zeros after them; an invalid row (a non-finite entry, a
         size <= 0, a coefficient outside [0, 1]) is zeros with length 1.  Float64 arithmetic, one rounding to float32;
-        bit-reproducible, row-independent, no synchronisation, graph-capturable after one call at the shape."""
+        bit-reproducible, row-independent, no synchronisation, graph-capturable after one call at the shape.
+
+        `orient` float64 [R, 6] and `pattern` float64 [R, 1, 2] (or [R, 2]), both or neither, make the two ends
+        directional (cmgan_rir_dir): the source's facing vector then the receiver's, of any length, and the first-order
+        coefficients alpha_s, alpha_m in [0, 1] (1 omni, 0.5 cardioid, 0 figure-of-eight).  A row whose alphas are both 1
+        has the bits of the call without the tables; a non-finite entry, an alpha outside [0, 1], a component beyond
+        1e100 or a zero vector at an end with alpha < 1 makes the row invalid."""
         R, K, N = check_rir_args(self.device, rooms, n_taps, K, n_images, fs, c, tw, out)
-        ws = self._grow("rir", int(self.lib.cmgan_rir_workspace_bytes(self._h, R, K, int(tw))),
-                        f"[{R}, {K}] with tw = {tw} is outside what cmgan_rir supports")
+        orient, pattern = check_rir_dir_args(self.device, R, 1, orient, pattern)
+        if orient is None:
+            ws = self._grow("rir", int(self.lib.cmgan_rir_workspace_bytes(self._h, R, K, int(tw))),
+                            f"[{R}, {K}] with tw = {tw} is outside what cmgan_rir supports")
+            rir, length = out if out is not None else self._rir_out(R, K)
+            self._call("cmgan_rir", rooms, n_taps, R, K, int(fs), float(c), int(tw), N[0], N[1], N[2], rir, K, length, ws,
+                       ws.numel())
+            return rir, length
+        ws = self._grow("rir_dir", int(self.lib.cmgan_rir_dir_workspace_bytes(self._h, R, K, int(tw))),
+                        f"[{R}, {K}] with tw = {tw} is outside what cmgan_rir_dir supports")
         rir, length = out if out is not None else self._rir_out(R, K)
-        self._call("cmgan_rir", rooms, n_taps, R, K, int(fs), float(c), int(tw), N[0], N[1], N[2], rir, K, length, ws,
-                   ws.numel())
+        self._call("cmgan_rir_dir", rooms, orient, pattern, n_taps, R, K, int(fs), float(c), int(tw), N[0], N[1], N[2], rir, K,
+                   length, ws, ws.numel())
         return rir, length
 
     @_on_device
     def rir_bands(self, rooms: torch.Tensor, bands: torch.Tensor, n_taps: torch.Tensor, K: int, filters: torch.Tensor,
-                  n_images, fs: int = 16000, c: float = 343.0, tw: int = 40, out=None):
+                  n_images, fs: int = 16000, c: float = 343.0, tw: int = 40, out=None, orient: Optional[torch.Tensor] = None,
+                  pattern: Optional[torch.Tensor] = None):
         """Room impulse responses with frequency-dependent walls and air absorption (cmgan_rir_bands, include/cmgan_hip.h):
         Engine.rir simulated in NB frequency bands at once - one image list, one accumulator per band - and joined by a
         filterbank.
@@ -1321,13 +1351,19 @@ class Engine:
         (float32 [R, K], int32 [R]) is written in place.  Returns (rir float32 [R, K], length int32 [R]), as Engine.rir
         does.  An invalid row (a non-finite entry in columns 0 - 8 or in its band table, a size <= 0, a coefficient
         outside [0, 1], a negative m) is zeros with length 1.  Float64 arithmetic, one rounding to float32;
-        bit-reproducible, row-independent, no synchronisation, graph-capturable after one call at the shape."""
+        bit-reproducible, row-independent, no synchronisation, graph-capturable after one call at the shape.
+
+        `orient` float64 [R, 6] and `pattern` float64 [R, NB, 2], both or neither, make the two ends directional
+        (cmgan_rir_bands_dir) as for Engine.rir, with one (alpha_s, alpha_m) pair per band."""
         R, K, N, NB, NF = check_rir_bands_args(self.device, rooms, bands, n_taps, K, filters, n_images, fs, c, tw, out)
-        ws = self._grow("rir_bands", int(self.lib.cmgan_rir_bands_workspace_bytes(self._h, R, K, int(tw), NB, NF)),
-                        f"[{R}, {K}] with tw = {tw}, {NB} bands and {NF} filter taps is outside what cmgan_rir_bands supports")
+        orient, pattern = check_rir_dir_args(self.device, R, NB, orient, pattern)
+        name = "cmgan_rir_bands" if orient is None else "cmgan_rir_bands_dir"
+        ws = self._grow(name[6:], int(getattr(self.lib, name + "_workspace_bytes")(self._h, R, K, int(tw), NB, NF)),
+                        f"[{R}, {K}] with tw = {tw}, {NB} bands and {NF} filter taps is outside what {name} supports")
         rir, length = out if out is not None else self._rir_out(R, K)
-        self._call("cmgan_rir_bands", rooms, bands, n_taps, R, K, NB, filters, NF, int(fs), float(c), int(tw), N[0], N[1],
-                   N[2], rir, K, length, ws, ws.numel())
+        tables = (rooms, bands) if orient is None else (rooms, bands, orient, pattern)
+        self._call(name, *tables, n_taps, R, K, NB, filters, NF, int(fs), float(c), int(tw), N[0], N[1], N[2], rir, K, length,
+                   ws, ws.numel())
         return rir, length
 
     @_on_device

@@ -304,13 +304,26 @@ class RoomSampler:
     and tilt that were drawn and not from the table's coefficients - and int64 noise seeds, a torch.randint from
     `generator` on the device after every other draw.  The tail's level is fitted to the `tail_window_ms` in front of the
     junction, so tail_ms must exceed that window (with `bands`, by the filterbank's delay too).  With None (the default)
-    the sampler draws the same numbers as before and `draw_tail` is an error."""
+    the sampler draws the same numbers as before and `draw_tail` is an error.
+
+    `source_pattern` / `mic_pattern` = (low, high) in [0, 1] turn on directivity (Engine.rir(orient=, pattern=)): a
+    first-order pattern alpha + (1 - alpha) cos(theta) at the talker and at the microphone, alpha uniform per row in its
+    range (1 omni, 0.5 cardioid, 0 figure-of-eight; None: 1).  `draw_dirs(tables)`, called after every other draw, gives
+    (orient float64 [..., 6], pattern float64 [..., max(bands, 1), 2]) for the [R, 15] table of `draw`, the [R, n, 15] of
+    `draw_sources` or, with path=True, the [..., P, 15] of `draw_path`: the talker's facing vector u at an angle uniform
+    in `facing_deg` = (low, high) degrees off the direction from source to receiver (0: facing the microphone) and an
+    azimuth uniform around it, the microphone's vector v uniform on the sphere.  With `bands`, alpha_s,b = clamp(alpha_s -
+    tilt (b - b_ref), 0, 1) with tilt drawn per row in `pattern_tilt` (per octave: more directional upwards); alpha_m
+    is flat.  On a path every waypoint keeps the row's angle, azimuth and patterns around ITS OWN direction to the
+    receiver: the talker keeps half-facing the microphone as it walks.  With all four at their defaults the sampler draws
+    what it drew before and `draw_dirs` is an error."""
 
     BAND_F0 = 125.0               # Hz: the centre of band 0
 
     def __init__(self, dims=((3.0, 3.0, 2.5), (10.0, 8.0, 4.0)), rt60=(0.2, 0.8), margin: float = 0.5,
                  generator: Optional[torch.Generator] = None, bands: Optional[int] = None, tilt=(0.0, 0.0), air=None,
-                 filter_taps: int = 511, tail_ms: Optional[float] = None, tail_window_ms: float = 30.0):
+                 filter_taps: int = 511, tail_ms: Optional[float] = None, tail_window_ms: float = 30.0,
+                 source_pattern=None, facing_deg=(0.0, 180.0), mic_pattern=None, pattern_tilt=(0.0, 0.0)):
         try:
             lo, hi = (tuple(float(v) for v in d) for d in dims)
         except (TypeError, ValueError):
@@ -346,6 +359,18 @@ class RoomSampler:
             raise ValueError(f"tail_window_ms must be a positive, finite number of milliseconds, got {tail_window_ms}")
         self.tail_ms, self.tail_window_ms = tail_ms, float(tail_window_ms)
         self._drawn = {}              # tail_ms: the rt60, n_full (draw), tilt and m (draw_bands) of the last draw, for draw_tail
+        # ---- directivity: judged last, so that every earlier error is what it was
+        self.directional = source_pattern is not None or mic_pattern is not None
+        alphas = lambda name, v: None if v is None else _pair(name, v, 0.0, 1.0, "None or (low, high) with 0 <= low <= high <= 1",
+                                                              "None or (low, high)", echo=True)
+        self.source_pattern, self.mic_pattern = alphas("source_pattern", source_pattern), alphas("mic_pattern", mic_pattern)
+        self.facing_deg = _pair("facing_deg", facing_deg, 0.0, 180.0, "(low, high) degrees with 0 <= low <= high <= 180", echo=True)
+        self.pattern_tilt = _pair("pattern_tilt", pattern_tilt, -math.inf, math.inf, "(low, high) with finite low <= high",
+                                  closed=False, echo=True)
+        if not self.directional and (self.facing_deg != (0.0, 180.0) or self.pattern_tilt != (0.0, 0.0)):
+            raise ValueError("facing_deg and pattern_tilt belong to directivity: give source_pattern or mic_pattern with them")
+        if self.pattern_tilt != (0.0, 0.0) and (self.bands is None or self.source_pattern is None):
+            raise ValueError("pattern_tilt tilts the talker's pattern over the bands: give bands=n and source_pattern with it")
 
     def max_junction(self, K: int, fs: int, c: float = SPEED_OF_SOUND) -> int:
         """The largest n_taps `draw` can return: K, or with `tail_ms` min(K, ceil((d / c + tail_ms / 1000) fs)) with d the
@@ -440,6 +465,51 @@ class RoomSampler:
             raise ValueError(f"sources must be the float64 [{R}, n, 15] tables of RoomSampler.draw_sources")
         junction = self._junction(sources, kept["n_full"][:, None], fs).contiguous()
         return TailDraw(kept["n_full"], decay, seed, junction, draw(R, sources.size(1)))
+
+    def draw_dirs(self, tables: torch.Tensor, path: bool = False, facing_deg=None):
+        """(orient float64 [..., 6], pattern float64 [..., max(bands, 1), 2]) for [..., 15] tables this sampler drew: the
+        tables of Engine.rir(orient=, pattern=) / Engine.rir_bands after a reshape to rows.  ONE rand(..., 7) from
+        `generator` on the device of `tables`, after every other draw: the places of alpha_s, alpha_m, the facing angle,
+        its azimuth, v's height and azimuth, and the tilt.  path=True: `tables` is [..., P, 15] of `draw_path`, drawn once
+        per walk (rand(..., 7) without the P) and applied at every waypoint.  `facing_deg` overrides the sampler's range
+        (DynamicMixer gives further sources (0, 180))."""
+        if not self.directional:
+            raise ValueError("this RoomSampler has no source_pattern or mic_pattern")
+        need = (3, 4) if path else (2, 3)
+        if not isinstance(tables, torch.Tensor) or tables.dtype != torch.float64 or tables.dim() not in need or tables.size(-1) != 15:
+            raise ValueError("tables must be the float64 [R, 15] table of RoomSampler.draw, the [R, n, 15] ones of draw_sources "
+                             "or, with path=True, the [..., P, 15] ones of draw_path")
+        f_lo, f_hi = self.facing_deg if facing_deg is None else _pair(
+            "facing_deg", facing_deg, 0.0, 180.0, "(low, high) degrees with 0 <= low <= high <= 180", echo=True)
+        dev, nb = tables.device, self.bands or 1
+        lead = tuple(tables.shape[:-2] if path else tables.shape[:-1])
+        u = torch.rand(*lead, 7, dtype=torch.float64, generator=self.generator, device=dev)
+        if path:
+            u = u[..., None, :]                                   # one draw per walk, at every waypoint
+        between = lambda rng, x: torch.ones_like(x) if rng is None else rng[0] + (rng[1] - rng[0]) * x
+        alpha_s, alpha_m = between(self.source_pattern, u[..., 0]), between(self.mic_pattern, u[..., 1])
+        theta = torch.deg2rad(between((f_lo, f_hi), u[..., 2]))[..., None]
+        phi = (2.0 * math.pi) * u[..., 3:4]
+        # the cone around w, the direction from source to receiver (the x axis where the two coincide)
+        w = tables[..., 6:9] - tables[..., 3:6]
+        far = torch.linalg.vector_norm(w, dim=-1, keepdim=True)
+        ex = torch.tensor([1.0, 0.0, 0.0], dtype=torch.float64).to(dev, non_blocking=True)
+        ey = torch.tensor([0.0, 1.0, 0.0], dtype=torch.float64).to(dev, non_blocking=True)
+        w = torch.where(far > 0.0, w / torch.where(far > 0.0, far, torch.ones_like(far)), ex)
+        e1 = torch.linalg.cross(w, torch.where(w[..., 0:1].abs() < 0.9, ex, ey).expand_as(w), dim=-1)
+        e1 = e1 / torch.linalg.vector_norm(e1, dim=-1, keepdim=True)
+        e2 = torch.linalg.cross(w, e1, dim=-1)
+        facing = torch.cos(theta) * w + torch.sin(theta) * (torch.cos(phi) * e1 + torch.sin(phi) * e2)
+        z = 2.0 * u[..., 4:5] - 1.0                               # v uniform on the sphere: height uniform, then the azimuth
+        rho, psi = torch.sqrt((1.0 - z * z).clamp_min(0.0)), (2.0 * math.pi) * u[..., 5:6]
+        mic = torch.cat([rho * torch.cos(psi), rho * torch.sin(psi), z], dim=-1).expand_as(facing)
+        step = torch.arange(nb, dtype=torch.float64).to(dev, non_blocking=True) - float(self.band_ref)
+        tilt = between(self.pattern_tilt, u[..., 6])
+        per_band = (alpha_s[..., None] - tilt[..., None] * step).clamp(0.0, 1.0)              # [..., nb]
+        pattern = torch.stack([per_band, alpha_m[..., None].expand_as(per_band)], dim=-1)
+        if path:
+            pattern = pattern.expand(*tables.shape[:-1], nb, 2)
+        return torch.cat([facing, mic], dim=-1).contiguous(), pattern.contiguous()
 
     def draw(self, R: int, K: int, fs: int, device=None):
         gen = self.generator
@@ -666,6 +736,7 @@ class RirBank:
     Recorded responses come from `from_dir` / `from_arrays`; `simulate` makes the bank on the device from random shoe-box
     rooms (Engine.rir, the image-source method) and keeps their table as `rooms` (float64 [R, 15], else None); with a
     banded sampler (RoomSampler(bands=n): Engine.rir_bands) also their band table as `bands` (float64 [R, n, 7]).
+    With a directional sampler (RoomSampler(source_pattern=, mic_pattern=)) `orient` and `pattern` keep its draw_dirs.
     `measure` leaves what the responses measure as in `stats` (a RirStats of [R, NB + 1] tensors, else None), and `where`
     selects rows by it."""
 
@@ -673,6 +744,7 @@ class RirBank:
                  bands: Optional[torch.Tensor] = None, stats: Optional[RirStats] = None):
         self.data, self.length, self.rooms, self.bands, self.stats = data, length, rooms, bands, stats
         self.tail: Optional[RirTail] = None      # simulate with RoomSampler(tail_ms=...): the fitted levels and the status
+        self.orient = self.pattern = None        # simulate with a directional RoomSampler: the tables of its draw_dirs
 
     def __len__(self) -> int:
         return self.data.size(0)
@@ -706,13 +778,16 @@ class RirBank:
         rooms, n_taps = sampler.draw(R, K, sample_rate, device=engine.device)
         N = sampler.n_images(K, sample_rate)
         filters = None if sampler.bands is None else sampler.filters(sample_rate, engine.device)
+        bands = None if filters is None else sampler.draw_bands(rooms)
+        t = None if sampler.tail_ms is None else sampler.draw_tail(rooms, sample_rate)
+        orient, pattern = sampler.draw_dirs(rooms) if sampler.directional else (None, None)      # (after every other draw)
         if filters is None:
-            bank = cls(*engine.rir(rooms, n_taps, K, N, fs=sample_rate), rooms)
+            bank = cls(*engine.rir(rooms, n_taps, K, N, fs=sample_rate, orient=orient, pattern=pattern), rooms)
         else:
-            bands = sampler.draw_bands(rooms)
-            bank = cls(*engine.rir_bands(rooms, bands, n_taps, K, filters, N, fs=sample_rate), rooms, bands)
-        if sampler.tail_ms is not None:                           # the responses end at their junctions: the diffuse tail
-            t = sampler.draw_tail(rooms, sample_rate)
+            bank = cls(*engine.rir_bands(rooms, bands, n_taps, K, filters, N, fs=sample_rate, orient=orient, pattern=pattern),
+                       rooms, bands)
+        bank.orient, bank.pattern = orient, pattern
+        if t is not None:                                         # the responses end at their junctions: the diffuse tail
             bank.tail = engine.rir_tail(bank.data, bank.length, t.n_full, t.decay, t.seed, filters, fs=sample_rate,
                                         window_ms=sampler.tail_window_ms)[2]
         if measure:
@@ -918,6 +993,12 @@ class DynamicMixer:
     was mixed with, and `room_stats=True` measures the extended responses.  Without `tail_ms` nothing of this is drawn or
     run.
 
+    `rooms=RoomSampler(source_pattern=..., mic_pattern=...)`: directional talkers and microphones (Engine.rir / rir_bands with
+    orient= and pattern=).  RoomSampler.draw_dirs is called where the responses are simulated, after every other draw of the
+    sampler: once for the talkers - on a path every waypoint keeps the walk's angle to the microphone - and once for the
+    sources, which face any way (`facing_deg=(0, 180)` whatever the sampler's range); `mixer.last_dirs` keeps the two
+    (orient, pattern) pairs.  Without the options nothing of this is drawn and the batch is bit-identical to before.
+
     `motion=(lo, hi)` metres per second (needs `rooms`; a `rir_bank` of fixed responses cannot move): talkers that walk
     (Engine.scene_path / cmgan_scene_path).  A waypoint every `motion_hop_ms` (H samples, `motion_hop`), P = 1 + ceil((N -
     1) / H) of them for the batch length N that reaches the mix, at most 64 (`waypoints(N)`).  Every row gets a path,
@@ -1010,6 +1091,7 @@ class DynamicMixer:
         self.rir_taps, self.n_images, self.last_bank = 0, None, None
         self.last_bands: Optional[torch.Tensor] = None      # rooms=RoomSampler(bands=n): the float64 [B, n, 7] table of the batch
         self.last_tail: Optional[TailDraw] = None           # rooms=RoomSampler(tail_ms=...): the batch's tail draw
+        self.last_dirs = None                               # a directional RoomSampler: ((orient, pattern) of the talkers, of the sources)
         if rooms is not None:
             if rir_bank is not None:
                 raise ValueError("give either a rir_bank or rooms, not both")
@@ -1242,20 +1324,29 @@ class DynamicMixer:
         # rir_len is the sampler's n_taps, or 1 for a dry row (whose response is then one tap that no row uses)
         filt = None if bands is None else self.rooms.filters(self.sample_rate, self.engine.device)
 
-        def simulate(rooms, taps, out, table):
+        def simulate(rooms, taps, out, table, dirs):
+            orient, pattern = (None, None) if dirs is None else (dirs[0].reshape(-1, 6), dirs[1].reshape(rooms.size(0), -1, 2))
             if table is None:
-                self.engine.rir(rooms, taps, K, self.n_images, fs=self.sample_rate, out=out)
+                self.engine.rir(rooms, taps, K, self.n_images, fs=self.sample_rate, out=out, orient=orient, pattern=pattern)
             else:
-                self.engine.rir_bands(rooms, table, taps, K, filt, self.n_images, fs=self.sample_rate, out=out)
+                self.engine.rir_bands(rooms, table, taps, K, filt, self.n_images, fs=self.sample_rate, out=out, orient=orient,
+                                      pattern=pattern)
+
+        # a directional sampler: its draw_dirs of the talkers, then of the sources (whatever way those face), after every
+        # other draw of the sampler; kept as `last_dirs`
+        aimed = self.rooms.directional
+        dirs = src_dirs = None
 
         def extend(out, n_full, decay, seed):                     # (a dry row's junction is 1: no window fits, it stays)
             self.engine.rir_tail(*out, n_full, decay, seed, filt, fs=self.sample_rate, window_ms=self.rooms.tail_window_ms)
 
         out = (sim.data[:talkers], sim.length[:talkers])
         if Pt == 1:
-            simulate(d.rooms, d.rir_len, out, bands)
+            dirs = self.rooms.draw_dirs(d.rooms) if aimed else None
+            simulate(d.rooms, d.rir_len, out, bands, dirs)
         else:
-            simulate(paths.path.reshape(talkers, 15), paths.taps.reshape(talkers), out, None if bands is None else each(bands, Pt))
+            dirs = self.rooms.draw_dirs(paths.path, path=True) if aimed else None
+            simulate(paths.path.reshape(talkers, 15), paths.taps.reshape(talkers), out, None if bands is None else each(bands, Pt), dirs)
         if tail is not None:
             extend(out, each(tail.n_full, Pt), each(tail.decay, Pt), each(tail.seed, Pt))
         if n_s:                                                   # the sources' responses: one call of B S (Ps) rows
@@ -1264,11 +1355,13 @@ class DynamicMixer:
                 rooms, taps = d.src_rooms, d.src_rir_len if tail is None else tail.src_junction
             else:
                 rooms, taps = paths.src_path, paths.src_taps
+            src_dirs = self.rooms.draw_dirs(rooms, path=Ps > 1, facing_deg=(0.0, 180.0)) if aimed else None
             simulate(rooms.reshape(B * n_s * Ps, 15), taps.reshape(B * n_s * Ps), out,
-                     None if bands is None else bands.repeat_interleave(n_s * Ps, dim=0))
+                     None if bands is None else bands.repeat_interleave(n_s * Ps, dim=0), src_dirs)
             if tail is not None:
                 extend(out, tail.n_full.repeat_interleave(n_s * Ps), tail.decay.repeat_interleave(n_s * Ps, dim=0),
                        each(tail.src_seed.reshape(B * n_s), Ps))
+        self.last_dirs = (dirs, src_dirs) if aimed else None
         return sim
 
     @staticmethod

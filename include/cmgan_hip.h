@@ -39,7 +39,7 @@ extern "C" {
 #define CMGAN_E_WORKSPACE   -5   /* workspace too small or misaligned              */
 #define CMGAN_E_HIP         -6   /* a HIP runtime call failed (see last_error)     */
 
-#define CMGAN_ABI_VERSION 18
+#define CMGAN_ABI_VERSION 19
 
 typedef struct cmgan_handle cmgan_handle;
 
@@ -775,7 +775,8 @@ int cmgan_scene_path(cmgan_handle* h, const float* clean_dev, int B, int L, long
  *   taps     h[k] = sum_images a w(k - tau) sinc(k - tau), 0 <= k < k_r, with w(t) = (1 + cos(pi t / tw)) / 2 for
  *            |t| < tw, else 0, and sinc(t) = sin(pi t) / (pi t), sinc(0) = 1; images with tau - tw >= K add nothing
  *   outputs  rir_dev[r * ld + k] = f32(h[k]) for k < k_r and exactly 0.0f for k_r <= k < K;  len_dev[r] = k_r
- * Not modelled: a high-pass filter, directivity; air absorption and frequency-dependent walls are cmgan_rir_bands, below.
+ * Not modelled: a high-pass filter; air absorption and frequency-dependent walls are cmgan_rir_bands, directional sources
+ * and receivers cmgan_rir_dir / cmgan_rir_bands_dir, both below.
  * All arithmetic is float64 and each tap is rounded to
  * float32 exactly once.  A block owns cmgan_rir_tile() consecutive taps of one row and adds the images that reach them in
  * one fixed enumeration order (nx, ny, p, nz ascending), staged cmgan_rir_list_capacity() at a time in an on-chip list by
@@ -815,7 +816,8 @@ int cmgan_rir(cmgan_handle* h, const double* rooms_dev, const int* n_taps_dev, i
  *            order: the filterbank's delay D is taken out, and the bands are simulated D taps past the row's end, so the
  *            join truncates nothing there.  The caller's image ranges must cover K + D taps
  *   outputs  rir_dev[r * ld + k] = f32(h[k]) for k < k_r and exactly 0.0f for k_r <= k < K;  len_dev[r] = k_r
- * Still not modelled: directivity, and a material per wall beyond what the caller writes into the band table.  The
+ * Still not modelled: a material per wall beyond what the caller writes into the band table (directivity:
+ * cmgan_rir_bands_dir, below).  The
  * guarantees are those of cmgan_rir: float64 throughout and one rounding to float32; per (tap, band) the images are added
  * in the one fixed enumeration order of cmgan_rir; no atomics; the same bits from run to run; row r's bits depend neither
  * on R nor on the other rows, and an N larger than needed changes no bit; nothing read from a table becomes an address.
@@ -833,6 +835,48 @@ size_t cmgan_rir_bands_workspace_bytes(const cmgan_handle* h, int R, int K, int 
 int cmgan_rir_bands(cmgan_handle* h, const double* rooms_dev, const double* bands_dev, const int* n_taps_dev, int R, int K,
                     int NB, const double* filt_dev, int NF, int fs, double c, int tw, int Nx, int Ny, int Nz,
                     float* rir_dev, long long ld, int* len_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- Room impulse responses of directional sources and receivers: first-order patterns, per band ---------------------
+ * cmgan_rir and cmgan_rir_bands treat both ends as points that radiate and hear equally in all directions.  These two
+ * calls give each end a facing vector and a first-order pattern alpha + (1 - alpha) cos(theta), per band.  Two more tables
+ * per call, float64, on the device, read by the kernels only:
+ *   orient_dev   [R, 6]: the source's facing vector u, then the receiver's v.  Any length: the kernels normalise them, with
+ *                |x| = sqrt(fma(z, z, fma(y, y, x x))) and three divisions, to the unit vectors u^ and v^
+ *   pattern_dev  [R, NB, 2]: per band alpha_s, alpha_m in [0, 1] - 1 omni, 0.75 sub-cardioid, 0.5 cardioid, 0.25
+ *                hyper-cardioid, 0 figure-of-eight, and anything between.  NB = 1 for cmgan_rir_dir
+ * For the image (n, p) of cmgan_rir, with its offset o = (1 - 2 p) s + 2 n L - m per axis and d = |o|: the image of the
+ * source looks along the mirrored vector u^_p = ((1 - 2 p_x) u^_x, (1 - 2 p_y) u^_y, (1 - 2 p_z) u^_z) - a reflection in
+ * a wall normal to an axis flips that component; n does not enter - and
+ *   cos_m = (o . v^) / d        cos_s = -(o . u^_p) / d        (both 0 when d == 0; o . w = fma(o_z, w_z, fma(o_y, w_y, o_x w_x)),
+ *                                                               and the kernels multiply by one shared reciprocal 1 / d)
+ *   g_b   = fma(1 - alpha_s,b, cos_s, alpha_s,b) * fma(1 - alpha_m,b, cos_m, alpha_m,b)      (signed: rear lobes are negative)
+ *   a_b   = (the amplitude of cmgan_rir, or of band b of cmgan_rir_bands) * g_b
+ * Everything else - the enumeration order, delay, window, sinc, CMGAN_RIR_DMIN, float64 with one rounding to float32, the
+ * join of the band call - is what the plain calls do, and so are their guarantees: no atomics, the same bits from run to
+ * run, row r independent of R and of the other rows, an N larger than needed changes no bit, nothing read from a table
+ * becomes an address.  The gain depends on the image and not on the tap: it is computed where an image enters the
+ * on-chip list, and the per-(image, tap) loop is the plain calls'.
+ *   - With every alpha of a row exactly 1, g_b == 1.0 exactly: the row has the bits of cmgan_rir / cmgan_rir_bands.  For
+ *     an end whose alphas are all 1 the vector may be anything finite, zero included.
+ *   - Swapping source and receiver together with their vectors and patterns maps the image set onto itself with the
+ *     same a_b (reciprocity).
+ *   - A row is invalid (zeros, len = 1, like the invalid rows of the plain calls) when, beyond their rules, an orient or
+ *     pattern entry is non-finite, an alpha is outside [0, 1], a vector component has |.| > 1e100, or an end that has
+ *     some alpha < 1 has a vector whose length (as computed above) is zero.
+ * Checked before any launch and before the handle is looked at: everything the plain call checks, and null or misaligned
+ * (8 bytes) orient_dev / pattern_dev.  Workspace: cmgan_rir_dir_workspace_bytes / cmgan_rir_bands_dir_workspace_bytes
+ * (h may be NULL; 0 when unsupported; non-decreasing in every argument; a little more than the plain calls': a row's
+ * record also holds u^, v^ and the alphas).  No synchronisation, no allocation; graph-capturable, and a replay reads the
+ * tables' current contents. */
+size_t cmgan_rir_dir_workspace_bytes(const cmgan_handle* h, int R, int K, int tw);
+int cmgan_rir_dir(cmgan_handle* h, const double* rooms_dev, const double* orient_dev, const double* pattern_dev,
+                  const int* n_taps_dev, int R, int K, int fs, double c, int tw, int Nx, int Ny, int Nz, float* rir_dev,
+                  long long ld, int* len_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+size_t cmgan_rir_bands_dir_workspace_bytes(const cmgan_handle* h, int R, int K, int tw, int NB, int NF);
+int cmgan_rir_bands_dir(cmgan_handle* h, const double* rooms_dev, const double* bands_dev, const double* orient_dev,
+                        const double* pattern_dev, const int* n_taps_dev, int R, int K, int NB, const double* filt_dev, int NF,
+                        int fs, double c, int tw, int Nx, int Ny, int Nz, float* rir_dev, long long ld, int* len_dev,
+                        void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---- What a room impulse response measures as: decay curve, EDT / T20 / T30, DRR, C50 / C80, D50, Ts ------------------
  * (the reference ships no impulse responses and no meter: src/data/dataloader.py:13-50 replays pairs mixed beforehand)
