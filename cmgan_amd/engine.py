@@ -504,6 +504,52 @@ def check_channel_args(device, wav, sos, n_sections=None, clip=None, lengths=Non
     return B, L, int(sos.size(1))
 
 
+DYNAMICS_TILE = 64            # samples per tile of cmgan_dynamics: one wave (= cmgan_dynamics_tile())
+DYNAMICS_BLOCK = 64 * DYNAMICS_TILE     # samples per block of its last pass: a tile per lane
+DYNAMICS_MAX_L = 2 ** 31 - 1 - DYNAMICS_BLOCK
+
+
+def dynamics_workspace_bytes(B: int, L: int) -> int:
+    """cmgan_dynamics_workspace_bytes: a float64 [B, tiles, 65] plane of tile maps, a float64 [B, tiles] plane of entry
+    states and a float64 [B, blocks] plane of peaks, each rounded up to 256 bytes; 0 for a shape the kernels do not take."""
+    if not (1 <= B <= 65535 and 1 <= L <= DYNAMICS_MAX_L):
+        return 0
+    up = lambda v: (v + 255) & ~255
+    nt = (L + DYNAMICS_TILE - 1) // DYNAMICS_TILE
+    nb = (L + DYNAMICS_BLOCK - 1) // DYNAMICS_BLOCK
+    return up(B * nt * (DYNAMICS_TILE + 1) * 8) + up(B * nt * 8) + up(B * nb * 8)
+
+
+def _overlap(a: torch.Tensor, b: torch.Tensor, B: int, L: int) -> bool:
+    """Whether the spans of two float32 [B, L] row batches intersect."""
+    span = lambda t: (t.data_ptr(), t.data_ptr() + 4 * ((B - 1) * (t.stride(0) if B > 1 else L) + L))
+    (a0, a1), (b0, b1) = span(a), span(b)
+    return a0 < b1 and b0 < a1
+
+
+def check_dynamics_args(device, wav, dyn, key=None, lengths=None, out=None):
+    """Argument rules of Engine.dynamics (shapes, dtypes, devices and overlaps; pure host code).  Returns (B, L)."""
+    B, L = _row_batch(device, wav, DYNAMICS_MAX_L)
+    tensor_arg(dyn, "dyn", torch.float64, device, f"[{B}, 6]", lambda t: tuple(t.shape) == (B, 6))
+    if key is not None:
+        tensor_arg(key, "key", torch.float32, device, f"[{B}, {L}]", lambda t: tuple(t.shape) == (B, L), contiguous=False)
+        if not _row_stride_ok(key, B, L):
+            raise ValueError(f"key: rows must be contiguous and at least L apart, got strides {tuple(key.stride())}")
+    if lengths is not None:
+        tensor_arg(lengths, "lengths", torch.int32, device, f"[{B}]", lambda t: tuple(t.shape) == (B,))
+    if out is not None:
+        tensor_arg(out, "out", torch.float32, device, f"[{B}, {L}]", lambda t: tuple(t.shape) == (B, L), contiguous=False)
+        if not _row_stride_ok(out, B, L):
+            raise ValueError(f"out: rows must be contiguous and at least L apart, got strides {tuple(out.stride())}")
+        for name, t in (("wav", wav), ("key", key)):
+            if t is None:
+                continue
+            same = out.data_ptr() == t.data_ptr() and (B == 1 or out.stride(0) == t.stride(0))
+            if not same and _overlap(out, t, B, L):
+                raise ValueError(f"out: overlaps {name}; only out = {name} itself (in place, the same row stride) is allowed")
+    return B, L
+
+
 WARP_TILE = 256               # outputs per block of cmgan_warp (= cmgan_warp_tile())
 WARP_MAX_RATE = 4.0           # rates in [1 / 4, 4] (= cmgan_warp_max_rate())
 WARP_ZEROS = (4, 64)          # zero crossings on either side of the filter's centre (64 = cmgan_warp_max_zeros())
@@ -610,7 +656,7 @@ class Engine:
             msg = self.lib.cmgan_last_error(None)
             raise _lib.CmganError(rc, msg.decode() if msg else "?")
         #: grow-only uint8 workspaces by name (_grow): "main", "branched" (enhance_graphed(branches > 1)), "conformer",
-        #: "metrics", "mix", "scene", "rir", "rir_bands", "rir_dir", "rir_bands_dir", "level", "channel" and ("resample", fs_in,
+        #: "metrics", "mix", "scene", "rir", "rir_bands", "rir_dir", "rir_bands_dir", "level", "channel", "dynamics" and ("resample", fs_in,
         #: fs_out), the rate pair's tap table
         self._wss: dict = {}
         self._graphs: dict = {}          # enhance_graphed: input shape -> (graph, in, out, token)
@@ -1470,6 +1516,36 @@ class Engine:
         self._call("cmgan_channel", wav, B, L, wav.stride(0) if B > 1 else L, lengths, sos, n_sections, S, clip, out,
                    out.stride(0) if B > 1 else L, st, ws, ws.numel())
         return (out, st) if status else out
+
+    # ---- dynamics: compressor, limiter, automatic gain control ----------------------
+    @_on_device
+    def dynamics(self, wav: torch.Tensor, dyn: torch.Tensor, key: Optional[torch.Tensor] = None,
+                 lengths: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, info: bool = False):
+        """A gain control per row on the GPU (cmgan_dynamics, include/cmgan_hip.h): the feed-forward compressor in the log
+        domain with separate attack and release times - a compressor, a limiter (slope 1) or an AGC by its parameters.
+
+        wav float32 [B, L] (rows contiguous, any row stride >= L); dyn float64 [B, 6] = (thr_db, slope, knee_db, a_att,
+        a_rel, makeup_db) per row (cmgan_amd.mixing.dynamics_params makes it from ratios and milliseconds); key float32
+        [B, L]: the signal whose level drives the gain (None: wav itself); lengths int32 [B] (None: every row has L samples;
+        samples from a row's length on are never read, and come out as zeros).  All on this Engine's device and read by
+        the kernels only.  `out` float32 [B, L] is written in place of a new tensor; out=wav runs in place, out=key is
+        allowed, any other overlap of out with wav or key is a ValueError.  Returns the float32 [B, L] result: float64
+        arithmetic with one rounding to float32.  info=True adds (status, peak_reduction_db): int32 [B], 1 for the rows that
+        are invalid (a non-finite entry, slope outside [0, 1], knee < 0, a coefficient outside [0, 1), a length outside
+        [0, L]) and come out as zeros, and float64 [B], the largest gain reduction of the row in dB.  A row with slope 0
+        and makeup 0 is copied bit for bit.  Bit-reproducible, row-independent, no synchronisation, graph-capturable after
+        one call at the shape."""
+        B, L = check_dynamics_args(self.device, wav, dyn, key, lengths, out)
+        ws = self._grow("dynamics", int(self.lib.cmgan_dynamics_workspace_bytes(B, L)),
+                        f"[{B}, {L}] is outside what cmgan_dynamics supports")
+        if out is None:
+            out = torch.empty(B, L, dtype=torch.float32, device=self.device)
+        st = torch.empty(B, dtype=torch.int32, device=self.device) if info else None
+        pk = torch.empty(B, dtype=torch.float64, device=self.device) if info else None
+        self._call("cmgan_dynamics", wav, B, L, wav.stride(0) if B > 1 else L, key,
+                   0 if key is None else (key.stride(0) if B > 1 else L), lengths, dyn, out, out.stride(0) if B > 1 else L,
+                   st, pk, ws, ws.numel())
+        return (out, st, pk) if info else out
 
     # ---- speed perturbation ---------------------------------------------------------
     def _out_and_info(self, B: int, L: int, N: Optional[int], out: Optional[torch.Tensor], info: bool, n_info: int):

@@ -731,6 +731,75 @@ class ChannelSampler:
         return sos, n_sections, n_sections.clone(), clip
 
 
+# ---- dynamics: the table of Engine.dynamics from ratios and milliseconds, and a sampler of it ------------------------
+def dynamics_params(threshold_db, ratio, knee_db, attack_ms, release_ms, makeup_db, fs) -> torch.Tensor:
+    """The float64 [..., 6] table of Engine.dynamics, (thr_db, slope, knee_db, a_att, a_rel, makeup_db) per row: slope =
+    1 - 1 / ratio (ratio = inf: 1, a limiter) and a = exp(-1 / (t fs)) for a time constant of t = ms / 1000 seconds (0 ms:
+    a = 0, instant).  Plain float64 tensor arithmetic on the device of its arguments, like the biquad designs; what the
+    result allows (ratio >= 1, knee >= 0, times >= 0) is judged per row by the kernels."""
+    thr = _f64(threshold_db)
+    ratio, knee, att, rel, makeup = (_f64(v, thr) for v in (ratio, knee_db, attack_ms, release_ms, makeup_db))
+    coeff = lambda ms: torch.exp(-1000.0 / (ms * float(fs)))
+    thr, slope, knee, a_att, a_rel, makeup = torch.broadcast_tensors(thr, 1.0 - 1.0 / ratio, knee, coeff(att), coeff(rel), makeup)
+    return torch.stack([thr, slope, knee, a_att, a_rel, makeup], dim=-1).contiguous()
+
+
+class DynamicsSampler:
+    """Random gain controls for Engine.dynamics: `draw(B, fs, device)` -> a float64 [B, 6] table (threshold_rel_db, slope,
+    knee_db, a_att, a_rel, m), and `table(drawn, wav)` -> the float64 [B, 6] table of Engine.dynamics for a batch.
+
+    Per row, with probability `p`, a processor: the threshold uniform in `threshold_rel_db`, in dB RELATIVE to the row's
+    peak where the processor runs (as ChannelSampler's clip_rel is); the ratio log-uniform in `ratio`, or infinite - a
+    limiter - with probability `p_limiter`; the knee width uniform in `knee_db`; attack and release times log-uniform in
+    `attack_ms` and `release_ms`; and m uniform in `makeup`, the share of the reduction at the row's peak that the
+    make-up gain gives back: makeup_db = m slope max(0, peak_db - thr_db).  A row that is not chosen gets slope 0 and m 0,
+    so Engine.dynamics copies it bit for bit.  `table` fills in the peak: thr_db = 20 log10(max |wav|) + threshold_rel_db;
+    a row that is silent or holds a non-finite sample gets slope 0 and make-up 0 as well.  Everything is drawn from
+    `generator` (None: the device's default one) on the device with tensor arithmetic: no host synchronisation."""
+
+    def __init__(self, p: float = 0.5, threshold_rel_db=(-30.0, -6.0), ratio=(2.0, 20.0), p_limiter: float = 0.2,
+                 knee_db=(0.0, 12.0), attack_ms=(1.0, 30.0), release_ms=(50.0, 500.0), makeup=(0.0, 1.0),
+                 generator: Optional[torch.Generator] = None):
+        self.p, self.p_limiter = _probability("p", p), _probability("p_limiter", p_limiter)
+        self.threshold_rel_db = _pair("threshold_rel_db", threshold_rel_db, -math.inf, math.inf, "(low, high) with finite low <= high",
+                                      closed=False)
+        self.ratio = _pair("ratio", ratio, 1.0, math.inf, "(low, high) with 1 <= low <= high < inf")
+        if self.ratio[1] == math.inf:
+            raise ValueError(f"ratio must be (low, high) with 1 <= low <= high < inf, got {ratio}; p_limiter draws the infinite one")
+        self.knee_db = _pair("knee_db", knee_db, 0.0, math.inf, "(low, high) with 0 <= low <= high < inf")
+        self.makeup = _pair("makeup", makeup, 0.0, math.inf, "(low, high) with 0 <= low <= high < inf")
+        for name, pair in (("knee_db", self.knee_db), ("makeup", self.makeup)):
+            if pair[1] == math.inf:
+                raise ValueError(f"{name} must be (low, high) with 0 <= low <= high < inf, got {pair}")
+        self.attack_ms, self.release_ms = _positive_pair("attack_ms", attack_ms), _positive_pair("release_ms", release_ms)
+        self.generator = generator
+
+    def draw(self, B: int, fs: int, device=None) -> torch.Tensor:
+        gen = self.generator
+        device = torch.device(device) if device is not None else (gen.device if gen is not None else torch.device("cpu"))
+        u = torch.rand(B, 8, dtype=torch.float64, generator=gen, device=device)
+        log_uniform = lambda r, v: torch.exp(math.log(r[0]) + (math.log(r[1]) - math.log(r[0])) * v)
+        uniform = lambda r, v: r[0] + (r[1] - r[0]) * v
+        ratio = torch.where(u[:, 2] < self.p_limiter, torch.full_like(u[:, 3], math.inf), log_uniform(self.ratio, u[:, 3]))
+        drawn = dynamics_params(uniform(self.threshold_rel_db, u[:, 1]), ratio, uniform(self.knee_db, u[:, 4]),
+                                log_uniform(self.attack_ms, u[:, 5]), log_uniform(self.release_ms, u[:, 6]),
+                                uniform(self.makeup, u[:, 7]), fs)
+        chosen = (u[:, 0] < self.p)[:, None]
+        keep = torch.tensor([True, False, True, True, True, False]).to(device, non_blocking=True)   # an unchosen row: slope 0, m 0
+        return torch.where(chosen | keep, drawn, torch.zeros_like(drawn))
+
+    @staticmethod
+    def table(drawn: torch.Tensor, wav: torch.Tensor) -> torch.Tensor:
+        """The float64 [B, 6] table of Engine.dynamics for the float32 [B, L] batch `wav` and a `draw`."""
+        top = wav.abs().amax(dim=1).to(torch.float64)
+        on = torch.isfinite(top) & (top > 0)
+        thr_rel, slope, knee, a_att, a_rel, m = drawn.unbind(dim=1)
+        thr = 20.0 * torch.log10(torch.where(on, top, torch.ones_like(top))) + thr_rel
+        slope = torch.where(on, slope, torch.zeros_like(slope))
+        makeup = m * slope * torch.clamp(-thr_rel, min=0.0)              # peak_db - thr_db = -threshold_rel_db
+        return torch.stack([thr, slope, knee, a_att, a_rel, makeup], dim=1).contiguous()
+
+
 class RirBank:
     """Room impulse responses as one float32 [R, Kmax] device allocation, rows zero-padded, plus `length` (int32 [R]).
     Recorded responses come from `from_dir` / `from_arrays`; `simulate` makes the bank on the device from random shoe-box
@@ -886,6 +955,19 @@ without `sources`), then the paths.  rir_index / rir_len are the [B, P] and src_
 of Engine.scene_path.  Draw and SceneDraw keep their fields: a mixer without motion never makes a PathDraw."""
 
 
+# DynamicMixer(dynamics=...): the float64 [B, 6] table of Engine.dynamics the batch went through, as `last_draw.dynamics`.
+# It is an attribute beside the fields, not one of them: the draws keep their fields, their order and their length.
+Draw.dynamics = SceneDraw.dynamics = PathDraw.dynamics = None
+_DYNAMICS_DRAWS = {cls: type(cls.__name__, (cls,), {"__doc__": cls.__doc__}) for cls in (Draw, SceneDraw, PathDraw)}
+
+
+def _with_dynamics(d, table: torch.Tensor):
+    """The draw `d` with `d.dynamics = table`."""
+    out = _DYNAMICS_DRAWS[type(d)](*d)
+    out.dynamics = table
+    return out
+
+
 class _Paths(NamedTuple):
     """The sampler's part of a PathDraw, before the responses are simulated: the tables and every waypoint's n_taps."""
     P: int
@@ -932,6 +1014,18 @@ class DynamicMixer:
     `target` through the row's first n_shared sections, without clipping: the model is then not asked to undo the
     microphone or to extend the bandwidth.  The mixer's peak guard (`peak`) acts BEFORE the channel, so a boosting
     equaliser can exceed it; that is what the clip is for.
+
+    `dynamics` (a DynamicsSampler): a gain control in the recording device - compressor, limiter, AGC (Engine.dynamics /
+    cmgan_dynamics) - between the mix and the channel, whose clipping stays the last thing that happens to the signal.
+    With None nothing is drawn or run and the outputs, `last_draw` and every generator state are what they are without
+    the argument.  With a sampler, a processor per row is drawn after every other draw, from the sampler's own generator;
+    its threshold is relative to max |noisy| of the row as the mix left it, and the table the kernels got stays readable
+    as `last_draw.dynamics` (float64 [B, 6]; an attribute beside the draw's fields) and the largest gain reduction per row
+    as `mixer.last_dynamics` (float64 [B], dB).  `dynamics_on="noisy"` (the default) processes `noisy` alone: the model is
+    asked to undo the gain control too.  `dynamics_on="both"` first applies the gain that `noisy` drives to `target`
+    (key=noisy), then processes `noisy`: the target carries the same gain trajectory and the task stays denoising.  A
+    make-up gain can lift a row above `peak`; such a row's `noisy` and `target` are then scaled by peak / max |noisy|,
+    the rule of Engine.mix's peak guard (every other row by exactly 1).
 
     `speed=(lo, hi)` with 1/4 <= lo <= hi <= 4: speed perturbation (Engine.warp / cmgan_warp), the one stage that changes
     the talker: tempo and pitch move together.  With None (the default) nothing is drawn or run and the outputs,
@@ -1021,7 +1115,8 @@ class DynamicMixer:
                  speed_zeros: int = 24, speed_rolloff: float = 0.95, sources=None, source_bank: Optional[NoiseBank] = None,
                  source_snr_db=(0.0, 20.0), dry_noise: bool = True, tempo=None, p_tempo: float = 1.0, pitch=None,
                  p_pitch: float = 1.0, stretch_hop: int = 256, stretch_search: int = 160, room_stats: bool = False,
-                 motion=None, p_motion: float = 1.0, motion_hop_ms: float = 250.0, source_motion=None):
+                 motion=None, p_motion: float = 1.0, motion_hop_ms: float = 250.0, source_motion=None,
+                 dynamics: Optional[DynamicsSampler] = None, dynamics_on: str = "noisy"):
         if sources is not None:
             given, counts = sources, "(low, high) whole numbers with 0 <= low <= high and 1 <= high <= 4"
             sources = _pair("sources", given, 0, 4, counts, "None or (low, high)", whole=True)
@@ -1116,6 +1211,13 @@ class DynamicMixer:
                     or not 1 <= round(motion_hop_ms * sample_rate / 1000.0) <= SCENE_MAX_HOP:
                 raise ValueError(f"motion_hop_ms must give a hop of 1 .. 2^30 samples, got {motion_hop_ms} ms at {sample_rate} Hz")
             self.motion_hop = int(round(motion_hop_ms * sample_rate / 1000.0))
+        # ---- dynamics
+        if dynamics_on not in ("noisy", "both"):
+            raise ValueError(f"dynamics_on must be 'noisy' or 'both', got {dynamics_on!r}")
+        if dynamics is not None and not isinstance(dynamics, DynamicsSampler):
+            raise TypeError(f"dynamics must be a DynamicsSampler or None, got {type(dynamics).__name__}")
+        self.dynamics, self.dynamics_on = dynamics, dynamics_on
+        self.last_dynamics: Optional[torch.Tensor] = None   # dynamics=...: the float64 [B] largest gain reduction per row, dB
 
     def waypoints(self, N: int) -> int:
         """P = 1 + ceil((N - 1) / H): the waypoints a batch of N samples needs; more than 64 is refused."""
@@ -1389,9 +1491,12 @@ class DynamicMixer:
         s = self.last_stretch = self.draw_stretch(B, d.speed)
         if paths is not None:                                     # who moves: the last draw of all
             d = self.last_draw = d._replace(n_path=self._draw_moving(B, paths))
+        dyn = None if self.dynamics is None else self.dynamics.draw(B, self.sample_rate, device=self.engine.device)
         clean = self._perturb(d, s, clean)
         shift, clean = self._level(d, clean)
         noisy, target, info = self._mix(d, clean, rir, shift)
+        if dyn is not None:
+            d = self.last_draw = self._dynamics(d, dyn, noisy, target)
         self._channel(d, noisy, target)
         return target, noisy, info
 
@@ -1454,6 +1559,19 @@ class DynamicMixer:
         dry = (self.noise_bank.data, d.noise_start, d.noise_len, d.noise_off, snr) if self.dry_noise else (None,) * 5
         return self.engine.scene(clean, *dry, d.n_src, self.source_bank.data, d.src_start, d.src_len, d.src_off, src_snr,
                                  bank, d.rir_index, d.rir_len, d.src_rir_index, d.src_rir_len, peak=self.peak, early=early)
+
+    def _dynamics(self, d: Draw, drawn: torch.Tensor, noisy: torch.Tensor, target: torch.Tensor):
+        """The gain control, in place: on noisy, and with dynamics_on="both" the gain that noisy drives on target first;
+        then the peak guard's rule once more, one factor for both.  Returns d with the table as `d.dynamics`."""
+        table = self.dynamics.table(drawn, noisy)
+        if self.dynamics_on == "both":
+            self.engine.dynamics(target, table, key=noisy, out=target)
+        _, _, self.last_dynamics = self.engine.dynamics(noisy, table, out=noisy, info=True)
+        top = noisy.abs().amax(dim=1)
+        scale = torch.where(top > self.peak, self.peak / top, torch.ones_like(top))[:, None]
+        noisy.mul_(scale)
+        target.mul_(scale)
+        return _with_dynamics(d, table)
 
     def _channel(self, d: Draw, noisy: torch.Tensor, target: torch.Tensor) -> None:
         """The recording channel, in place: on noisy, and with channel_on="both" the shared sections on target."""

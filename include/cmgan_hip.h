@@ -39,7 +39,7 @@ extern "C" {
 #define CMGAN_E_WORKSPACE   -5   /* workspace too small or misaligned              */
 #define CMGAN_E_HIP         -6   /* a HIP runtime call failed (see last_error)     */
 
-#define CMGAN_ABI_VERSION 19
+#define CMGAN_ABI_VERSION 20
 
 typedef struct cmgan_handle cmgan_handle;
 
@@ -1088,6 +1088,46 @@ size_t cmgan_channel_workspace_bytes(int B, int L, int S);
 int cmgan_channel(cmgan_handle* h, const float* x_dev, int B, int L, long long ldx, const int* lengths_dev,
                   const double* sos_dev, const int* n_sections_dev, int S, const double* clip_dev, float* y_dev,
                   long long ldy, int* status_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- Dynamics: compressor, limiter, automatic gain control (the reference has no augmentation, as above) ---------------
+ * Per row a feed-forward gain control in the log domain, the level detector after the gain computer, with the smooth
+ * branching peak detector (Giannoulis, Massberg and Reiss, JAES 60 (6), 2012), for B rows wav_dev[b * ldw + i] of float32
+ * samples, written to out_dev[b * ldo + i].  The level is taken from key_dev[b * ldk + i] (NULL: from wav itself).  All
+ * per-row tables are in DEVICE memory and read by the kernels only: lengths_dev int32 [B] (NULL: n = L), dyn_dev float64
+ * [B][6] = (thr_db, slope, knee_db, a_att, a_rel, makeup_db) with slope = 1 - 1 / ratio (1: a limiter) and a = exp(-1 /
+ * (t fs)) for a time constant of t seconds; status_dev int32 [B] and peak_reduction_db_dev float64 [B] (each may be NULL).
+ * In float64, for row b with n = lengths[b] and the key row k:
+ *   xg   = 20 log10(max(|k_i|, 1e-6))                   (a key sample that is not finite counts as silence: c_i = 0)
+ *   c_i  = 0                                            if 2 (xg - thr) < -knee
+ *        = slope t (t / (2 knee)), t = xg - thr + knee / 2   if 2 |xg - thr| <= knee and knee > 0
+ *        = slope (xg - thr)                             otherwise                     (the wanted reduction in dB, >= 0)
+ *   y_i  = a_att y_(i-1) + (1 - a_att) c_i  if c_i > y_(i-1)  else  a_rel y_(i-1) + (1 - a_rel) c_i,      y_(-1) = 0
+ *   out_i = wav_i 10^((makeup - y_i) / 20), rounded ONCE to float32, for i < n;  out[b, i] = 0 for n <= i < L.
+ * peak_reduction_db[b] is the largest y_i of the row (0 for an empty or invalid row).  Samples at i >= n are never read.
+ * A row is INVALID - status 1 (else 0) and L zeros - when an entry of its table is not finite, slope is outside [0, 1],
+ * knee < 0, a_att or a_rel is outside [0, 1), or lengths[b] is outside [0, L].  A row with slope 0, or with every sample
+ * under the knee, and makeup 0 is copied bit for bit; a non-finite wav sample stays at its own index and touches no other.
+ * Method.  With a_att <= a_rel a step is y -> max(a_att y + (1 - a_att) c_i, a_rel y + (1 - a_rel) c_i), two increasing
+ * affine maps (with a_att > a_rel the same on -y and -c).  Increasing maps distribute over max, so a tile of T =
+ * cmgan_dynamics_tile() steps is y -> max over k = 0 .. T of (a_att^k a_rel^(T-k) y + b_k), one offset per number of attack
+ * steps, and the offsets follow from a (max, +) recurrence over the tile.  A wave owns a tile and a lane an offset; the
+ * tiles' maps are folded per row in ascending order (a serial chain of n / T steps, a fused multiply-add per lane and a
+ * wave maximum each), and every tile is then run from its entry state in the branching form above.  Float64 on the VALU;
+ * no atomics; the same bits come out from run to run, and row b's bits depend neither on B, nor on the other rows, nor on
+ * the strides, nor on L beyond n.  Against the serial loop the detector differs by float64 roundings that depend on T.
+ * out_dev == wav_dev with ldo == ldw (in place) is allowed, and so is out_dev == key_dev with ldo == ldk; any other
+ * intersection of out's span [out, out + (B-1) ldo + L) with wav's or key's is CMGAN_E_BADARG.  Checked before any launch
+ * and before the handle is looked at (the message of a call with h == NULL is read with cmgan_last_error(NULL)): null wav /
+ * dyn / out, misaligned pointers (4 bytes for float32 / int32, 8 for float64), 1 <= B <= 65535, 1 <= L <= 2^31 - 1 - 64 x
+ * cmgan_dynamics_tile(), ldw >= L, ldo >= L, ldk >= L with a key, the overlaps above, a workspace that is null, not
+ * 256-byte aligned or smaller than cmgan_dynamics_workspace_bytes(B, L) (0 for an unsupported shape; non-decreasing in B
+ * and L); each is CMGAN_E_BADARG.  Three launches, four with peak_reduction_db; no synchronisation, no allocation;
+ * graph-capturable, and a replay reads the current contents of every device table.                                     */
+int cmgan_dynamics_tile(void);
+size_t cmgan_dynamics_workspace_bytes(int B, int L);
+int cmgan_dynamics(cmgan_handle* h, const float* wav_dev, int B, int L, long long ldw, const float* key_dev, long long ldk,
+                   const int* lengths_dev, const double* dyn_dev, float* out_dev, long long ldo, int* status_dev,
+                   double* peak_reduction_db_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---- Speed perturbation (the reference has no counterpart: its data path replays fixed pairs, src/data/dataloader.py) ---
  * Every row of a [B, L] float32 batch x_dev[b * ldx + k] is resampled by its OWN rate into N outputs y_dev[b * ldy + i]:
