@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CMGAN_HIP_LIB") or os.path.join(HERE, "lib", "libcmgan_hip.so")
 
 OK = 0
-ABI_VERSION = 20
+ABI_VERSION = 21
 MFMA_F32, MFMA_F16X3, MFMA_F16X1, MFMA_F16MIX = 0, 1, 2, 3
 # CMGAN_MIX_* bits of Config.single_mask (include/cmgan_hip.h)
 MIX = {"conv": 1, "ff1": 2, "ff2": 4, "qkv": 8, "attn": 16, "pw1": 32, "dwpw2": 64}
@@ -251,6 +251,13 @@ SIGNATURES = {
     "cmgan_dynamics_workspace_bytes": (c_size_t, [c_int, c_int]),
     "cmgan_dynamics": (c_int, [c_void_p, c_void_p, c_int, c_int, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p,
                                c_longlong, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "cmgan_noise_tile": (c_int, []),
+    "cmgan_noise_max_filter": (c_int, []),
+    "cmgan_noise_max_tones": (c_int, []),
+    "cmgan_noise_max_points": (c_int, []),
+    "cmgan_noise_workspace_bytes": (c_size_t, [c_int]),
+    "cmgan_noise": (c_int, [c_void_p, c_void_p, c_int, c_int, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                            c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "cmgan_warp_tile": (c_int, []),
     "cmgan_warp_max_rate": (c_double, []),
     "cmgan_warp_max_zeros": (c_int, []),

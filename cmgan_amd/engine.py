@@ -550,6 +550,62 @@ def check_dynamics_args(device, wav, dyn, key=None, lengths=None, out=None):
     return B, L
 
 
+NOISE_TILE = 256              # outputs per block of cmgan_noise (= cmgan_noise_tile())
+NOISE_MAX_FILTER = 1023       # taps of a row's colouring filter (= cmgan_noise_max_filter())
+NOISE_MAX_TONES = 8           # tones per row (= cmgan_noise_max_tones())
+NOISE_MAX_POINTS = 4096       # envelope points per row (= cmgan_noise_max_points())
+NOISE_MAX_N = 2 ** 31 - 1 - NOISE_TILE
+NOISE_MAX_INDEX = 2 ** 40     # start + n may not exceed it
+
+
+def noise_workspace_bytes(N: int) -> int:
+    """cmgan_noise_workspace_bytes: one int32 [N] of verdicts, rounded up to 256 bytes; 0 for an N the kernels do not take."""
+    return (N * 4 + 255) & ~255 if 1 <= N <= 65535 else 0
+
+
+def check_noise_args(device, seed, fir, n, lengths=None, start=None, env=None, env_hop=None, tones=None, n_tones=None,
+                     impulse=None, out=None):
+    """Argument rules of Engine.noise (shapes, dtypes, devices and host scalars; pure host code).  Returns (N, K, NF, P, H,
+    M): P = H = 0 without an envelope, M = 0 without tones."""
+    tensor_arg(seed, "seed", torch.int64, device, "[N] with 1 <= N <= 65535", lambda t: t.dim() == 1 and 1 <= t.size(0) <= 65535)
+    N = int(seed.size(0))
+    tensor_arg(fir, "fir", torch.float64, device, f"[{N}, NF] with 1 <= NF <= {NOISE_MAX_FILTER}",
+               lambda t: t.dim() == 2 and t.size(0) == N and 1 <= t.size(1) <= NOISE_MAX_FILTER)
+    if not _whole_in(n, 0, NOISE_MAX_N):
+        raise ValueError(f"n must be a length in [0, 2^31 - 1 - {NOISE_TILE}], got {n}")
+    K = int(n)
+    row = lambda t: tuple(t.shape) == (N,)
+    if lengths is not None:
+        tensor_arg(lengths, "lengths", torch.int32, device, f"[{N}]", row)
+    if start is not None:
+        tensor_arg(start, "start", torch.int64, device, f"[{N}]", row)
+    P = H = 0
+    if env is not None:
+        tensor_arg(env, "env", torch.float64, device, f"[{N}, P] with 1 <= P <= {NOISE_MAX_POINTS}",
+                   lambda t: t.dim() == 2 and t.size(0) == N and 1 <= t.size(1) <= NOISE_MAX_POINTS)
+        if env_hop is None or not _whole_in(env_hop, 1, 2 ** 31 - 1):
+            raise ValueError(f"env_hop must be the samples between two points of env, a whole number in [1, 2^31 - 1], got {env_hop}")
+        P, H = int(env.size(1)), int(env_hop)
+    elif env_hop is not None:
+        raise ValueError("env_hop given without env")
+    M = 0
+    if tones is not None:
+        tensor_arg(tones, "tones", torch.float64, device, f"[{N}, M, 3] with 0 <= M <= {NOISE_MAX_TONES}",
+                   lambda t: t.dim() == 3 and t.size(0) == N and t.size(1) <= NOISE_MAX_TONES and t.size(2) == 3)
+        M = int(tones.size(1))
+        if n_tones is not None:
+            tensor_arg(n_tones, "n_tones", torch.int32, device, f"[{N}]", row)
+    elif n_tones is not None:
+        raise ValueError("n_tones given without tones")
+    if impulse is not None:
+        tensor_arg(impulse, "impulse", torch.float64, device, f"[{N}, 2]", lambda t: tuple(t.shape) == (N, 2))
+    if out is not None:
+        tensor_arg(out, "out", torch.float32, device, f"[{N}, {K}]", lambda t: tuple(t.shape) == (N, K), contiguous=False)
+        if K > 0 and not _row_stride_ok(out, N, K):
+            raise ValueError(f"out: rows must be contiguous and at least n apart, got strides {tuple(out.stride())}")
+    return N, K, int(fir.size(1)), P, H, M
+
+
 WARP_TILE = 256               # outputs per block of cmgan_warp (= cmgan_warp_tile())
 WARP_MAX_RATE = 4.0           # rates in [1 / 4, 4] (= cmgan_warp_max_rate())
 WARP_ZEROS = (4, 64)          # zero crossings on either side of the filter's centre (64 = cmgan_warp_max_zeros())
@@ -656,7 +712,7 @@ class Engine:
             msg = self.lib.cmgan_last_error(None)
             raise _lib.CmganError(rc, msg.decode() if msg else "?")
         #: grow-only uint8 workspaces by name (_grow): "main", "branched" (enhance_graphed(branches > 1)), "conformer",
-        #: "metrics", "mix", "scene", "rir", "rir_bands", "rir_dir", "rir_bands_dir", "level", "channel", "dynamics" and ("resample", fs_in,
+        #: "metrics", "mix", "scene", "rir", "rir_bands", "rir_dir", "rir_bands_dir", "level", "channel", "dynamics", "noise" and ("resample", fs_in,
         #: fs_out), the rate pair's tap table
         self._wss: dict = {}
         self._graphs: dict = {}          # enhance_graphed: input shape -> (graph, in, out, token)
@@ -1546,6 +1602,41 @@ class Engine:
                    0 if key is None else (key.stride(0) if B > 1 else L), lengths, dyn, out, out.stride(0) if B > 1 else L,
                    st, pk, ws, ws.numel())
         return (out, st, pk) if info else out
+
+    # ---- synthetic noise -------------------------------------------------------------
+    @_on_device
+    def noise(self, seed: torch.Tensor, fir: torch.Tensor, n: int, lengths: Optional[torch.Tensor] = None,
+              start: Optional[torch.Tensor] = None, env: Optional[torch.Tensor] = None, env_hop: Optional[int] = None,
+              tones: Optional[torch.Tensor] = None, n_tones: Optional[torch.Tensor] = None,
+              impulse: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, info: bool = False):
+        """Synthetic noise on the GPU (cmgan_noise, include/cmgan_hip.h): per row a unit-variance Philox noise - with clicks -
+        coloured by the row's own FIR filter, under a piecewise-linear envelope, plus a sum of tones (a hum).
+
+        seed int64 [N], one noise key per row; fir float64 [N, NF], 1 <= NF <= 1023 (cmgan_amd.mixing.noise_fir designs it
+        from a magnitude); n: the samples per row; lengths int32 [N] (None: n; columns from a row's length on come out as
+        zeros); start int64 [N]: the absolute index of a row's first sample (None: 0); env float64 [N, P], P <= 4096, the
+        gain at points `env_hop` samples apart, interpolated linearly, the last point holding (None: 1); tones float64
+        [N, M, 3] = (cycles per sample in [0, 0.5], amplitude, phase in cycles), M <= 8, of which row r uses the first
+        n_tones[r] (int32 [N]; None: all M); impulse float64 [N, 2] = (thr, amplitude): an index carries a click, uniform
+        in +-amplitude, with probability thr / 2^32, thr a whole number in [0, 2^32) (None: no clicks).  All on this
+        Engine's device and read by the kernels only.  `out` float32 [N, n] (rows contiguous, any row stride >= n) is
+        written in place of a new tensor.  Returns the float32 [N, n] result: float64 arithmetic with one rounding to
+        float32; info=True adds the int32 [N] status, 1 for the rows that are invalid (a non-finite table entry, a length
+        outside [0, n], n_tones outside [0, M], a frequency outside [0, 0.5], a thr that is no whole number in [0, 2^32),
+        start < 0 or start + n > 2^40) and come out as zeros.  Every sample is a pure function of the row's tables and
+        its absolute index: a row made whole and the same row made in pieces with `start` advanced have the same bits.
+        Bit-reproducible, row-independent, no synchronisation, graph-capturable after one call at the shape."""
+        N, K, NF, P, H, M = check_noise_args(self.device, seed, fir, n, lengths, start, env, env_hop, tones, n_tones, impulse,
+                                             out)
+        ws = self._grow("noise", int(self.lib.cmgan_noise_workspace_bytes(N)), f"{N} rows are outside what cmgan_noise supports")
+        if out is None:
+            out = torch.empty(N, K, dtype=torch.float32, device=self.device)
+        st = torch.empty(N, dtype=torch.int32, device=self.device)
+        if M == 0:
+            tones = n_tones = None
+        self._call("cmgan_noise", out if K > 0 else None, N, K, out.stride(0) if N > 1 and K > 0 else K, seed, start, lengths, fir,
+                   NF, env, P, H, tones, n_tones, M, impulse, st, ws, ws.numel())
+        return (out, st) if info else out
 
     # ---- speed perturbation ---------------------------------------------------------
     def _out_and_info(self, B: int, L: int, N: Optional[int], out: Optional[torch.Tensor], info: bool, n_info: int):

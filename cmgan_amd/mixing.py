@@ -26,6 +26,10 @@ takes - with `clean` the training target (the dry clip, or the clip with its ear
     # talkers that walk: a path of responses per row, cross-faded by emission time (Engine.scene_path / cmgan_scene_path);
     # with tail_ms the 9 responses per row of a 2 s batch cost little beside the mix itself
     mixer = DynamicMixer(engine, noise, rooms=RoomSampler(tail_ms=80.0), rir_seconds=1.0, motion=(0.5, 1.5), p_motion=0.5)
+    # no recorded noise at all: every row of every batch a fresh synthetic noise - spectrum, modulation, hum and clicks of
+    # its own (Engine.noise / cmgan_noise); or a fixed bank of it
+    mixer = DynamicMixer(engine, None, rirs, noise=NoiseSampler(slope_db=(-9, 3), p_hum=0.2, p_clicks=0.1))
+    noise = NoiseBank.synthesize(engine, NoiseSampler(), items=256, seconds=10.0)
     # the recording channel: a random equaliser, a band limit and clipping per row (Engine.channel / cmgan_channel)
     mixer = DynamicMixer(engine, noise, rirs, channel=ChannelSampler(p_bandlimit=0.2, p_clip=0.1))
     clean = torch.utils.data.DataLoader(clean_only("data/train", 32000), batch_size=32, pin_memory=True, drop_last=True)
@@ -53,7 +57,7 @@ import torch.utils.data
 from .data import _natural_key, fit_length, read_wav
 from .engine import RIR_TAIL_MAX_WINDOW, SCENE_MAX_HOP, SCENE_MAX_WAYPOINTS, STRETCH_HOP, STRETCH_SEARCH, RirStats, RirTail, _whole_in
 
-__all__ = ["NoiseBank", "RirBank", "RoomSampler", "sabine_beta", "octave_filterbank", "DynamicMixer", "MixingLoader", "CleanDataset",
+__all__ = ["NoiseBank", "NoiseSampler", "NoiseDraw", "noise_fir", "power_law_magnitude", "RirBank", "RoomSampler", "sabine_beta", "octave_filterbank", "DynamicMixer", "MixingLoader", "CleanDataset",
            "clean_only", "Draw", "SceneDraw", "tile", "ChannelSampler", "biquad_peaking", "biquad_low_shelf", "biquad_high_shelf",
            "biquad_lowpass", "biquad_highpass", "butter_lowpass_sos", "warp_len", "stretch_len", "StretchDraw", "TailDraw", "PathDraw"]
 
@@ -175,7 +179,7 @@ def _read_dir(path: str, sample_rate: int, engine) -> list:
 
 class NoiseBank:
     """Noise recordings of any lengths as ONE flat float32 device allocation plus index tables: `start` / `length`
-    (int64 [items]) say where item k lies in `data`."""
+    (int64 [items]) say where item k lies in `data`.  `synthesize` makes the items on the device instead (Engine.noise)."""
 
     def __init__(self, data: torch.Tensor, start: torch.Tensor, length: torch.Tensor):
         self.data, self.start, self.length = data, start, length
@@ -201,6 +205,36 @@ class NoiseBank:
     def from_dir(cls, path: str, sample_rate: int, engine) -> "NoiseBank":
         """Every .wav under `path` (natural order); files at another rate go through Engine.resample."""
         return cls.from_arrays(_read_dir(path, sample_rate, engine), device=engine.device)
+
+    draw = None                                   # synthesize: the NoiseDraw the items were made from
+
+    @classmethod
+    def synthesize(cls, engine, sampler: "NoiseSampler", items: int, seconds: float, sample_rate: int = 16000,
+                   out: Optional[torch.Tensor] = None) -> "NoiseBank":
+        """`items` noises of `seconds` each, drawn by `sampler` and made on the device by ONE Engine.noise call (cmgan_noise)
+        into a float32 [items, K] allocation that IS the bank's flat `data`: item k starts at k K, nothing is copied.  The
+        draw is kept as `draw`.  `out`: a contiguous float32 [items, K] tensor to write instead of a new one."""
+        if not isinstance(sampler, NoiseSampler):
+            raise TypeError(f"sampler must be a NoiseSampler, got {type(sampler).__name__}")
+        if not _whole_in(items, 1, 65535):
+            raise ValueError(f"items must be a whole number in [1, 65535], got {items}")
+        K = int(round(float(seconds) * sample_rate))
+        if K < 1:
+            raise ValueError(f"seconds must give at least one sample, got {seconds} s at {sample_rate} Hz")
+        return cls._synthesize(engine, sampler, int(items), K, sample_rate, out)
+
+    @classmethod
+    def _synthesize(cls, engine, sampler: "NoiseSampler", items: int, K: int, sample_rate: int, out: Optional[torch.Tensor]):
+        """`synthesize` for items of K samples."""
+        if out is not None and not (isinstance(out, torch.Tensor) and tuple(out.shape) == (items, K) and out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous float32 [{items}, {K}] tensor")
+        d = sampler.draw(items, K, sample_rate, device=engine.device)
+        rows = engine.noise(d.seed, d.fir, K, env=d.env, env_hop=sampler.hop(sample_rate), tones=d.tones, n_tones=d.n_tones,
+                            impulse=d.impulse, out=out)
+        index = torch.arange(items, dtype=torch.int64).to(engine.device, non_blocking=True)
+        bank = cls(rows.reshape(-1), index * K, torch.full_like(index, K))
+        bank.draw = d
+        return bank
 
 
 def sabine_beta(rt60, dims) -> torch.Tensor:
@@ -800,6 +834,168 @@ class DynamicsSampler:
         return torch.stack([thr, slope, knee, a_att, a_rel, makeup], dim=1).contiguous()
 
 
+# ---- synthetic noise: the colouring filter of Engine.noise from a magnitude, and a sampler of its tables ----------------
+NOISE_GRID = 4096             # points of the frequency grid the magnitudes are given on: [N, NOISE_GRID / 2 + 1]
+NOISE_MAX_TAPS = 1023         # = cmgan_noise_max_filter()
+NOISE_MAX_TONES = 8           # = cmgan_noise_max_tones()
+NOISE_MAX_POINTS = 4096       # = cmgan_noise_max_points()
+
+
+def power_law_magnitude(slope_db_per_octave, fs, f_lo: float = 62.5, band=None) -> torch.Tensor:
+    """The magnitude (max(f, f_lo) / 1 kHz)^(slope / 6.0206) on the grid of `noise_fir`, f = i fs / 4096 for i = 0 .. 2048:
+    float64 [..., 2049] for a slope of shape [...], in dB per octave of AMPLITUDE - -3 is pink, -6 brown, 0 white.  Below
+    f_lo the law is held, so that a falling one stays finite at DC.  band=(lo, hi) in Hz (floats or tensors of the slope's
+    shape) multiplies by raised-cosine edges on the octave scale, half an octave wide and centred on lo and hi.  Plain
+    float64 tensor arithmetic on the device of its arguments, like the biquad designs."""
+    slope = _f64(slope_db_per_octave)
+    fs, f_lo = float(fs), float(f_lo)
+    if not (0.0 < fs < math.inf and 0.0 < f_lo < math.inf):
+        raise ValueError(f"fs and f_lo must be positive and finite, got fs = {fs}, f_lo = {f_lo}")
+    f = torch.arange(NOISE_GRID // 2 + 1, dtype=torch.float64).to(slope.device, non_blocking=True) * (fs / NOISE_GRID)
+    mag = torch.exp2(torch.log2(torch.clamp(f, min=f_lo) / 1000.0) * (slope[..., None] / (20.0 * math.log10(2.0))))
+    if band is not None:
+        lo, hi = (_f64(v, slope)[..., None] for v in band)
+        u = torch.log2(torch.clamp(f, min=1e-300))               # (-996 at DC: below every lower edge)
+        rise = torch.clamp((u - torch.log2(lo) + 0.25) / 0.5, 0.0, 1.0)
+        fall = torch.clamp((u - torch.log2(hi) + 0.25) / 0.5, 0.0, 1.0)
+        mag = mag * (0.5 - 0.5 * torch.cos(math.pi * rise)) * (0.5 + 0.5 * torch.cos(math.pi * fall))
+    return mag
+
+
+def noise_fir(magnitude: torch.Tensor, n_taps: int) -> torch.Tensor:
+    """The colouring filter of Engine.noise by frequency sampling: float64 [N, n_taps] from `magnitude`, float64 [N, 2049]
+    on the 4096-point grid (bin i at i fs / 4096).  The zero-phase inverse real FFT is centred at (n_taps - 1) // 2, cut to
+    n_taps taps, multiplied by the Hann window 0.5 - 0.5 cos(2 pi (i + 1) / (n_taps + 1)) and normalised to sum h^2 = 1, so
+    that the filtered unit-variance noise has unit variance whatever its colour.  A row whose taps are all zero stays
+    zero.  Plain float64 tensor arithmetic on the device of `magnitude`."""
+    if not isinstance(magnitude, torch.Tensor) or magnitude.dtype != torch.float64 or magnitude.dim() != 2 \
+            or magnitude.size(1) != NOISE_GRID // 2 + 1:
+        raise ValueError(f"magnitude must be a float64 [N, {NOISE_GRID // 2 + 1}] tensor on the {NOISE_GRID}-point grid")
+    if not _whole_in(n_taps, 1, NOISE_MAX_TAPS):
+        raise ValueError(f"n_taps must be a whole number in [1, {NOISE_MAX_TAPS}], got {n_taps}")
+    NF = int(n_taps)
+    j = torch.arange(NF, dtype=torch.int64).to(magnitude.device, non_blocking=True)
+    h = torch.fft.irfft(magnitude.to(torch.complex128), n=NOISE_GRID, dim=1)[:, (j - (NF - 1) // 2) % NOISE_GRID]
+    h = h * (0.5 - 0.5 * torch.cos(2.0 * math.pi * (j + 1).to(torch.float64) / (NF + 1)))
+    norm = torch.sqrt((h * h).sum(dim=1, keepdim=True))
+    return (h / torch.where(norm > 0, norm, torch.ones_like(norm))).contiguous()
+
+
+class NoiseDraw(NamedTuple):
+    """NoiseSampler.draw: the tables of Engine.noise for N rows, all on the device.  seed int64 [N]; fir float64 [N,
+    n_taps]; env float64 [N, P], the gain at points `NoiseSampler.hop(fs)` samples apart; tones float64 [N, M, 3] and n_tones
+    int32 [N] (None with p_hum = 0); impulse float64 [N, 2] (None with p_clicks = 0)."""
+    seed: torch.Tensor
+    fir: torch.Tensor
+    env: torch.Tensor
+    tones: Optional[torch.Tensor]
+    n_tones: Optional[torch.Tensor]
+    impulse: Optional[torch.Tensor]
+
+
+class NoiseSampler:
+    """Random noises for Engine.noise: `draw(N, n, fs, device)` -> a NoiseDraw for N rows of n samples.
+
+    Per row: a spectrum - a power law with the slope uniform in `slope_db` (dB per octave: -3 pink, -6 brown, 0 white),
+    with `band_hz` = (lo, hi) also a band whose two edges are log-uniform in its lower and upper half on the octave
+    scale - designed into `n_taps` taps by `noise_fir`; an envelope 10^(d(t) / 20) at points `env_hop_ms` apart, d the sum
+    of three sinusoids with rates log-uniform in `mod_rate_hz` and uniform phases, scaled so that the largest |d| of the
+    row's points is a depth uniform in `mod_depth_db`; with probability `p_hum` a hum - a fundamental chosen from `hum_hz`
+    with equal probability, a number of harmonics uniform in `hum_harmonics` (whole numbers, at most 8; those above fs / 2
+    are dropped), each 6 dB below the one before, the fundamental's RMS uniform in `hum_db` relative to the unit-variance
+    noise, phases uniform; with probability `p_clicks` clicks - `click_rate_hz` (log-uniform) of them per second on
+    average, their amplitude uniform in +-10^(click_db / 20), `click_db` uniform and relative to the noise's RMS; they pass
+    the row's filter like the noise.  Everything is drawn from `generator` (None: the device's default one) on the
+    device with tensor arithmetic: no host synchronisation.  No row of a draw is invalid."""
+
+    def __init__(self, slope_db=(-9.0, 3.0), band_hz=None, mod_depth_db=(0.0, 12.0), mod_rate_hz=(0.5, 8.0), p_hum: float = 0.2,
+                 hum_hz=(50.0, 60.0), hum_db=(-30.0, -10.0), hum_harmonics=(1, 5), p_clicks: float = 0.1,
+                 click_rate_hz=(1.0, 20.0), click_db=(10.0, 30.0), n_taps: int = 255, env_hop_ms: float = 20.0,
+                 generator: Optional[torch.Generator] = None):
+        finite = "(low, high) with finite low <= high"
+        self.slope_db = _pair("slope_db", slope_db, -math.inf, math.inf, finite, closed=False)
+        self.band_hz = None if band_hz is None else _positive_pair("band_hz", band_hz, "None or (low, high)")
+        self.mod_depth_db = _pair("mod_depth_db", mod_depth_db, 0.0, math.inf, "(low, high) with 0 <= low <= high < inf")
+        if self.mod_depth_db[1] == math.inf:
+            raise ValueError(f"mod_depth_db must be (low, high) with 0 <= low <= high < inf, got {mod_depth_db}")
+        self.mod_rate_hz = _positive_pair("mod_rate_hz", mod_rate_hz)
+        self.p_hum, self.p_clicks = _probability("p_hum", p_hum), _probability("p_clicks", p_clicks)
+        try:
+            self.hum_hz = tuple(float(f) for f in hum_hz)
+        except (TypeError, ValueError):
+            self.hum_hz = ()
+        if not self.hum_hz or not all(0.0 < f < math.inf for f in self.hum_hz):
+            raise ValueError(f"hum_hz must be one or more positive frequencies to choose from, got {hum_hz}")
+        self.hum_db = _pair("hum_db", hum_db, -math.inf, math.inf, finite, closed=False)
+        counts = f"(low, high) whole numbers with 1 <= low <= high <= {NOISE_MAX_TONES}"
+        self.hum_harmonics = _pair("hum_harmonics", hum_harmonics, 1, NOISE_MAX_TONES, counts, whole=True)
+        self.click_rate_hz = _positive_pair("click_rate_hz", click_rate_hz)
+        self.click_db = _pair("click_db", click_db, -math.inf, math.inf, finite, closed=False)
+        if not _whole_in(n_taps, 1, NOISE_MAX_TAPS):
+            raise ValueError(f"n_taps must be a whole number in [1, {NOISE_MAX_TAPS}], got {n_taps}")
+        if isinstance(env_hop_ms, bool) or not isinstance(env_hop_ms, (int, float)) or not 0.0 < env_hop_ms < math.inf:
+            raise ValueError(f"env_hop_ms must be a positive, finite number of milliseconds, got {env_hop_ms}")
+        self.n_taps, self.env_hop_ms, self.generator = int(n_taps), float(env_hop_ms), generator
+
+    def hop(self, fs: int) -> int:
+        """H, the samples between two points of the envelope: env_hop_ms at fs, rounded, at least 1 (Engine.noise's env_hop)."""
+        return max(1, int(round(self.env_hop_ms * float(fs) / 1000.0)))
+
+    def points(self, n: int, fs: int) -> int:
+        """P, the envelope points that n samples from index 0 reach: 2 + (n - 1) div H; more than 4096 is refused."""
+        P = 2 + max(int(n) - 1, 0) // self.hop(fs)
+        if P > NOISE_MAX_POINTS:
+            raise ValueError(f"{n} samples with an envelope point every {self.hop(fs)} need {P} points; up to {NOISE_MAX_POINTS} "
+                             f"are supported: raise env_hop_ms")
+        return P
+
+    def draw(self, N: int, n: int, fs: int, device=None) -> NoiseDraw:
+        gen = self.generator
+        device = torch.device(device) if device is not None else (gen.device if gen is not None else torch.device("cpu"))
+        fs = float(fs)
+        H, P, M = self.hop(fs), self.points(n, fs), self.hum_harmonics[1]
+        if self.band_hz is not None and not self.band_hz[1] <= 0.5 * fs:
+            raise ValueError(f"band_hz = {self.band_hz} must lie at or below fs / 2 = {0.5 * fs} Hz")
+        seed = torch.randint(0, 2 ** 63 - 1, (N,), dtype=torch.int64, generator=gen, device=device)
+        u = torch.rand(N, 17 + M, dtype=torch.float64, generator=gen, device=device)
+        uniform = lambda r, v: r[0] + (r[1] - r[0]) * v
+        log_uniform = lambda r, v: torch.exp(math.log(r[0]) + (math.log(r[1]) - math.log(r[0])) * v)
+        # ---- the spectrum
+        band = None
+        if self.band_hz is not None:
+            lo, hi = self.band_hz
+            mid = math.sqrt(lo * hi)
+            band = (log_uniform((lo, mid), u[:, 1]), log_uniform((mid, hi), u[:, 2]))
+        fir = noise_fir(power_law_magnitude(uniform(self.slope_db, u[:, 0]), fs, band=band), self.n_taps)
+        # ---- the envelope
+        t = torch.arange(P, dtype=torch.float64).to(device, non_blocking=True) * (H / fs)
+        rate, phase = log_uniform(self.mod_rate_hz, u[:, 3:6]), u[:, 6:9]
+        d = torch.sin(2.0 * math.pi * (rate[:, :, None] * t[None, None, :] + phase[:, :, None])).sum(dim=1)
+        top = d.abs().amax(dim=1, keepdim=True)
+        d = d / torch.where(top > 0, top, torch.ones_like(top)) * uniform(self.mod_depth_db, u[:, 9])[:, None]
+        env = torch.pow(10.0, d / 20.0).contiguous()
+        # ---- the hum
+        tones = n_tones = None
+        if self.p_hum > 0.0:
+            choice = torch.tensor(self.hum_hz, dtype=torch.float64).to(device, non_blocking=True)
+            f0 = choice[torch.clamp((u[:, 11] * len(self.hum_hz)).to(torch.int64), max=len(self.hum_hz) - 1)]
+            lo, hi = self.hum_harmonics
+            count = lo + torch.clamp((u[:, 12] * (hi - lo + 1)).to(torch.int64), max=hi - lo)
+            m = torch.arange(M, dtype=torch.float64).to(device, non_blocking=True)
+            nu = f0[:, None] * (m[None, :] + 1.0) / fs
+            amp = (math.sqrt(2.0) * torch.pow(10.0, uniform(self.hum_db, u[:, 13]) / 20.0))[:, None] * torch.exp2(-m)[None, :]
+            audible = (nu <= 0.5).sum(dim=1)                      # (nu rises with m: the audible harmonics come first)
+            n_tones = torch.where(u[:, 10] < self.p_hum, torch.minimum(count, audible), torch.zeros_like(count)).to(torch.int32)
+            tones = torch.stack([torch.clamp(nu, max=0.5), amp, u[:, 17:17 + M]], dim=2).contiguous()
+        # ---- the clicks
+        impulse = None
+        if self.p_clicks > 0.0:
+            thr = torch.clamp(torch.floor(log_uniform(self.click_rate_hz, u[:, 14]) / fs * 2.0 ** 32), 0.0, 2.0 ** 32 - 1.0)
+            thr = torch.where(u[:, 15] < self.p_clicks, thr, torch.zeros_like(thr))
+            impulse = torch.stack([thr, torch.pow(10.0, uniform(self.click_db, u[:, 16]) / 20.0)], dim=1).contiguous()
+        return NoiseDraw(seed, fir, env, tones, n_tones, impulse)
+
+
 class RirBank:
     """Room impulse responses as one float32 [R, Kmax] device allocation, rows zero-padded, plus `length` (int32 [R]).
     Recorded responses come from `from_dir` / `from_arrays`; `simulate` makes the bank on the device from random shoe-box
@@ -1080,6 +1276,14 @@ class DynamicMixer:
     what they are without the argument, and with True they are the same too.  An unmeasured bank, or neither a bank nor
     rooms, is refused.
 
+    `noise` (a NoiseSampler, with `noise_bank` = None): no recorded noise at all.  Every call first synthesizes B rows of the
+    length the batch will have (Engine.noise / cmgan_noise; the sampler draws from its own generator) into one persistent
+    [B, N] allocation, overwritten in place, and installs it as `noise_bank`: the item, offset and SNR draws and every
+    kernel behind them then run against it as against any bank, and `sources` without a `source_bank` takes its point
+    noises from the same rows.  The sampler's draw stays readable as `mixer.last_noise`.  `noise` and a `noise_bank`
+    together are refused, and so is neither.  With `noise=None` nothing is drawn or launched, and the outputs, `last_draw`
+    and every generator state are what they are without the argument.
+
     `rooms=RoomSampler(tail_ms=...)`: the hybrid room simulator.  The image-source calls stop at every response's junction
     (the talkers' and each located source's own) and Engine.rir_tail / cmgan_rir_tail adds a diffuse tail up to the
     response's whole length, so `rir_seconds` of a second or two stay affordable.  The tail draw (`mixer.last_tail`, a
@@ -1116,7 +1320,7 @@ class DynamicMixer:
                  source_snr_db=(0.0, 20.0), dry_noise: bool = True, tempo=None, p_tempo: float = 1.0, pitch=None,
                  p_pitch: float = 1.0, stretch_hop: int = 256, stretch_search: int = 160, room_stats: bool = False,
                  motion=None, p_motion: float = 1.0, motion_hop_ms: float = 250.0, source_motion=None,
-                 dynamics: Optional[DynamicsSampler] = None, dynamics_on: str = "noisy"):
+                 dynamics: Optional[DynamicsSampler] = None, dynamics_on: str = "noisy", noise: Optional[NoiseSampler] = None):
         if sources is not None:
             given, counts = sources, "(low, high) whole numbers with 0 <= low <= high and 1 <= high <= 4"
             sources = _pair("sources", given, 0, 4, counts, "None or (low, high)", whole=True)
@@ -1218,6 +1422,17 @@ class DynamicMixer:
             raise TypeError(f"dynamics must be a DynamicsSampler or None, got {type(dynamics).__name__}")
         self.dynamics, self.dynamics_on = dynamics, dynamics_on
         self.last_dynamics: Optional[torch.Tensor] = None   # dynamics=...: the float64 [B] largest gain reduction per row, dB
+        # ---- synthetic noise: judged last, so that every earlier error is what it was
+        if noise is not None and not isinstance(noise, NoiseSampler):
+            raise TypeError(f"noise must be a NoiseSampler or None, got {type(noise).__name__}")
+        if noise is not None and noise_bank is not None:
+            raise ValueError("give either a noise_bank or noise=NoiseSampler(...), not both")
+        if noise is None and noise_bank is None:
+            raise ValueError("the mixer needs noise: give a noise_bank, or noise=NoiseSampler(...) to synthesize it")
+        self.noise = noise
+        self.last_noise: Optional[NoiseDraw] = None         # noise=...: the draw the batch's noise rows were made from
+        self._noise_rows: Optional[torch.Tensor] = None     # noise=...: the persistent float32 [B, N] allocation behind noise_bank
+        self._own_sources = source_bank is None             # sources take their point noises from the noise bank
 
     def waypoints(self, N: int) -> int:
         """P = 1 + ceil((N - 1) / H): the waypoints a batch of N samples needs; more than 64 is refused."""
@@ -1475,8 +1690,20 @@ class DynamicMixer:
         gain = torch.sqrt(torch.pow(10.0, level_db / 10.0) / active)
         return torch.where(ok, gain, torch.ones_like(gain)).to(torch.float32)
 
+    def _synthesize(self, B: int, N: int) -> None:
+        """noise=...: B fresh rows of N samples (NoiseBank.synthesize, one Engine.noise call) into the persistent allocation,
+        overwritten in place, installed as `noise_bank` - and as `source_bank` where the sources share it."""
+        if self._noise_rows is None or tuple(self._noise_rows.shape) != (B, N):
+            self._noise_rows = torch.empty(B, N, dtype=torch.float32, device=self.engine.device)
+        self.noise_bank = NoiseBank._synthesize(self.engine, self.noise, B, N, self.sample_rate, self._noise_rows)
+        self.last_noise = self.noise_bank.draw
+        if self._own_sources:
+            self.source_bank = self.noise_bank
+
     def __call__(self, clean: torch.Tensor):
         B = clean.size(0)
+        if self.noise is not None:                                # the batch's noise: made before every draw
+            self._synthesize(B, self.stretch_len(clean.size(1)))
         d = self.last_draw = self.draw(B)
         bands = self.last_bands = self.draw_bands(d)
         tail = self.last_tail = self.draw_tail(d)

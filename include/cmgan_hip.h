@@ -39,7 +39,7 @@ extern "C" {
 #define CMGAN_E_WORKSPACE   -5   /* workspace too small or misaligned              */
 #define CMGAN_E_HIP         -6   /* a HIP runtime call failed (see last_error)     */
 
-#define CMGAN_ABI_VERSION 20
+#define CMGAN_ABI_VERSION 21
 
 typedef struct cmgan_handle cmgan_handle;
 
@@ -1128,6 +1128,53 @@ size_t cmgan_dynamics_workspace_bytes(int B, int L);
 int cmgan_dynamics(cmgan_handle* h, const float* wav_dev, int B, int L, long long ldw, const float* key_dev, long long ldk,
                    const int* lengths_dev, const double* dyn_dev, float* out_dev, long long ldo, int* status_dev,
                    double* peak_reduction_db_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---- Synthetic noise (the reference has no noise source of its own: its data path replays pairs mixed beforehand) -------
+ * out_dev is a float32 [N, K] array, row r at out_dev[r * ld]: a noise of its own colour, modulation, hum and clicks per
+ * row, made from a seed and small per-row tables.  All tables are in DEVICE memory and read by the kernels only: seed_dev
+ * int64 [N] (the Philox key: low word, high word), start_dev int64 [N] (NULL: 0), len_dev int32 [N] (NULL: K), fir_dev
+ * float64 [N][NF], env_dev float64 [N][P] (NULL: no envelope, then P = H = 0), tones_dev float64 [N][M][3] = (nu, amp, phi)
+ * with nu in cycles per sample and phi in cycles (NULL exactly when M = 0), n_tones_dev int32 [N] (NULL: M for every row;
+ * only with tones_dev), imp_dev float64 [N][2] = (thr, amp), thr a whole number in [0, 2^32) (NULL: no clicks),
+ * status_dev int32 [N], written.  In float64, for row r, 0 <= k < len[r] and the absolute sample index n = start[r] + k:
+ *   nu[q]  = (w0 + w1 + w2 + w3 - 2 (2^32 - 1)) / CMGAN_RIR_TAIL_NOISE_DIV, (w0 .. w3) = Philox4x32-10 at the counter (q mod
+ *            2^32, q div 2^32, 0, 0) under the key seed[r] - for q < 2^32 the nu of cmgan_rir_tail; unit variance; the
+ *            numerator is an exact integer, the division is IEEE's
+ *   imp[q] = amp ((double)((int64)v1 - 2^31) / 2^31) if v0 < thr, else 0, (v0, v1, ..) = Philox at the counter (q mod 2^32,
+ *            q div 2^32, 1, 0); thr = 0: no clicks, and the second block is not computed
+ *   e[q]   = nu[q] + imp[q] for q >= 0, 0 for q < 0
+ *   s[n]   = sum_{j = 0 .. NF-1} fir[r][j] e[n - j], j ascending, one fma per term into one accumulator from 0
+ *   g[n]   = fma(env[r][p1] - env[r][p0], (double)(n - p0 H) / (double)H, env[r][p0]), p0 = min(n div H, P - 1),
+ *            p1 = min(p0 + 1, P - 1): the envelope's points lie H samples apart and the last one holds; g = 1 without env
+ *   t[n]   = sum_{m < n_tones[r]} amp_m sinpi(2 frac(fma(nu_m, (double)n, phi_m))), m ascending, one fma per term from 0,
+ *            frac(x) = x - floor(x), which is exact
+ *   out[r, k] = (float) fma(g[n], s[n], t[n]), ONE rounding to float32;  out[r, k] = 0 for len[r] <= k < K.
+ * A row is INVALID - status 1 (else 0) and K zeros - when an entry of fir, env or imp of the row, or of the tones it uses,
+ * is not finite, len[r] is outside [0, K], n_tones[r] is outside [0, M], a nu_m is outside [0, 0.5], thr is no whole number
+ * in [0, 2^32), start[r] < 0 or start[r] + K > 2^40.  Tone columns from n_tones[r] on are never read.
+ * Every sample is a pure function of the row's tables and n, so a row made whole and the same row made in pieces, start
+ * advanced by the samples already made, have the same bits.  Float64 on the VALU; no atomics; the same bits come out from
+ * run to run, and row r's bits depend neither on N, nor on the other rows, nor on ld, nor on K beyond len[r].  Two launches:
+ * a judge (one block per row, the verdict goes to the workspace) and the rows on a grid (tile of cmgan_noise_tile() = 256
+ * outputs, row), a thread per output: the block computes e once for the 256 + NF - 1 indices its outputs reach and stages
+ * it in LDS as float64 (10.2 KB at NF = 1023); the taps, the same for the whole block, come through scalar loads.  With
+ * K = 0 only the judge runs (out_dev may be NULL).
+ * Checked before any launch and before the handle is looked at (the message of a call with h == NULL is read with
+ * cmgan_last_error(NULL)): null out (K > 0) / seed / fir / status, misaligned pointers (4 bytes for float32 / int32, 8 for
+ * float64 / int64), 1 <= N <= 65535, 0 <= K <= 2^31 - 1 - cmgan_noise_tile(), ld >= K, 1 <= NF <= cmgan_noise_max_filter()
+ * (1023), with env 1 <= P <= cmgan_noise_max_points() (4096) and H >= 1 and without it P = H = 0, 0 <= M <=
+ * cmgan_noise_max_tones() (8) with tones NULL exactly when M = 0 and n_tones only beside tones, a workspace that is null, not
+ * 256-byte aligned or smaller than cmgan_noise_workspace_bytes(N) (0 for an unsupported N); each is CMGAN_E_BADARG.  No
+ * synchronisation, no allocation; graph-capturable, and a replay reads the current contents of every device table.      */
+int cmgan_noise_tile(void);
+int cmgan_noise_max_filter(void);
+int cmgan_noise_max_tones(void);
+int cmgan_noise_max_points(void);
+size_t cmgan_noise_workspace_bytes(int N);
+int cmgan_noise(cmgan_handle* h, float* out_dev, int N, int K, long long ld, const long long* seed_dev,
+                const long long* start_dev, const int* len_dev, const double* fir_dev, int NF, const double* env_dev, int P, int H,
+                const double* tones_dev, const int* n_tones_dev, int M, const double* imp_dev, int* status_dev,
+                void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---- Speed perturbation (the reference has no counterpart: its data path replays fixed pairs, src/data/dataloader.py) ---
  * Every row of a [B, L] float32 batch x_dev[b * ldx + k] is resampled by its OWN rate into N outputs y_dev[b * ldy + i]:
