@@ -650,6 +650,63 @@ def check_pitch_args(device, wav, factor, n_out=None, hop=256, search=160, zeros
     return B, L
 
 
+TRANSMIT_FRAME = (16, 4096)   # samples per frame of cmgan_transmit
+TRANSMIT_LAG = (16, 1024)     # the lags its concealment may search (1024 = cmgan_transmit_max_lag())
+TRANSMIT_WINDOW = (16, 1024)  # its matching window (1024 = cmgan_transmit_max_window())
+TRANSMIT_CODECS = {"none": 0, "pcm16": 1, "ulaw": 2, "alaw": 3}    # the values of Engine.transmit's codec table
+
+
+def transmit_scalars(fs=16000, frame=None, pmin=None, pmax=None, window=None, fade=None):
+    """The host values of Engine.transmit with the defaults filled in from fs - frame fs / 50, pmin fs / 200, pmax 3 fs /
+    200, window fs / 50, fade fs / 100 - as (frame, pmin, pmax, window, fade); a ValueError names what is out of range."""
+    if not _whole_in(fs, 1, 2 ** 31 - 1):
+        raise ValueError(f"fs must be a sample rate (a whole number >= 1), got {fs}")
+    fs = int(fs)
+    given = {"frame": (frame, fs // 50, TRANSMIT_FRAME), "pmin": (pmin, fs // 200, TRANSMIT_LAG),
+             "pmax": (pmax, 3 * fs // 200, TRANSMIT_LAG), "window": (window, fs // 50, TRANSMIT_WINDOW),
+             "fade": (fade, fs // 100, (1, 2 ** 31 - 1))}
+    val = {}
+    for name, (v, default, (lo, hi)) in given.items():
+        note = "" if v is not None else f" (the default at fs = {fs})"
+        v = default if v is None else v
+        if not _whole_in(v, lo, hi):
+            raise ValueError(f"{name} must be a whole number in [{lo}, {hi}], got {v}{note}")
+        val[name] = int(v)
+    if val["pmin"] > val["pmax"]:
+        raise ValueError(f"pmin must not exceed pmax, got pmin = {val['pmin']}, pmax = {val['pmax']}")
+    return val["frame"], val["pmin"], val["pmax"], val["window"], val["fade"]
+
+
+def check_transmit_args(device, wav, lost, frame=None, codec=None, plc=None, lengths=None, fs=16000, pmin=None, pmax=None,
+                        window=None, fade=None, out=None):
+    """Argument rules of Engine.transmit (shapes, dtypes, devices and host scalars; pure host code): every error is a
+    ValueError that names the argument.  Returns (B, L, frame, pmin, pmax, window, fade), the host values as
+    `transmit_scalars` fills them in."""
+    try:
+        B, L = _row_batch(device, wav)
+    except (TypeError, RuntimeError) as e:
+        raise ValueError(str(e)) from None
+    F, pmin, pmax, W, A = transmit_scalars(fs, frame, pmin, pmax, window, fade)
+    K = -(-L // F)
+    tensor_arg(lost, "lost", torch.uint8, device, f"[{B}, n_frames] with n_frames >= ceil(L / frame) = {K}",
+               lambda t: t.dim() == 2 and t.size(0) == B and t.size(1) >= K, contiguous=False, error=ValueError)
+    if not _row_stride_ok(lost, B, lost.size(1)):
+        raise ValueError(f"lost: rows must be contiguous and at least n_frames apart, got strides {tuple(lost.stride())}")
+    row = lambda t: tuple(t.shape) == (B,)
+    for name, t in (("codec", codec), ("plc", plc), ("lengths", lengths)):
+        if t is not None:
+            tensor_arg(t, name, torch.int32, device, f"[{B}]", row, error=ValueError)
+    if out is not None:
+        tensor_arg(out, "out", torch.float32, device, f"[{B}, {L}]", lambda t: tuple(t.shape) == (B, L), contiguous=False,
+                   error=ValueError)
+        if not _row_stride_ok(out, B, L):
+            raise ValueError(f"out: rows must be contiguous and at least L apart, got strides {tuple(out.stride())}")
+        same = out.data_ptr() == wav.data_ptr() and (B == 1 or out.stride(0) == wav.stride(0))
+        if not same and _overlap(out, wav, B, L):
+            raise ValueError("out: overlaps wav; only out = wav itself (in place, the same row stride) is allowed")
+    return B, L, F, pmin, pmax, W, A
+
+
 def metric_frames(L: int, fs: int):
     """(WSS / segSNR frames, LLR frames) of an L-sample signal: the two counts of cmgan_amd.metrics."""
     win = int(np.round(30 * fs / 1000))
@@ -1703,6 +1760,50 @@ class Engine:
         self._call("cmgan_stretch", wav, B, L, wav.stride(0) if B > 1 else L, lengths, rate, int(hop), int(search), out, N,
                    out.stride(0) if B > 1 else N, n, st, pos, srch)
         return (out, n, st, pos, srch) if info else out
+
+    # ---- transmission: codec, packet loss and concealment ---------------------------------
+    @_on_device
+    def transmit(self, wav: torch.Tensor, lost: torch.Tensor, frame: Optional[int] = None, codec: Optional[torch.Tensor] = None,
+                 plc: Optional[torch.Tensor] = None, lengths: Optional[torch.Tensor] = None, fs: int = 16000,
+                 pmin: Optional[int] = None, pmax: Optional[int] = None, window: Optional[int] = None, fade: Optional[int] = None,
+                 out: Optional[torch.Tensor] = None, info: bool = False):
+        """A telephone or VoIP link per row on the GPU (cmgan_transmit, include/cmgan_hip.h): a codec, frames that are
+        lost, and a receiver that covers the holes by repeating the last pitch period or leaves them as gaps.
+
+        wav float32 [B, L] (rows contiguous, any row stride >= L); lost uint8 [B, n_frames] with n_frames >= ceil(L /
+        frame): non-zero where a frame of `frame` samples is lost (cmgan_amd.mixing.TransmissionSampler draws bursty
+        patterns); codec int32 [B]: 0 none, 1 16-bit PCM, 2 G.711 mu-law, 3 G.711 A-law (TRANSMIT_CODECS; None: none); plc
+        int32 [B]: 1 conceals a run of lost frames, 0 leaves zeros (None: conceal); lengths int32 [B] (None: every row
+        has L samples; samples from a row's length on are never read and come out as zeros, and neither are the table
+        columns behind its last frame).  All on this Engine's device and read by the kernels only.  The host values
+        default from `fs`: frame fs / 50 (20 ms), the lag range pmin = fs / 200 .. pmax = 3 fs / 200 (66 .. 200 Hz), the
+        matching window fs / 50 and the fade unit fade = fs / 100: a concealed run keeps its level for `fade` samples,
+        then falls by 20 % per `fade` and is silent from 6 `fade` on (60 ms).  `out` float32 [B, L] is written in place of
+        a new tensor; out=wav runs in place.  Returns the float32 [B, L] result: float64 arithmetic with one rounding to
+        float32 per concealed sample; codec 0 with no lost frame copies the row bit for bit.  info=True adds (status int32
+        [B], lag int32 [B, n_frames]): status 1 marks the rows that are invalid (a codec outside 0 .. 3, a plc outside 0
+        .. 1, a length outside [0, L]) and come out as zeros; lag holds the pitch lag at the frame that starts a concealed
+        run, 0 at a row's other frames and -1 behind its last (a view of a table as wide as lost's rows are apart, when
+        lost is a column slice of a wider one).  The lags are exact: a host model finds the same.
+        Bit-reproducible, row-independent, two launches (the second one block per row), no workspace, no synchronisation,
+        graph-capturable."""
+        B, L, F, pmin, pmax, W, A = check_transmit_args(self.device, wav, lost, frame, codec, plc, lengths, fs, pmin, pmax,
+                                                         window, fade, out)
+        if codec is None:
+            codec = torch.zeros(B, dtype=torch.int32, device=self.device)
+        if plc is None:
+            plc = torch.ones(B, dtype=torch.int32, device=self.device)
+        if out is None:
+            out = torch.empty(B, L, dtype=torch.float32, device=self.device)
+        st = torch.empty(B, dtype=torch.int32, device=self.device) if info else None
+        # the kernels know ONE leading dimension for both tables, lost's: lag is allocated as wide as lost's rows are apart
+        # (a column slice of a wider table included) and returned as its first n_frames columns
+        n_frames = lost.size(1)
+        ldl = lost.stride(0) if B > 1 else n_frames
+        lag = torch.empty(B, ldl, dtype=torch.int32, device=self.device) if info else None
+        self._call("cmgan_transmit", wav, B, L, wav.stride(0) if B > 1 else L, lengths, lost, ldl, codec, plc, F, pmin, pmax,
+                   W, A, out, out.stride(0) if B > 1 else L, st, lag)
+        return (out, st, lag[:, :n_frames]) if info else out
 
     @_on_device
     def pitch_shift(self, wav: torch.Tensor, factor: torch.Tensor, n_out: Optional[int] = None, hop: int = 256,

@@ -41,6 +41,9 @@ takes - with `clean` the training target (the dry clip, or the clip with its ear
     # tempo and pitch perturbation: a time stretch that keeps the pitch (Engine.stretch / cmgan_stretch, WSOLA), and that
     # stretch followed by a warp.  stretch_len(L, tempo=, pitch=, speed=) is the batch length clips of L samples give
     mixer = DynamicMixer(engine, noise, rirs, tempo=(0.9, 1.1), pitch=(-2, 2))
+    # the link behind the recording device: G.711 or 16-bit PCM, bursts of lost packets, and a receiver that conceals them
+    # by repeating the last pitch period or leaves gaps (Engine.transmit / cmgan_transmit): the last stage of the chain
+    mixer = DynamicMixer(engine, noise, rirs, transmission=TransmissionSampler(p=0.5, loss=(0.01, 0.2), burst=(1.0, 4.0)))
 """
 from __future__ import annotations
 
@@ -55,11 +58,12 @@ import torch
 import torch.utils.data
 
 from .data import _natural_key, fit_length, read_wav
-from .engine import RIR_TAIL_MAX_WINDOW, SCENE_MAX_HOP, SCENE_MAX_WAYPOINTS, STRETCH_HOP, STRETCH_SEARCH, RirStats, RirTail, _whole_in
+from .engine import RIR_TAIL_MAX_WINDOW, SCENE_MAX_HOP, SCENE_MAX_WAYPOINTS, STRETCH_HOP, STRETCH_SEARCH, RirStats, RirTail, _whole_in, transmit_scalars
 
 __all__ = ["NoiseBank", "NoiseSampler", "NoiseDraw", "noise_fir", "power_law_magnitude", "RirBank", "RoomSampler", "sabine_beta", "octave_filterbank", "DynamicMixer", "MixingLoader", "CleanDataset",
            "clean_only", "Draw", "SceneDraw", "tile", "ChannelSampler", "biquad_peaking", "biquad_low_shelf", "biquad_high_shelf",
-           "biquad_lowpass", "biquad_highpass", "butter_lowpass_sos", "warp_len", "stretch_len", "StretchDraw", "TailDraw", "PathDraw"]
+           "biquad_lowpass", "biquad_highpass", "butter_lowpass_sos", "warp_len", "stretch_len", "StretchDraw", "TailDraw", "PathDraw",
+           "TransmissionSampler", "TransmitDraw", "TransmitInfo"]
 
 SPEED_OF_SOUND = 343.0        # m/s, the default `c` of Engine.rir
 RIR_TW = 40                   # the default half-width of its fractional-delay filter, in samples
@@ -834,6 +838,92 @@ class DynamicsSampler:
         return torch.stack([thr, slope, knee, a_att, a_rel, makeup], dim=1).contiguous()
 
 
+# ---- transmission: codec, bursty packet loss and concealment per row, as tables of Engine.transmit --------------------------
+class TransmitDraw(NamedTuple):
+    """What a TransmissionSampler drew for a batch, device tensors: the tables of Engine.transmit and what they came from."""
+    lost: torch.Tensor        # uint8 [B, n_frames]: 1 where the frame is lost
+    codec: torch.Tensor       # int32 [B]: 0 none, 1 16-bit PCM, 2 mu-law, 3 A-law
+    plc: torch.Tensor         # int32 [B]: 1 conceal, 0 leave gaps
+    rate: torch.Tensor        # float64 [B]: the mean loss of the row's chain (0 for a row that was not chosen)
+    burst: torch.Tensor       # float64 [B]: its mean burst length in frames, raised to 1 / (1 - rate) where it was smaller
+
+
+class TransmitInfo(NamedTuple):
+    """`DynamicMixer.last_transmission`: the draw, and what Engine.transmit reported for `noisy` (status int32 [B], lag int32
+    [B, n_frames]) and, with transmission_on="both", the lags of `target` (None otherwise)."""
+    draw: TransmitDraw
+    status: torch.Tensor
+    lag: torch.Tensor
+    target_lag: Optional[torch.Tensor] = None
+
+
+class TransmissionSampler:
+    """Random telephone / VoIP links for Engine.transmit: `draw(B, n_frames, device)` -> `TransmitDraw(lost, codec, plc, rate,
+    burst)`.
+
+    Per row, with probability `p`, a link: a mean loss `rate` uniform in `loss` (fractions in [0, 1)), a mean burst length
+    uniform in `burst` (frames, >= 1), a codec - 16-bit PCM, mu-law or A-law with probabilities `p_pcm16`, `p_ulaw`,
+    `p_alaw` (their sum at most 1), none otherwise - and a receiver that conceals with probability `p_conceal` (else
+    it plays gaps).  A row that is not chosen has no loss, codec 0 and rate 0.  `frame_ms` is the packet length the
+    mixer turns into Engine.transmit's `frame`.
+
+    The loss pattern is a Gilbert-Elliott chain that starts in the good state, with mean loss `rate` and mean burst
+    length `burst` frames: q = 1 / burst is the chance of leaving the bad state and p_gb = rate q / (1 - rate) that of
+    entering it.  A burst shorter than 1 / (1 - rate) is raised to it: that limit is independent loss (p_gb = 1 - q =
+    rate).  ONE uniform u_k per frame drives both states - u < p_gb: lost, whatever the state was; u >= 1 - q: received,
+    whatever it was; in between the state stays - so frame k takes the verdict of the latest frame at or before it whose u
+    falls outside the middle band (received with none): a cummax of an index, no loop (`pattern`).  Everything is drawn
+    from `generator` (None: the device's default one) on the device with tensor arithmetic, one rand call of [B, 5 +
+    n_frames] float64: no host synchronisation."""
+
+    def __init__(self, p: float = 0.5, loss=(0.01, 0.2), burst=(1.0, 4.0), frame_ms: float = 20.0, p_conceal: float = 0.8,
+                 p_pcm16: float = 0.2, p_ulaw: float = 0.2, p_alaw: float = 0.2, generator: Optional[torch.Generator] = None):
+        self.p, self.p_conceal = _probability("p", p), _probability("p_conceal", p_conceal)
+        self.p_pcm16, self.p_ulaw, self.p_alaw = (
+            _probability(name, v) for name, v in (("p_pcm16", p_pcm16), ("p_ulaw", p_ulaw), ("p_alaw", p_alaw)))
+        if self.p_pcm16 + self.p_ulaw + self.p_alaw > 1.0 + 1e-12:
+            raise ValueError(f"p_pcm16 + p_ulaw + p_alaw must not exceed 1, got {self.p_pcm16 + self.p_ulaw + self.p_alaw}")
+        self.loss = _pair("loss", loss, 0.0, 1.0, "(low, high) fractions with 0 <= low <= high < 1")
+        if self.loss[1] >= 1.0:
+            raise ValueError(f"loss must be (low, high) fractions with 0 <= low <= high < 1, got {loss}")
+        self.burst = _pair("burst", burst, 1.0, math.inf, "(low, high) frames with 1 <= low <= high < inf")
+        if self.burst[1] == math.inf:
+            raise ValueError(f"burst must be (low, high) frames with 1 <= low <= high < inf, got {burst}")
+        if isinstance(frame_ms, bool) or not isinstance(frame_ms, (int, float)) or not 0.0 < frame_ms < math.inf:
+            raise ValueError(f"frame_ms must be a packet length > 0 in milliseconds, got {frame_ms}")
+        self.frame_ms, self.generator = float(frame_ms), generator
+
+    def frame(self, fs: int) -> int:
+        """The packet length in samples at `fs`."""
+        return int(round(self.frame_ms * fs / 1000.0))
+
+    @staticmethod
+    def pattern(u: torch.Tensor, p_gb: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
+        """The chain's closed form: uint8 [B, n] from uniforms u [B, n] and the rows' p_gb and q [B]."""
+        B, n = u.shape
+        lose, keep = u < p_gb[:, None], u >= (1.0 - q)[:, None]
+        k = torch.arange(n, device=u.device)[None, :].expand(B, n)
+        last = torch.cummax(torch.where(lose | keep, k, torch.full_like(k, -1)), dim=1).values if n else k
+        verdict = torch.gather(lose, 1, last.clamp(min=0))
+        return ((last >= 0) & verdict).to(torch.uint8)
+
+    def draw(self, B: int, n_frames: int, device=None) -> TransmitDraw:
+        gen = self.generator
+        device = torch.device(device) if device is not None else (gen.device if gen is not None else torch.device("cpu"))
+        u = torch.rand(B, 5 + int(n_frames), dtype=torch.float64, generator=gen, device=device)
+        uniform = lambda r, v: r[0] + (r[1] - r[0]) * v
+        chosen = u[:, 0] < self.p
+        rate = torch.where(chosen, uniform(self.loss, u[:, 1]), torch.zeros_like(u[:, 1]))
+        burst = torch.maximum(uniform(self.burst, u[:, 2]), 1.0 / (1.0 - rate))
+        q = 1.0 / burst
+        p_gb = rate * q / (1.0 - rate)
+        plc = (u[:, 3] < self.p_conceal).to(torch.int32)
+        a, b, c = self.p_pcm16, self.p_pcm16 + self.p_ulaw, self.p_pcm16 + self.p_ulaw + self.p_alaw
+        kind = (u[:, 4] < c).to(torch.int32) * (1 + (u[:, 4] >= a).to(torch.int32) + (u[:, 4] >= b).to(torch.int32))
+        codec = kind * chosen.to(torch.int32)
+        return TransmitDraw(self.pattern(u[:, 5:], p_gb, q).contiguous(), codec, plc, rate, burst)
+
+
 # ---- synthetic noise: the colouring filter of Engine.noise from a magnitude, and a sampler of its tables ----------------
 NOISE_GRID = 4096             # points of the frequency grid the magnitudes are given on: [N, NOISE_GRID / 2 + 1]
 NOISE_MAX_TAPS = 1023         # = cmgan_noise_max_filter()
@@ -1309,7 +1399,18 @@ class DynamicMixer:
     the stretch draws included.  `source_motion=(lo, hi)` (needs `sources` and `rooms`) walks every located source the
     same way, a path per source drawn after the talkers'.  `last_draw` is then a PathDraw and the mixer returns a
     SceneInfo.  `room_stats=True` measures waypoint 0 of every talker.  Doppler is not modelled.  With both None (the
-    default) nothing is drawn or run: outputs, `last_draw` and every generator state are what they are without them."""
+    default) nothing is drawn or run: outputs, `last_draw` and every generator state are what they are without them.
+
+    `transmission` (a TransmissionSampler): the link between the recording device and the listener (Engine.transmit /
+    cmgan_transmit), the LAST stage, behind the channel: a codec, packets of `frame_ms` that are lost in bursts, and a
+    receiver that conceals them or not.  With None nothing is drawn or launched, and the outputs, `last_draw` and every
+    generator state are what they are without the argument.  With a sampler, a link per row is drawn after every other
+    draw of the call, from the sampler's own generator, for the ceil(N / frame) packets of the batch, and `noisy` goes
+    through it in place (lags, window and fade at Engine.transmit's defaults for `sample_rate`).  `transmission_on=
+    "noisy"` (the default) leaves the target as it is: the model is asked to undo the link too.  `transmission_on="both"`
+    also sends `target` through the same call with the same tables - it loses the same packets and conceals them from its
+    OWN history - so the task stays denoising.  `mixer.last_transmission` is a TransmitInfo: the draw, and the status and
+    lags the kernels reported."""
 
     def __init__(self, engine, noise_bank: NoiseBank, rir_bank: Optional[RirBank] = None, snr_db=(0.0, 20.0),
                  early_ms: Optional[float] = 50.0, p_reverb: float = 1.0, peak: float = 0.99,
@@ -1320,7 +1421,8 @@ class DynamicMixer:
                  source_snr_db=(0.0, 20.0), dry_noise: bool = True, tempo=None, p_tempo: float = 1.0, pitch=None,
                  p_pitch: float = 1.0, stretch_hop: int = 256, stretch_search: int = 160, room_stats: bool = False,
                  motion=None, p_motion: float = 1.0, motion_hop_ms: float = 250.0, source_motion=None,
-                 dynamics: Optional[DynamicsSampler] = None, dynamics_on: str = "noisy", noise: Optional[NoiseSampler] = None):
+                 dynamics: Optional[DynamicsSampler] = None, dynamics_on: str = "noisy", noise: Optional[NoiseSampler] = None,
+                 transmission: Optional["TransmissionSampler"] = None, transmission_on: str = "noisy"):
         if sources is not None:
             given, counts = sources, "(low, high) whole numbers with 0 <= low <= high and 1 <= high <= 4"
             sources = _pair("sources", given, 0, 4, counts, "None or (low, high)", whole=True)
@@ -1433,6 +1535,18 @@ class DynamicMixer:
         self.last_noise: Optional[NoiseDraw] = None         # noise=...: the draw the batch's noise rows were made from
         self._noise_rows: Optional[torch.Tensor] = None     # noise=...: the persistent float32 [B, N] allocation behind noise_bank
         self._own_sources = source_bank is None             # sources take their point noises from the noise bank
+        # ---- transmission: judged last, so that every earlier error is what it was
+        if transmission_on not in ("noisy", "both"):
+            raise ValueError(f"transmission_on must be 'noisy' or 'both', got {transmission_on!r}")
+        if transmission is not None and not isinstance(transmission, TransmissionSampler):
+            raise TypeError(f"transmission must be a TransmissionSampler or None, got {type(transmission).__name__}")
+        if transmission is not None:                        # the packet length and Engine.transmit's defaults at this rate
+            try:
+                transmit_scalars(self.sample_rate, transmission.frame(self.sample_rate))
+            except ValueError as e:
+                raise ValueError(f"transmission at sample_rate = {sample_rate}: {e}") from None
+        self.transmission, self.transmission_on = transmission, transmission_on
+        self.last_transmission: Optional[TransmitInfo] = None
 
     def waypoints(self, N: int) -> int:
         """P = 1 + ceil((N - 1) / H): the waypoints a batch of N samples needs; more than 64 is refused."""
@@ -1719,12 +1833,18 @@ class DynamicMixer:
         if paths is not None:                                     # who moves: the last draw of all
             d = self.last_draw = d._replace(n_path=self._draw_moving(B, paths))
         dyn = None if self.dynamics is None else self.dynamics.draw(B, self.sample_rate, device=self.engine.device)
+        # the link is the last draw of the call: _perturb, _level, _mix, _dynamics and _channel below draw nothing (a stage that
+        # does would have to draw above this line, or a sampler on the device's default generator would no longer come last)
+        link = None if self.transmission is None else self.transmission.draw(
+            B, -(-self.stretch_len(clean.size(1)) // self.transmission.frame(self.sample_rate)), device=self.engine.device)
         clean = self._perturb(d, s, clean)
         shift, clean = self._level(d, clean)
         noisy, target, info = self._mix(d, clean, rir, shift)
         if dyn is not None:
             d = self.last_draw = self._dynamics(d, dyn, noisy, target)
         self._channel(d, noisy, target)
+        if link is not None:
+            self._transmission(link, noisy, target)
         return target, noisy, info
 
     # ---- the stages of a call, in its order -------------------------------------------------------------------------
@@ -1808,6 +1928,14 @@ class DynamicMixer:
         self.engine.channel(noisy, sos, n_sections, self.channel_clip(clip_rel, noisy), out=noisy)
         if self.channel_on == "both":
             self.engine.channel(target, sos, n_shared, out=target)
+
+    def _transmission(self, link: TransmitDraw, noisy: torch.Tensor, target: torch.Tensor) -> None:
+        """The link, in place: on noisy, and with transmission_on="both" the same tables on target."""
+        frame = self.transmission.frame(self.sample_rate)
+        send = lambda x: self.engine.transmit(x, link.lost, frame, link.codec, link.plc, fs=self.sample_rate, out=x, info=True)
+        target_lag = send(target)[2] if self.transmission_on == "both" else None
+        _, status, lag = send(noisy)
+        self.last_transmission = TransmitInfo(link, status, lag, target_lag)
 
     @staticmethod
     def channel_clip(clip_rel: torch.Tensor, noisy: torch.Tensor) -> torch.Tensor:

@@ -39,7 +39,7 @@ extern "C" {
 #define CMGAN_E_WORKSPACE   -5   /* workspace too small or misaligned              */
 #define CMGAN_E_HIP         -6   /* a HIP runtime call failed (see last_error)     */
 
-#define CMGAN_ABI_VERSION 21
+#define CMGAN_ABI_VERSION 22
 
 typedef struct cmgan_handle cmgan_handle;
 
@@ -1260,6 +1260,65 @@ int cmgan_stretch_max_search(void);
 int cmgan_stretch(cmgan_handle* h, const float* x_dev, int B, int L, long long ldx, const int* lengths_dev,
                   const double* rate_dev, int hop, int search, float* y_dev, int N, long long ldy, int* out_len_dev,
                   int* status_dev, int* pos_dev, int* searched_dev, void* stream);
+
+/* ---- Transmission: codec, packet loss and concealment (the reference has no counterpart: its data path replays fixed
+ * pairs, src/data/dataloader.py, so the enhancer never meets speech that came over a telephone or VoIP link) -----------
+ * Every row of a [B, L] float32 batch x_dev[b * ldx + k] is companded by its OWN codec, loses its OWN frames and has the
+ * holes covered by repeating the last pitch period (after ITU-T G.711 Appendix I, simplified so that every step is
+ * stated) or left as gaps; the result is y_dev[b * ldy + k].  lengths_dev int32 [B] (NULL: n = L), lost_dev uint8
+ * [B][ldl] (non-zero: the frame is lost), codec_dev and plc_dev int32 [B], status_dev int32 [B] and lag_dev int32 [B][ldl]
+ * (the last two may be NULL) are in DEVICE memory and read / written by the kernels only; frame = F (16 .. 4096), pmin and
+ * pmax (the lag range, 16 <= pmin <= pmax <= cmgan_transmit_max_lag() = 1024), window = W (the matching window, 16 ..
+ * cmgan_transmit_max_window() = 1024) and fade = A (the fade unit, >= 1) are host values.  For row b with n = lengths[b]
+ * and K = ceil(n / F); table columns k >= K and samples at i >= n are never read:
+ *   1. Codec.  z[i] = codec(x[i]) for 0 <= i < n.
+ *        0  none: z is x bit for bit, NaN included
+ *        1, 2, 3 start from q = sat16(rint(x[i] * 32768)): round half to even, NaN -> 0, +-inf saturate
+ *        1  16-bit PCM: z = q / 32768
+ *        2  G.711 mu-law: z = ulaw2lin(lin2ulaw(q)) / 32768
+ *        3  G.711 A-law:  z = alaw2lin(lin2alaw(q)) / 32768        (both maps exactly those of Python's audioop at width 2)
+ *   2. Loss.  y starts as z.  A run is a maximal set of consecutive lost frames k0 .. k1 - 1, s = k0 F, e = min(k1 F, n);
+ *      runs are handled in ascending order; h(i) = y[i] as it stands for 0 <= i < s, earlier concealment included, and 0
+ *      for i < 0.
+ *        plc = 0:  y[s .. e) = 0; nothing else changes.
+ *        plc = 1:
+ *          lag     P = the pmin <= P <= pmax with the largest 2 C - E,  C = sum_{i<W} h(s-W+i) h(s-W-P+i),  E = sum_{i<W}
+ *                  h(s-W-P+i)^2, float64 sums in ascending i (the score and the arithmetic of cmgan_stretch; products of
+ *                  float32 values are exact); a NaN score counts as -inf; among equal maxima the smallest P wins, so
+ *                  silence, and a run at the start of the row, take pmin
+ *          period  Q = floor(P / 4);  v[i] = h(s-P+i) for 0 <= i < P - Q;  v[i] = fl(1-t) h(s-P+i) + t h(s-2P+i) with t =
+ *                  (i - (P-Q) + 1) / (Q + 1) for P - Q <= i < P: the buffer ends where it begins
+ *          gain    g(j) = min(1, max(0, (6A - j) / (5A))): an exact integer numerator and one IEEE division; 1 for the
+ *                  first A samples, then falling by 20 % per A, 0 from 6A on
+ *          fill    y[s+j] = f32(g(j) v[j mod P]) for 0 <= j < e - s; where g = 1 and j mod P < P - Q the sample is a bit
+ *                  copy of the history
+ *          fade back (if e < n)  R = min(Q, F, n - e), M = e - s, and for 0 <= i < R with t = (i + 1) / (R + 1):
+ *                  y[e+i] = f32(fl(1-t) g(M+i) v[(M+i) mod P] + t z[e+i]); frame k1 is good, so the fade stays inside it
+ *        Float64 arithmetic with one rounding to float32 per stored sample.
+ *   y[i] = 0 for n <= i < L;  status[b] = 0;  lag[b, k] = P at the frame that starts a concealed run, 0 at every other
+ *   frame k < K, -1 for K <= k < ldl.
+ * A row is INVALID - status 1, L zeros, every lag -1 - when its codec lies outside 0 .. 3, its plc outside 0 .. 1 or its
+ * length outside [0, L].  codec = 0 with no lost frame copies the row bit for bit.  Non-finite samples are no error.
+ * Method.  Step 1 is one elementwise launch over the batch, 8 bytes per sample.  The concealment is a serial chain along
+ * a row (a later loss conceals from a history that may itself be concealed), so in step 2 one block owns a row and walks
+ * its runs: a batch of B rows keeps B compute units busy.  A run stages W + pmax history samples and v on chip as float64
+ * (24 KB at most); every lag has a thread of its own, which runs both sums in one ascending chain; the best (score, P)
+ * is reduced by wave shuffles and one step through LDS, in an order that cannot change the winner because the order on
+ * that key is total; the block reads its own earlier writes to y back behind a barrier.  No atomics, no workspace; row
+ * b's bits depend neither on B, nor on the other rows, nor on the padding behind ldx / ldy, nor on table columns from K
+ * on, nor on L beyond n.
+ * Checked before the launch and before the handle is looked at (the message of a call with h == NULL is read with
+ * cmgan_last_error(NULL)): null x / lost / codec / plc / y, pointers to float32 / int32 that are not 4-byte aligned,
+ * 1 <= B <= 65535, L >= 1, ldx >= L, ldy >= L, 16 <= frame <= 4096, 16 <= pmin <= pmax <= 1024, 16 <= window <= 1024,
+ * fade >= 1, ldl >= ceil(L / frame), and any intersection of [x, x + (B-1) ldx + L) with [y, y + (B-1) ldy + L) other than
+ * y == x with ldy == ldx (in place); each is CMGAN_E_BADARG.  Two launches, no synchronisation, no allocation;
+ * graph-capturable, and a replay reads the current contents of x, the tables and the lengths.                      */
+int cmgan_transmit_max_lag(void);
+int cmgan_transmit_max_window(void);
+int cmgan_transmit(cmgan_handle* h, const float* x_dev, int B, int L, long long ldx, const int* lengths_dev,
+                   const unsigned char* lost_dev, long long ldl, const int* codec_dev, const int* plc_dev, int frame,
+                   int pmin, int pmax, int window, int fade, float* y_dev, long long ldy, int* status_dev, int* lag_dev,
+                   void* stream);
 
 /* Names + durations (ms) of the kernels of the most recent forward when
  * profiling is enabled with cmgan_set_profiling(h, 1): HIP events are recorded
