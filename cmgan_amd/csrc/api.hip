@@ -619,6 +619,8 @@ static WsPlan plan_ws(const cmgan_config& c, int B, int T) {
     p.w = take(cur, M * 128);
     p.dm = take(cur, (size_t)B * T * W2 * 4 + 64);
     p.dc = take(cur, (size_t)B * T * W2 * 4 + 64);
+    // the most tiles any conv of the forward can have, whichever kernel a plane width selects (tscnet_impl): the fp32
+    // tiling at F has the most (128 positions per tile against 254 / 126, and F >= F')
     const size_t nt = std::max({(size_t)conv3_ntiles(T, (int)F), (size_t)conv_in_ntiles((int)P),
                                 (size_t)conv3x_ntiles(T, (int)F, 64), (size_t)conv3x_ntiles(T, (int)F, 128)});
     p.partials = take(cur, (size_t)B * nt * 128 * 2);
@@ -907,6 +909,10 @@ static int tscnet_impl(cmgan_handle* h, const float* spec, int B, int T, float* 
     const float* cx_tail = W(h, WID(G_CPLX, CX_TAIL_W), ok);
     const float* cx_bias = W(h, WID(G_CPLX, CX_BIAS), ok);
     const bool x3 = h->cfg.mfma_mode != CMGAN_MFMA_F32;
+    // The split-f16 conv kernel cannot walk planes narrower than its load step (conv3x_walkable, conv_x3.hip): such a
+    // plane takes the fp32 conv3_kernel, per plane width and kernel - x3e = the encoder's convs at F, x3d = the decoders'
+    // dense blocks at F', x3s = the sub-pixel conv at F'.  The conformers stay in the handle's mode.
+    const bool x3e = x3 && conv3x_walkable(F, 64), x3d = x3 && conv3x_walkable(F2, 64), x3s = x3 && conv3x_walkable(F2, 128);
     const Conv3xFn conv3x = (h->cfg.single_mask & CMGAN_MIX_CONV) ? launch_conv3_x1 : launch_conv3_x3;
     auto conformer_x = [&](LaunchCtx c, const ConfWeights& w_, const ConfWeightsX3& w16_, const ConfBuffers& b_, const TokMap& m_,
                            long M_, float* taps_, bool outer_, const unsigned char* mask_) {
@@ -953,15 +959,15 @@ static int tscnet_impl(cmgan_handle* h, const float* spec, int B, int T, float* 
         float* sc[4] = {nsc(1), nsc(2), nsc(3), nsc(4)};
         float* sh[4] = {nsh(1), nsh(2), nsh(3), nsh(4)};
         float* imgs[3] = {f + p.img[0], f + p.img[1], f + p.img[2]};
-        run_dense_block(ctx, x3, dbe, f + p.e[0], nsc(0), nsh(0), c1pr, slots, partials, sc, sh, B, T, F, x3 ? imgs : nullptr, conv3x, frozen,
+        run_dense_block(ctx, x3e, dbe, f + p.e[0], nsc(0), nsh(0), c1pr, slots, partials, sc, sh, B, T, F, x3e ? imgs : nullptr, conv3x, frozen,
                         run, 1);
     }
     {   // conv_2: (1,3) stride (1,2) pad (0,1) == stride-1 conv keeping the even columns
         ConvArgs a{};
         a.in[0] = f + p.e[4]; a.nscale[0] = nsc(4); a.nshift[0] = nsh(4); a.nalpha[0] = dbe.prelu[3];
         a.nslots = 1; a.w = c2w; a.bias = c2b; a.out = f + p.xb; a.partials = partials;
-        a.T = T; a.F = F; a.dil = 1; a.mode = 1; a.ntiles = x3 ? conv3x_ntiles(T, F, 64) : conv3_ntiles(T, F);
-        if (x3) conv3x(ctx, a, c2w16, B, 1, 64);
+        a.T = T; a.F = F; a.dil = 1; a.mode = 1; a.ntiles = x3e ? conv3x_ntiles(T, F, 64) : conv3_ntiles(T, F);
+        if (x3e) conv3x(ctx, a, c2w16, B, 1, 64);
         else launch_conv3(ctx, a, B, 1, 64);
         finalize(5, a.ntiles, 64, 0, (double)P2, c2gb, f + p.xb, F2);
         launch_in_apply(ctx, f + p.xb, nsc(5), nsh(5), c2pr, f + p.xa, B, P2);
@@ -999,7 +1005,7 @@ static int tscnet_impl(cmgan_handle* h, const float* spec, int B, int T, float* 
     // ---- decoders (generator.py:133-139, 151-156) ------------------------------------
     float* dslots[4] = {f + p.e[1], f + p.e[2], f + p.e[3], f + p.e[4]};
     float* sp = f + p.e[0];
-    const int nt2 = x3 ? conv3x_ntiles(T, F2, 128) : conv3_ntiles(T, F2);
+    const int nt2 = x3s ? conv3x_ntiles(T, F2, 128) : conv3_ntiles(T, F2);
     for (int dec = 0; dec < 2; ++dec) {
         const DenseW& d = dec == 0 ? dbm : dbc;
         const int j0 = dec == 0 ? 6 : 10;
@@ -1007,7 +1013,7 @@ static int tscnet_impl(cmgan_handle* h, const float* spec, int B, int T, float* 
         float* sh[4] = {nsh(j0), nsh(j0 + 1), nsh(j0 + 2), nsh(j0 + 3)};
         float* imgs[3] = {f + p.img[0], f + p.img[1], f + p.img[2]};
         // both blocks start from xa and nothing writes imgs[0] in between: the second one reuses the first one's image
-        run_dense_block(ctx, x3, d, f + p.xa, nullptr, nullptr, nullptr, dslots, partials, sc, sh, B, T, F2, x3 ? imgs : nullptr, conv3x, frozen,
+        run_dense_block(ctx, x3d, d, f + p.xa, nullptr, nullptr, nullptr, dslots, partials, sc, sh, B, T, F2, x3d ? imgs : nullptr, conv3x, frozen,
                         run, j0, dec == 1);
         if (dec == 0) {
             // mask head: sub_pixel -> pixel shuffle -> conv_1 are one linear map (build_mask_head), evaluated in fp32 in
@@ -1020,7 +1026,7 @@ static int tscnet_impl(cmgan_handle* h, const float* spec, int B, int T, float* 
         a.nslots = 1; a.w = cx_spw; a.bias = cx_spb;
         a.out = sp; a.partials = partials;
         a.T = T; a.F = F2; a.dil = 1; a.mode = 2; a.ntiles = nt2;
-        if (x3) conv3x(ctx, a, cx_spw16, B, 1, 128);
+        if (x3s) conv3x(ctx, a, cx_spw16, B, 1, 128);
         else launch_conv3(ctx, a, B, 1, 128);
         finalize(14, nt2, 128, 1, (double)T * W2, cx_gb, sp, W2);
         launch_tail_proj(ctx, sp, nsc(14), nsh(14), cx_pr, cx_tail, f + p.dc, B, (long)T * W2);

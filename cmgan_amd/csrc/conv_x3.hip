@@ -77,7 +77,8 @@ __device__ __forceinline__ const float* sel4(const float* const (&p)[4], int i) 
     const unsigned dFb = (unsigned)(a.dil * a.F) * 256u;                                                 \
     const unsigned dFs = revt_ ? dFb : 0u - dFb;          /* byte step from frame t to the logical frame t - dil */ \
     const float osc_ = (TRAINV && a.oscale != nullptr) ? *a.oscale : 1.0f;                               \
-    /* (t, f) of row e by one division and 32-row steps (every F + 1 here is > 32) */                    \
+    /* (t, f) of row e by one division, then RSTEP-row steps with ONE wrap each: exact only for          \
+       F + 1 >= RSTEP (conv3x_walkable below; narrower planes take conv3_kernel, which divides per row) */ \
     const int qfirst_ = q0 - 1 + (tid >> 3);                                                             \
     int tt_ = (qfirst_ < 0 ? 0 : qfirst_) / Fp, ff_ = qfirst_ - tt_ * Fp;    /* q = -1 -> (0, -1): padding */ \
     _Pragma("unroll") for (int e = 0; e < NACT; ++e) {                                                   \
@@ -418,6 +419,17 @@ using namespace X3_NS;
 int conv3x_ntiles(int T, int F, int cout) {
     const int tile = (cout == 128 ? 16 * CX_NPB128 * CX_NWV128 : 16 * CX_NPB64 * CX_NWV64) - 2;
     return (T * (F + 1) + tile - 1) / tile;
+}
+
+// conv3x_kernel finds the (t, f) of its rows by one division per thread and then fixed steps with at most one wrap per
+// step: the staging map (CX_SETUP) steps RSTEP = 8 * NWV rows, the epilogue (CX_EPILOGUE) 16.  Both are exact only
+// while a plane row (F + 1 positions with the virtual zero column) is at least as long as the step; on a narrower
+// plane rows that hold data are staged as padding and outputs that exist are not stored (every address stays inside
+// the clip, the numbers are wrong).  Callers send such planes to conv3_kernel (conv.hip), which has no limit.
+// tests/test_conv_x3_tile_model.py walks both maps on the host and pins this predicate to them.
+bool conv3x_walkable(int F, int cout) {
+    const int rstep = 8 * (cout == 128 ? CX_NWV128 : CX_NWV64);
+    return F + 1 >= (rstep > 16 ? rstep : 16);
 }
 
 void launch_conv3_x3_dgrad(LaunchCtx ctx, const ConvArgs& a, const void* w16, int B) {

@@ -222,6 +222,10 @@ void launch_attn_sp_out_x3(LaunchCtx, const _Float16* qimg, const _Float16* kimg
                            const _Float16* rel_img, int max_pos, float* x, const TokMap& seq, const _Float16* woi,
                            const float* bo);
 int  conv3x_ntiles(int T, int F, int cout);
+// false when a plane of F bins is too narrow for conv3x_kernel's row walk (conv_x3.hip; F + 1 >= 64 for the 64-channel
+// kernels, >= 32 for the 128-channel sub-pixel kernel): the caller launches conv3_kernel instead - the limit lives with
+// the kernel.  Holds for the single-product twin too (same tiles).
+bool conv3x_walkable(int F, int cout);
 void launch_conv3_x3(LaunchCtx, const ConvArgs&, const void* w16, int B, int time_taps, int cout);
 void launch_conv3_x3_dgrad(LaunchCtx, const ConvArgs&, const void* w16, int B);      // 2 time taps, 64 -> 64, revt / accum honoured
 void launch_selftest_x3(hipStream_t, const void* a_img, const float* b_fm, float* d, int M32);

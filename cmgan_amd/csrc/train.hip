@@ -2655,9 +2655,9 @@ __global__ __launch_bounds__(256) void db_dgrad_setup_kernel(float* __restrict__
 }
 
 // the inference conv kernel steps its staging rows by 64 per load and assumes a plane row (F + 1 positions with the
-// virtual zero column) is at least that long: true for every model size (F = 201 / 101 / 601 / 301); tiny test planes
-// take the per-position fp32 kernel
-static bool db_x3_forward(int F) { return F + 1 >= 64; }
+// virtual zero column) is at least that long (conv3x_walkable, conv_x3.hip): true for every model size (F = 201 / 101 /
+// 601 / 301); tiny test planes take the per-position fp32 kernel
+static bool db_x3_forward(int F) { return conv3x_walkable(F, 64); }
 
 static void db_pack_images(LaunchCtx ctx, const DenseTrainParams& p, float* ws, const DbPlan& pl, int F, bool pack = true) {
     if (!pack) return;
@@ -3090,10 +3090,11 @@ __global__ void rc_pack_x3_kernel(const float* __restrict__ w, int Co, _Float16*
     *reinterpret_cast<f16x8*>(o) = hi;
     *reinterpret_cast<f16x8*>(o + 512) = lo;
 }
-// the plane must be long enough for the kernel's tiles (db_x3_forward) and the geometry one of the two the modes express
+// the plane must be long enough for the kernel's tiles (db_x3_forward; the 64-channel limit for both geometries, as the
+// training step always had it) and the geometry one of the two the modes express
 static bool rc_x3_forward(const RcGeom& gm, int NG) {
     static const bool k_on = env_knob("CMGAN_RC_FWD_X3", 1, 0, 1) != 0;
-    return k_on && gm.KW == 3 && gm.PL == 1 && gm.Fi + 1 >= 64 &&
+    return k_on && gm.KW == 3 && gm.PL == 1 && conv3x_walkable(gm.Fi, 64) &&
            ((NG == 2 && gm.SF == 1 && gm.Fo == gm.Fi) || (NG == 1 && gm.SF == 2 && gm.Fo == (gm.Fi - 1) / 2 + 1));
 }
 // img: the fp32 fragment image of rc_pack_kernel; the split-f16 path rebuilds it in place (same size) from the raw weight

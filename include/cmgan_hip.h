@@ -101,6 +101,14 @@ typedef struct cmgan_config {
 #define CMGAN_MIX_PW1   32    /* conv module: LN -> pointwise 64 -> 256 -> GLU  src/models/conformer.py:161-164          */
 #define CMGAN_MIX_DWPW2 64    /* depthwise k = 31 -> Swish -> pointwise 128 -> 64   src/models/conformer.py:165-170      */
 #define CMGAN_MIX_ALL  127
+/* Plane widths and conv kernels.  In the three split-f16 modes the encoder / decoder convs run on the f16 matrix pipe only
+ * where the plane is wide enough for that kernel's row walk (conv_x3.hip, conv3x_walkable); a narrower plane takes the
+ * fp32 conv kernel of the F32 mode, conv by conv, with the same weights.  F = n_fft / 2 + 1, F' = (F + 1) / 2:
+ *   encoder dense block, conv_2   (plane F)    split-f16 for F  >= 63 (n_fft >= 124), else fp32
+ *   decoder dense blocks          (plane F')   split-f16 for F' >= 63 (n_fft >= 248), else fp32
+ *   complex decoder sub-pixel conv (plane F')  split-f16 for F' >= 31 (n_fft >= 120), else fp32
+ * The conformers, conv_1, the mask head and the tails do not depend on the width.  The default 16 kHz (F 201 / F' 101)
+ * and 48 kHz (601 / 301) models are far above every limit; small n_fft is at least as accurate as before, not faster. */
 
 /* Fills *cfg with the reference's 16 kHz defaults (above). */
 void cmgan_default_config(cmgan_config* cfg);
