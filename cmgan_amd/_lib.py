@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CMGAN_HIP_LIB") or os.path.join(HERE, "lib", "libcmgan_hip.so")
 
 OK = 0
-ABI_VERSION = 22
+ABI_VERSION = 23
 MFMA_F32, MFMA_F16X3, MFMA_F16X1, MFMA_F16MIX = 0, 1, 2, 3
 # CMGAN_MIX_* bits of Config.single_mask (include/cmgan_hip.h)
 MIX = {"conv": 1, "ff1": 2, "ff2": 4, "qkv": 8, "attn": 16, "pw1": 32, "dwpw2": 64}
@@ -272,6 +272,10 @@ SIGNATURES = {
     "cmgan_transmit_max_window": (c_int, []),
     "cmgan_transmit": (c_int, [c_void_p, c_void_p, c_int, c_int, c_longlong, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p,
                                c_int, c_int, c_int, c_int, c_int, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p]),
+    "cmgan_suppress_max_window": (c_int, []),
+    "cmgan_suppress_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "cmgan_suppress": (c_int, [c_void_p, c_void_p, c_int, c_int, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_int,
+                               c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "cmgan_set_profiling": (c_int, [c_void_p, c_int]),
     "cmgan_profile_read": (c_int, [c_void_p, POINTER(KernelTime), c_int]),
 }

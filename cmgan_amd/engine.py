@@ -707,6 +707,54 @@ def check_transmit_args(device, wav, lost, frame=None, codec=None, plc=None, len
     return B, L, F, pmin, pmax, W, A
 
 
+SUPPRESS_N_FFT = (256, 512, 1024)      # the transform sizes of cmgan_suppress
+SUPPRESS_MAX_WINDOW = 128              # frames of its minimum search (= cmgan_suppress_max_window())
+SUPPRESS_MAX_L = 2 ** 31 - 1 - 2048
+SUPPRESS_RULES = {"off": 0, "wiener": 1, "specsub": 2, "logmmse": 3}    # column 0 of Engine.suppress's table
+
+
+def suppress_frames(L: int, n_fft: int) -> int:
+    """T = ceil(L / h) + 1 with h = n_fft / 2: the frames of an L-sample batch, the middle axis of Engine.suppress's gains."""
+    h = n_fft // 2
+    return -(-L // h) + 1
+
+
+def suppress_workspace_bytes(B: int, L: int, n_fft: int) -> int:
+    """cmgan_suppress_workspace_bytes: a complex128 [B, T, F] plane of spectra and a float64 [B, T, F] plane of periodograms
+    and gains (T = suppress_frames(L, n_fft), F = n_fft / 2 + 1), each rounded up to 256 bytes; 0 for a shape the kernels do
+    not take."""
+    if not (1 <= B <= 65535 and 1 <= L <= SUPPRESS_MAX_L and n_fft in SUPPRESS_N_FFT):
+        return 0
+    up = lambda v: (v + 255) & ~255
+    cells = B * suppress_frames(L, n_fft) * (n_fft // 2 + 1)
+    return up(cells * 16) + up(cells * 8)
+
+
+def check_suppress_args(device, wav, table, n_fft=512, lengths=None, key=None, out=None):
+    """Argument rules of Engine.suppress (shapes, dtypes, devices, overlaps and n_fft; pure host code).  Returns (B, L)."""
+    if isinstance(n_fft, bool) or n_fft not in SUPPRESS_N_FFT:
+        raise ValueError(f"n_fft must be one of {SUPPRESS_N_FFT}, got {n_fft}")
+    B, L = _row_batch(device, wav, SUPPRESS_MAX_L)
+    tensor_arg(table, "table", torch.float64, device, f"[{B}, 7]", lambda t: tuple(t.shape) == (B, 7))
+    if key is not None:
+        tensor_arg(key, "key", torch.float32, device, f"[{B}, {L}]", lambda t: tuple(t.shape) == (B, L), contiguous=False)
+        if not _row_stride_ok(key, B, L):
+            raise ValueError(f"key: rows must be contiguous and at least L apart, got strides {tuple(key.stride())}")
+    if lengths is not None:
+        tensor_arg(lengths, "lengths", torch.int32, device, f"[{B}]", lambda t: tuple(t.shape) == (B,))
+    if out is not None:
+        tensor_arg(out, "out", torch.float32, device, f"[{B}, {L}]", lambda t: tuple(t.shape) == (B, L), contiguous=False)
+        if not _row_stride_ok(out, B, L):
+            raise ValueError(f"out: rows must be contiguous and at least L apart, got strides {tuple(out.stride())}")
+        for name, t in (("wav", wav), ("key", key)):
+            if t is None:
+                continue
+            same = out.data_ptr() == t.data_ptr() and (B == 1 or out.stride(0) == t.stride(0))
+            if not same and _overlap(out, t, B, L):
+                raise ValueError(f"out: overlaps {name}; only out = {name} itself (in place, the same row stride) is allowed")
+    return B, L
+
+
 def metric_frames(L: int, fs: int):
     """(WSS / segSNR frames, LLR frames) of an L-sample signal: the two counts of cmgan_amd.metrics."""
     win = int(np.round(30 * fs / 1000))
@@ -769,7 +817,7 @@ class Engine:
             msg = self.lib.cmgan_last_error(None)
             raise _lib.CmganError(rc, msg.decode() if msg else "?")
         #: grow-only uint8 workspaces by name (_grow): "main", "branched" (enhance_graphed(branches > 1)), "conformer",
-        #: "metrics", "mix", "scene", "rir", "rir_bands", "rir_dir", "rir_bands_dir", "level", "channel", "dynamics", "noise" and ("resample", fs_in,
+        #: "metrics", "mix", "scene", "rir", "rir_bands", "rir_dir", "rir_bands_dir", "level", "channel", "dynamics", "noise", "suppress" and ("resample", fs_in,
         #: fs_out), the rate pair's tap table
         self._wss: dict = {}
         self._graphs: dict = {}          # enhance_graphed: input shape -> (graph, in, out, token)
@@ -1804,6 +1852,40 @@ class Engine:
         self._call("cmgan_transmit", wav, B, L, wav.stride(0) if B > 1 else L, lengths, lost, ldl, codec, plc, F, pmin, pmax,
                    W, A, out, out.stride(0) if B > 1 else L, st, lag)
         return (out, st, lag[:, :n_frames]) if info else out
+
+    # ---- suppression: the device's own noise suppressor, and the classical baseline -----------
+    @_on_device
+    def suppress(self, wav: torch.Tensor, table: torch.Tensor, n_fft: int = 512, lengths: Optional[torch.Tensor] = None,
+                 key: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, info: bool = False):
+        """A single-channel noise suppressor per row on the GPU (cmgan_suppress, include/cmgan_hip.h): a short-time spectral
+        gain from a minimum-tracking noise estimate and the decision-directed a-priori SNR - the Wiener rule, power spectral
+        subtraction or Ephraim and Malah's log-MMSE rule.
+
+        wav float32 [B, L] (rows contiguous, any row stride >= L); table float64 [B, 7] = (rule, a_dd, a_n, D, bias, g_min,
+        xi_min) per row (cmgan_amd.mixing.suppress_params makes it from audio units; rule 0 copies the row bit for bit);
+        n_fft 256, 512 or 1024: frames of n_fft samples under a square-root Hann window every n_fft / 2; lengths int32 [B]
+        (None: every row has L samples; samples from a row's length on are never read, and come out as zeros); key float32
+        [B, L]: the signal whose spectrum drives the gains (None: wav itself).  All on this Engine's device and read by the
+        kernels only.  `out` float32 [B, L] is written in place of a new tensor; out=wav runs in place, out=key is allowed,
+        any other overlap of out with wav or key is a ValueError.  Returns the float32 [B, L] result: float64 arithmetic
+        with one rounding to float32.  info=True adds (status, gain): int32 [B], 1 for the rows that are invalid (a table
+        entry that is not finite or out of range, a rule or D that is no integer, a length outside [0, L]) and come out as
+        zeros, and float64 [B, T, n_fft / 2 + 1] with T = suppress_frames(L, n_fft), the gain of every frame and bin (1 at
+        rule 0, 0 behind a row's last frame).  Bit-reproducible, row-independent, three launches, no synchronisation,
+        graph-capturable after one call at the shape."""
+        B, L = check_suppress_args(self.device, wav, table, n_fft, lengths, key, out)
+        ws = self._grow("suppress", int(self.lib.cmgan_suppress_workspace_bytes(B, L, int(n_fft))),
+                        f"[{B}, {L}] at n_fft = {n_fft} is outside what cmgan_suppress supports")
+        if out is None:
+            out = torch.empty(B, L, dtype=torch.float32, device=self.device)
+        st = torch.empty(B, dtype=torch.int32, device=self.device) if info else None
+        gain = None
+        if info:
+            gain = torch.empty(B, suppress_frames(L, int(n_fft)), int(n_fft) // 2 + 1, dtype=torch.float64, device=self.device)
+        self._call("cmgan_suppress", wav, B, L, wav.stride(0) if B > 1 else L, key,
+                   0 if key is None else (key.stride(0) if B > 1 else L), lengths, table, int(n_fft), out,
+                   out.stride(0) if B > 1 else L, st, gain, ws, ws.numel())
+        return (out, st, gain) if info else out
 
     @_on_device
     def pitch_shift(self, wav: torch.Tensor, factor: torch.Tensor, n_out: Optional[int] = None, hop: int = 256,

@@ -60,6 +60,21 @@ def enhance_one_track(model: TSCNet, noisy: torch.Tensor, cut_len: int = 16000 *
 
 
 @torch.no_grad()
+def suppress_one_track(engine, noisy: torch.Tensor, rule: str = "logmmse", sample_rate: int = 16000) -> torch.Tensor:
+    """The classical baseline beside the model: noisy float32 [1, L] on the GPU -> [1, L] on the GPU through Engine.suppress
+    (cmgan_suppress) with textbook settings - `rule` "logmmse", "wiener" or "specsub" ("off" copies), a floor of -20 dB, the
+    noise taken as 1.5 times the smallest smoothed periodogram of the last second, decision-directed smoothing 0.98,
+    frames of 32 ms (n_fft 512 below 32 kHz, 1024 from there).  `evaluation` does not call it: score its result like any
+    other estimate."""
+    from .mixing import suppress_n_fft, suppress_params
+    if noisy.dim() != 2 or noisy.size(0) != 1:
+        raise ValueError("expected a mono track shaped [1, L] (torchaudio.load layout)")
+    n_fft = suppress_n_fft(int(sample_rate))
+    table = suppress_params(rule, fs=int(sample_rate), n_fft=n_fft).reshape(1, 7).to(engine.device)
+    return engine.suppress(noisy.to(device=engine.device, dtype=torch.float32).contiguous(), table, n_fft)
+
+
+@torch.no_grad()
 def enhance_batch(model: TSCNet, wav: torch.Tensor) -> torch.Tensor:
     """Equal-length clips [B, L] (L % hop == 0), per-row RMS scale (src/train.py:75-79):
     one fused ABI call (cmgan_enhance)."""

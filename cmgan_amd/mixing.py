@@ -44,6 +44,9 @@ takes - with `clean` the training target (the dry clip, or the clip with its ear
     # the link behind the recording device: G.711 or 16-bit PCM, bursts of lost packets, and a receiver that conceals them
     # by repeating the last pitch period or leaves gaps (Engine.transmit / cmgan_transmit): the last stage of the chain
     mixer = DynamicMixer(engine, noise, rirs, transmission=TransmissionSampler(p=0.5, loss=(0.01, 0.2), burst=(1.0, 4.0)))
+    # the device's own noise suppressor (Wiener, spectral subtraction or log-MMSE; Engine.suppress / cmgan_suppress), between
+    # the channel and the link
+    mixer = DynamicMixer(engine, noise, rirs, suppressor=SuppressorSampler(p=0.5, floor_db=(-25.0, -6.0)))
 """
 from __future__ import annotations
 
@@ -58,12 +61,13 @@ import torch
 import torch.utils.data
 
 from .data import _natural_key, fit_length, read_wav
-from .engine import RIR_TAIL_MAX_WINDOW, SCENE_MAX_HOP, SCENE_MAX_WAYPOINTS, STRETCH_HOP, STRETCH_SEARCH, RirStats, RirTail, _whole_in, transmit_scalars
+from .engine import (RIR_TAIL_MAX_WINDOW, SCENE_MAX_HOP, SCENE_MAX_WAYPOINTS, STRETCH_HOP, STRETCH_SEARCH, SUPPRESS_MAX_WINDOW,
+                     SUPPRESS_N_FFT, SUPPRESS_RULES, RirStats, RirTail, _whole_in, transmit_scalars)
 
 __all__ = ["NoiseBank", "NoiseSampler", "NoiseDraw", "noise_fir", "power_law_magnitude", "RirBank", "RoomSampler", "sabine_beta", "octave_filterbank", "DynamicMixer", "MixingLoader", "CleanDataset",
            "clean_only", "Draw", "SceneDraw", "tile", "ChannelSampler", "biquad_peaking", "biquad_low_shelf", "biquad_high_shelf",
            "biquad_lowpass", "biquad_highpass", "butter_lowpass_sos", "warp_len", "stretch_len", "StretchDraw", "TailDraw", "PathDraw",
-           "TransmissionSampler", "TransmitDraw", "TransmitInfo"]
+           "TransmissionSampler", "TransmitDraw", "TransmitInfo", "SuppressorSampler", "SuppressDraw", "suppress_params", "suppress_n_fft"]
 
 SPEED_OF_SOUND = 343.0        # m/s, the default `c` of Engine.rir
 RIR_TW = 40                   # the default half-width of its fractional-delay filter, in samples
@@ -924,6 +928,89 @@ class TransmissionSampler:
         return TransmitDraw(self.pattern(u[:, 5:], p_gb, q).contiguous(), codec, plc, rate, burst)
 
 
+# ---- suppression: the table of Engine.suppress from audio units, and a sampler of it ---------------------------------------
+def suppress_n_fft(fs: int) -> int:
+    """The transform size the mixer and the baseline use at `fs`: 512 below 32 kHz (32 ms at 16 kHz), 1024 from there."""
+    return 512 if fs < 32000 else 1024
+
+
+def suppress_params(rule, floor_db=-20.0, bias=1.5, a_dd=0.98, a_n=0.8, window_s=1.0, xi_min_db=-25.0, fs=16000,
+                    n_fft: Optional[int] = None) -> torch.Tensor:
+    """The float64 [..., 7] table of Engine.suppress, (rule, a_dd, a_n, D, bias, g_min, xi_min) per row, from audio units:
+    `rule` is "off", "wiener", "specsub" or "logmmse" (SUPPRESS_RULES; or a tensor of the codes 0 .. 3), g_min =
+    10^(floor_db / 20) is the largest attenuation, D = round(window_s fs / (n_fft / 2)) frames the minimum search looks back
+    over, kept inside 1 .. 128, xi_min = 10^(xi_min_db / 10); bias, a_dd and a_n go in as they are.  n_fft None: the size
+    suppress_n_fft(fs) gives.  Plain float64 tensor arithmetic on the device of its arguments; what the result allows is
+    judged per row by the kernels."""
+    if isinstance(rule, str):
+        if rule not in SUPPRESS_RULES:
+            raise ValueError(f"rule must be one of {tuple(SUPPRESS_RULES)}, got {rule!r}")
+        rule = float(SUPPRESS_RULES[rule])
+    if not _whole_in(fs, 1, 2 ** 31 - 1):
+        raise ValueError(f"fs must be a sample rate (a whole number >= 1), got {fs}")
+    n_fft = suppress_n_fft(int(fs)) if n_fft is None else n_fft
+    if isinstance(n_fft, bool) or n_fft not in SUPPRESS_N_FFT:
+        raise ValueError(f"n_fft must be one of {SUPPRESS_N_FFT}, got {n_fft}")
+    like = next((v for v in (rule, floor_db, bias, a_dd, a_n, window_s, xi_min_db) if isinstance(v, torch.Tensor)), None)
+    rule, floor, bias, a_dd, a_n, window, xi = (_f64(v, like) for v in (rule, floor_db, bias, a_dd, a_n, window_s, xi_min_db))
+    D = torch.clamp(torch.round(window * (float(fs) / (n_fft // 2))), 1.0, float(SUPPRESS_MAX_WINDOW))
+    cols = torch.broadcast_tensors(rule, a_dd, a_n, D, bias, torch.pow(10.0, floor / 20.0), torch.pow(10.0, xi / 10.0))
+    return torch.stack(cols, dim=-1).contiguous()
+
+
+class SuppressDraw(NamedTuple):
+    """What a SuppressorSampler drew for a batch: the float64 [B, 7] table of Engine.suppress and its n_fft."""
+    table: torch.Tensor
+    n_fft: int
+
+
+class SuppressorSampler:
+    """Random noise suppressors for Engine.suppress: `draw(B, fs, device)` -> `SuppressDraw(table, n_fft)`.
+
+    Per row, with probability `p`, a suppressor: the rule - Wiener, power spectral subtraction or log-MMSE with
+    probabilities `p_wiener`, `p_specsub` and the rest (their sum at most 1) - a gain floor uniform in `floor_db` (dB, at
+    most 0), a noise over-estimation `bias` uniform in (0, 16], the decision-directed smoothing `a_dd` and the periodogram
+    smoothing `a_n` uniform in their ranges inside [0, 1), and a minimum-search window uniform in `window_s` seconds;
+    `xi_min_db` is one value for all.  A row that is not chosen gets rule 0, which Engine.suppress copies bit for bit; its
+    other entries stay valid.  n_fft is suppress_n_fft(fs).  Everything is drawn from `generator` (None: the device's default
+    one) on the device with tensor arithmetic, one rand call of [B, 7] float64: no host synchronisation."""
+
+    def __init__(self, p: float = 0.5, p_wiener: float = 1.0 / 3.0, p_specsub: float = 1.0 / 3.0, floor_db=(-25.0, -6.0),
+                 bias=(1.0, 3.0), a_dd=(0.9, 0.99), window_s=(0.4, 1.5), a_n=(0.7, 0.9), xi_min_db: float = -25.0,
+                 generator: Optional[torch.Generator] = None):
+        self.p, self.p_wiener, self.p_specsub = (
+            _probability(name, v) for name, v in (("p", p), ("p_wiener", p_wiener), ("p_specsub", p_specsub)))
+        if self.p_wiener + self.p_specsub > 1.0 + 1e-12:
+            raise ValueError(f"p_wiener + p_specsub must not exceed 1, got {self.p_wiener + self.p_specsub}")
+        self.floor_db = _pair("floor_db", floor_db, -math.inf, 0.0, "(low, high) dB with -inf < low <= high <= 0")
+        if self.floor_db[0] == -math.inf:
+            raise ValueError(f"floor_db must be (low, high) dB with -inf < low <= high <= 0, got {floor_db}")
+        self.bias = _pair("bias", bias, 0.0, 16.0, "(low, high) with 0 < low <= high <= 16")
+        if self.bias[0] <= 0.0:
+            raise ValueError(f"bias must be (low, high) with 0 < low <= high <= 16, got {bias}")
+        self.a_dd, self.a_n = (_pair(name, v, 0.0, 1.0, "(low, high) with 0 <= low <= high < 1") for name, v in (("a_dd", a_dd), ("a_n", a_n)))
+        for name, pair, given in (("a_dd", self.a_dd, a_dd), ("a_n", self.a_n, a_n)):
+            if pair[1] >= 1.0:
+                raise ValueError(f"{name} must be (low, high) with 0 <= low <= high < 1, got {given}")
+        self.window_s = _positive_pair("window_s", window_s)
+        if isinstance(xi_min_db, bool) or not isinstance(xi_min_db, (int, float)) or not -math.inf < xi_min_db <= 0.0:
+            raise ValueError(f"xi_min_db must be a finite level <= 0 in dB, got {xi_min_db}")
+        self.xi_min_db, self.generator = float(xi_min_db), generator
+
+    def draw(self, B: int, fs: int, device=None) -> SuppressDraw:
+        gen = self.generator
+        device = torch.device(device) if device is not None else (gen.device if gen is not None else torch.device("cpu"))
+        u = torch.rand(B, 7, dtype=torch.float64, generator=gen, device=device)
+        uniform = lambda r, v: r[0] + (r[1] - r[0]) * v
+        a, b = self.p_wiener, self.p_wiener + self.p_specsub
+        rule = 1.0 + (u[:, 1] >= a).to(torch.float64) + (u[:, 1] >= b).to(torch.float64)
+        rule = torch.where(u[:, 0] < self.p, rule, torch.zeros_like(rule))
+        n_fft = suppress_n_fft(int(fs))
+        table = suppress_params(rule, uniform(self.floor_db, u[:, 2]), uniform(self.bias, u[:, 3]), uniform(self.a_dd, u[:, 4]),
+                                uniform(self.a_n, u[:, 6]), uniform(self.window_s, u[:, 5]), self.xi_min_db, fs, n_fft)
+        return SuppressDraw(table, n_fft)
+
+
 # ---- synthetic noise: the colouring filter of Engine.noise from a magnitude, and a sampler of its tables ----------------
 NOISE_GRID = 4096             # points of the frequency grid the magnitudes are given on: [N, NOISE_GRID / 2 + 1]
 NOISE_MAX_TAPS = 1023         # = cmgan_noise_max_filter()
@@ -1410,7 +1497,16 @@ class DynamicMixer:
     "noisy"` (the default) leaves the target as it is: the model is asked to undo the link too.  `transmission_on="both"`
     also sends `target` through the same call with the same tables - it loses the same packets and conceals them from its
     OWN history - so the task stays denoising.  `mixer.last_transmission` is a TransmitInfo: the draw, and the status and
-    lags the kernels reported."""
+    lags the kernels reported.
+
+    `suppressor` (a SuppressorSampler): the recording device's own single-channel noise suppressor (Engine.suppress /
+    cmgan_suppress), between the channel and the link: what it leaves behind - musical noise, speech attenuated where the
+    SNR is low, a floor that pumps with the estimate - is what most real "noisy" recordings carry.  With None nothing is
+    drawn or launched, and the outputs, `last_draw` and every generator state are what they are without the argument.
+    With a sampler, a suppressor per row is drawn after the dynamics draw and before the link's, from the sampler's own
+    generator, and `noisy` goes through it in place at n_fft = suppress_n_fft(sample_rate).  `suppressor_on="noisy"` (the
+    default) leaves the target as it is; `suppressor_on="both"` first gives `target` the gains that `noisy` drives (key =
+    noisy), so the task stays denoising.  `mixer.last_suppression` is the SuppressDraw (table, n_fft)."""
 
     def __init__(self, engine, noise_bank: NoiseBank, rir_bank: Optional[RirBank] = None, snr_db=(0.0, 20.0),
                  early_ms: Optional[float] = 50.0, p_reverb: float = 1.0, peak: float = 0.99,
@@ -1422,7 +1518,8 @@ class DynamicMixer:
                  p_pitch: float = 1.0, stretch_hop: int = 256, stretch_search: int = 160, room_stats: bool = False,
                  motion=None, p_motion: float = 1.0, motion_hop_ms: float = 250.0, source_motion=None,
                  dynamics: Optional[DynamicsSampler] = None, dynamics_on: str = "noisy", noise: Optional[NoiseSampler] = None,
-                 transmission: Optional["TransmissionSampler"] = None, transmission_on: str = "noisy"):
+                 transmission: Optional["TransmissionSampler"] = None, transmission_on: str = "noisy",
+                 suppressor: Optional["SuppressorSampler"] = None, suppressor_on: str = "noisy"):
         if sources is not None:
             given, counts = sources, "(low, high) whole numbers with 0 <= low <= high and 1 <= high <= 4"
             sources = _pair("sources", given, 0, 4, counts, "None or (low, high)", whole=True)
@@ -1547,6 +1644,13 @@ class DynamicMixer:
                 raise ValueError(f"transmission at sample_rate = {sample_rate}: {e}") from None
         self.transmission, self.transmission_on = transmission, transmission_on
         self.last_transmission: Optional[TransmitInfo] = None
+        # ---- suppressor: judged after the transmission, so that every earlier error is what it was
+        if suppressor_on not in ("noisy", "both"):
+            raise ValueError(f"suppressor_on must be 'noisy' or 'both', got {suppressor_on!r}")
+        if suppressor is not None and not isinstance(suppressor, SuppressorSampler):
+            raise TypeError(f"suppressor must be a SuppressorSampler or None, got {type(suppressor).__name__}")
+        self.suppressor, self.suppressor_on = suppressor, suppressor_on
+        self.last_suppression: Optional[SuppressDraw] = None    # suppressor=...: the table and n_fft the batch went through
 
     def waypoints(self, N: int) -> int:
         """P = 1 + ceil((N - 1) / H): the waypoints a batch of N samples needs; more than 64 is refused."""
@@ -1833,8 +1937,9 @@ class DynamicMixer:
         if paths is not None:                                     # who moves: the last draw of all
             d = self.last_draw = d._replace(n_path=self._draw_moving(B, paths))
         dyn = None if self.dynamics is None else self.dynamics.draw(B, self.sample_rate, device=self.engine.device)
-        # the link is the last draw of the call: _perturb, _level, _mix, _dynamics and _channel below draw nothing (a stage that
-        # does would have to draw above this line, or a sampler on the device's default generator would no longer come last)
+        sup = None if self.suppressor is None else self.suppressor.draw(B, self.sample_rate, device=self.engine.device)
+        # the link is the last draw of the call: _perturb, _level, _mix, _dynamics, _channel and _suppression below draw nothing (a
+        # stage that does would have to draw above this line, or a sampler on the device's default generator would no longer come last)
         link = None if self.transmission is None else self.transmission.draw(
             B, -(-self.stretch_len(clean.size(1)) // self.transmission.frame(self.sample_rate)), device=self.engine.device)
         clean = self._perturb(d, s, clean)
@@ -1843,6 +1948,8 @@ class DynamicMixer:
         if dyn is not None:
             d = self.last_draw = self._dynamics(d, dyn, noisy, target)
         self._channel(d, noisy, target)
+        if sup is not None:
+            self._suppression(sup, noisy, target)
         if link is not None:
             self._transmission(link, noisy, target)
         return target, noisy, info
@@ -1928,6 +2035,14 @@ class DynamicMixer:
         self.engine.channel(noisy, sos, n_sections, self.channel_clip(clip_rel, noisy), out=noisy)
         if self.channel_on == "both":
             self.engine.channel(target, sos, n_shared, out=target)
+
+    def _suppression(self, sup: SuppressDraw, noisy: torch.Tensor, target: torch.Tensor) -> None:
+        """The device's noise suppressor, in place: on noisy, and with suppressor_on="both" the gains that noisy drives on
+        target first."""
+        if self.suppressor_on == "both":
+            self.engine.suppress(target, sup.table, sup.n_fft, key=noisy, out=target)
+        self.engine.suppress(noisy, sup.table, sup.n_fft, out=noisy)
+        self.last_suppression = sup
 
     def _transmission(self, link: TransmitDraw, noisy: torch.Tensor, target: torch.Tensor) -> None:
         """The link, in place: on noisy, and with transmission_on="both" the same tables on target."""

@@ -39,7 +39,7 @@ extern "C" {
 #define CMGAN_E_WORKSPACE   -5   /* workspace too small or misaligned              */
 #define CMGAN_E_HIP         -6   /* a HIP runtime call failed (see last_error)     */
 
-#define CMGAN_ABI_VERSION 22
+#define CMGAN_ABI_VERSION 23
 
 typedef struct cmgan_handle cmgan_handle;
 
@@ -1327,6 +1327,68 @@ int cmgan_transmit(cmgan_handle* h, const float* x_dev, int B, int L, long long 
                    const unsigned char* lost_dev, long long ldl, const int* codec_dev, const int* plc_dev, int frame,
                    int pmin, int pmax, int window, int fade, float* y_dev, long long ldy, int* status_dev, int* lag_dev,
                    void* stream);
+
+/* ---- Suppression: the recording device's own noise suppressor (the reference has no counterpart: its data path replays
+ * fixed pairs, src/data/dataloader.py, so the enhancer never meets what a phone's or a headset's suppressor leaves behind;
+ * the same call is the classical baseline - Wiener, spectral subtraction, Ephraim and Malah's log-MMSE) -----------------
+ * Every row of a [B, L] float32 batch x_dev[b * ldx + k] goes through a short-time spectral gain of its OWN; the result is
+ * y_dev[b * ldy + k].  key_dev (NULL: the key is x) is a batch of the same shape whose spectrum drives the gains.
+ * lengths_dev int32 [B] (NULL: n = L), table_dev float64 [B][7], status_dev int32 [B] and gain_dev float64 [B][T][F] (the
+ * last two may be NULL) are in DEVICE memory and read / written by the kernels only.  n_fft = N is a host value, 256, 512
+ * or 1024; h = N / 2 (the hop), F = N / 2 + 1, T = ceil(L / h) + 1.  A table row is
+ *   0 rule    0 off, 1 Wiener, 2 power spectral subtraction, 3 log-MMSE            an integer 0 .. 3
+ *   1 a_dd    decision-directed smoothing                                          [0, 1)
+ *   2 a_n     periodogram smoothing                                                [0, 1)
+ *   3 D       minimum-search window in frames                                      an integer 1 .. cmgan_suppress_max_window() = 128
+ *   4 bias    noise over-estimation                                                (0, 16]
+ *   5 g_min   gain floor                                                           (0, 1]
+ *   6 xi_min                                                                       [0, 1]
+ * For row b with n = lengths[b], T_b = ceil(n / h) + 1 (0 when n = 0) and w[k] = sin(pi k / N), the square root of the
+ * periodic Hann window (w[k]^2 + w[k + h]^2 = 1):
+ *   1. Analysis.  Frame t holds s_t[k] = x~[(t - 1) h + k] w[k], k = 0 .. N-1, with x~ the row as float64 inside [0, n) and 0
+ *      outside; Y_t[f] = sum_k s_t[k] e^{-2 pi i f k / N}, K_t the same from the key, A_t[f] = Re(K_t[f])^2 + Im(K_t[f])^2.
+ *   2. Gain, per bin f, t ascending:
+ *        P_t   = a_n P_{t-1} + (1 - a_n) A_t,  P_{-1} = A_0
+ *        lam_t = max(bias min_{max(0, t-D+1) <= u <= t} P_u, 2^-60)
+ *        gam_t = min(A_t / lam_t, 40)
+ *        xi_t  = max(a_dd G_{t-1}^2 gam_{t-1} + (1 - a_dd) max(gam_t - 1, 0), xi_min)        (t = 0: without the first term)
+ *        q     = xi_t / (1 + xi_t)
+ *        G     = q (rule 1);  sqrt(q) (rule 2);  min(q exp(E1(max(q gam_t, 2^-30)) / 2), 1) (rule 3);   G_t = max(G, g_min)
+ *      E1 is the exponential integral, by two fixed formulas:
+ *        x < 2:   E1(x) = (-gamma - ln x) + x s_1,  s_K = c_K,  s_k = fma(s_{k+1}, x, c_k),  c_k = (-1)^(k+1) / (k k!), K = 26 (k!
+ *                 a running float64 product, gamma = 0.5772156649015329);
+ *        x >= 2:  E1(x) = e^-x d / n from the continued fraction e^-x / (x + 1 - 1 / (x + 3 - 4 / (x + 5 - 9 / ...))) cut at
+ *                 depth 40 and run backwards: (n, d) = (x + 81, 1), then for k = 40 .. 1: (n, d) <- ((x + 2 k - 1) n - k^2 d, n).
+ *      Both are within 1e-15 (absolute) of E1 on [2^-30, 45]; only the absolute error reaches G.
+ *   3. Synthesis.  Z_t = G_t Y_t, z_t its real inverse transform with the factor 1 / N; for 0 <= i < n, t = floor(i / h), r =
+ *      i mod h:   y[i] = f32(z_t[r + h] w[r + h] + z_{t+1}[r] w[r]),  the earlier frame first.
+ *   y[i] = 0 for n <= i < L (samples from n on are never read);  status[b] = 0;  gain[b, t, f] = G_t[f] for t < T_b, 0 for T_b
+ *   <= t < T.
+ * Rule 0 copies the row's n samples bit for bit, NaN included, computes nothing and reports gains of 1.  A row is INVALID
+ * - status 1, L zeros, gains 0 - when a table entry is not finite or outside its range, rule or D is no integer, or the
+ * length lies outside [0, L]; the other entries are judged at rule 0 too.  Non-finite samples are no error: they stay in
+ * their row.  Float64 arithmetic with one rounding to float32 per sample; every step is a continuous function of its
+ * inputs, so a float64 model agrees to rounding.
+ * Method.  Three launches.  A block per (row, frame) windows the frame into LDS as complex float64, runs a radix-2 transform
+ * there and writes bins 0 .. N / 2 to the workspace (complex128 [B][T][F]) and A to a float64 [B][T][F] plane; with a key the
+ * same code runs again on the key's frame, so a key that is x gives the bits of no key.  The gain is a serial chain along
+ * t per (row, bin): a thread per bin, a wave per 64 consecutive bins, G written over A; the sliding minimum is exact (a
+ * ring of D values per thread in LDS, suffix minima of the last block of D frames and a running prefix of this one).  A
+ * block per (row, h outputs) then rebuilds the two frames its span needs and adds them in the stated order.  No atomics;
+ * row b's bits depend neither on B, nor on the other rows, nor on the padding behind ldx / ldk / ldy, nor on L beyond n.
+ * cmgan_suppress_workspace_bytes(B, L, n_fft) is what ws must hold (256-byte aligned; 24 B T F bytes, each plane rounded
+ * up to 256; 0 for a shape the kernels do not take).
+ * Checked before the launch and before the handle is looked at (the message of a call with h == NULL is read with
+ * cmgan_last_error(NULL)): null x / table / y, pointers to float32 / int32 that are not 4-byte aligned, float64 pointers
+ * that are not 8-byte aligned, n_fft other than 256 / 512 / 1024, 1 <= B <= 65535, 1 <= L <= 2^31 - 1 - 2048, ldx >= L, ldy
+ * >= L, ldk >= L with a key, any intersection of y's span with x's other than y == x with ldy == ldx (in place) and with the
+ * key's other than y == key with ldy == ldk, and the workspace; each is CMGAN_E_BADARG.  No synchronisation, no
+ * allocation; graph-capturable, and a replay reads the current contents of x, the key, the table and the lengths.   */
+int cmgan_suppress_max_window(void);
+size_t cmgan_suppress_workspace_bytes(int B, int L, int n_fft);
+int cmgan_suppress(cmgan_handle* h, const float* x_dev, int B, int L, long long ldx, const float* key_dev, long long ldk,
+                   const int* lengths_dev, const double* table_dev, int n_fft, float* y_dev, long long ldy, int* status_dev,
+                   double* gain_dev, void* ws, size_t ws_bytes, void* stream);
 
 /* Names + durations (ms) of the kernels of the most recent forward when
  * profiling is enabled with cmgan_set_profiling(h, 1): HIP events are recorded
