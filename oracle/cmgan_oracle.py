@@ -260,8 +260,31 @@ def _instance_norm(x, w, b, key):
     return (x - mean) / torch.sqrt(var + EPS) * w.view(1, -1, 1, 1) + b.view(1, -1, 1, 1)
 
 
+class prelu_inputs:
+    """Context manager: every PReLU of the generator's conv path (the InstanceNorm + PReLU pairs and the mask head's
+    per-bin output PReLU) stores min |input| in d[<its state-dict prefix>] - how far the nearest pre-activation is from
+    the kink, for tests whose gradient bars assume that rounding moves none across it."""
+    active = None
+
+    def __init__(self, store: dict):
+        self.store = store
+
+    def __enter__(self):
+        self.prev, prelu_inputs.active = prelu_inputs.active, self
+        return self.store
+
+    def __exit__(self, *exc):
+        prelu_inputs.active = self.prev
+
+
+def _note_prelu_input(key, x):
+    if prelu_inputs.active is not None:
+        prelu_inputs.active.store[key] = float(x.detach().abs().min())
+
+
 def _in_prelu(sd, norm, prelu, x):
     x = _instance_norm(x, sd[norm + ".weight"], sd[norm + ".bias"], norm)
+    _note_prelu_input(prelu, x)
     return F.prelu(x, sd[prelu + ".weight"])
 
 
@@ -316,6 +339,7 @@ def mask_decoder(sd, x):
     x = _in_prelu(sd, p + ".norm", p + ".prelu", x)
     x = F.conv2d(x, sd[p + ".final_conv.weight"], sd[p + ".final_conv.bias"])
     a = sd[p + ".prelu_out.weight"].view(1, 1, 1, -1)          # slope per frequency bin
+    _note_prelu_input(p + ".prelu_out", x)
     return torch.where(x >= 0, x, a * x)
 
 
