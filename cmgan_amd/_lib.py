@@ -138,6 +138,8 @@ SIGNATURES = {
                                                c_void_p, c_void_p]),
     "cmgan_loss_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float,
                                     c_float, c_float, c_void_p, c_void_p, c_void_p]),
+    "cmgan_loss_backward_aux": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float,
+                                        c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cmgan_disc_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "cmgan_disc_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(DiscParams), c_void_p, c_int, c_void_p,
                                    c_void_p, c_size_t, c_void_p]),
@@ -276,6 +278,10 @@ SIGNATURES = {
     "cmgan_suppress_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "cmgan_suppress": (c_int, [c_void_p, c_void_p, c_int, c_int, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p, c_int,
                                c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "cmgan_aux_loss_max_resolutions": (c_int, []),
+    "cmgan_aux_loss_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_void_p]),
+    "cmgan_aux_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_double, c_double, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "cmgan_set_profiling": (c_int, [c_void_p, c_int]),
     "cmgan_profile_read": (c_int, [c_void_p, POINTER(KernelTime), c_int]),
 }

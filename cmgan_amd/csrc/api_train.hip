@@ -371,6 +371,25 @@ extern "C" int cmgan_loss_backward(cmgan_handle* h, const float* est_real, const
     return check_launch(h, "loss_backward");
 }
 
+extern "C" int cmgan_loss_backward_aux(cmgan_handle* h, const float* est_real, const float* est_imag,
+                                       const float* clean_spec, int B, int T, const float* est_audio,
+                                       const float* clean_audio, float w_ri, float w_mag, float w_time,
+                                       const float* g_audio, float* d_real, float* d_imag, void* stream) {
+    if (!g_audio)                                             // the same launch, so the same bits
+        return cmgan_loss_backward(h, est_real, est_imag, clean_spec, B, T, est_audio, clean_audio, w_ri, w_mag, w_time, d_real,
+                                   d_imag, stream);
+    if (!h) return CMGAN_E_BADARG;
+    if (!est_real || !est_imag || !clean_spec || !d_real || !d_imag || B <= 0 || T <= 1)
+        return fail(h, CMGAN_E_BADARG, "cmgan_loss_backward_aux: bad argument");
+    if ((est_audio == nullptr) != (clean_audio == nullptr))
+        return fail(h, CMGAN_E_BADARG, "cmgan_loss_backward_aux: the time term needs est_audio and clean_audio");
+    if (w_time != 0.f && !est_audio)
+        return fail(h, CMGAN_E_BADARG, "cmgan_loss_backward_aux: w_time != 0 needs est_audio and clean_audio");
+    launch_loss_backward(begin(h, stream), est_real, est_imag, clean_spec, est_audio, clean_audio, B, T,
+                         h->cfg.num_features, h->cfg.n_fft, h->cfg.hop, w_ri, w_mag, w_time, d_real, d_imag, g_audio);
+    return check_launch(h, "loss_backward_aux");
+}
+
 // ---- metric discriminator --------------------------------------------------------------------------------------------
 static bool disc_params_ok(const cmgan_disc_params* p, bool need_uv) {
     if (!p) return false;

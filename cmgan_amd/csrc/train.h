@@ -115,7 +115,7 @@ void launch_tsc_epilogue_backward(LaunchCtx, const float* spec, const float* d_r
 // gradient of w_ri loss_ri + w_mag loss_mag + w_time time_loss (train.py:133-148) with respect to est_real / est_imag
 void launch_loss_backward(LaunchCtx, const float* est_real, const float* est_imag, const float* clean_spec,
                           const float* est_audio, const float* clean_audio, int B, int T, int F, int nfft, int hop, float w_ri,
-                          float w_mag, float w_time, float* d_real, float* d_imag);
+                          float w_mag, float w_time, float* d_real, float* d_imag, const float* g_audio = nullptr);
 // Column sums of one 16-token tile's LayerNorm-gradient rows - a = dxn * xhat (dgamma), b = dxn (dbeta), 16 features of
 // each per lane in the chain layout - reduced over the tile's tokens with DPP row sums and written as row `tile` of two
 // [tiles][64] slabs: the column-sum pass then reads 1/16 of what the full [M,64] tensors were (which existed only to

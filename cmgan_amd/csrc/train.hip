@@ -3611,9 +3611,13 @@ void launch_tsc_epilogue_backward(LaunchCtx ctx, const float* spec, const float*
 //   dL/der = s gUr + (p-1) |e|^(p-3) er (er gUr + ei gUi),   s = |e|^(p-1)   (same for ei).
 __device__ __forceinline__ float hamming_periodic(int k, int n) { return 0.54f - 0.46f * cospif(2.0f * (float)k / (float)n); }
 
+// AUX: a caller's waveform gradient g_audio [B, hop (T-1)] (cmgan_loss_backward_aux) joins the time term's per-sample gradient
+// before the window and envelope step; the time term itself may then be absent.  AUX = false is cmgan_loss_backward.
+template <bool AUX>
 __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__ est_real, const float* __restrict__ est_imag,
                                                        const float* __restrict__ clean_spec, const float* __restrict__ est_audio,
-                                                       const float* __restrict__ clean_audio, int B, int T, int F, int nfft,
+                                                       const float* __restrict__ clean_audio,
+                                                       const float* __restrict__ g_audio, int B, int T, int F, int nfft,
                                                        int hop, float w_ri, float w_mag, float w_time,
                                                        float* __restrict__ d_real, float* __restrict__ d_imag) {
     extern __shared__ float sm[];
@@ -3622,7 +3626,8 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__
     float* ts = sm + 2 * nfft;      // [nfft] sin(2 pi j / nfft)
     const int b = blockIdx.x / T, t = blockIdx.x - b * T;
     const long La = (long)hop * (T - 1);
-    const bool has_time = est_audio && clean_audio && w_time != 0.f;
+    const bool has_l1 = est_audio && clean_audio && w_time != 0.f;
+    const bool has_time = has_l1 || AUX;
     if (has_time) {
         const float ga = w_time / (float)((double)B * (double)La);
         for (int k = threadIdx.x; k < nfft; k += 256) {
@@ -3637,8 +3642,9 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__
                 int t0 = (int)((n - nfft + hop) / hop); if (t0 < 0) t0 = 0;
                 int t1 = (int)(n / hop); if (t1 > T - 1) t1 = T - 1;
                 for (int tt = t0; tt <= t1; ++tt) { const float w = hamming_periodic((int)(n - (long)tt * hop), nfft); env = fmaf(w, w, env); }
-                const float d = est_audio[b * La + a] - clean_audio[b * La + a];
-                const float sg = d > 0.f ? ga : (d < 0.f ? -ga : 0.f);
+                const float d = has_l1 ? est_audio[b * La + a] - clean_audio[b * La + a] : 0.f;
+                float sg = d > 0.f ? ga : (d < 0.f ? -ga : 0.f);
+                if (AUX) sg += g_audio[b * La + a];
                 v = sg * hamming_periodic(k, nfft) / env;
             }
             df[k] = v;
@@ -3677,8 +3683,13 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__
 }
 void launch_loss_backward(LaunchCtx ctx, const float* est_real, const float* est_imag, const float* clean_spec,
                           const float* est_audio, const float* clean_audio, int B, int T, int F, int nfft, int hop, float w_ri,
-                          float w_mag, float w_time, float* d_real, float* d_imag) {
-    LAUNCH(ctx, "loss_backward", (loss_bwd_kernel<<<B * T, 256, 3 * nfft * sizeof(float), ctx.stream>>>(
-                                     est_real, est_imag, clean_spec, est_audio, clean_audio, B, T, F, nfft, hop, w_ri, w_mag, w_time,
-                                     d_real, d_imag)));
+                          float w_mag, float w_time, float* d_real, float* d_imag, const float* g_audio) {
+    if (g_audio)
+        LAUNCH(ctx, "loss_backward", (loss_bwd_kernel<true><<<B * T, 256, 3 * nfft * sizeof(float), ctx.stream>>>(
+                                         est_real, est_imag, clean_spec, est_audio, clean_audio, g_audio, B, T, F, nfft, hop, w_ri,
+                                         w_mag, w_time, d_real, d_imag)));
+    else
+        LAUNCH(ctx, "loss_backward", (loss_bwd_kernel<false><<<B * T, 256, 3 * nfft * sizeof(float), ctx.stream>>>(
+                                         est_real, est_imag, clean_spec, est_audio, clean_audio, nullptr, B, T, F, nfft, hop, w_ri,
+                                         w_mag, w_time, d_real, d_imag)));
 }

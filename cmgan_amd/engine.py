@@ -755,6 +755,75 @@ def check_suppress_args(device, wav, table, n_fft=512, lengths=None, key=None, o
     return B, L
 
 
+AUX_N_FFT = (256, 512, 1024, 2048)      # the window lengths of Engine.aux_loss (hop = n / 4)
+AUX_MAX_RESOLUTIONS = 4
+AUX_MAX_L = 2 ** 31 - 1 - 4096
+
+
+class AuxLossOut(NamedTuple):
+    """Engine.aux_loss: device tensors, nothing copied to the host."""
+    total: torch.Tensor              # float32 [3]: A, its multi-resolution part, its SI-SDR part
+    rows: torch.Tensor               # float64 [B, 2 R + 1]: (sc, lm) per resolution in n_ffts' order, then SI-SDR in dB
+    grad: Optional[torch.Tensor]     # float32 [B, L] = dA / d est, or None (grad=False)
+
+
+def check_aux_settings(n_ffts, w_mr, w_si):
+    """The settings of Engine.aux_loss / training.AuxLoss (pure host code): 1 .. 4 distinct window lengths from AUX_N_FFT,
+    two finite weights >= 0.  Returns (tuple of ints, float, float)."""
+    try:
+        res = tuple(n_ffts)
+    except TypeError:
+        raise TypeError(f"n_ffts: expected a sequence of window lengths, got {type(n_ffts).__name__}") from None
+    if not 1 <= len(res) <= AUX_MAX_RESOLUTIONS:
+        raise ValueError(f"n_ffts: need 1 to {AUX_MAX_RESOLUTIONS} resolutions, got {len(res)}")
+    for n in res:
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or int(n) not in AUX_N_FFT:
+            raise ValueError(f"n_ffts: a resolution must be one of {AUX_N_FFT}, got {n!r}")
+    res = tuple(int(n) for n in res)
+    if len(set(res)) != len(res):
+        raise ValueError(f"n_ffts: the resolutions must be distinct, got {res}")
+    out = []
+    for name, w in (("w_mr", w_mr), ("w_si", w_si)):
+        if isinstance(w, bool) or not isinstance(w, (int, float, np.integer, np.floating)):
+            raise TypeError(f"{name}: expected a number, got {type(w).__name__}")
+        if not (np.isfinite(w) and w >= 0):
+            raise ValueError(f"{name}: must be finite and >= 0, got {w}")
+        out.append(float(w))
+    return res, out[0], out[1]
+
+
+def aux_loss_workspace_bytes(B: int, L: int, n_ffts) -> int:
+    """cmgan_aux_loss_workspace_bytes: per resolution (T = 1 + L // (n / 4) frames of F = n / 2 + 1 bins) a complex128 and a
+    float64 [B, T, F] plane and float64 [B, T, 3] partial sums, then float64 [B, ceil(L / 4096), 5], [B, 4, 2] and [B, 4];
+    each rounded up to 256 bytes.  0 for arguments the kernels do not take."""
+    try:
+        res, _, _ = check_aux_settings(n_ffts, 0.0, 0.0)
+    except (TypeError, ValueError):
+        return 0
+    if not (1 <= B <= 65535 and max(res) // 2 < L <= AUX_MAX_L):
+        return 0
+    up = lambda v: (v + 255) & ~255
+    total = 0
+    for n in res:
+        T, F = 1 + L // (n // 4), n // 2 + 1
+        total += up(B * T * F * 16) + up(B * T * F * 8) + up(B * T * 3 * 8)
+    return total + up(B * (-(-L // 4096)) * 5 * 8) + up(B * 4 * 2 * 8) + up(B * 4 * 8)
+
+
+def check_aux_loss_args(device, est, ref, n_ffts=(512, 1024, 2048), w_mr=1.0, w_si=0.0):
+    """Argument rules of Engine.aux_loss (pure host code).  Returns (B, L, n_ffts, w_mr, w_si)."""
+    res, w_mr, w_si = check_aux_settings(n_ffts, w_mr, w_si)
+    tensor_arg(est, "est", torch.float32, device, "[B, L]", lambda t: t.dim() == 2 and t.size(0) >= 1)
+    B, L = (int(v) for v in est.shape)
+    tensor_arg(ref, "ref", torch.float32, device, f"[{B}, {L}]", lambda t: tuple(t.shape) == (B, L))
+    if B > 65535:
+        raise ValueError(f"est: at most 65535 rows, got {B}")
+    if not max(res) // 2 < L <= AUX_MAX_L:
+        raise ValueError(f"est: rows must hold more than {max(res) // 2} samples (reflect padding of the {max(res)}-point "
+                         f"window) and at most {AUX_MAX_L}, got {L}")
+    return B, L, res, w_mr, w_si
+
+
 def metric_frames(L: int, fs: int):
     """(WSS / segSNR frames, LLR frames) of an L-sample signal: the two counts of cmgan_amd.metrics."""
     win = int(np.round(30 * fs / 1000))
@@ -817,7 +886,7 @@ class Engine:
             msg = self.lib.cmgan_last_error(None)
             raise _lib.CmganError(rc, msg.decode() if msg else "?")
         #: grow-only uint8 workspaces by name (_grow): "main", "branched" (enhance_graphed(branches > 1)), "conformer",
-        #: "metrics", "mix", "scene", "rir", "rir_bands", "rir_dir", "rir_bands_dir", "level", "channel", "dynamics", "noise", "suppress" and ("resample", fs_in,
+        #: "metrics", "mix", "scene", "rir", "rir_bands", "rir_dir", "rir_bands_dir", "level", "channel", "dynamics", "noise", "suppress", "aux_loss" and ("resample", fs_in,
         #: fs_out), the rate pair's tap table
         self._wss: dict = {}
         self._graphs: dict = {}          # enhance_graphed: input shape -> (graph, in, out, token)
@@ -1886,6 +1955,35 @@ class Engine:
                    0 if key is None else (key.stride(0) if B > 1 else L), lengths, table, int(n_fft), out,
                    out.stride(0) if B > 1 else L, st, gain, ws, ws.numel())
         return (out, st, gain) if info else out
+
+    # ---- auxiliary losses: multi-resolution STFT loss and negative SI-SDR, with their gradient ----------
+    def _aux_workspace(self, B: int, L: int, n_ffts) -> torch.Tensor:
+        arr = (ctypes.c_int * len(n_ffts))(*n_ffts)
+        return self._grow("aux_loss", int(self.lib.cmgan_aux_loss_workspace_bytes(self._h, B, L, len(n_ffts), arr)),
+                          f"[{B}, {L}] at n_ffts = {tuple(n_ffts)} is outside what cmgan_aux_loss supports")
+
+    @_on_device
+    def aux_loss(self, est: torch.Tensor, ref: torch.Tensor, n_ffts=(512, 1024, 2048), w_mr: float = 1.0, w_si: float = 0.0,
+                 grad: bool = True) -> AuxLossOut:
+        """The multi-resolution STFT loss and negative SI-SDR of an estimate against a reference, with the gradient with
+        respect to the estimate (cmgan_aux_loss, include/cmgan_hip.h, "Auxiliary losses", states every formula).
+
+        est, ref float32 [B, L], contiguous, on this Engine's device; n_ffts 1 to 4 distinct window lengths from (256, 512,
+        1024, 2048), hop n / 4, periodic Hann, centred frames with reflect padding (L > max(n_ffts) / 2); w_mr, w_si >= 0
+        weigh the batch MEANS of the two terms: total = sum_b (w_mr / B) MR_b - (w_si / B) SISDR_b, so a row's outputs do
+        not depend on its neighbours.  Returns AuxLossOut(total float32 [3], rows float64 [B, 2 R + 1], grad float32 [B, L])
+        of device tensors; rows holds (spectral convergence, log-magnitude L1) per resolution and the row's SI-SDR in dB
+        whatever the weights are, so grad=False (grad is then None, total and rows keep their bits) is a scorer.  float64
+        arithmetic with one rounding, bit-reproducible, row-independent, no synchronisation; graph-capturable after one
+        call at the shape.  The gradient is never formed over est or ref."""
+        B, L, res, w_mr, w_si = check_aux_loss_args(self.device, est, ref, n_ffts, w_mr, w_si)
+        ws = self._aux_workspace(B, L, res)
+        rows = torch.empty(B, 2 * len(res) + 1, dtype=torch.float64, device=self.device)
+        total = torch.empty(3, dtype=torch.float32, device=self.device)
+        g = torch.empty(B, L, dtype=torch.float32, device=self.device) if grad else None
+        self._call("cmgan_aux_loss", est, ref, B, L, len(res), (ctypes.c_int * len(res))(*res), w_mr / B, w_si / B, rows, total,
+                   g, ws, ws.numel())
+        return AuxLossOut(total, rows, g)
 
     @_on_device
     def pitch_shift(self, wav: torch.Tensor, factor: torch.Tensor, n_out: Optional[int] = None, hop: int = 256,

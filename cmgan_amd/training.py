@@ -40,6 +40,10 @@ wheel - PESQ labels are an input).
                              185-193 without the metric-discriminator term): STFT, forward, ISTFT, loss, loss gradient
                              (incl. the ISTFT adjoint), backward, ONE gradient all-reduce, ONE AdamW launch.
 
+* `AuxLoss`                - settings of the optional auxiliary term of every training entry point (`aux=`): the
+                             multi-resolution STFT loss and negative SI-SDR of est_audio against the RMS-scaled clean
+                             batch (csrc/auxloss.hip), added to the loss and, through cmgan_loss_backward_aux, to its gradient.
+
 * `DiscriminatorTrain`     - the metric discriminator (src/models/discriminator.py:29-64) with spectral-norm power
                              iteration, forward + backward (csrc/disc.hip).
 * `adversarial_train_step` - Trainer.train_step (train.py:173-205): the generator step incl. the 0.05 * gen_loss_GAN
@@ -51,15 +55,16 @@ draws the dropout masks with torch's generator (plumbing) and passes pointers.
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Dict, Optional, Tuple
 
 import torch
 
 from ._lib import (AttnParams, ConvModParams, DecoderParams, DenseParams, DiscParams, EncoderParams, FfnParams)
 from .dist import FlatBucket, all_agree, allreduce_mean, broadcast_from_rank0, get_rank
-from .engine import Engine
+from .engine import Engine, check_aux_settings
 
-__all__ = ["Trainer", "batch_pesq", "GraphedTrainStep", "DiscriminatorTrain", "adversarial_train_step", "GeneratorTrain", "generator_train_step", "DenseEncoderTrain", "DecoderTrain", "DenseBlockTrain", "TSCBTrain", "ConformerBlockTrain", "FeedForwardTrain", "ConvModuleTrain", "AttentionTrain", "AdamW", "step_lr", "generator_loss_terms", "dropout_mask", "forward_generator_step",
+__all__ = ["Trainer", "AuxLoss", "batch_pesq", "GraphedTrainStep", "DiscriminatorTrain", "adversarial_train_step", "GeneratorTrain", "generator_train_step", "DenseEncoderTrain", "DecoderTrain", "DenseBlockTrain", "TSCBTrain", "ConformerBlockTrain", "FeedForwardTrain", "ConvModuleTrain", "AttentionTrain", "AdamW", "step_lr", "generator_loss_terms", "dropout_mask", "forward_generator_step",
            "validation_step"]
 
 _KEYS = ("fn.norm.weight", "fn.norm.bias", "fn.fn.net.0.weight", "fn.fn.net.0.bias",
@@ -796,6 +801,7 @@ class GeneratorTrain(_TrainModule):
         self.mask_decoder = DecoderTrain("mask", engine=eng, views=_subviews(views, "mask_decoder"))
         self.complex_decoder = DecoderTrain("complex", engine=eng, views=_subviews(views, "complex_decoder"))
         self._saved = None
+        self.last_aux = None                                    # (total, rows) of the last step's AuxLoss term, on the device
         self._mask_rng: Dict[int, torch.Tensor] = {}            # seed -> device {seed, offset} of the keep-mask generator
 
     def _draw_keep_bytes(self, nbytes: int, p: float, generator: Optional[torch.Generator]) -> torch.Tensor:
@@ -919,15 +925,62 @@ class GeneratorTrain(_TrainModule):
         return out
 
 
+@dataclass(frozen=True)
+class AuxLoss:
+    """Settings of the auxiliary audio-domain term of a training step (`aux=`): the multi-resolution STFT loss at the window
+    lengths `n_ffts` (1 to 4 distinct values from 256, 512, 1024, 2048) weighted `w_mr`, and negative SI-SDR in dB weighted
+    `w_si`, both as batch means (Engine.aux_loss).  Validated here, on the host; no default weighs a term in."""
+    n_ffts: tuple = (512, 1024, 2048)
+    w_mr: float = 0.0
+    w_si: float = 0.0
+
+    def __post_init__(self):
+        res, w_mr, w_si = check_aux_settings(self.n_ffts, self.w_mr, self.w_si)
+        object.__setattr__(self, "n_ffts", res)
+        object.__setattr__(self, "w_mr", w_mr)
+        object.__setattr__(self, "w_si", w_si)
+
+
+def _check_aux(aux) -> None:
+    if aux is not None and not isinstance(aux, AuxLoss):
+        raise TypeError(f"aux: expected an AuxLoss or None, got {type(aux).__name__}")
+
+
+def _aux_term(gen: "GeneratorTrain", aux: Optional[AuxLoss], est_audio, clean_cut, c):
+    """Engine.aux_loss of est_audio against clean_cut * c - est_audio lives in the RMS-normalised domain, so its target does
+    too (the reference's own time term keeps the raw clean batch) - kept as gen.last_aux = (total, rows); None without `aux`."""
+    if aux is None:
+        return None
+    out = gen.engine.aux_loss(est_audio, clean_cut * c[:, None], aux.n_ffts, aux.w_mr, aux.w_si, grad=True)
+    gen.last_aux = (out.total, out.rows)
+    return out
+
+
+def _loss_backward(eng, aux_out, est_real, est_imag, clean_spec, est_audio, clean_cut, loss_weights):
+    """(d_real, d_imag) of the non-adversarial loss, with the auxiliary term's waveform gradient when there is one."""
+    B, T = est_real.shape[0], est_real.shape[2]
+    d_real, d_imag = torch.empty_like(est_real), torch.empty_like(est_imag)
+    w = [float(x) for x in loss_weights[:3]]
+    if aux_out is None:
+        eng._call("cmgan_loss_backward", est_real, est_imag, clean_spec, B, T, est_audio, clean_cut, *w, d_real, d_imag)
+    else:
+        eng._call("cmgan_loss_backward_aux", est_real, est_imag, clean_spec, B, T, est_audio, clean_cut, *w, aux_out.grad,
+                  d_real, d_imag)
+    return d_real, d_imag
+
+
 def generator_train_step(gen: GeneratorTrain, optimizer: "AdamW", clean: torch.Tensor, noisy: torch.Tensor,
                          loss_weights=(0.1, 0.9, 0.2), generator: Optional[torch.Generator] = None, masks="draw",
-                         lr: Optional[float] = None, update: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+                         lr: Optional[float] = None, update: bool = True,
+                         aux: Optional[AuxLoss] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """One optimisation step of the generator on the non-adversarial loss - Trainer.train_step's generator half
     (train.py:153-193) with forward_generator_step (train.py:72-122) and calculate_generator_loss (train.py:124-151)
     minus the metric-discriminator term: returns (loss, float32[4] terms) of THIS rank before the update.
     clean, noisy: float32 [B, L] on the GPU, L a multiple of hop.  `masks="draw"` draws fresh dropout masks from
     `generator`; pass `gen.masks(...)`-shaped masks to fix them, or None to disable dropout.  `update=False` stops
-    after the backward pass (gradients in the bucket; no all-reduce, no optimiser launch)."""
+    after the backward pass (gradients in the bucket; no all-reduce, no optimiser launch).  `aux`: an AuxLoss adds its term
+    to the loss and the gradient (`terms` keeps its shape; the term's own values are gen.last_aux = (total, rows))."""
+    _check_aux(aux)
     eng = gen.engine
     clean, noisy = eng._in(clean, "clean"), eng._in(noisy, "noisy")
     B = noisy.shape[0]
@@ -942,9 +995,10 @@ def generator_train_step(gen: GeneratorTrain, optimizer: "AdamW", clean: torch.T
     La = est_audio.shape[-1]
     clean_cut = clean[:, :La].contiguous()                      # train.py:187: the time term sees the RAW clean batch
     loss, terms = generator_loss_terms(eng, est_real, est_imag, clean_spec, est_audio, clean_cut, loss_weights)
-    d_real, d_imag = torch.empty_like(est_real), torch.empty_like(est_imag)
-    eng._call("cmgan_loss_backward", est_real, est_imag, clean_spec, B, T, est_audio, clean_cut, float(loss_weights[0]),
-              float(loss_weights[1]), float(loss_weights[2]), d_real, d_imag)
+    aux_out = _aux_term(gen, aux, est_audio, clean_cut, c)
+    if aux_out is not None:
+        loss = loss + aux_out.total[0]
+    d_real, d_imag = _loss_backward(eng, aux_out, est_real, est_imag, clean_spec, est_audio, clean_cut, loss_weights)
     gen.backward(d_real, d_imag)                                # train.py:190 (loss.backward())
     if update:                                                  # False: stop after the backward (GraphedTrainStep)
         gen.allreduce_gradients()                               # DDP's gradient mean, one collective
@@ -1077,7 +1131,7 @@ class DiscriminatorTrain(_TrainModule):
 
 
 def _adversarial_generator_half(gen: GeneratorTrain, disc: DiscriminatorTrain, clean: torch.Tensor, noisy: torch.Tensor,
-                                loss_weights, generator, masks, disc_masks):
+                                loss_weights, generator, masks, disc_masks, aux: Optional[AuxLoss] = None):
     """train.py:100-151, 188-190: STFTs, train-mode generator forward, the full generator loss (RI, magnitude, time and
     the 0.05 x metric-discriminator term) and its backward.  Leaves the generator's gradient bucket filled and returns
     (loss, terms, gan, ctx); ctx carries what the discriminator half needs (est is 'detached' there: only values)."""
@@ -1103,9 +1157,10 @@ def _adversarial_generator_half(gen: GeneratorTrain, disc: DiscriminatorTrain, c
     score = disc.forward(xy, disc_masks[0], train=True, slot=0)               # train.py:126-128
     gan, dscore = disc.score_mse(score, None, scale=float(loss_weights[3]))    # train.py:129-131
     loss = base + float(loss_weights[3]) * gan
-    d_real, d_imag = torch.empty_like(est_real), torch.empty_like(est_imag)
-    eng._call("cmgan_loss_backward", est_real, est_imag, clean_spec, B, T, est_audio, clean_cut, float(loss_weights[0]),
-              float(loss_weights[1]), float(loss_weights[2]), d_real, d_imag)
+    aux_out = _aux_term(gen, aux, est_audio, clean_cut, c)
+    if aux_out is not None:
+        loss = loss + aux_out.total[0]
+    d_real, d_imag = _loss_backward(eng, aux_out, est_real, est_imag, clean_spec, est_audio, clean_cut, loss_weights)
     dxy = disc.backward(dscore, slot=0, need_input_grad=True)
     eng._call("cmgan_mag_pair_backward", est_real, est_imag, dxy, B, T, 1.0, d_real, d_imag)
     gen.backward(d_real, d_imag)                                              # train.py:190
@@ -1134,7 +1189,8 @@ def _agree_on_labels(pesq_score, device):
 def adversarial_train_step(gen: GeneratorTrain, disc: DiscriminatorTrain, opt_g: "AdamW", opt_d: "AdamW",
                            clean: torch.Tensor, noisy: torch.Tensor, pesq_score: Optional[torch.Tensor],
                            loss_weights=(0.1, 0.9, 0.2, 0.05), generator: Optional[torch.Generator] = None,
-                           masks="draw", disc_masks="draw", lr: Optional[float] = None, update: bool = True):
+                           masks="draw", disc_masks="draw", lr: Optional[float] = None, update: bool = True,
+                           aux: Optional[AuxLoss] = None):
     """Trainer.train_step (train.py:173-205): the generator step on the FULL loss (train.py:124-151: RI, magnitude,
     time and 0.05 x metric-discriminator terms), then the discriminator step (train.py:153-171) on `pesq_score`
     [B] = (PESQ - 1) / 3.5 of (clean, est_audio) - the labels discriminator.batch_pesq computes on the CPU; None (a
@@ -1148,9 +1204,12 @@ def adversarial_train_step(gen: GeneratorTrain, disc: DiscriminatorTrain, opt_g:
     Multi-rank: whether the discriminator step (which contains a collective) runs is decided by ALL ranks together - a
     batch whose labels are missing on any rank is skipped on every rank (one MIN all-reduce of a flag); a rank-local
     decision would let one rank's next generator all-reduce pair with the others' discriminator all-reduce (the
-    reference has this hazard through DDP, train.py:194-201)."""
+    reference has this hazard through DDP, train.py:194-201).
+    `aux`: an AuxLoss adds its term to the generator loss and gradient, as in generator_train_step."""
+    _check_aux(aux)
     eng = gen.engine
-    loss, terms, gan, ctx = _adversarial_generator_half(gen, disc, clean, noisy, loss_weights, generator, masks, disc_masks)
+    loss, terms, gan, ctx = _adversarial_generator_half(gen, disc, clean, noisy, loss_weights, generator, masks, disc_masks,
+                                                        aux)
     if update:
         gen.allreduce_gradients()
         opt_g.step(lr)                                                        # train.py:191
@@ -1183,12 +1242,15 @@ class GraphedTrainStep:
     {seed, offset} state lives in device memory and advances on the device, so every replay sees fresh masks (the
     discriminator head's small mask still comes from torch's graph-safe generator).  `dropout=False` captures the step without dropout
     (deterministic: used by the parity test against the eager step).  Without a discriminator the step is
-    `generator_train_step` (graph A1 + B_g)."""
+    `generator_train_step` (graph A1 + B_g).  With `aux` (an AuxLoss) the auxiliary term's launches are part of graph A1
+    and `last_aux` = (total, rows) holds its values after every replay."""
 
     def __init__(self, gen: GeneratorTrain, opt_g: AdamW, batch: int, length: int, disc: Optional[DiscriminatorTrain] = None,
-                 opt_d: Optional[AdamW] = None, loss_weights=(0.1, 0.9, 0.2, 0.05), dropout: bool = True):
+                 opt_d: Optional[AdamW] = None, loss_weights=(0.1, 0.9, 0.2, 0.05), dropout: bool = True,
+                 aux: Optional[AuxLoss] = None):
         if (disc is None) != (opt_d is None):
             raise ValueError("pass both the discriminator and its optimiser, or neither")
+        _check_aux(aux)
         self.gen, self.disc, self.opt_g, self.opt_d = gen, disc, opt_g, opt_d
         eng = gen.engine
         dev = eng.device
@@ -1200,17 +1262,20 @@ class GraphedTrainStep:
         self._convs = [c.conv for blk in gen.blocks for c in (blk.time, blk.freq)]
         masks = "draw" if dropout else None
         gen.mask_rng_state(None)                                        # the keep-mask stream's device state exists
+        if aux is not None:                                             # its workspace is the engine's, grown before capture
+            eng._aux_workspace(batch, length // eng.cfg.hop * eng.cfg.hop, aux.n_ffts)
         torch.cuda.synchronize(dev)
         self.graph_a, self.graph_b = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         self.graph_a2 = self.graph_bd = None
         self._ctx = None
         with torch.cuda.graph(self.graph_a):                            # ends where the all-reduce / optimiser starts
             if disc is None:
-                self.out = generator_train_step(gen, opt_g, self.clean, self.noisy, w3, masks=masks, update=False)
+                self.out = generator_train_step(gen, opt_g, self.clean, self.noisy, w3, masks=masks, update=False, aux=aux)
             else:
                 loss, terms, gan, self._ctx = _adversarial_generator_half(gen, disc, self.clean, self.noisy, loss_weights,
-                                                                          None, masks, masks)
+                                                                          None, masks, masks, aux)
                 self.out = (loss, terms, gan)
+        self.last_aux = gen.last_aux if aux is not None else None       # static tensors of graph A1
         with torch.cuda.graph(self.graph_b):
             opt_g.step()
         if disc is not None:
@@ -1274,8 +1339,10 @@ class Trainer:
     def __init__(self, train_ds, test_ds, generator_state: Dict[str, torch.Tensor],
                  discriminator_state: Dict[str, torch.Tensor], device=None, init_lr: float = 5e-4, decay_epoch: int = 30,
                  loss_weights=(0.1, 0.9, 0.2, 0.05), n_fft: int = 400, hop: int = 100, pesq_fn=batch_pesq,
-                 log_interval: int = 500, log=print):
+                 log_interval: int = 500, log=print, aux: Optional[AuxLoss] = None):
         from .generator import TSCNet
+        _check_aux(aux)
+        self.aux, self.last_aux = aux, None
         self.train_ds, self.test_ds = train_ds, test_ds
         self.engine = eng = Engine(n_fft=n_fft, hop=hop, device=device)
         self.gen = GeneratorTrain(generator_state, engine=eng)                            # train.py:52
@@ -1317,7 +1384,8 @@ class Trainer:
         lr = step_lr(self.epoch, self.init_lr, self.decay_epoch)
         self.sync_buffers()
         loss, _, _, loss_d = adversarial_train_step(self.gen, self.disc, self.optimizer, self.optimizer_disc, clean, noisy,
-                                                    self.pesq_fn, self.loss_weights, lr=lr)
+                                                    self.pesq_fn, self.loss_weights, lr=lr, aux=self.aux)
+        self.last_aux = self.gen.last_aux if self.aux is not None else None
         return float(loss), (float(loss_d) if loss_d is not None else 0.0)
 
     @torch.no_grad()

@@ -1390,6 +1390,57 @@ int cmgan_suppress(cmgan_handle* h, const float* x_dev, int B, int L, long long 
                    const int* lengths_dev, const double* table_dev, int n_fft, float* y_dev, long long ldy, int* status_dev,
                    double* gain_dev, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Auxiliary losses: multi-resolution STFT loss and negative SI-SDR with their gradient (the reference has no
+ * counterpart: its generator loss sees one 400-point resolution and a sample-wise L1, src/train.py:124-151) ------------
+ * est, ref float32 [B, L], contiguous.  n_fft_host: n_res (1 .. cmgan_aux_loss_max_resolutions() = 4) DISTINCT values from
+ * {256, 512, 1024, 2048}, a HOST array read at call time.  All arithmetic is float64; every float32 output is rounded once.
+ * Per resolution n: hop h = n / 4, periodic Hann window w[k] = 0.5 - 0.5 cos(2 pi k / n), frames centred with reflect
+ * padding of n / 2 as torch.stft(center=True, pad_mode="reflect") (so L > max n / 2), T = 1 + L / h frames (integer
+ * division), F = n / 2 + 1 bins, and with X_x[t, f] the windowed frame's DFT of x in {e = est, r = ref}:
+ *   m_x = sqrt(max(|X_x|^2, 1e-7))      (below the clamp the derivative with respect to X is 0)
+ *   N = sum (m_r - m_e)^2,  D = sum m_r^2 over (t, f);   sc = sqrt(N) / sqrt(D), sc = 0 with a zero derivative where N == 0
+ *   lm = mean over (t, f) of |ln m_r - ln m_e|, sign(0) = 0 in its derivative
+ * Per row b: MR_b = mean over the resolutions of (sc + lm), and with x' = x - mean(x):
+ *   a = <e', r'> / (<r', r'> + 1e-8),  s = a r',  q = e' - s,  SISDR_b = 10 log10((<s, s> + 1e-8) / (<q, q> + 1e-8))  [dB]
+ *   (the five sums of e, r, e e, r r, e r are formed in one pass and centred afterwards)
+ *   dSISDR / de = (10 / ln 10) (ce e' + cr r'),  ce = -2 / Q,  cr = 2 a R / ((R + 1e-8) S) + (2 a / Q) (1 + 1e-8 / (R + 1e-8)),
+ *   R = <r', r'>, S = <s, s> + 1e-8, Q = <q, q> + 1e-8
+ * Total A = sum over b ascending of (k_mr MR_b - k_si SISDR_b); the caller passes k_mr = w_mr / B and k_si = w_si / B, so a
+ * row's outputs depend on its own samples and the two scalars only.  A term whose weight is exactly 0 is left out of A and
+ * of the gradient (its values are still written).  Outputs:
+ *   rows_dev     float64 [B, 2 n_res + 1]: (sc, lm) per resolution in the caller's order, then SISDR_b
+ *   total_dev    float32 [3]: A, its multi-resolution part, its SI-SDR part
+ *   g_audio_dev  float32 [B, L] = dA / de, with the adjoint of the reflect padding (margin samples fold back onto the
+ *                interior; per sample: the resolutions in the caller's order, in each the sample's own position, then its
+ *                mirror in the left margin, then in the right one, each over its up to four frames ascending; then the
+ *                SI-SDR term), or NULL for the values alone (rows and total then have the bits they have with a gradient).
+ *                It may not overlap est or ref: the gradient is not formed in place.  ref is data and gets no gradient.
+ * A row with est == ref bit for bit has sc = lm = 0 exactly in every resolution (both signals pass through one loop
+ * body), and with k_si = 0 a gradient of exact zeros; an all-zero est row has a gradient of exact zeros.  Fixed-order
+ * reductions, no atomics: bit-reproducible, row-independent (a non-finite sample stays in its row's outputs and in the
+ * total).  The workspace (256-byte aligned) holds, per resolution, the estimate's spectra as complex128 [B, T, F] (the
+ * frame gradients overwrite them), m_r as float64 [B, T, F] and three partial sums per frame, then the SI-SDR tiles.
+ * cmgan_aux_loss_workspace_bytes returns 0 for arguments cmgan_aux_loss rejects (its handle is not read and may be
+ * NULL).  CMGAN_E_BADARG before anything is launched: a null est / ref / rows / total, a resolution outside the set, a
+ * duplicate, n_res outside 1 .. 4, L <= max n / 2, B outside 1 .. 65535, a NaN weight, g_audio over est or ref, a
+ * workspace that is too small or misaligned.  n_res + 3 launches without a gradient, up to 2 n_res + 4 with one; no host
+ * synchronisation, no allocation; graph-capturable, and a replay reads the current contents of est and ref.           */
+int cmgan_aux_loss_max_resolutions(void);
+size_t cmgan_aux_loss_workspace_bytes(cmgan_handle* h, int B, int L, int n_res, const int* n_fft_host);
+int cmgan_aux_loss(cmgan_handle* h, const float* est_dev, const float* ref_dev, int B, int L, int n_res,
+                   const int* n_fft_host, double k_mr, double k_si, double* rows_dev, float* total_dev, float* g_audio_dev,
+                   void* ws, size_t ws_bytes, void* stream);
+
+/* cmgan_loss_backward with a caller's waveform gradient: g_audio [B, hop (T-1)] float32 (the gradient of any further
+ * audio-domain term with respect to est_audio, cmgan_aux_loss's for one) is added to the time term's per-sample gradient
+ * w_time sign(est - clean) / (B La) before the window and envelope step of the istft adjoint.  With w_time = 0 and a
+ * g_audio, est_audio and clean_audio may be NULL.  g_audio = NULL is cmgan_loss_backward itself: the same launch, the
+ * same bits.                                                                                                        */
+int cmgan_loss_backward_aux(cmgan_handle* h, const float* est_real_dev, const float* est_imag_dev,
+                            const float* clean_spec_dev, int B, int T, const float* est_audio_dev,
+                            const float* clean_audio_dev, float w_ri, float w_mag, float w_time,
+                            const float* g_audio_dev, float* d_real_dev, float* d_imag_dev, void* stream);
+
 /* Names + durations (ms) of the kernels of the most recent forward when
  * profiling is enabled with cmgan_set_profiling(h, 1): HIP events are recorded
  * around every launch on the caller's stream.  cmgan_profile_read synchronises
