@@ -824,6 +824,50 @@ def check_aux_loss_args(device, est, ref, n_ffts=(512, 1024, 2048), w_mr=1.0, w_
     return B, L, res, w_mr, w_si
 
 
+STOI_MIN_L = 6554                       # the shortest 16 kHz row with 31 frames at 10 kHz (one 30-frame window)
+STOI_MAX_L = (2 ** 31 - 1) // 5 - 4096
+
+
+class StoiLossOut(NamedTuple):
+    """Engine.stoi_loss: device tensors, nothing copied to the host."""
+    total: torch.Tensor              # float32 [1]: A = sum_b -(weight / B) STOI_b over the rows without a status
+    rows: torch.Tensor               # float64 [B, 2]: (STOI or ESTOI, kept frames); the value is NaN where the row has a status
+    status: torch.Tensor             # int32 [B]: bit 0 = fewer than 31 kept frames, bit 1 = the value is not finite
+    grad: Optional[torch.Tensor]     # float32 [B, L] = dA / d est (exact zeros on a row with a status), or None (grad=False)
+
+
+def check_stoi_settings(w_stoi, extended):
+    """The settings of Engine.stoi_loss / training.AuxLoss (pure host code): a finite weight >= 0 and a bool.  Returns
+    (float, bool)."""
+    if isinstance(w_stoi, bool) or not isinstance(w_stoi, (int, float, np.integer, np.floating)):
+        raise TypeError(f"w_stoi: expected a number, got {type(w_stoi).__name__}")
+    if not (np.isfinite(w_stoi) and w_stoi >= 0):
+        raise ValueError(f"w_stoi: must be finite and >= 0, got {w_stoi}")
+    if not isinstance(extended, (bool, np.bool_)):
+        raise TypeError(f"stoi_extended: expected a bool, got {type(extended).__name__}")
+    return float(w_stoi), bool(extended)
+
+
+def stoi_frames(L: int) -> int:
+    """Frames of 256 samples (hop 128) that a 16 kHz row of L samples has at 10 kHz, before the silent ones are removed."""
+    n10 = -(-5 * L // 8)
+    return -(-(n10 - 256) // 128) if n10 > 256 else 0
+
+
+def check_stoi_loss_args(device, est, ref, weight=1.0, extended=False):
+    """Argument rules of Engine.stoi_loss (pure host code).  Returns (B, L, weight, extended)."""
+    weight, extended = check_stoi_settings(weight, extended)
+    tensor_arg(est, "est", torch.float32, device, "[B, L]", lambda t: t.dim() == 2 and t.size(0) >= 1)
+    B, L = (int(v) for v in est.shape)
+    tensor_arg(ref, "ref", torch.float32, device, f"[{B}, {L}]", lambda t: tuple(t.shape) == (B, L))
+    if B > 65535:
+        raise ValueError(f"est: at most 65535 rows, got {B}")
+    if not STOI_MIN_L <= L <= STOI_MAX_L:
+        raise ValueError(f"est: rows must hold at least {STOI_MIN_L} samples (31 frames at 10 kHz, one 30-frame window) and at "
+                         f"most {STOI_MAX_L}, got {L}")
+    return B, L, weight, extended
+
+
 def metric_frames(L: int, fs: int):
     """(WSS / segSNR frames, LLR frames) of an L-sample signal: the two counts of cmgan_amd.metrics."""
     win = int(np.round(30 * fs / 1000))
@@ -886,7 +930,7 @@ class Engine:
             msg = self.lib.cmgan_last_error(None)
             raise _lib.CmganError(rc, msg.decode() if msg else "?")
         #: grow-only uint8 workspaces by name (_grow): "main", "branched" (enhance_graphed(branches > 1)), "conformer",
-        #: "metrics", "mix", "scene", "rir", "rir_bands", "rir_dir", "rir_bands_dir", "level", "channel", "dynamics", "noise", "suppress", "aux_loss" and ("resample", fs_in,
+        #: "metrics", "mix", "scene", "rir", "rir_bands", "rir_dir", "rir_bands_dir", "level", "channel", "dynamics", "noise", "suppress", "aux_loss", "stoi_loss" and ("resample", fs_in,
         #: fs_out), the rate pair's tap table
         self._wss: dict = {}
         self._graphs: dict = {}          # enhance_graphed: input shape -> (graph, in, out, token)
@@ -1984,6 +2028,42 @@ class Engine:
         self._call("cmgan_aux_loss", est, ref, B, L, len(res), (ctypes.c_int * len(res))(*res), w_mr / B, w_si / B, rows, total,
                    g, ws, ws.numel())
         return AuxLossOut(total, rows, g)
+
+    # ---- intelligibility: negative STOI / ESTOI as a loss term with its gradient, ESTOI as a score ----------
+    def _stoi_workspace(self, B: int, L: int) -> torch.Tensor:
+        return self._grow("stoi_loss", int(self.lib.cmgan_stoi_loss_workspace_bytes(self._h, B, L, 16000)),
+                          f"[{B}, {L}] is outside what cmgan_stoi_loss supports: 16 kHz rows of at least {STOI_MIN_L} samples")
+
+    @_on_device
+    def stoi_loss(self, est: torch.Tensor, ref: torch.Tensor, weight: float = 1.0, extended: bool = False,
+                  grad: bool = True) -> StoiLossOut:
+        """Negative STOI (extended=True: ESTOI) of a 16 kHz estimate against a reference as a loss, with the gradient with
+        respect to the estimate (cmgan_stoi_loss, include/cmgan_hip.h, "Intelligibility loss", states every formula).
+
+        est, ref float32 [B, L], contiguous, on this Engine's device, L >= 6554 (31 frames at 10 kHz).  total = sum over the
+        rows of -(weight / B) STOI_b, so a row's outputs do not depend on its neighbours.  The forward is Engine.metrics'
+        STOI column sum for sum; the silent-frame decision is made from `ref` alone and is a constant of the gradient.
+        Returns StoiLossOut(total float32 [1], rows float64 [B, 2] = (value, kept frames), status int32 [B], grad float32
+        [B, L]) of device tensors.  A row whose reference keeps fewer than 31 frames (status bit 0) or whose value is not
+        finite (bit 1: an all-zero estimate) has NaN in rows, is left out of total and has a gradient of exact zeros.
+        grad=False: grad is None, the rest keeps its bits.  float64 arithmetic with one rounding, bit-reproducible,
+        row-independent, no synchronisation; graph-capturable after one call at the shape.  The gradient is never formed
+        over est or ref."""
+        B, L, weight, extended = check_stoi_loss_args(self.device, est, ref, weight, extended)
+        ws = self._stoi_workspace(B, L)
+        rows = torch.empty(B, 2, dtype=torch.float64, device=self.device)
+        total = torch.empty(1, dtype=torch.float32, device=self.device)
+        status = torch.empty(B, dtype=torch.int32, device=self.device)
+        g = torch.empty(B, L, dtype=torch.float32, device=self.device) if grad else None
+        self._call("cmgan_stoi_loss", est, ref, B, L, 16000, 1 if extended else 0, weight / B, rows, total, status, g, ws,
+                   ws.numel())
+        return StoiLossOut(total, rows, status, g)
+
+    def estoi(self, clean: torch.Tensor, enhanced: torch.Tensor) -> torch.Tensor:
+        """ESTOI (Jensen and Taal 2016) of every row of a 16 kHz batch: float64 [B] on the device, NaN where the row has a
+        status (Engine.stoi_loss).  clean, enhanced float32 [B, L] as Engine.stoi_loss takes them; the values alone, no
+        gradient is formed."""
+        return self.stoi_loss(enhanced, clean, 1.0, True, grad=False).rows[:, 0].contiguous()
 
     @_on_device
     def pitch_shift(self, wav: torch.Tensor, factor: torch.Tensor, n_out: Optional[int] = None, hop: int = 256,

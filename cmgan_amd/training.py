@@ -62,7 +62,7 @@ import torch
 
 from ._lib import (AttnParams, ConvModParams, DecoderParams, DenseParams, DiscParams, EncoderParams, FfnParams)
 from .dist import FlatBucket, all_agree, allreduce_mean, broadcast_from_rank0, get_rank
-from .engine import Engine, check_aux_settings
+from .engine import AuxLossOut, Engine, check_aux_settings, check_stoi_settings
 
 __all__ = ["Trainer", "AuxLoss", "batch_pesq", "GraphedTrainStep", "DiscriminatorTrain", "adversarial_train_step", "GeneratorTrain", "generator_train_step", "DenseEncoderTrain", "DecoderTrain", "DenseBlockTrain", "TSCBTrain", "ConformerBlockTrain", "FeedForwardTrain", "ConvModuleTrain", "AttentionTrain", "AdamW", "step_lr", "generator_loss_terms", "dropout_mask", "forward_generator_step",
            "validation_step"]
@@ -929,16 +929,23 @@ class GeneratorTrain(_TrainModule):
 class AuxLoss:
     """Settings of the auxiliary audio-domain term of a training step (`aux=`): the multi-resolution STFT loss at the window
     lengths `n_ffts` (1 to 4 distinct values from 256, 512, 1024, 2048) weighted `w_mr`, and negative SI-SDR in dB weighted
-    `w_si`, both as batch means (Engine.aux_loss).  Validated here, on the host; no default weighs a term in."""
+    `w_si`, both as batch means (Engine.aux_loss); negative STOI - ESTOI with `stoi_extended` - weighted `w_stoi`, a batch
+    mean as well (Engine.stoi_loss: 16 kHz, rows of at least 6554 samples).  Validated here, on the host; no default weighs
+    a term in."""
     n_ffts: tuple = (512, 1024, 2048)
     w_mr: float = 0.0
     w_si: float = 0.0
+    w_stoi: float = 0.0
+    stoi_extended: bool = False
 
     def __post_init__(self):
         res, w_mr, w_si = check_aux_settings(self.n_ffts, self.w_mr, self.w_si)
+        w_stoi, extended = check_stoi_settings(self.w_stoi, self.stoi_extended)
         object.__setattr__(self, "n_ffts", res)
         object.__setattr__(self, "w_mr", w_mr)
         object.__setattr__(self, "w_si", w_si)
+        object.__setattr__(self, "w_stoi", w_stoi)
+        object.__setattr__(self, "stoi_extended", extended)
 
 
 def _check_aux(aux) -> None:
@@ -948,12 +955,28 @@ def _check_aux(aux) -> None:
 
 def _aux_term(gen: "GeneratorTrain", aux: Optional[AuxLoss], est_audio, clean_cut, c):
     """Engine.aux_loss of est_audio against clean_cut * c - est_audio lives in the RMS-normalised domain, so its target does
-    too (the reference's own time term keeps the raw clean batch) - kept as gen.last_aux = (total, rows); None without `aux`."""
+    too (the reference's own time term keeps the raw clean batch) - kept as gen.last_aux = (total, rows); None without `aux`.
+    With w_stoi != 0 Engine.stoi_loss joins: its total is added to the term's and its gradient to the term's with one
+    elementwise add (alone, it is the term: Engine.aux_loss is not run), and gen.last_aux = (total, rows, stoi_rows) with
+    total float32 [4] = (all, multi-resolution part, SI-SDR part, STOI part) and rows empty ([B, 0]) when STOI is alone."""
     if aux is None:
         return None
-    out = gen.engine.aux_loss(est_audio, clean_cut * c[:, None], aux.n_ffts, aux.w_mr, aux.w_si, grad=True)
-    gen.last_aux = (out.total, out.rows)
-    return out
+    eng = gen.engine
+    if aux.w_stoi == 0.0:
+        out = eng.aux_loss(est_audio, clean_cut * c[:, None], aux.n_ffts, aux.w_mr, aux.w_si, grad=True)
+        gen.last_aux = (out.total, out.rows)
+        return out
+    target = clean_cut * c[:, None]
+    st = eng.stoi_loss(est_audio, target, aux.w_stoi, aux.stoi_extended, grad=True)
+    if aux.w_mr == 0.0 and aux.w_si == 0.0:
+        total = torch.cat([st.total, st.total.new_zeros(2), st.total])
+        rows, grad = st.rows.new_empty(st.rows.shape[0], 0), st.grad
+    else:
+        out = eng.aux_loss(est_audio, target, aux.n_ffts, aux.w_mr, aux.w_si, grad=True)
+        total = torch.cat([out.total[:1] + st.total, out.total[1:], st.total])
+        rows, grad = out.rows, out.grad.add_(st.grad)
+    gen.last_aux = (total, rows, st.rows)
+    return AuxLossOut(total, rows, grad)
 
 
 def _loss_backward(eng, aux_out, est_real, est_imag, clean_spec, est_audio, clean_cut, loss_weights):
@@ -1243,7 +1266,7 @@ class GraphedTrainStep:
     discriminator head's small mask still comes from torch's graph-safe generator).  `dropout=False` captures the step without dropout
     (deterministic: used by the parity test against the eager step).  Without a discriminator the step is
     `generator_train_step` (graph A1 + B_g).  With `aux` (an AuxLoss) the auxiliary term's launches are part of graph A1
-    and `last_aux` = (total, rows) holds its values after every replay."""
+    and `last_aux` = (total, rows) - (total, rows, stoi_rows) with `w_stoi` - holds its values after every replay."""
 
     def __init__(self, gen: GeneratorTrain, opt_g: AdamW, batch: int, length: int, disc: Optional[DiscriminatorTrain] = None,
                  opt_d: Optional[AdamW] = None, loss_weights=(0.1, 0.9, 0.2, 0.05), dropout: bool = True,
@@ -1262,8 +1285,12 @@ class GraphedTrainStep:
         self._convs = [c.conv for blk in gen.blocks for c in (blk.time, blk.freq)]
         masks = "draw" if dropout else None
         gen.mask_rng_state(None)                                        # the keep-mask stream's device state exists
-        if aux is not None:                                             # its workspace is the engine's, grown before capture
-            eng._aux_workspace(batch, length // eng.cfg.hop * eng.cfg.hop, aux.n_ffts)
+        if aux is not None:                                             # its workspaces are the engine's, grown before capture
+            La = length // eng.cfg.hop * eng.cfg.hop
+            if aux.w_stoi == 0.0 or aux.w_mr != 0.0 or aux.w_si != 0.0:
+                eng._aux_workspace(batch, La, aux.n_ffts)
+            if aux.w_stoi != 0.0:
+                eng._stoi_workspace(batch, La)
         torch.cuda.synchronize(dev)
         self.graph_a, self.graph_b = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         self.graph_a2 = self.graph_bd = None

@@ -1441,6 +1441,66 @@ int cmgan_loss_backward_aux(cmgan_handle* h, const float* est_real_dev, const fl
                             const float* clean_audio_dev, float w_ri, float w_mag, float w_time,
                             const float* g_audio_dev, float* d_real_dev, float* d_imag_dev, void* stream);
 
+/* ---- Intelligibility loss: negative STOI / ESTOI of an estimate against a reference, with its gradient ----------------
+ * est, ref float32 [B, L], contiguous, fs = 16000 only.  The forward is cmgan_metrics' STOI sum for sum (Taal et al. 2011 as
+ * the reference's compute_metrics.py has it, quirks included); extended = 1 is ESTOI (Jensen and Taal 2016) on the same
+ * envelopes.  All arithmetic is float64; every float32 output is rounded once.  Per row, for x in {e = est, r = ref}:
+ *   x10[n] = sum over i ascending of x[i] h[(n + 11) 8 - 5 i]: scipy.signal.resample_poly(x, 5, 8), h = table 4 of
+ *            cmgan_metrics_table(16000, ...) (169 taps with the pre-pad), N10 = ceil(5 L / 8) samples
+ *   level[s] = 20 log10(sqrt(sum_m (r10[128 s - 1 + m] hann[m])^2) / 16), m < 256 (read ONE SAMPLE EARLY, index -1 wraps to
+ *            N10 - 1), s < nS = ceil((N10 - 256) / 128), hann = table 3; frame s is KEPT iff ((level[s] - max level) + 40) > 0,
+ *            decided from the reference alone; K kept frames src[0] < .. < src[K - 1]
+ *   xs[t] = sum over p in (t / 128 - 1, t / 128) with 0 <= p < K, earlier first, of x10[128 src[p] + o] hann[o], o = t - 128 p
+ *   X_k[j] = sum_n xs[128 j + n] hann[n] e^{-2 pi i k n / 512}, n < 256, envelope frames j < K - 1 (one radix-2 loop for both
+ *            signals); env_x[band, j] = sqrt(sum over the band's bins k ascending of |X_k / ws|^2), ws = sum hann, the 15
+ *            one-third-octave bands of table 2
+ *   window w < K - 30 covers frames w .. w + 29; with X = env_r, Y = env_e there, sums over the frames i ascending:
+ *     extended = 0: per band alpha = sqrt(sum X^2 / sum Y^2), y'_i = min(Y_i alpha, X_i (1 + 10^(15/20))),
+ *            xn = (X - mean X) / |X - mean X|, yn = (y' - mean y') / |y' - mean y'|, s_band = sum_i xn_i yn_i;
+ *            d_w = (sum over the bands ascending of s_band) / 15
+ *     extended = 1: both 15 x 30 matrices get every row (band) minus its mean over the 30 frames and divided by its norm,
+ *            then every column (frame) minus its mean over the 15 bands and divided by its norm (cx, cy); no clipping, no
+ *            alpha; d_w = (sum over the frames ascending of (sum over the bands ascending of cx cy)) / 30
+ *   STOI_b = (sum of d_w, the block's tree of metrics_finalize) / (K - 30)
+ * Total A = sum over b ascending of (-k STOI_b) over the rows WITHOUT a status; the caller passes k = w / B, so a row's
+ * outputs depend on its own samples and k only.  Outputs:
+ *   rows_dev     float64 [B, 2]: (STOI_b, K)
+ *   total_dev    float32 [1]: A
+ *   status_dev   int32 [B]: bit 0 = fewer than 31 kept frames (no window), bit 1 = the value is not finite (an all-zero est
+ *                gives sum Y^2 = 0).  A row with a status has NaN for its value, is left out of A and gets a gradient of
+ *                exact zeros: one silent clip does not put NaN into a training step
+ *   g_audio_dev  float32 [B, L] = dA / de, or NULL for the values alone (rows, total and status then have the bits they have
+ *                with a gradient).  It may not overlap est or ref.  ref, the keep mask and all that is made of ref are
+ *                constants.  Every stage is a gather in ascending order (no atomics), c_b = -k / (K - 30):
+ *     D_w[band, i] = d d_w / d Y[band, w + i]:
+ *       extended = 0: u_i = (xn_i - yn_i s_band) / |y' - mean y'|, q_i = u_i - mean u, m_i = 1 where Y_i alpha <= X_i (1 + c)
+ *            (the derivative of min follows the selected branch, the estimate's at a tie), T = sum_i m_i q_i Y_i,
+ *            D_w[band, i] = (m_i q_i alpha - (alpha / sum Y^2) T Y_i) / 15
+ *       extended = 1: dc = cx / 30; per frame over the bands: u = (dc - cy (cy . dc)) / nu, da = u - mean u; per band over
+ *            the frames: v = (da - ya (ya . da)) / n, D_w[band, .] = v - mean v   (ya the row-normalised estimate, n its row
+ *            norm, nu the column norm of the second step)
+ *     1. g[band, j] = c_b (sum over w = max(0, j - 29) .. min(j, K - 31) ascending of D_w[band, j - w])
+ *     2. G_k = g[band, j] Y_k[j] / (ws^2 env_e[band, j]) on the band's bins (0 where env_e == 0) and 0 on all others;
+ *        z[j, n] = hann[n] Re sum_k G_k e^{+2 pi i k n / 512}, n < 256: one conjugate 512-point transform per frame
+ *     3. g10[n] = sum over s in (n / 128 - 1, n / 128) with 0 <= s < nS and s kept as src[p], earlier first, of
+ *        hann[o] (sum over j in (t / 128 - 1, t / 128) with 0 <= j < K - 1, earlier first, of z[j, t - 128 j]),
+ *        o = n - 128 s, t = 128 p + o
+ *     4. g_audio[i] = (float) sum over n ascending of g10[n] h[(n + 11) 8 - 5 i] over the taps that exist
+ * A row with est == ref bit for bit has STOI_b (extended = 0) equal to what cmgan_metrics gives it.  Fixed-order
+ * reductions: bit-reproducible, row-independent, never in place.  The workspace (256-byte aligned) holds the tables, both
+ * 10 kHz signals, levels, the keep maps, both envelopes, the estimate's bins 0 .. 255 per frame (the backward reads them
+ * and does not transform twice), d_w, D_w, the frame gradients and g10; the kept-frame counts are read from it and the
+ * grids are sized for the worst case.  cmgan_stoi_loss_workspace_bytes returns 0 for a shape cmgan_stoi_loss rejects (its
+ * handle is not read and may be NULL).  Before anything is launched: CMGAN_E_UNSUPPORTED for fs != 16000; CMGAN_E_BADARG
+ * for a null est / ref / rows / total / status, a misaligned buffer, B outside 1 .. 65535, an L too short for 31 frames at
+ * 10 kHz (L < 6554), extended outside {0, 1}, a NaN k, g_audio over est or ref, a workspace that is too small or
+ * misaligned.  8 launches without a gradient, 11 with one; no host synchronisation, no allocation; graph-capturable, and
+ * a replay reads the current contents of est and ref.                                                                */
+size_t cmgan_stoi_loss_workspace_bytes(cmgan_handle* h, int B, int L, int fs);
+int cmgan_stoi_loss(cmgan_handle* h, const float* est_dev, const float* ref_dev, int B, int L, int fs, int extended, double k,
+                    double* rows_dev, float* total_dev, int* status_dev, float* g_audio_dev, void* ws, size_t ws_bytes,
+                    void* stream);
+
 /* Names + durations (ms) of the kernels of the most recent forward when
  * profiling is enabled with cmgan_set_profiling(h, 1): HIP events are recorded
  * around every launch on the caller's stream.  cmgan_profile_read synchronises
