@@ -285,6 +285,10 @@ SIGNATURES = {
     "cmgan_stoi_loss_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "cmgan_stoi_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_size_t, c_void_p]),
+    "cmgan_phase_loss_tile_frames": (c_int, []),
+    "cmgan_phase_loss_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "cmgan_phase_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_double, c_double,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "cmgan_set_profiling": (c_int, [c_void_p, c_int]),
     "cmgan_profile_read": (c_int, [c_void_p, POINTER(KernelTime), c_int]),
 }

@@ -19,7 +19,7 @@ LIB = os.path.join(LIBDIR, "libcmgan_hip.so")
 SOURCES = ["api.hip", "api_train.hip", "conformer.hip", "conformer_x3.hip", "attn32_x3.hip", "ffn32_x3.hip", "conv.hip", "conv_x3.hip",
            "in_running.hip", "stft.hip", "stft_fft.hip", "train.hip", "train_x3.hip", "disc.hip", "metrics.hip", "resample.hip", "rir.hip",
            "level.hip", "channel.hip", "dynamics.hip", "warp.hip", "scene.hip", "stretch.hip", "rir_stats.hip", "rir_tail.hip", "noise.hip",
-           "transmit.hip", "suppress.hip", "auxloss.hip", "stoiloss.hip"]
+           "transmit.hip", "suppress.hip", "auxloss.hip", "stoiloss.hip", "phaseloss.hip"]
 # pure-VALU kernels that WANT packed fp32 instructions (complex arithmetic of the FFT front / back end): built without
 # the "-packed-fp32-ops" feature removal below
 PACKED_FP32_SOURCES = {"stft_fft.hip"}

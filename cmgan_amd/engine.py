@@ -868,6 +868,52 @@ def check_stoi_loss_args(device, est, ref, weight=1.0, extended=False):
     return B, L, weight, extended
 
 
+PHASE_MAX_T = 1000000
+PHASE_MAX_F = 1024
+
+
+class PhaseLossOut(NamedTuple):
+    """Engine.phase_loss: device tensors, nothing copied to the host."""
+    total: torch.Tensor              # float32 [4]: (A, its IP part, its GD part, its IAF part), A = sum_b sum_i (w_i / B) value_i
+    rows: torch.Tensor               # float64 [B, 3]: (ip, gd, iaf), the means over the row's own non-void terms
+    counts: torch.Tensor             # int32 [B, 3]: the non-void terms of each mean
+    status: torch.Tensor             # int32 [B]: bit i = term i has no non-void term (value 0, no gradient)
+    g_real: Optional[torch.Tensor]   # float32, est_real's shape = dA / d est_real (exact zeros on void cells), or None
+    g_imag: Optional[torch.Tensor]
+
+
+def check_phase_settings(w_ip, w_gd, w_iaf, floor):
+    """The settings of Engine.phase_loss / training.AuxLoss (pure host code): three finite weights >= 0 and a finite
+    magnitude floor >= 0.  Returns four floats."""
+    out = []
+    for name, v in (("w_ip", w_ip), ("w_gd", w_gd), ("w_iaf", w_iaf), ("phase_floor", floor)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise TypeError(f"{name}: expected a number, got {type(v).__name__}")
+        if not (np.isfinite(v) and v >= 0):
+            raise ValueError(f"{name}: must be finite and >= 0, got {v}")
+        out.append(float(v))
+    return tuple(out)
+
+
+def check_phase_loss_args(device, F, est_real, est_imag, clean_spec, w_ip=1.0, w_gd=1.0, w_iaf=1.0, floor=0.0):
+    """Argument rules of Engine.phase_loss (pure host code); F is the Engine's.  Returns (B, T, w_ip, w_gd, w_iaf, floor)."""
+    w_ip, w_gd, w_iaf, floor = check_phase_settings(w_ip, w_gd, w_iaf, floor)
+    tensor_arg(est_real, "est_real", torch.float32, device, f"[B, T, {F}] or [B, 1, T, {F}]",
+               lambda t: t.dim() in (3, 4) and (t.dim() == 3 or t.size(1) == 1) and t.size(0) >= 1 and t.size(-2) >= 1
+               and t.size(-1) == F)
+    shape = tuple(est_real.shape)
+    B, T = int(shape[0]), int(shape[-2])
+    tensor_arg(est_imag, "est_imag", torch.float32, device, f"{list(shape)}", lambda t: tuple(t.shape) == shape)
+    tensor_arg(clean_spec, "clean_spec", torch.float32, device, f"[{B}, 2, {T}, {F}]", lambda t: tuple(t.shape) == (B, 2, T, F))
+    if B > 65535:
+        raise ValueError(f"est_real: at most 65535 rows, got {B}")
+    if T > PHASE_MAX_T:
+        raise ValueError(f"est_real: at most {PHASE_MAX_T} frames, got {T}")
+    if F > PHASE_MAX_F:
+        raise ValueError(f"est_real: at most {PHASE_MAX_F} bins, got {F}")
+    return B, T, w_ip, w_gd, w_iaf, floor
+
+
 def metric_frames(L: int, fs: int):
     """(WSS / segSNR frames, LLR frames) of an L-sample signal: the two counts of cmgan_amd.metrics."""
     win = int(np.round(30 * fs / 1000))
@@ -930,7 +976,7 @@ class Engine:
             msg = self.lib.cmgan_last_error(None)
             raise _lib.CmganError(rc, msg.decode() if msg else "?")
         #: grow-only uint8 workspaces by name (_grow): "main", "branched" (enhance_graphed(branches > 1)), "conformer",
-        #: "metrics", "mix", "scene", "rir", "rir_bands", "rir_dir", "rir_bands_dir", "level", "channel", "dynamics", "noise", "suppress", "aux_loss", "stoi_loss" and ("resample", fs_in,
+        #: "metrics", "mix", "scene", "rir", "rir_bands", "rir_dir", "rir_bands_dir", "level", "channel", "dynamics", "noise", "suppress", "aux_loss", "stoi_loss", "phase_loss" and ("resample", fs_in,
         #: fs_out), the rate pair's tap table
         self._wss: dict = {}
         self._graphs: dict = {}          # enhance_graphed: input shape -> (graph, in, out, token)
@@ -2064,6 +2110,40 @@ class Engine:
         status (Engine.stoi_loss).  clean, enhanced float32 [B, L] as Engine.stoi_loss takes them; the values alone, no
         gradient is formed."""
         return self.stoi_loss(enhanced, clean, 1.0, True, grad=False).rows[:, 0].contiguous()
+
+    # ---- phase: the anti-wrapping terms of MP-SENet on the emitted spectrum, with their gradient ----------
+    def _phase_workspace(self, B: int, T: int) -> torch.Tensor:
+        return self._grow("phase_loss", int(self.lib.cmgan_phase_loss_workspace_bytes(self._h, B, T)),
+                          f"[{B}, {T}] is outside what cmgan_phase_loss supports: 1 .. 65535 rows of 1 .. {PHASE_MAX_T} frames")
+
+    @_on_device
+    def phase_loss(self, est_real: torch.Tensor, est_imag: torch.Tensor, clean_spec: torch.Tensor, w_ip: float = 1.0,
+                   w_gd: float = 1.0, w_iaf: float = 1.0, floor: float = 0.0, grad: bool = True) -> PhaseLossOut:
+        """The anti-wrapping instantaneous-phase, group-delay and instantaneous-angular-frequency terms (MP-SENet) of the
+        spectrum est_real + i est_imag against clean_spec, with the gradient with respect to est_real and est_imag
+        (cmgan_phase_loss, include/cmgan_hip.h, "Phase loss", states every formula and order of summation).
+
+        est_real, est_imag float32 [B, 1, T, F] (or [B, T, F]), clean_spec float32 [B, 2, T, F], contiguous, on this Engine's
+        device, F the Engine's.  A cell whose estimate or clean magnitude is 0 or below `floor`, or that holds a non-finite
+        value, is void and takes its terms with it; each term is the mean over the row's own non-void terms, and w_ip,
+        w_gd, w_iaf >= 0 weigh the batch MEANS: total[0] = sum_b sum_i (w_i / B) value_i, so a row's outputs do not depend
+        on its neighbours.  Returns PhaseLossOut(total float32 [4], rows float64 [B, 3], counts int32 [B, 3], status int32
+        [B], g_real, g_imag float32 of est_real's shape) of device tensors.  A term without a non-void term (T = 1 has no
+        IAF pair) has value 0, no gradient and its bit in status.  grad=False: g_real and g_imag are None, the rest keeps
+        its bits.  float64 arithmetic with one rounding, bit-reproducible, row-independent, no synchronisation;
+        graph-capturable after one call at the shape.  The gradient is never formed over an input."""
+        B, T, w_ip, w_gd, w_iaf, floor = check_phase_loss_args(self.device, self.F, est_real, est_imag, clean_spec, w_ip, w_gd,
+                                                               w_iaf, floor)
+        ws = self._phase_workspace(B, T)
+        rows = torch.empty(B, 3, dtype=torch.float64, device=self.device)
+        counts = torch.empty(B, 3, dtype=torch.int32, device=self.device)
+        total = torch.empty(4, dtype=torch.float32, device=self.device)
+        status = torch.empty(B, dtype=torch.int32, device=self.device)
+        g_real = torch.empty_like(est_real) if grad else None
+        g_imag = torch.empty_like(est_imag) if grad else None
+        self._call("cmgan_phase_loss", est_real, est_imag, clean_spec, B, T, w_ip / B, w_gd / B, w_iaf / B, floor, rows, counts,
+                   total, status, g_real, g_imag, ws, ws.numel())
+        return PhaseLossOut(total, rows, counts, status, g_real, g_imag)
 
     @_on_device
     def pitch_shift(self, wav: torch.Tensor, factor: torch.Tensor, n_out: Optional[int] = None, hop: int = 256,

@@ -42,7 +42,9 @@ wheel - PESQ labels are an input).
 
 * `AuxLoss`                - settings of the optional auxiliary term of every training entry point (`aux=`): the
                              multi-resolution STFT loss and negative SI-SDR of est_audio against the RMS-scaled clean
-                             batch (csrc/auxloss.hip), added to the loss and, through cmgan_loss_backward_aux, to its gradient.
+                             batch (csrc/auxloss.hip), added to the loss and, through cmgan_loss_backward_aux, to its gradient;
+                             and the spectrum-side anti-wrapping phase terms of (est_real, est_imag) against clean_spec
+                             (csrc/phaseloss.hip), whose gradient is added to d_real / d_imag directly.
 
 * `DiscriminatorTrain`     - the metric discriminator (src/models/discriminator.py:29-64) with spectral-norm power
                              iteration, forward + backward (csrc/disc.hip).
@@ -62,7 +64,7 @@ import torch
 
 from ._lib import (AttnParams, ConvModParams, DecoderParams, DenseParams, DiscParams, EncoderParams, FfnParams)
 from .dist import FlatBucket, all_agree, allreduce_mean, broadcast_from_rank0, get_rank
-from .engine import AuxLossOut, Engine, check_aux_settings, check_stoi_settings
+from .engine import AuxLossOut, Engine, check_aux_settings, check_phase_settings, check_stoi_settings
 
 __all__ = ["Trainer", "AuxLoss", "batch_pesq", "GraphedTrainStep", "DiscriminatorTrain", "adversarial_train_step", "GeneratorTrain", "generator_train_step", "DenseEncoderTrain", "DecoderTrain", "DenseBlockTrain", "TSCBTrain", "ConformerBlockTrain", "FeedForwardTrain", "ConvModuleTrain", "AttentionTrain", "AdamW", "step_lr", "generator_loss_terms", "dropout_mask", "forward_generator_step",
            "validation_step"]
@@ -802,6 +804,7 @@ class GeneratorTrain(_TrainModule):
         self.complex_decoder = DecoderTrain("complex", engine=eng, views=_subviews(views, "complex_decoder"))
         self._saved = None
         self.last_aux = None                                    # (total, rows) of the last step's AuxLoss term, on the device
+        self.last_phase = None                                  # (total, rows, counts, status) of its phase term (Engine.phase_loss)
         self._mask_rng: Dict[int, torch.Tensor] = {}            # seed -> device {seed, offset} of the keep-mask generator
 
     def _draw_keep_bytes(self, nbytes: int, p: float, generator: Optional[torch.Generator]) -> torch.Tensor:
@@ -930,13 +933,20 @@ class AuxLoss:
     """Settings of the auxiliary audio-domain term of a training step (`aux=`): the multi-resolution STFT loss at the window
     lengths `n_ffts` (1 to 4 distinct values from 256, 512, 1024, 2048) weighted `w_mr`, and negative SI-SDR in dB weighted
     `w_si`, both as batch means (Engine.aux_loss); negative STOI - ESTOI with `stoi_extended` - weighted `w_stoi`, a batch
-    mean as well (Engine.stoi_loss: 16 kHz, rows of at least 6554 samples).  Validated here, on the host; no default weighs
-    a term in."""
+    mean as well (Engine.stoi_loss: 16 kHz, rows of at least 6554 samples).  The spectrum-side term: the anti-wrapping
+    instantaneous-phase, group-delay and instantaneous-angular-frequency losses of (est_real, est_imag) against clean_spec,
+    weighted `w_ip`, `w_gd`, `w_iaf` as batch means, cells with a magnitude below `phase_floor` left out
+    (Engine.phase_loss); its gradient joins d_real / d_imag directly, and with the three audio weights at 0 no audio-domain
+    term is run at all.  Validated here, on the host; no default weighs a term in."""
     n_ffts: tuple = (512, 1024, 2048)
     w_mr: float = 0.0
     w_si: float = 0.0
     w_stoi: float = 0.0
     stoi_extended: bool = False
+    w_ip: float = 0.0
+    w_gd: float = 0.0
+    w_iaf: float = 0.0
+    phase_floor: float = 0.0
 
     def __post_init__(self):
         res, w_mr, w_si = check_aux_settings(self.n_ffts, self.w_mr, self.w_si)
@@ -946,6 +956,20 @@ class AuxLoss:
         object.__setattr__(self, "w_si", w_si)
         object.__setattr__(self, "w_stoi", w_stoi)
         object.__setattr__(self, "stoi_extended", extended)
+        for name, v in zip(("w_ip", "w_gd", "w_iaf", "phase_floor"),
+                           check_phase_settings(self.w_ip, self.w_gd, self.w_iaf, self.phase_floor)):
+            object.__setattr__(self, name, v)
+
+    @property
+    def phase(self) -> bool:
+        """Whether the spectrum-side phase term is weighed in."""
+        return self.w_ip != 0.0 or self.w_gd != 0.0 or self.w_iaf != 0.0
+
+    @property
+    def audio(self) -> bool:
+        """Whether an audio-domain term is run: always without the phase term (as before it existed), with it only when an
+        audio weight is non-zero."""
+        return not self.phase or self.w_mr != 0.0 or self.w_si != 0.0 or self.w_stoi != 0.0
 
 
 def _check_aux(aux) -> None:
@@ -958,8 +982,12 @@ def _aux_term(gen: "GeneratorTrain", aux: Optional[AuxLoss], est_audio, clean_cu
     too (the reference's own time term keeps the raw clean batch) - kept as gen.last_aux = (total, rows); None without `aux`.
     With w_stoi != 0 Engine.stoi_loss joins: its total is added to the term's and its gradient to the term's with one
     elementwise add (alone, it is the term: Engine.aux_loss is not run), and gen.last_aux = (total, rows, stoi_rows) with
-    total float32 [4] = (all, multi-resolution part, SI-SDR part, STOI part) and rows empty ([B, 0]) when STOI is alone."""
+    total float32 [4] = (all, multi-resolution part, SI-SDR part, STOI part) and rows empty ([B, 0]) when STOI is alone.
+    An AuxLoss with phase weights only runs no audio-domain term: None, and gen.last_aux = None."""
     if aux is None:
+        return None
+    if not aux.audio:
+        gen.last_aux = None
         return None
     eng = gen.engine
     if aux.w_stoi == 0.0:
@@ -979,8 +1007,20 @@ def _aux_term(gen: "GeneratorTrain", aux: Optional[AuxLoss], est_audio, clean_cu
     return AuxLossOut(total, rows, grad)
 
 
-def _loss_backward(eng, aux_out, est_real, est_imag, clean_spec, est_audio, clean_cut, loss_weights):
-    """(d_real, d_imag) of the non-adversarial loss, with the auxiliary term's waveform gradient when there is one."""
+def _phase_term(gen: "GeneratorTrain", aux: Optional[AuxLoss], est_real, est_imag, clean_spec):
+    """Engine.phase_loss of the emitted spectrum against clean_spec when `aux` weighs a phase term in, kept as gen.last_phase
+    = (total, rows, counts, status); else None, and gen.last_phase = None."""
+    if aux is None or not aux.phase:
+        gen.last_phase = None
+        return None
+    out = gen.engine.phase_loss(est_real, est_imag, clean_spec, aux.w_ip, aux.w_gd, aux.w_iaf, aux.phase_floor, grad=True)
+    gen.last_phase = (out.total, out.rows, out.counts, out.status)
+    return out
+
+
+def _loss_backward(eng, aux_out, est_real, est_imag, clean_spec, est_audio, clean_cut, loss_weights, phase_out=None):
+    """(d_real, d_imag) of the non-adversarial loss, with the auxiliary term's waveform gradient when there is one and, after
+    it, the phase term's spectrum gradient: one elementwise add each."""
     B, T = est_real.shape[0], est_real.shape[2]
     d_real, d_imag = torch.empty_like(est_real), torch.empty_like(est_imag)
     w = [float(x) for x in loss_weights[:3]]
@@ -989,6 +1029,9 @@ def _loss_backward(eng, aux_out, est_real, est_imag, clean_spec, est_audio, clea
     else:
         eng._call("cmgan_loss_backward_aux", est_real, est_imag, clean_spec, B, T, est_audio, clean_cut, *w, aux_out.grad,
                   d_real, d_imag)
+    if phase_out is not None:                                   # (B T F is odd in general and cmgan_add takes whole float4s:
+        d_real.add_(phase_out.g_real)                           # the tensor add that joins the STOI gradient in _aux_term)
+        d_imag.add_(phase_out.g_imag)
     return d_real, d_imag
 
 
@@ -1002,7 +1045,8 @@ def generator_train_step(gen: GeneratorTrain, optimizer: "AdamW", clean: torch.T
     clean, noisy: float32 [B, L] on the GPU, L a multiple of hop.  `masks="draw"` draws fresh dropout masks from
     `generator`; pass `gen.masks(...)`-shaped masks to fix them, or None to disable dropout.  `update=False` stops
     after the backward pass (gradients in the bucket; no all-reduce, no optimiser launch).  `aux`: an AuxLoss adds its term
-    to the loss and the gradient (`terms` keeps its shape; the term's own values are gen.last_aux = (total, rows))."""
+    to the loss and the gradient (`terms` keeps its shape; the term's own values are gen.last_aux = (total, rows), those of
+    its phase term gen.last_phase = (total, rows, counts, status))."""
     _check_aux(aux)
     eng = gen.engine
     clean, noisy = eng._in(clean, "clean"), eng._in(noisy, "noisy")
@@ -1021,7 +1065,10 @@ def generator_train_step(gen: GeneratorTrain, optimizer: "AdamW", clean: torch.T
     aux_out = _aux_term(gen, aux, est_audio, clean_cut, c)
     if aux_out is not None:
         loss = loss + aux_out.total[0]
-    d_real, d_imag = _loss_backward(eng, aux_out, est_real, est_imag, clean_spec, est_audio, clean_cut, loss_weights)
+    phase_out = _phase_term(gen, aux, est_real, est_imag, clean_spec)
+    if phase_out is not None:
+        loss = loss + phase_out.total[0]
+    d_real, d_imag = _loss_backward(eng, aux_out, est_real, est_imag, clean_spec, est_audio, clean_cut, loss_weights, phase_out)
     gen.backward(d_real, d_imag)                                # train.py:190 (loss.backward())
     if update:                                                  # False: stop after the backward (GraphedTrainStep)
         gen.allreduce_gradients()                               # DDP's gradient mean, one collective
@@ -1183,7 +1230,10 @@ def _adversarial_generator_half(gen: GeneratorTrain, disc: DiscriminatorTrain, c
     aux_out = _aux_term(gen, aux, est_audio, clean_cut, c)
     if aux_out is not None:
         loss = loss + aux_out.total[0]
-    d_real, d_imag = _loss_backward(eng, aux_out, est_real, est_imag, clean_spec, est_audio, clean_cut, loss_weights)
+    phase_out = _phase_term(gen, aux, est_real, est_imag, clean_spec)
+    if phase_out is not None:
+        loss = loss + phase_out.total[0]
+    d_real, d_imag = _loss_backward(eng, aux_out, est_real, est_imag, clean_spec, est_audio, clean_cut, loss_weights, phase_out)
     dxy = disc.backward(dscore, slot=0, need_input_grad=True)
     eng._call("cmgan_mag_pair_backward", est_real, est_imag, dxy, B, T, 1.0, d_real, d_imag)
     gen.backward(d_real, d_imag)                                              # train.py:190
@@ -1266,7 +1316,8 @@ class GraphedTrainStep:
     discriminator head's small mask still comes from torch's graph-safe generator).  `dropout=False` captures the step without dropout
     (deterministic: used by the parity test against the eager step).  Without a discriminator the step is
     `generator_train_step` (graph A1 + B_g).  With `aux` (an AuxLoss) the auxiliary term's launches are part of graph A1
-    and `last_aux` = (total, rows) - (total, rows, stoi_rows) with `w_stoi` - holds its values after every replay."""
+    and `last_aux` = (total, rows) - (total, rows, stoi_rows) with `w_stoi` - holds its values after every replay, as
+    `last_phase` = (total, rows, counts, status) holds those of its phase term."""
 
     def __init__(self, gen: GeneratorTrain, opt_g: AdamW, batch: int, length: int, disc: Optional[DiscriminatorTrain] = None,
                  opt_d: Optional[AdamW] = None, loss_weights=(0.1, 0.9, 0.2, 0.05), dropout: bool = True,
@@ -1287,10 +1338,12 @@ class GraphedTrainStep:
         gen.mask_rng_state(None)                                        # the keep-mask stream's device state exists
         if aux is not None:                                             # its workspaces are the engine's, grown before capture
             La = length // eng.cfg.hop * eng.cfg.hop
-            if aux.w_stoi == 0.0 or aux.w_mr != 0.0 or aux.w_si != 0.0:
+            if aux.audio and (aux.w_stoi == 0.0 or aux.w_mr != 0.0 or aux.w_si != 0.0):
                 eng._aux_workspace(batch, La, aux.n_ffts)
             if aux.w_stoi != 0.0:
                 eng._stoi_workspace(batch, La)
+            if aux.phase:
+                eng._phase_workspace(batch, La // eng.cfg.hop + 1)
         torch.cuda.synchronize(dev)
         self.graph_a, self.graph_b = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         self.graph_a2 = self.graph_bd = None
@@ -1303,6 +1356,7 @@ class GraphedTrainStep:
                                                                           None, masks, masks, aux)
                 self.out = (loss, terms, gan)
         self.last_aux = gen.last_aux if aux is not None else None       # static tensors of graph A1
+        self.last_phase = gen.last_phase if aux is not None else None
         with torch.cuda.graph(self.graph_b):
             opt_g.step()
         if disc is not None:
@@ -1369,7 +1423,7 @@ class Trainer:
                  log_interval: int = 500, log=print, aux: Optional[AuxLoss] = None):
         from .generator import TSCNet
         _check_aux(aux)
-        self.aux, self.last_aux = aux, None
+        self.aux, self.last_aux, self.last_phase = aux, None, None
         self.train_ds, self.test_ds = train_ds, test_ds
         self.engine = eng = Engine(n_fft=n_fft, hop=hop, device=device)
         self.gen = GeneratorTrain(generator_state, engine=eng)                            # train.py:52
@@ -1413,6 +1467,7 @@ class Trainer:
         loss, _, _, loss_d = adversarial_train_step(self.gen, self.disc, self.optimizer, self.optimizer_disc, clean, noisy,
                                                     self.pesq_fn, self.loss_weights, lr=lr, aux=self.aux)
         self.last_aux = self.gen.last_aux if self.aux is not None else None
+        self.last_phase = self.gen.last_phase if self.aux is not None else None
         return float(loss), (float(loss_d) if loss_d is not None else 0.0)
 
     @torch.no_grad()

@@ -1501,6 +1501,56 @@ int cmgan_stoi_loss(cmgan_handle* h, const float* est_dev, const float* ref_dev,
                     double* rows_dev, float* total_dev, int* status_dev, float* g_audio_dev, void* ws, size_t ws_bytes,
                     void* stream);
 
+/* ---- Phase loss: the anti-wrapping phase terms of MP-SENet (Lu, Ai, Ling 2023) on the emitted spectrum, with their gradient --
+ * est_real, est_imag float32 [B, T, F] (the [B, 1, T, F] TSCNet outputs), clean_spec float32 [B, 2, T, F], contiguous; F is
+ * the handle's num_features (1 .. 1024).  The power compression keeps the angle, so the angle of est_real + i est_imag against
+ * the angle of clean_spec is the phase error in the model's own domain.  All arithmetic is float64; every float32 output is
+ * rounded once.  Per cell (t, f) of row b:
+ *   p = atan2(est_imag, est_real),  q = atan2(clean_im, clean_re)
+ *   r(x) = remainder(x, TWO_PI), the IEEE operation (exact), TWO_PI the double nearest 2 pi;  AW(x) = |r(x)|;
+ *   s(x) = the sign of r(x), 0 at r = 0
+ *   the cell is VOID when re^2 + im^2 of the estimate or of the clean cell (exact float64 squares, their sum rounded once)
+ *   is 0 or below floor * floor, or one of its four inputs is not finite; a void cell makes void every term it is part of
+ * Per row b, over the row's own non-void terms only:
+ *   ip_b  = (sum of AW(p - q) over the cells) / N_ip
+ *   gd_b  = (sum of AW((p[t,f] - p[t,f-1]) - (q[t,f] - q[t,f-1])) over the pairs with f >= 1) / N_gd
+ *   iaf_b = (sum of AW((p[t,f] - p[t-1,f]) - (q[t,f] - q[t-1,f])) over the pairs with t >= 1) / N_iaf
+ * N_ip, N_gd, N_iaf count the non-void terms: integers, constants of the gradient.  A term with count 0 has value 0, no
+ * gradient and a status bit (T = 1 has no IAF pair).  MP-SENet's matrix form of the group delay also carries a boundary
+ * column for f = 0; it is LEFT OUT here: only differences of neighbours enter.
+ * Order of summation: a row is cut into tiles of cmgan_phase_loss_tile_frames() = 8 frames; a pair belongs to the tile of
+ * its later cell.  Thread j of the tile's 256 adds the terms of its bins f = j, j + 256, .. over the tile's frames ascending,
+ * bins ascending within a frame; the 256 threads are added by halving (j += j + 128, then + 64, .. + 1); the tiles of a row
+ * are added ascending.  Total: x_i = k_i value_i (left out, 0, where k_i == 0 exactly), A = sum over b ascending of
+ * (x_ip + x_gd) + x_iaf, each part the sum over b ascending of its x.  The caller passes k = w / B, so a row's outputs
+ * depend on its own cells and k only.  Outputs:
+ *   rows_dev    float64 [B, 3]: (ip_b, gd_b, iaf_b)
+ *   counts_dev  int32 [B, 3]: (N_ip, N_gd, N_iaf)
+ *   total_dev   float32 [4]: (A, its IP part, its GD part, its IAF part)
+ *   status_dev  int32 [B]: bit 0 = N_ip is 0, bit 1 = N_gd is 0, bit 2 = N_iaf is 0 (whatever the k)
+ *   g_real_dev, g_imag_dev  float32 [B, T, F] = dA / d est_real, dA / d est_imag, or BOTH NULL for the values alone (rows,
+ *               counts, total and status then have the bits they have with a gradient).  A gather per cell, no atomics:
+ *     D = c_ip s_ip[t,f];  D += c_gd (s_gd[t,f] - s_gd[t,f+1]);  D += c_iaf (s_iaf[t,f] - s_iaf[t+1,f])
+ *     with c_i = k_i / N_i (0 where k_i == 0 or N_i == 0; N_i is read from counts_dev), s_gd[t,f] the sign of the pair whose
+ *     later cell is (t, f), and terms that do not exist or are void contributing 0;
+ *     g_real = (float)(D (-im / |z|^2)),  g_imag = (float)(D (re / |z|^2)),  |z|^2 = re^2 + im^2 as above.
+ *     A void cell, and a cell with D == 0, gets exact (positive) zeros.  clean_spec, the void map and the counts are constants.
+ * A row with est == clean bit for bit, and one with est = 2 clean, has values of exact zeros (and a gradient of exact
+ * zeros).  Fixed-order reductions: bit-reproducible, row-independent (a NaN stays in its own row, whose cells are void),
+ * never in place.  The workspace (256-byte aligned) holds six float64 per tile.  cmgan_phase_loss_workspace_bytes returns 0
+ * for B outside 1 .. 65535 or T outside 1 .. 1000000; its size does not depend on F, so its handle is not read and may be
+ * NULL.  CMGAN_E_BADARG before anything is launched, and before the handle is looked at: a null est / clean / rows / counts /
+ * total / status, a misaligned buffer, B or T outside their ranges, a NaN k, a NaN or negative floor, only one of the two
+ * gradient buffers, a workspace that is too small or misaligned; then a null handle; then, with the handle's F: F above
+ * 1024, a gradient buffer over an input or over the other.  3 launches for the values, 4 with the gradient; no host
+ * synchronisation, no allocation; graph-capturable, and a replay reads the current contents of the inputs.              */
+int cmgan_phase_loss_tile_frames(void);
+size_t cmgan_phase_loss_workspace_bytes(cmgan_handle* h, int B, int T);
+int cmgan_phase_loss(cmgan_handle* h, const float* est_real_dev, const float* est_imag_dev, const float* clean_spec_dev, int B,
+                     int T, double k_ip, double k_gd, double k_iaf, double floor, double* rows_dev, int* counts_dev,
+                     float* total_dev, int* status_dev, float* g_real_dev, float* g_imag_dev, void* ws, size_t ws_bytes,
+                     void* stream);
+
 /* Names + durations (ms) of the kernels of the most recent forward when
  * profiling is enabled with cmgan_set_profiling(h, 1): HIP events are recorded
  * around every launch on the caller's stream.  cmgan_profile_read synchronises
