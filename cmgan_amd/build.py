@@ -27,7 +27,7 @@ PACKED_FP32_SOURCES = {"stft_fft.hip"}
 X1_SOURCES = ["conformer_x3.hip", "attn32_x3.hip", "ffn32_x3.hip", "conv_x3.hip"]
 X1_FLAGS = ["-DX3_SINGLE", "-DX3_TERMS=1"]
 HEADERS = ["common.hip.h", "kernels.h", "weights.h", "api_internal.h", "train.h", "stft_fft_tables.h", "warp_common.hip.h", "philox.hip.h",
-           os.path.join("..", "..", "include", "cmgan_hip.h")]
+           "stoi_common.hip.h", "lds_f64.hip.h", "host_ranges.h", os.path.join("..", "..", "include", "cmgan_hip.h")]
 # the generator FORWARD path: what bench.py measures and what the PMC evidence under profiles/ was collected on.  The
 # training-step slices (train.hip, api_train.hip, train.h) and the public header (which grows with them) are left
 # out, so committed counters stay valid while the training side is being built.

@@ -26,11 +26,14 @@
 //                the sample's own padded position, then over its mirror in the left margin, then in the right one; then
 //                the SI-SDR term; one rounding.  Gather form: nothing is added to memory.
 // Storing X_e and m_r (24 bytes a cell) instead of transforming twice: the backward then runs one transform a frame.
+// The LDS store rule, the twiddles and the radix-2 passes are lds_f64.hip.h's, shared with suppress.hip and stoiloss.hip.
 #include <float.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "api_internal.h"
+#include "host_ranges.h"
+#include "lds_f64.hip.h"
 
 namespace {
 
@@ -61,47 +64,6 @@ struct AuxArgs {
     int B, L, R, tiles;
 };
 
-// (suppress.hip, sp_put: a complex value into LDS as two 64-bit stores)
-typedef __attribute__((address_space(3))) volatile double lds_double;
-
-__device__ inline void ax_put(double2* p, double re, double im) {
-    lds_double* q = (lds_double*)p;
-    q[0] = re;
-    q[1] = im;
-}
-
-__device__ inline int ax_bitrev(int k, int logN) { return (int)(__brev((unsigned)k) >> (32 - logN)); }
-
-// tw[k] = e^{-2 pi i k / N}, k < N / 2: the argument 2 k / N is exact
-__device__ inline void ax_twiddles(double2* tw, int N) {
-    for (int k = threadIdx.x; k < (N >> 1); k += AX_TPB) {
-        double s, c;
-        sincospi((double)(2 * k) / (double)N, &s, &c);
-        ax_put(tw + k, c, -s);
-    }
-}
-
-// the radix-2 decimation-in-time passes over one bit-reversed frame of N points in LDS; sign = -1 conjugates the twiddles.
-// Every product is a fused multiply-add by name.  Ends behind a barrier.
-__device__ inline void ax_fft(double2* buf, const double2* tw, int N, int logN, double sign) {
-    const int half_n = N >> 1;
-    for (int s = 1; s <= logN; ++s) {
-        __syncthreads();
-        const int half = 1 << (s - 1);
-        for (int j = threadIdx.x; j < half_n; j += AX_TPB) {
-            const int pos = j & (half - 1);
-            const int i0 = ((j >> (s - 1)) << s) + pos, i1 = i0 + half;
-            double2 w = tw[pos << (logN - s)];
-            w.y *= sign;
-            const double2 u = buf[i0], v = buf[i1];
-            const double vr = fma(v.x, w.x, -(v.y * w.y)), vi = fma(v.x, w.y, v.y * w.x);
-            ax_put(buf + i0, u.x + vr, u.y + vi);
-            ax_put(buf + i1, u.x - vr, u.y - vi);
-        }
-    }
-    __syncthreads();
-}
-
 __device__ inline double ax_hann(int k, int N) {
 #pragma clang fp contract(off)
     return 0.5 - 0.5 * cospi((double)(2 * k) / (double)N);
@@ -127,7 +89,7 @@ __global__ __launch_bounds__(AX_TPB) void aux_spectra(AuxArgs a, int ri) {
     const int t = blockIdx.x, b = blockIdx.y, N = r.N, h = N >> 2, F = r.F;
     double2* buf = ax_lds;
     double2* tw = ax_lds + N;
-    ax_twiddles(tw, N);
+    twiddles<AX_TPB>(tw, N);
     const size_t at = ((size_t)b * r.T + t) * F;
     double2* X = (double2*)(a.ws + r.X) + at;
     double* M = (double*)(a.ws + r.M) + at;
@@ -139,9 +101,9 @@ __global__ __launch_bounds__(AX_TPB) void aux_spectra(AuxArgs a, int ri) {
             long long i = (long long)t * h + k - (N >> 1);              // reflect padding: L > N / 2, one fold is enough
             if (i < 0) i = -i;
             if (i >= a.L) i = 2LL * (a.L - 1) - i;
-            ax_put(buf + ax_bitrev(k, r.logN), (double)src[i] * ax_hann(k, N), 0.0);
+            lds_put(buf + bitrev(k, r.logN), (double)src[i] * ax_hann(k, N), 0.0);
         }
-        ax_fft(buf, tw, N, r.logN, 1.0);
+        fft<AX_TPB>(buf, tw, N, r.logN, 1.0);
         for (int f = threadIdx.x; f < F; f += AX_TPB) {
             const double2 v = buf[f];
             const double P = fma(v.x, v.x, v.y * v.y);
@@ -252,7 +214,7 @@ __global__ __launch_bounds__(AX_TPB) void aux_grad(AuxArgs a, int ri) {
     const int t = blockIdx.x, b = blockIdx.y, N = r.N, F = r.F;
     double2* buf = ax_lds;
     double2* tw = ax_lds + N;
-    ax_twiddles(tw, N);
+    twiddles<AX_TPB>(tw, N);
     const size_t at = ((size_t)b * r.T + t) * F;
     double2* X = (double2*)(a.ws + r.X) + at;
     const double* M = (const double*)(a.ws + r.M) + at;
@@ -276,9 +238,9 @@ __global__ __launch_bounds__(AX_TPB) void aux_grad(AuxArgs a, int ri) {
             re = c * v.x;
             im = (f == 0 || f == F - 1) ? 0.0 : c * v.y;                 // their imaginary parts reach no real output
         }
-        ax_put(buf + ax_bitrev(f, r.logN), re, im);
+        lds_put(buf + bitrev(f, r.logN), re, im);
     }
-    ax_fft(buf, tw, N, r.logN, -1.0);                                   // (its first barrier: every X[f] has been read)
+    fft<AX_TPB>(buf, tw, N, r.logN, -1.0);                                   // (its first barrier: every X[f] has been read)
     double* z = (double*)X;                                             // the frame gradient over the frame's own spectrum
     for (int k = threadIdx.x; k < N; k += AX_TPB) z[k] = buf[k].x * ax_hann(k, N);
 }
@@ -321,8 +283,6 @@ __global__ __launch_bounds__(AX_TPB) void aux_join(AuxArgs a) {
     a.g[(size_t)b * L + i] = (float)g;
 }
 
-inline size_t ax_up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // null: fine; else what is wrong with the shape
 inline const char* ax_shape_error(int B, int L, int n_res, const int* n_fft) {
     if (B < 1 || B > 65535) return "need 1 <= B <= 65535";
@@ -350,28 +310,23 @@ inline size_t ax_layout(AuxArgs& a, int B, int L, int n_res, const int* n_fft) {
         r.F = r.N / 2 + 1;
         const size_t cells = (size_t)B * (size_t)r.T * (size_t)r.F;
         r.X = off;
-        off += ax_up256(cells * 2 * sizeof(double));
+        off += up256(cells * 2 * sizeof(double));
         r.M = off;
-        off += ax_up256(cells * sizeof(double));
+        off += up256(cells * sizeof(double));
         r.P = off;
-        off += ax_up256((size_t)B * (size_t)r.T * 3 * sizeof(double));
+        off += up256((size_t)B * (size_t)r.T * 3 * sizeof(double));
     }
     a.B = B;
     a.L = L;
     a.R = n_res;
     a.tiles = (L + AX_SI_TILE - 1) / AX_SI_TILE;
     a.SI = off;
-    off += ax_up256((size_t)B * (size_t)a.tiles * 5 * sizeof(double));
+    off += up256((size_t)B * (size_t)a.tiles * 5 * sizeof(double));
     a.ND = off;
-    off += ax_up256((size_t)B * AX_MAX_RES * 2 * sizeof(double));
+    off += up256((size_t)B * AX_MAX_RES * 2 * sizeof(double));
     a.CO = off;
-    off += ax_up256((size_t)B * 4 * sizeof(double));
+    off += up256((size_t)B * 4 * sizeof(double));
     return off;
-}
-
-inline bool ax_overlap(const void* p, const void* q, size_t bytes) {
-    const uintptr_t p0 = (uintptr_t)p, q0 = (uintptr_t)q;
-    return p0 < q0 + bytes && q0 < p0 + bytes;
 }
 
 }  // namespace
@@ -396,7 +351,7 @@ extern "C" int cmgan_aux_loss(cmgan_handle* h, const float* est, const float* re
         return fail(h, CMGAN_E_BADARG, "cmgan_aux_loss: %s (B=%d L=%d n_res=%d)", what, B, L, n_res);
     if (!(k_mr == k_mr) || !(k_si == k_si)) return fail(h, CMGAN_E_BADARG, "cmgan_aux_loss: k_mr and k_si must be numbers");
     const size_t bytes = (size_t)B * (size_t)L * sizeof(float);
-    if (g_audio && (ax_overlap(g_audio, est, bytes) || ax_overlap(g_audio, ref, bytes)))
+    if (g_audio && (bytes_overlap(g_audio, bytes, est, bytes) || bytes_overlap(g_audio, bytes, ref, bytes)))
         return fail(h, CMGAN_E_BADARG, "cmgan_aux_loss: g_audio overlaps est or ref; the gradient is not formed in place");
     AuxArgs a;
     const size_t need = ax_layout(a, B, L, n_res, n_fft_host);

@@ -32,6 +32,7 @@
 #include <stdint.h>
 
 #include "api_internal.h"
+#include "host_ranges.h"
 
 namespace {
 
@@ -334,8 +335,6 @@ __global__ __launch_bounds__(CH_TPB) void channel_apply(ChannelArgs a) {
     }
 }
 
-inline size_t ch_up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 inline int ch_tiles(int L) { return (L + CH_TILE - 1) / CH_TILE; }
 
 inline int ch_padded(int S) { return S <= 1 ? 1 : (S <= 2 ? 2 : (S <= 4 ? 4 : 8)); }
@@ -348,10 +347,10 @@ inline ChannelLayout ch_layout(int B, int L, int S) {
     const size_t N = 2 * (size_t)ch_padded(S);
     ChannelLayout l;
     l.sections = 0;
-    l.pw = ch_up256((size_t)B * sizeof(int));
-    l.seg = l.pw + ch_up256((size_t)B * CH_NPOW * N * N * sizeof(double));
-    l.inc = l.seg + ch_up256((size_t)B * ch_tiles(L) * N * sizeof(double));
-    l.total = l.inc + ch_up256((size_t)B * ch_tiles(L) * N * sizeof(double));
+    l.pw = up256((size_t)B * sizeof(int));
+    l.seg = l.pw + up256((size_t)B * CH_NPOW * N * N * sizeof(double));
+    l.inc = l.seg + up256((size_t)B * ch_tiles(L) * N * sizeof(double));
+    l.total = l.inc + up256((size_t)B * ch_tiles(L) * N * sizeof(double));
     return l;
 }
 

@@ -42,6 +42,7 @@
 #include <stdint.h>
 
 #include "api_internal.h"
+#include "host_ranges.h"
 
 namespace {
 
@@ -261,8 +262,6 @@ __global__ __launch_bounds__(DY_T) void dynamics_peak(DynArgs a) {
     if (lane == 0) a.peak[b] = pk;
 }
 
-inline size_t dy_up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct DynLayout {
     size_t seg, inc, part, total;   // byte offsets: float64 [B][nt][65] | float64 [B][nt] | float64 [B][nb]
     int nt, nb;
@@ -273,20 +272,13 @@ inline DynLayout dy_layout(int B, int L) {
     l.nt = (L + DY_T - 1) / DY_T;
     l.nb = (L + DY_BLOCK - 1) / DY_BLOCK;
     l.seg = 0;
-    l.inc = l.seg + dy_up256((size_t)B * l.nt * DY_ENT * sizeof(double));
-    l.part = l.inc + dy_up256((size_t)B * l.nt * sizeof(double));
-    l.total = l.part + dy_up256((size_t)B * l.nb * sizeof(double));
+    l.inc = l.seg + up256((size_t)B * l.nt * DY_ENT * sizeof(double));
+    l.part = l.inc + up256((size_t)B * l.nt * sizeof(double));
+    l.total = l.part + up256((size_t)B * l.nb * sizeof(double));
     return l;
 }
 
 inline bool dy_shape_ok(int B, int L) { return B >= 1 && B <= 65535 && L >= 1 && L <= DY_MAX_L; }
-
-// do the spans [p, p + (B-1) ld + L) of two float32 batches intersect?
-inline bool dy_overlap(const float* p, long long ldp, const float* q, long long ldq, int B, int L) {
-    const uintptr_t p0 = (uintptr_t)p, p1 = p0 + ((size_t)(B - 1) * (size_t)ldp + (size_t)L) * sizeof(float);
-    const uintptr_t q0 = (uintptr_t)q, q1 = q0 + ((size_t)(B - 1) * (size_t)ldq + (size_t)L) * sizeof(float);
-    return p0 < q1 && q0 < p1;
-}
 
 }  // namespace
 
@@ -310,9 +302,9 @@ extern "C" int cmgan_dynamics(cmgan_handle* h, const float* wav, int B, int L, l
                     "ldo=%lld ldk=%lld)", B, L, ldw, ldo, ldk);
     if (L > DY_MAX_L)
         return fail(h, CMGAN_E_BADARG, "cmgan_dynamics: rows of up to %d samples are supported (L=%d)", DY_MAX_L, L);
-    if (!((const float*)out == wav && ldo == ldw) && dy_overlap(wav, ldw, out, ldo, B, L))   // in place is the one overlap there may be
+    if (!((const float*)out == wav && ldo == ldw) && rows_overlap(wav, ldw, out, ldo, B, L))   // in place is the one overlap there may be
         return fail(h, CMGAN_E_BADARG, "cmgan_dynamics: wav and out overlap; only out == wav with ldo == ldw (in place) is allowed");
-    if (key && !((const float*)out == key && ldo == ldk) && dy_overlap(key, ldk, out, ldo, B, L))
+    if (key && !((const float*)out == key && ldo == ldk) && rows_overlap(key, ldk, out, ldo, B, L))
         return fail(h, CMGAN_E_BADARG, "cmgan_dynamics: key and out overlap; only out == key with ldo == ldk is allowed");
     const DynLayout l = dy_layout(B, L);
     if (!ws || ((uintptr_t)ws & 255) || ws_bytes < l.total)

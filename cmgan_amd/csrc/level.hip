@@ -33,6 +33,7 @@
 #include <stdint.h>
 
 #include "api_internal.h"
+#include "host_ranges.h"
 
 namespace {
 
@@ -312,8 +313,6 @@ __global__ __launch_bounds__(LV_TPB) void level_select(LevelArgs a) {
     a.level[(size_t)b * 3 + 2] = frac;
 }
 
-inline size_t lv_up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 inline int lv_tiles(int L) { return (L + LV_TILE - 1) / LV_TILE; }
 
 struct LevelLayout {
@@ -324,10 +323,10 @@ struct LevelLayout {
 inline LevelLayout lv_layout(int B, int L) {
     LevelLayout l;
     l.tiles = 0;
-    l.tile_stride = lv_up256((size_t)B * lv_tiles(L) * sizeof(double));
+    l.tile_stride = up256((size_t)B * lv_tiles(L) * sizeof(double));
     l.sq = 5 * l.tile_stride;
-    l.cross = l.sq + lv_up256((size_t)B * sizeof(double));
-    l.total = l.cross + lv_up256((size_t)B * lv_tiles(L) * 16 * sizeof(int));
+    l.cross = l.sq + up256((size_t)B * sizeof(double));
+    l.total = l.cross + up256((size_t)B * lv_tiles(L) * 16 * sizeof(int));
     return l;
 }
 

@@ -15,6 +15,8 @@
 //   metrics_stoi_corr  (clip, window): the 30-frame correlations of every band
 //   metrics_finalize   (clip): STOI mean, composites
 // Data-dependent counts (kept STOI frames) are read from the workspace; grids are sized for the worst case.
+// The STOI chain up to the band correlation (tables, resampler, level, keep mask, envelopes, correlation) is the set of
+// bodies in stoi_common.hip.h, which stoiloss.hip (cmgan_stoi_loss) calls too: the loss is this scorer's STOI by construction.
 #include <math.h>
 #include <stdint.h>
 
@@ -22,14 +24,13 @@
 #include <vector>
 
 #include "api_internal.h"
+#include "host_ranges.h"
+#include "stoi_common.hip.h"
 
 namespace {
 
 constexpr int MT_NB = 25;              // WSS critical bands
 constexpr int MT_BANKW = 64;           // weights kept per band (the widest band keeps 36 bins at either rate)
-constexpr int MT_STOI_FS = 10000, MT_STOI_N = 256, MT_STOI_HOP = 128, MT_STOI_NFFT = 512, MT_STOI_J = 15,
-              MT_STOI_SEG = 30;
-constexpr double MT_STOI_DYN = 40.0;
 constexpr int MT_MAXP = 16;            // LPC order at 16 kHz
 constexpr int MT_TPB = 256;
 constexpr double MT_EPS = 2.220446049250313e-16;   // np.spacing(1.0)
@@ -55,30 +56,6 @@ const double CB_WIDTH[MT_NB] = {70.0, 70.0, 70.0, 70.0, 70.0, 70.0, 70.0, 77.372
                                 127.914, 140.423, 153.823, 168.154, 183.457, 199.776, 217.153, 235.631, 255.255,
                                 276.072, 298.126, 321.465, 346.136};
 struct CriticalBands { double centre[MT_NB], width[MT_NB]; };   // passed by value to the table kernel
-
-// Frame geometry of one sample rate (metrics.py: _win_hop, wss, llr, stoi / scipy resample_poly's padding rules).
-struct Geom {
-    int fs, win, hop, nfft, half, order;
-    int up, down, half_len, fir_len, pre_remove;     // fir_len counts the zero pre-pad
-};
-
-__host__ __device__ inline bool geom_of(int fs, Geom& g) {
-    if (fs != 16000 && fs != 8000) return false;
-    g.fs = fs;
-    g.win = fs == 16000 ? 480 : 240;                 // int(np.round(30 * fs / 1000))
-    g.hop = g.win / 4;
-    g.nfft = fs == 16000 ? 1024 : 512;               // 2 ** ceil(log2(2 * win))
-    g.half = g.nfft / 2;
-    g.order = fs < 10000 ? 10 : 16;
-    g.up = 5;                                        // 10000 / gcd(10000, fs), fs / gcd(10000, fs)
-    g.down = fs == 16000 ? 8 : 4;
-    const int max_rate = g.up > g.down ? g.up : g.down;
-    g.half_len = 10 * max_rate;
-    const int pre = g.down - g.half_len % g.down;
-    g.fir_len = pre + 2 * g.half_len + 1;
-    g.pre_remove = (g.half_len + pre) / g.down;
-    return true;
-}
 
 __host__ __device__ inline double taper_value(int win, int n) {   // 0.5 (1 - cos(2 pi n / (win + 1))), n = 1..win
     return 0.5 * (1.0 - cos(2.0 * M_PI * (double)(n + 1) / (double)(win + 1)));
@@ -111,68 +88,6 @@ inline void bank_band(const double* centre, const double* width, int fs, int hal
     *count = c < MT_BANKW ? c : MT_BANKW;
 }
 
-// STOI one-third-octave bands (metrics.py: _third_octave_bands(10000, 512, 15, 150)): out[0] = bands kept, then the
-// [first, end) bins of all 15 bands.  stoi_band fills band k, stoi_kept the count once all bands are in.
-__host__ __device__ inline void stoi_band(int k, double* out) {
-    const int nbins = MT_STOI_NFFT / 2 + 1;
-    const double step = (double)MT_STOI_FS / MT_STOI_NFFT;       // np.linspace(0, fs, nfft + 1)
-    const double lo = 150.0 * pow(2.0, (double)(2 * k - 1) / 6.0);
-    const double hi = 150.0 * pow(2.0, (double)(2 * k + 1) / 6.0);
-    int a = 0, bb = 0;
-    double ba = INFINITY, bh = INFINITY;
-    for (int i = 0; i < nbins; ++i) {
-        const double f = (double)i * step;
-        const double da = (f - lo) * (f - lo), dh = (f - hi) * (f - hi);
-        if (da < ba) { ba = da; a = i; }
-        if (dh < bh) { bh = dh; bb = i; }
-    }
-    out[1 + 2 * k] = a;
-    out[2 + 2 * k] = bb;
-}
-
-__host__ __device__ inline int stoi_kept(double* out) {
-    int last = -1;
-    for (int i = 0; i < MT_STOI_J - 1; ++i) {
-        const double w0 = fmax(out[2 + 2 * i] - out[1 + 2 * i], 0.0), w1 = fmax(out[4 + 2 * i] - out[3 + 2 * i], 0.0);
-        if (w1 >= w0 && w1 != 0) last = i;
-    }
-    out[0] = last + 2;
-    return last + 2;
-}
-
-__host__ __device__ inline double hann_inner(int n, int m) {    // scipy.signal.windows.hann(n + 2)[1 : n + 1]
-    const int M = n + 2;
-    const double step = (M_PI - -M_PI) / (double)(M - 1);
-    const double fac = (double)(m + 1) * step + -M_PI;
-    return 0.5 + 0.5 * cos(fac);
-}
-
-__host__ __device__ inline double bessel_i0(double x) {         // power series; x <= 5 here
-    double term = 1.0, sum = 1.0;
-    const double q = 0.25 * x * x;
-    for (int k = 1; k < 200; ++k) {
-        term *= q / ((double)k * (double)k);
-        sum += term;
-        if (term < 1e-18 * sum) break;
-    }
-    return sum;
-}
-
-// firwin(2 half_len + 1, 1 / max_rate, window=('kaiser', 5.0)) without the final normalisation (tap j, 0-based)
-__host__ __device__ inline double fir_raw(const Geom& g, int j) {
-    const int M = 2 * g.half_len + 1;
-    const double cutoff = 1.0 / (double)(g.up > g.down ? g.up : g.down);
-    const double alpha = 0.5 * (M - 1);
-    const double m = (double)j - alpha;
-    double y = M_PI * (cutoff * m == 0.0 ? 1.0e-20 : cutoff * m);   // np.sinc
-    double h = cutoff * (sin(y) / y);
-    h -= 0.0 * 1.0;                                                // left band edge 0: 0 * sinc(0)
-    const double wa = (M - 1) / 2.0;
-    const double r = ((double)j - wa) / wa;
-    const double win = bessel_i0(5.0 * sqrt(1.0 - r * r)) / bessel_i0(5.0);
-    return h * win;
-}
-
 inline void fir_taps(const Geom& g, double* out) {   // out[fir_len]: pre-pad zeros, taps / sum * up
     const int M = 2 * g.half_len + 1, pre = g.fir_len - M;
     double s = 0.0;
@@ -184,52 +99,6 @@ inline void fir_taps(const Geom& g, double* out) {   // out[fir_len]: pre-pad ze
 // ------------------------------------------------------------------------------------------ device helpers
 __device__ inline double ld(const float* p, size_t i, double off) { return (double)p[i] + off; }
 
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// sum over the block (blockDim.x a multiple of 64, <= 1024); red = 16 doubles of LDS; every thread gets the result
-__device__ inline double block_sum(double v, double* red) {
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wid] = v;
-    __syncthreads();
-    double s = 0.0;
-    for (int i = 0; i < nw; ++i) s += red[i];
-    return s;
-}
-
-// in-place radix-2 DIT FFT of two length-(1 << logn) sequences in LDS, input in bit-reversed order; tw = exp(-2 pi i k /
-// 1024), k < 512 (interleaved re, im)
-__device__ void fft2_lds(double* ar, double* ai, double* br, double* bi, int logn, const double* tw) {
-    const int n = 1 << logn;
-    for (int s = 1; s <= logn; ++s) {
-        const int hm = 1 << (s - 1);
-        for (int t = threadIdx.x; t < n / 2; t += blockDim.x) {
-            const int j = t & (hm - 1);
-            const int i0 = ((t >> (s - 1)) << s) + j, i1 = i0 + hm;
-            const int k = j << (10 - s);
-            const double wr = tw[2 * k], wi = tw[2 * k + 1];
-            double xr = ar[i1] * wr - ai[i1] * wi, xi = ar[i1] * wi + ai[i1] * wr;
-            ar[i1] = ar[i0] - xr; ai[i1] = ai[i0] - xi;
-            ar[i0] += xr; ai[i0] += xi;
-            xr = br[i1] * wr - bi[i1] * wi; xi = br[i1] * wi + bi[i1] * wr;
-            br[i1] = br[i0] - xr; bi[i1] = bi[i0] - xi;
-            br[i0] += xr; bi[i0] += xi;
-        }
-        __syncthreads();
-    }
-}
-
-__device__ inline double fmin_nan(double a, double b) {    // np.minimum: NaN propagates
-    return (a != a || b != b) ? NAN : (a < b ? a : b);
-}
-
-__device__ inline int bitrev(int i, int logn) { return (int)(__brev((unsigned)i) >> (32 - logn)); }
-
 // ------------------------------------------------------------------------------------------ kernels
 // one block: every table entry by its own thread where the entries are independent
 __global__ __launch_bounds__(MT_TPB) void metrics_tables(int fs, CriticalBands cb, double* tb) {
@@ -237,17 +106,8 @@ __global__ __launch_bounds__(MT_TPB) void metrics_tables(int fs, CriticalBands c
     Geom g;
     geom_of(fs, g);
     const int t = threadIdx.x, lane = t & 63, wid = t >> 6, nw = blockDim.x >> 6;
-    const int M = 2 * g.half_len + 1, pre = g.fir_len - M;
     for (int n = t; n < g.win; n += blockDim.x) tb[TB_TAPER + n] = taper_value(g.win, n);
-    for (int m = t; m < MT_STOI_N; m += blockDim.x) tb[TB_HANN + m] = hann_inner(MT_STOI_N, m);
-    for (int k = t; k < 512; k += blockDim.x) {
-        double sn, cs;
-        sincospi((double)k / 512.0, &sn, &cs);
-        tb[TB_TW + 2 * k] = cs;
-        tb[TB_TW + 2 * k + 1] = -sn;
-    }
-    for (int j = t; j < g.fir_len; j += blockDim.x) tb[TB_FIR + j] = j < pre ? 0.0 : fir_raw(g, j - pre);
-    if (t < MT_STOI_J) stoi_band(t, tb + TB_EDGES);
+    stoi_tables_fill(g, tb + TB_HANN, tb + TB_TW, tb + TB_FIR, tb + TB_EDGES);
     // WSS bank: one band per wave at a time, 64 bins per step; the kept bins are contiguous, so the first one found
     // fixes every weight's slot
     for (int b = wid; b < MT_NB; b += nw) {
@@ -266,17 +126,9 @@ __global__ __launch_bounds__(MT_TPB) void metrics_tables(int fs, CriticalBands c
         }
     }
     __syncthreads();
-    if (t == 0) {
-        double sum = 0.0;
-        for (int j = 0; j < M; ++j) sum += tb[TB_FIR + pre + j];
-        fir_sum = sum;
-        sum = 0.0;
-        for (int m = 0; m < MT_STOI_N; ++m) sum += tb[TB_HANN + m];
-        tb[TB_HSUM] = sum;
-        stoi_kept(tb + TB_EDGES);
-    }
+    stoi_tables_sums(g, tb + TB_HANN, tb + TB_HSUM, tb + TB_FIR, &fir_sum, tb + TB_EDGES);
     __syncthreads();
-    for (int j = t; j < M; j += blockDim.x) tb[TB_FIR + pre + j] = tb[TB_FIR + pre + j] / fir_sum * (double)g.up;
+    stoi_tables_norm(g, tb + TB_FIR, fir_sum);
 }
 
 struct FrameArgs {
@@ -446,32 +298,14 @@ __global__ __launch_bounds__(MT_TPB) void metrics_frames(FrameArgs a, int fs) {
 // scipy.signal.resample_poly(x, 10000, fs): out[n] = sum_i x[i] h[(n + pre_remove) down - i up]
 __global__ __launch_bounds__(MT_TPB) void metrics_resample(const float* x, const float* y, double offset, int L, int N10,
                                                            int fs, const double* tb, double* x10, double* y10) {
-    Geom g;
-    geom_of(fs, g);
-    const int n = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
-    if (n >= N10) return;
-    const float* src = (blockIdx.z ? y : x) + (size_t)b * L;
-    double* dst = (blockIdx.z ? y10 : x10) + (size_t)b * N10;
-    const long long pos = (long long)(n + g.pre_remove) * g.down;
-    long long i_hi = pos / g.up;
-    if (i_hi > L - 1) i_hi = L - 1;
-    long long i_lo = pos - (g.fir_len - 1) <= 0 ? 0 : (pos - (g.fir_len - 1) + g.up - 1) / g.up;
-    const double* h = tb + TB_FIR;
-    double acc = 0.0;
-    for (long long i = i_lo; i <= i_hi; ++i) acc += ld(src, (size_t)i, offset) * h[pos - i * g.up];
-    dst[n] = acc;
+    stoi_resample<true>(x, y, offset, L, N10, fs, tb + TB_FIR, x10, y10);
 }
 
 // STOI silence test: level of frame s (start s * 128), samples read one early with index -1 wrapping
 __global__ __launch_bounds__(MT_TPB) void metrics_stoi_level(const double* x10, int N10, int nS, const double* tb,
                                                              double* level) {
     __shared__ double red[16];
-    const int s = blockIdx.x, b = blockIdx.y, m = threadIdx.x;
-    long long idx = (long long)s * MT_STOI_HOP - 1 + m;
-    if (idx < 0) idx += N10;
-    const double v = x10[(size_t)b * N10 + idx] * tb[TB_HANN + m];
-    const double e = block_sum(v * v, red);
-    if (m == 0) level[(size_t)b * nS + s] = 20.0 * log10(sqrt(e) / 16.0);
+    stoi_level(x10, N10, nS, tb + TB_HANN, red, level);
 }
 
 __device__ inline unsigned long long okey(double v) {        // order-preserving integer image; NaN sorts last
@@ -582,56 +416,8 @@ __global__ __launch_bounds__(MT_TPB) void metrics_clip(ClipArgs a) {
         sd = block_sum(sd, red + 8);
         if (t == 0) { out[1] = lt; out[3] = 10.0 * log10(sx / sd); }
     } else {
-        const double* lv = a.level + (size_t)b * a.nS;
-        int* src = a.src + (size_t)b * a.nS;
-        double mx = -INFINITY;
-        bool nan = false;
-        for (int i = t; i < a.nS; i += blockDim.x) {
-            nan |= lv[i] != lv[i];
-            mx = fmax(mx, lv[i]);
-        }
-        // max of the block (NaN propagates like np.max)
-        const int lane = t & 63, wid = t >> 6, nw = blockDim.x >> 6;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
-        nan = __any(nan);
-        if (lane == 0) { red[wid] = mx; wtot[wid] = nan; }
-        __syncthreads();
-        mx = red[0];
-        for (int w = 1; w < nw; ++w) { mx = fmax(mx, red[w]); nan |= wtot[w] != 0; }
-        if (nan) mx = NAN;
-        __syncthreads();
-        int total = 0;
-        for (int i0 = 0; i0 < a.nS; i0 += blockDim.x) {
-            const int i = i0 + t;
-            const bool keep = i < a.nS && ((lv[i] - mx) + MT_STOI_DYN) > 0;
-            const unsigned long long bal = __ballot(keep);
-            const int before = __popcll(bal & ((1ull << lane) - 1ull));
-            if (lane == 0) wtot[wid] = __popcll(bal);
-            __syncthreads();
-            int off = total;
-            for (int w = 0; w < wid; ++w) off += wtot[w];
-            if (keep) src[off + before] = i;
-            for (int w = 0; w < nw; ++w) total += wtot[w];
-            __syncthreads();
-        }
-        if (t == 0) a.kept[b] = total;
+        stoi_keep<false>(a.level, a.nS, a.src, nullptr, a.kept, b, red, wtot);
     }
-}
-
-// overlap-add sample t of the kept frames (at most two sources), in np.add.at's order
-__device__ inline double ola(const double* x10, const int* src, int K, int t, const double* hann) {
-    const int p = t / MT_STOI_HOP;
-    double acc = 0.0;
-    if (p - 1 >= 0 && p - 1 < K) {
-        const int o = t - (p - 1) * MT_STOI_HOP;
-        acc += x10[(size_t)src[p - 1] * MT_STOI_HOP + o] * hann[o];
-    }
-    if (p < K) {
-        const int o = t - p * MT_STOI_HOP;
-        acc += x10[(size_t)src[p] * MT_STOI_HOP + o] * hann[o];
-    }
-    return acc;
 }
 
 // band envelopes of envelope frame j of the silence-removed signals: [2][B][15][nS]
@@ -639,40 +425,10 @@ __global__ __launch_bounds__(MT_TPB) void metrics_stoi_env(const double* x10, co
                                                            const int* src_all, const int* kept, const double* tb,
                                                            double* env, int B) {
     __shared__ double xr[MT_STOI_NFFT], xi[MT_STOI_NFFT], yr[MT_STOI_NFFT], yi[MT_STOI_NFFT];
-    const int j = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
+    const int j = blockIdx.x, b = blockIdx.y;
     const int K = kept[b];
     if (j >= K - 1) return;
-    const int* src = src_all + (size_t)b * nS;
-    const double* hann = tb + TB_HANN;
-    const double* xb = x10 + (size_t)b * N10;
-    const double* yb = y10 + (size_t)b * N10;
-    for (int n = t; n < MT_STOI_NFFT; n += blockDim.x) {
-        double vx = 0.0, vy = 0.0;
-        if (n < MT_STOI_N) {
-            const int ts = j * MT_STOI_HOP + n;
-            vx = ola(xb, src, K, ts, hann) * hann[n];
-            vy = ola(yb, src, K, ts, hann) * hann[n];
-        }
-        const int r = bitrev(n, 9);
-        xr[r] = vx; xi[r] = 0.0;
-        yr[r] = vy; yi[r] = 0.0;
-    }
-    __syncthreads();
-    fft2_lds(xr, xi, yr, yi, 9, tb + TB_TW);
-    const int nb = (int)tb[TB_EDGES];
-    if (t < 2 * nb) {
-        const int sig = t / nb, band = t % nb;
-        const double* re = sig ? yr : xr;
-        const double* im = sig ? yi : xi;
-        const double ws = tb[TB_HSUM];
-        const int lo = (int)tb[TB_EDGES + 1 + 2 * band], hi = (int)tb[TB_EDGES + 2 + 2 * band];
-        double e = 0.0;
-        for (int k = lo; k < hi; ++k) {
-            const double r = re[k] / ws, i = im[k] / ws;
-            e += r * r + i * i;
-        }
-        env[(((size_t)sig * B + b) * MT_STOI_J + band) * nS + j] = sqrt(e);
-    }
+    stoi_env(x10, y10, N10, nS, src_all, K, j, b, tb + TB_HANN, tb + TB_HSUM, tb + TB_TW, tb + TB_EDGES, env, B, xr, xi, yr, yi);
 }
 
 // correlation of window w (frames w .. w+29) summed over the bands / J
@@ -685,27 +441,7 @@ __global__ __launch_bounds__(64) void metrics_stoi_corr(const double* env, int n
     if (t < nb) {
         const double* X = env + ((size_t)b * MT_STOI_J + t) * nS + w;
         const double* Y = env + (((size_t)B + b) * MT_STOI_J + t) * nS + w;
-        double sx2 = 0.0, sy2 = 0.0, sx = 0.0;
-        for (int i = 0; i < MT_STOI_SEG; ++i) { sx2 += X[i] * X[i]; sy2 += Y[i] * Y[i]; sx += X[i]; }
-        const double alpha = sqrt(sx2 / sy2);
-        const double mxv = sx / MT_STOI_SEG;
-        double sy = 0.0;
-        for (int i = 0; i < MT_STOI_SEG; ++i) sy += fmin_nan(Y[i] * alpha, X[i] * (1.0 + clipc));
-        const double myv = sy / MT_STOI_SEG;
-        double nx = 0.0, ny = 0.0;
-        for (int i = 0; i < MT_STOI_SEG; ++i) {
-            const double a = X[i] - mxv, c = fmin_nan(Y[i] * alpha, X[i] * (1.0 + clipc)) - myv;
-            nx += a * a;
-            ny += c * c;
-        }
-        nx = sqrt(nx);
-        ny = sqrt(ny);
-        double s = 0.0;
-        for (int i = 0; i < MT_STOI_SEG; ++i) {
-            const double a = X[i] - mxv, c = fmin_nan(Y[i] * alpha, X[i] * (1.0 + clipc)) - myv;
-            s += (a / nx) * (c / ny);
-        }
-        sc[t] = s;
+        sc[t] = stoi_band_corr(X, Y, clipc).s;
     }
     __syncthreads();
     if (t == 0) {
@@ -749,8 +485,6 @@ struct Plan {
     size_t tb, wss, llr, seg, x10, y10, level, src, kept, env, corr, clip, total;   // byte offsets
 };
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // 0 = ok, else a CMGAN_E_* code with `why` set
 int plan_metrics(int B, int L, int fs, Plan& p, const char** why) {
     if (B <= 0 || L <= 0) { *why = "B and L must be positive"; return CMGAN_E_BADARG; }
@@ -764,9 +498,7 @@ int plan_metrics(int B, int L, int fs, Plan& p, const char** why) {
     p.nf = p.nfw > p.nfl ? p.nfw : p.nfl;
     p.kw = (int)std::nearbyint((double)p.nfw * 0.95);
     p.kl = (int)std::nearbyint((double)p.nfl * 0.95);
-    const long long n10 = ((long long)L * g.up + g.down - 1) / g.down;
-    p.N10 = (int)n10;
-    p.nS = n10 > MT_STOI_N ? (int)((n10 - MT_STOI_N + MT_STOI_HOP - 1) / MT_STOI_HOP) : 0;
+    stoi_frames(L, g, &p.N10, &p.nS);
     if (p.nfw < 1 || p.nfl < 1 || p.nS < MT_STOI_SEG + 1) {
         *why = "L is too short for one 30-frame STOI window";
         return CMGAN_E_BADSHAPE;

@@ -34,6 +34,7 @@
 #include <stdint.h>
 
 #include "api_internal.h"
+#include "host_ranges.h"
 #include "philox.hip.h"
 
 namespace {
@@ -165,8 +166,6 @@ __global__ __launch_bounds__(NZ_TPB) void noise_rows(NoiseArgs a) {
 }
 
 // ---------------------------------------------------------------- the host side
-inline size_t nz_up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" int cmgan_noise_tile(void) { return NZ_TILE; }
@@ -174,7 +173,7 @@ extern "C" int cmgan_noise_max_filter(void) { return NZ_MAX_FILTER; }
 extern "C" int cmgan_noise_max_tones(void) { return NZ_MAX_TONES; }
 extern "C" int cmgan_noise_max_points(void) { return NZ_MAX_POINTS; }
 
-extern "C" size_t cmgan_noise_workspace_bytes(int N) { return N >= 1 && N <= 65535 ? nz_up256((size_t)N * sizeof(int)) : 0; }
+extern "C" size_t cmgan_noise_workspace_bytes(int N) { return N >= 1 && N <= 65535 ? up256((size_t)N * sizeof(int)) : 0; }
 
 extern "C" int cmgan_noise(cmgan_handle* h, float* out, int N, int K, long long ld, const long long* seed, const long long* start,
                            const int* len, const double* fir, int NF, const double* env, int P, int H, const double* tones,
@@ -197,7 +196,7 @@ extern "C" int cmgan_noise(cmgan_handle* h, float* out, int N, int K, long long 
     if (M < 0 || M > NZ_MAX_TONES || (M == 0) != (tones == nullptr) || (n_tones && !tones))
         return fail(h, CMGAN_E_BADARG, "cmgan_noise: need 0 <= M <= %d tones, the tone table null with M = 0 and only then, and "
                     "no tone counts without it (M=%d)", NZ_MAX_TONES, M);
-    const size_t need = nz_up256((size_t)N * sizeof(int));
+    const size_t need = up256((size_t)N * sizeof(int));
     if (!ws || ((uintptr_t)ws & 255) || ws_bytes < need)
         return fail(h, CMGAN_E_BADARG, "cmgan_noise: the workspace must be 256-byte aligned and hold %zu bytes (%zu given)",
                     need, ws ? ws_bytes : (size_t)0);

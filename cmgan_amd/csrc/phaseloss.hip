@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "api_internal.h"
+#include "host_ranges.h"
 
 namespace {
 
@@ -209,16 +210,9 @@ __global__ __launch_bounds__(PL_TPB) void pl_grad(PhaseArgs a) {
     }
 }
 
-inline size_t pl_up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 inline bool pl_shape_ok(int B, int T) { return B >= 1 && B <= 65535 && T >= 1 && T <= PL_MAX_T; }
 
 inline int pl_tiles(int T) { return (T + PL_TT - 1) / PL_TT; }
-
-inline bool pl_overlap(const void* p, size_t pb, const void* q, size_t qb) {
-    const uintptr_t p0 = (uintptr_t)p, q0 = (uintptr_t)q;
-    return p0 < q0 + qb && q0 < p0 + pb;
-}
 
 }  // namespace
 
@@ -226,7 +220,7 @@ extern "C" int cmgan_phase_loss_tile_frames(void) { return PL_TT; }
 
 extern "C" size_t cmgan_phase_loss_workspace_bytes(cmgan_handle*, int B, int T) {
     if (!pl_shape_ok(B, T)) return 0;
-    return pl_up256((size_t)B * (size_t)pl_tiles(T) * 6 * sizeof(double));
+    return up256((size_t)B * (size_t)pl_tiles(T) * 6 * sizeof(double));
 }
 
 extern "C" int cmgan_phase_loss(cmgan_handle* h, const float* est_real, const float* est_imag, const float* clean_spec, int B,
@@ -259,10 +253,10 @@ extern "C" int cmgan_phase_loss(cmgan_handle* h, const float* est_real, const fl
     if (g_real) {
         float* const g[2] = {g_real, g_imag};
         for (int i = 0; i < 2; ++i)
-            if (pl_overlap(g[i], bytes, est_real, bytes) || pl_overlap(g[i], bytes, est_imag, bytes) ||
-                pl_overlap(g[i], bytes, clean_spec, 2 * bytes))
+            if (bytes_overlap(g[i], bytes, est_real, bytes) || bytes_overlap(g[i], bytes, est_imag, bytes) ||
+                bytes_overlap(g[i], bytes, clean_spec, 2 * bytes))
                 return fail(h, CMGAN_E_BADARG, "cmgan_phase_loss: a gradient buffer overlaps an input; the gradient is not formed in place");
-        if (pl_overlap(g_real, bytes, g_imag, bytes))
+        if (bytes_overlap(g_real, bytes, g_imag, bytes))
             return fail(h, CMGAN_E_BADARG, "cmgan_phase_loss: g_real overlaps g_imag");
     }
     PhaseArgs a;

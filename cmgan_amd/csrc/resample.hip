@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "api_internal.h"
+#include "host_ranges.h"
 
 namespace {
 
@@ -212,9 +213,7 @@ inline int rs_tile(const RsGeom& g) {
     return n > RS_TPB ? RS_TPB : (int)n;
 }
 
-inline size_t rs_up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-inline size_t rs_ws_bytes(const RsGeom& g) { return rs_up256((size_t)g.up * g.T * sizeof(double)); }
+inline size_t rs_ws_bytes(const RsGeom& g) { return up256((size_t)g.up * g.T * sizeof(double)); }
 
 }  // namespace
 

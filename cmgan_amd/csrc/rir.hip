@@ -59,6 +59,7 @@
 #include <stdint.h>
 
 #include "api_internal.h"
+#include "host_ranges.h"
 
 namespace {
 
@@ -585,8 +586,6 @@ __global__ __launch_bounds__(RR_TPB) void rir_bands_join(BandArgs a) {
 }
 
 // ---------------------------------------------------------------- the host side
-inline size_t rr_up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 inline bool rr_shape_ok(int R, int K, int tw) {
     return R >= 1 && R <= 65535 && K >= 1 && K <= RR_MAX_K && tw >= 1 && tw <= RR_MAX_TW;
 }
@@ -596,11 +595,11 @@ inline bool rb_shape_ok(int R, int K, int tw, int NB, int NF) {
 }
 
 template <bool DIR>
-inline size_t rr_rec_bytes(int R) { return rr_up256((size_t)R * rr_rec_words<DIR>() * sizeof(double)); }
+inline size_t rr_rec_bytes(int R) { return up256((size_t)R * rr_rec_words<DIR>() * sizeof(double)); }
 template <bool DIR>
-inline size_t rb_rec_bytes(int R, int NB) { return rr_up256((size_t)R * rb_rec_words<DIR>(NB) * sizeof(double)); }
+inline size_t rb_rec_bytes(int R, int NB) { return up256((size_t)R * rb_rec_words<DIR>(NB) * sizeof(double)); }
 inline size_t rb_hb_bytes(int R, int K, int NB, int NF) {
-    return rr_up256((size_t)R * NB * (size_t)(K + (NF - 1) / 2) * sizeof(double));
+    return up256((size_t)R * NB * (size_t)(K + (NF - 1) / 2) * sizeof(double));
 }
 
 // Judges every argument but the workspace and fills `a`; `bt` is null for cmgan_rir and holds bands, filt, NB and NF for

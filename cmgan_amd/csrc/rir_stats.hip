@@ -33,6 +33,7 @@
 #include <stdint.h>
 
 #include "api_internal.h"
+#include "host_ranges.h"
 
 namespace {
 
@@ -326,8 +327,6 @@ __global__ __launch_bounds__(RS_TPB) void rir_stats_scan(StatsArgs a) {
 }
 
 // ---------------------------------------------------------------- the host side
-inline size_t rs_up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 inline int rs_tiles(int K) { return (K + RS_TILE - 1) / RS_TILE; }
 
 inline bool rs_shape_ok(int R, int K, int NB, int NF) {
@@ -340,12 +339,12 @@ struct StatsLayout {
 };
 
 inline StatsLayout rs_layout(int R, int K, int NB) {
-    const size_t slices = (size_t)R * (NB + 1), curve = rs_up256(slices * rs_tiles(K) * RS_TILE * sizeof(double));
+    const size_t slices = (size_t)R * (NB + 1), curve = up256(slices * rs_tiles(K) * RS_TILE * sizeof(double));
     StatsLayout l;
     l.e = 0;
     l.edc = curve;
     l.tsum = 2 * curve;
-    l.total = l.tsum + rs_up256(slices * rs_tiles(K) * sizeof(double));
+    l.total = l.tsum + up256(slices * rs_tiles(K) * sizeof(double));
     return l;
 }
 

@@ -34,6 +34,7 @@
 #include <stdint.h>
 
 #include "api_internal.h"
+#include "host_ranges.h"
 #include "philox.hip.h"
 
 namespace {
@@ -177,8 +178,6 @@ __global__ __launch_bounds__(RT_TPB) void rir_tail_taps(TailArgs a) {
 }
 
 // ---------------------------------------------------------------- the host side
-inline size_t rt_up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 inline bool rt_shape_ok(int R, int K, int NB, int NF) {
     return R >= 1 && R <= 65535 && K >= 1 && K <= RT_MAX_K && NB >= 0 && NB <= RT_MAX_BANDS && NF >= 1 && NF <= RT_MAX_FILTER
         && (NF & 1);
@@ -190,7 +189,7 @@ extern "C" int cmgan_rir_tail_tile(void) { return RT_TILE; }
 extern "C" int cmgan_rir_tail_max_window(void) { return RT_MAX_WINDOW; }
 
 extern "C" size_t cmgan_rir_tail_workspace_bytes(const cmgan_handle*, int R, int K, int NB, int NF) {
-    return rt_shape_ok(R, K, NB, NF) ? rt_up256((size_t)R * sizeof(int)) : 0;
+    return rt_shape_ok(R, K, NB, NF) ? up256((size_t)R * sizeof(int)) : 0;
 }
 
 extern "C" int cmgan_rir_tail(cmgan_handle* h, float* rir, int R, int K, long long ld, int* len, const int* n_taps,
@@ -219,7 +218,7 @@ extern "C" int cmgan_rir_tail(cmgan_handle* h, float* rir, int R, int K, long lo
         return fail(h, CMGAN_E_UNSUPPORTED, "cmgan_rir_tail: responses of up to %d taps are supported (K=%d)", RT_MAX_K, K);
     if (NF > RT_MAX_FILTER)
         return fail(h, CMGAN_E_UNSUPPORTED, "cmgan_rir_tail: filters of up to %d taps are supported (NF=%d)", RT_MAX_FILTER, NF);
-    const size_t need = rt_up256((size_t)R * sizeof(int));
+    const size_t need = up256((size_t)R * sizeof(int));
     if (!ws || ((uintptr_t)ws & 255) || ws_bytes < need)
         return fail(h, CMGAN_E_BADARG, "cmgan_rir_tail: the workspace must be 256-byte aligned and hold %zu bytes (%zu given)",
                     need, ws ? ws_bytes : (size_t)0);

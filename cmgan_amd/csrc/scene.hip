@@ -59,6 +59,7 @@
 #include <hip/hip_runtime.h>
 
 #include "api_internal.h"
+#include "host_ranges.h"
 
 namespace {
 
@@ -153,8 +154,6 @@ __device__ inline int mx_direct_index(const float* h, int K, float* s_v, int* s_
     }
     return s_i[0] < K ? s_i[0] : 0;
 }
-
-inline size_t mx_up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 inline int mx_tiles(int L) { return (L + MX_TILE - 1) / MX_TILE; }
 
@@ -595,10 +594,10 @@ struct SceneLayout {
 inline SceneLayout sc_layout(int B, int L, int S) {
     SceneLayout l;
     l.d = 0;
-    l.part = mx_up256((size_t)B * sizeof(int));
-    l.part_stride = mx_up256((size_t)B * mx_tiles(L) * sizeof(double));
+    l.part = up256((size_t)B * sizeof(int));
+    l.part_stride = up256((size_t)B * mx_tiles(L) * sizeof(double));
     l.rows = l.part + (3 + (size_t)S) * l.part_stride;
-    l.row_stride = mx_up256((size_t)B * L * sizeof(double));
+    l.row_stride = up256((size_t)B * L * sizeof(double));
     l.total = l.rows + (2 + (size_t)S) * l.row_stride;
     return l;
 }
@@ -615,7 +614,7 @@ struct PathSpec {
     const int* src_n_path;
 };
 
-inline size_t sp_total(int B, int L, int S, int P) { return sc_layout(B, L, S).total + mx_up256((size_t)B * P * sizeof(int)); }
+inline size_t sp_total(int B, int L, int S, int P) { return sc_layout(B, L, S).total + up256((size_t)B * P * sizeof(int)); }
 
 // cmgan_scene, and cmgan_mix as its S = 0 case: `api` is the name of the entry point that was called, for the messages.
 // Every argument is judged before the handle is, so that the errors below need no GPU (the message of a call without a

@@ -1,8 +1,9 @@
 // stoiloss.hip - negative STOI / ESTOI as a training objective on a pair of [B, L] float32 batches at 16 kHz, with its
 // gradient with respect to the estimate (cmgan_stoi_loss, include/cmgan_hip.h, "Intelligibility loss").  The forward is
 // cmgan_metrics' STOI (metrics.hip: metrics_resample / _stoi_level / _clip role 2 / _stoi_env / _stoi_corr / _finalize),
-// formula for formula and sum for sum; its __host__ __device__ helpers are copied from there as they are.  For estimate e
-// and reference r of one row:
+// formula for formula and sum for sum: the two files' kernels call the same bodies in stoi_common.hip.h, and this file
+// keeps what is the loss's own (the ESTOI branch, the row's value and the gradient).  For estimate e and reference r of
+// one row:
 //
 //   x10 = resample_poly(x, 5, 8):  x10[n] = sum_i x[i] h[(n + 11) 8 - 5 i], i ascending, h = table 4 of cmgan_metrics_table
 //   level[s] = 20 log10(sqrt(sum_m (r10[s 128 - 1 + m] hann[m])^2) / 16), index -1 wraps;  keep s iff ((level[s] - max) + 40) > 0
@@ -34,7 +35,7 @@
 //   4  g16[i] = sum over n ascending of g10[n] h[(n + 11) 8 - 5 i] over the taps that exist; then the rounding
 //
 // Launches (a call without a gradient stops after sl_total):
-//   sl_tables    inner Hann and its sum, resample_poly taps, twiddles, band edges (metrics_tables' entries, the same code)
+//   sl_tables    inner Hann and its sum, resample_poly taps, twiddles, band edges (metrics_tables' entries, the same body)
 //   sl_resample  a thread per 10 kHz sample of either signal
 //   sl_level     a block per (row, frame) of the reference
 //   sl_keep      a block per row: the keep mask, its scan (src), the inverse map and K
@@ -52,12 +53,12 @@
 #include <cmath>
 
 #include "api_internal.h"
+#include "host_ranges.h"
+#include "lds_f64.hip.h"
+#include "stoi_common.hip.h"
 
 namespace {
 
-constexpr int MT_STOI_FS = 10000, MT_STOI_N = 256, MT_STOI_HOP = 128, MT_STOI_NFFT = 512, MT_STOI_J = 15,
-              MT_STOI_SEG = 30;
-constexpr double MT_STOI_DYN = 40.0;
 constexpr int MT_TPB = 256;
 constexpr int SL_BINS = 256;           // bins 0 .. 255 of the estimate's frames are kept (the bands end below 256)
 
@@ -70,142 +71,6 @@ constexpr int TB_FIR_CAP = 192;
 constexpr int TB_TW = 576;             // [512][2] exp(-2 pi i k / 1024)
 constexpr int TB_TOTAL = 1600;
 static_assert(8 + 161 <= TB_FIR_CAP && TB_FIR + TB_FIR_CAP <= TB_TW && TB_TW + 1024 <= TB_TOTAL, "table layout");
-
-// ---- metrics.hip's helpers, as they are -----------------------------------------------------------------------------
-struct Geom {
-    int fs, win, hop, nfft, half, order;
-    int up, down, half_len, fir_len, pre_remove;     // fir_len counts the zero pre-pad
-};
-
-__host__ __device__ inline bool geom_of(int fs, Geom& g) {
-    if (fs != 16000 && fs != 8000) return false;
-    g.fs = fs;
-    g.win = fs == 16000 ? 480 : 240;                 // int(np.round(30 * fs / 1000))
-    g.hop = g.win / 4;
-    g.nfft = fs == 16000 ? 1024 : 512;               // 2 ** ceil(log2(2 * win))
-    g.half = g.nfft / 2;
-    g.order = fs < 10000 ? 10 : 16;
-    g.up = 5;                                        // 10000 / gcd(10000, fs), fs / gcd(10000, fs)
-    g.down = fs == 16000 ? 8 : 4;
-    const int max_rate = g.up > g.down ? g.up : g.down;
-    g.half_len = 10 * max_rate;
-    const int pre = g.down - g.half_len % g.down;
-    g.fir_len = pre + 2 * g.half_len + 1;
-    g.pre_remove = (g.half_len + pre) / g.down;
-    return true;
-}
-
-__host__ __device__ inline void stoi_band(int k, double* out) {
-    const int nbins = MT_STOI_NFFT / 2 + 1;
-    const double step = (double)MT_STOI_FS / MT_STOI_NFFT;       // np.linspace(0, fs, nfft + 1)
-    const double lo = 150.0 * pow(2.0, (double)(2 * k - 1) / 6.0);
-    const double hi = 150.0 * pow(2.0, (double)(2 * k + 1) / 6.0);
-    int a = 0, bb = 0;
-    double ba = INFINITY, bh = INFINITY;
-    for (int i = 0; i < nbins; ++i) {
-        const double f = (double)i * step;
-        const double da = (f - lo) * (f - lo), dh = (f - hi) * (f - hi);
-        if (da < ba) { ba = da; a = i; }
-        if (dh < bh) { bh = dh; bb = i; }
-    }
-    out[1 + 2 * k] = a;
-    out[2 + 2 * k] = bb;
-}
-
-__host__ __device__ inline int stoi_kept(double* out) {
-    int last = -1;
-    for (int i = 0; i < MT_STOI_J - 1; ++i) {
-        const double w0 = fmax(out[2 + 2 * i] - out[1 + 2 * i], 0.0), w1 = fmax(out[4 + 2 * i] - out[3 + 2 * i], 0.0);
-        if (w1 >= w0 && w1 != 0) last = i;
-    }
-    out[0] = last + 2;
-    return last + 2;
-}
-
-__host__ __device__ inline double hann_inner(int n, int m) {    // scipy.signal.windows.hann(n + 2)[1 : n + 1]
-    const int M = n + 2;
-    const double step = (M_PI - -M_PI) / (double)(M - 1);
-    const double fac = (double)(m + 1) * step + -M_PI;
-    return 0.5 + 0.5 * cos(fac);
-}
-
-__host__ __device__ inline double bessel_i0(double x) {         // power series; x <= 5 here
-    double term = 1.0, sum = 1.0;
-    const double q = 0.25 * x * x;
-    for (int k = 1; k < 200; ++k) {
-        term *= q / ((double)k * (double)k);
-        sum += term;
-        if (term < 1e-18 * sum) break;
-    }
-    return sum;
-}
-
-// firwin(2 half_len + 1, 1 / max_rate, window=('kaiser', 5.0)) without the final normalisation (tap j, 0-based)
-__host__ __device__ inline double fir_raw(const Geom& g, int j) {
-    const int M = 2 * g.half_len + 1;
-    const double cutoff = 1.0 / (double)(g.up > g.down ? g.up : g.down);
-    const double alpha = 0.5 * (M - 1);
-    const double m = (double)j - alpha;
-    double y = M_PI * (cutoff * m == 0.0 ? 1.0e-20 : cutoff * m);   // np.sinc
-    double h = cutoff * (sin(y) / y);
-    h -= 0.0 * 1.0;                                                // left band edge 0: 0 * sinc(0)
-    const double wa = (M - 1) / 2.0;
-    const double r = ((double)j - wa) / wa;
-    const double win = bessel_i0(5.0 * sqrt(1.0 - r * r)) / bessel_i0(5.0);
-    return h * win;
-}
-
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// sum over the block (blockDim.x a multiple of 64, <= 1024); red = 16 doubles of LDS; every thread gets the result
-__device__ inline double block_sum(double v, double* red) {
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wid] = v;
-    __syncthreads();
-    double s = 0.0;
-    for (int i = 0; i < nw; ++i) s += red[i];
-    return s;
-}
-
-// in-place radix-2 DIT FFT of two length-(1 << logn) sequences in LDS, input in bit-reversed order; tw = exp(-2 pi i k /
-// 1024), k < 512 (interleaved re, im)
-__device__ void fft2_lds(double* ar, double* ai, double* br, double* bi, int logn, const double* tw) {
-    const int n = 1 << logn;
-    for (int s = 1; s <= logn; ++s) {
-        const int hm = 1 << (s - 1);
-        for (int t = threadIdx.x; t < n / 2; t += blockDim.x) {
-            const int j = t & (hm - 1);
-            const int i0 = ((t >> (s - 1)) << s) + j, i1 = i0 + hm;
-            const int k = j << (10 - s);
-            const double wr = tw[2 * k], wi = tw[2 * k + 1];
-            double xr = ar[i1] * wr - ai[i1] * wi, xi = ar[i1] * wi + ai[i1] * wr;
-            ar[i1] = ar[i0] - xr; ai[i1] = ai[i0] - xi;
-            ar[i0] += xr; ai[i0] += xi;
-            xr = br[i1] * wr - bi[i1] * wi; xi = br[i1] * wi + bi[i1] * wr;
-            br[i1] = br[i0] - xr; bi[i1] = bi[i0] - xi;
-            br[i0] += xr; bi[i0] += xi;
-        }
-        __syncthreads();
-    }
-}
-
-__device__ inline double fmin_nan(double a, double b) {    // np.minimum: NaN propagates
-    return (a != a || b != b) ? NAN : (a < b ? a : b);
-}
-
-__device__ inline int bitrev(int i, int logn) { return (int)(__brev((unsigned)i) >> (32 - logn)); }
-
-// a double into LDS as a 64-bit store that stays one: a store of more than 64 bits keeps reading its data registers after
-// it issues, and the compiler does not guard them against the next VALU write (tools/isa_lint.py)
-typedef __attribute__((address_space(3))) volatile double lds_double;       // (volatile: not merged; LDS by name, or it goes flat)
-
-__device__ inline void sl_put(double* p, double v) { *(lds_double*)p = v; }
 
 // ---- the call's arguments and workspace ------------------------------------------------------------------------------
 struct SlArgs {
@@ -238,116 +103,30 @@ __global__ __launch_bounds__(MT_TPB) void sl_tables(int fs, double* tb) {
     __shared__ double fir_sum;
     Geom g;
     geom_of(fs, g);
-    const int t = threadIdx.x;
-    const int M = 2 * g.half_len + 1, pre = g.fir_len - M;
-    for (int m = t; m < MT_STOI_N; m += blockDim.x) tb[TB_HANN + m] = hann_inner(MT_STOI_N, m);
-    for (int k = t; k < 512; k += blockDim.x) {
-        double sn, cs;
-        sincospi((double)k / 512.0, &sn, &cs);
-        tb[TB_TW + 2 * k] = cs;
-        tb[TB_TW + 2 * k + 1] = -sn;
-    }
-    for (int j = t; j < g.fir_len; j += blockDim.x) tb[TB_FIR + j] = j < pre ? 0.0 : fir_raw(g, j - pre);
-    if (t < MT_STOI_J) stoi_band(t, tb + TB_EDGES);
+    stoi_tables_fill(g, tb + TB_HANN, tb + TB_TW, tb + TB_FIR, tb + TB_EDGES);
     __syncthreads();
-    if (t == 0) {
-        double sum = 0.0;
-        for (int j = 0; j < M; ++j) sum += tb[TB_FIR + pre + j];
-        fir_sum = sum;
-        sum = 0.0;
-        for (int m = 0; m < MT_STOI_N; ++m) sum += tb[TB_HANN + m];
-        tb[TB_HSUM] = sum;
-        stoi_kept(tb + TB_EDGES);
-    }
+    stoi_tables_sums(g, tb + TB_HANN, tb + TB_HSUM, tb + TB_FIR, &fir_sum, tb + TB_EDGES);
     __syncthreads();
-    for (int j = t; j < M; j += blockDim.x) tb[TB_FIR + pre + j] = tb[TB_FIR + pre + j] / fir_sum * (double)g.up;
+    stoi_tables_norm(g, tb + TB_FIR, fir_sum);
 }
 
 // scipy.signal.resample_poly(x, 10000, fs): out[n] = sum_i x[i] h[(n + pre_remove) down - i up]; z = 0 the reference
 __global__ __launch_bounds__(MT_TPB) void sl_resample(SlArgs a, int fs) {
-    Geom g;
-    geom_of(fs, g);
-    const int n = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
-    if (n >= a.N10) return;
-    const float* src = (blockIdx.z ? a.est : a.ref) + (size_t)b * a.L;
-    double* dst = (blockIdx.z ? a.e10 : a.r10) + (size_t)b * a.N10;
-    const long long pos = (long long)(n + g.pre_remove) * g.down;
-    long long i_hi = pos / g.up;
-    if (i_hi > a.L - 1) i_hi = a.L - 1;
-    long long i_lo = pos - (g.fir_len - 1) <= 0 ? 0 : (pos - (g.fir_len - 1) + g.up - 1) / g.up;
-    const double* h = a.tb + TB_FIR;
-    double acc = 0.0;
-    for (long long i = i_lo; i <= i_hi; ++i) acc += (double)src[(size_t)i] * h[pos - i * g.up];
-    dst[n] = acc;
+    stoi_resample<false>(a.ref, a.est, 0.0, a.L, a.N10, fs, a.tb + TB_FIR, a.r10, a.e10);
 }
 
 // silence test: level of the reference's frame s (start s * 128), samples read one early with index -1 wrapping
 __global__ __launch_bounds__(MT_TPB) void sl_level(SlArgs a) {
     __shared__ double red[16];
-    const int s = blockIdx.x, b = blockIdx.y, m = threadIdx.x;
-    long long idx = (long long)s * MT_STOI_HOP - 1 + m;
-    if (idx < 0) idx += a.N10;
-    const double v = a.r10[(size_t)b * a.N10 + idx] * a.tb[TB_HANN + m];
-    const double e = block_sum(v * v, red);
-    if (m == 0) a.level[(size_t)b * a.nS + s] = 20.0 * log10(sqrt(e) / 16.0);
+    stoi_level(a.r10, a.N10, a.nS, a.tb + TB_HANN, red, a.level);
 }
 
 // the keep mask and its exclusive scan (metrics_clip, role 2), and the inverse map
 __global__ __launch_bounds__(MT_TPB) void sl_keep(SlArgs a) {
     __shared__ double red[16];
     __shared__ int wtot[16];
-    const int b = blockIdx.x, t = threadIdx.x;
-    const double* lv = a.level + (size_t)b * a.nS;
-    int* src = a.src + (size_t)b * a.nS;
-    int* inv = a.inv + (size_t)b * a.nS;
-    double mx = -INFINITY;
-    bool nan = false;
-    for (int i = t; i < a.nS; i += blockDim.x) {
-        nan |= lv[i] != lv[i];
-        mx = fmax(mx, lv[i]);
-    }
-    // max of the block (NaN propagates like np.max)
-    const int lane = t & 63, wid = t >> 6, nw = blockDim.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
-    nan = __any(nan);
-    if (lane == 0) { red[wid] = mx; wtot[wid] = nan; }
-    __syncthreads();
-    mx = red[0];
-    for (int w = 1; w < nw; ++w) { mx = fmax(mx, red[w]); nan |= wtot[w] != 0; }
-    if (nan) mx = NAN;
-    __syncthreads();
-    int total = 0;
-    for (int i0 = 0; i0 < a.nS; i0 += blockDim.x) {
-        const int i = i0 + t;
-        const bool keep = i < a.nS && ((lv[i] - mx) + MT_STOI_DYN) > 0;
-        const unsigned long long bal = __ballot(keep);
-        const int before = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wtot[wid] = __popcll(bal);
-        __syncthreads();
-        int off = total;
-        for (int w = 0; w < wid; ++w) off += wtot[w];
-        if (keep) src[off + before] = i;
-        if (i < a.nS) inv[i] = keep ? off + before : -1;
-        for (int w = 0; w < nw; ++w) total += wtot[w];
-        __syncthreads();
-    }
-    if (t == 0) a.kept[b] = total;
-}
-
-// overlap-add sample t of the kept frames (at most two sources), in np.add.at's order
-__device__ inline double ola(const double* x10, const int* src, int K, int t, const double* hann) {
-    const int p = t / MT_STOI_HOP;
-    double acc = 0.0;
-    if (p - 1 >= 0 && p - 1 < K) {
-        const int o = t - (p - 1) * MT_STOI_HOP;
-        acc += x10[(size_t)src[p - 1] * MT_STOI_HOP + o] * hann[o];
-    }
-    if (p < K) {
-        const int o = t - p * MT_STOI_HOP;
-        acc += x10[(size_t)src[p] * MT_STOI_HOP + o] * hann[o];
-    }
-    return acc;
+    const int b = blockIdx.x;
+    stoi_keep<true>(a.level, a.nS, a.src, a.inv, a.kept, b, red, wtot);
 }
 
 // band envelopes of envelope frame j of the silence-removed signals (x = reference, y = estimate), and the estimate's bins
@@ -357,37 +136,8 @@ __global__ __launch_bounds__(MT_TPB) void sl_env(SlArgs a) {
     const int K = a.kept[b], nS = a.nS, B = a.B;
     if (j >= K - 1) return;
     const double* tb = a.tb;
-    const int* src = a.src + (size_t)b * nS;
-    const double* hann = tb + TB_HANN;
-    const double* xb = a.r10 + (size_t)b * a.N10;
-    const double* yb = a.e10 + (size_t)b * a.N10;
-    for (int n = t; n < MT_STOI_NFFT; n += blockDim.x) {
-        double vx = 0.0, vy = 0.0;
-        if (n < MT_STOI_N) {
-            const int ts = j * MT_STOI_HOP + n;
-            vx = ola(xb, src, K, ts, hann) * hann[n];
-            vy = ola(yb, src, K, ts, hann) * hann[n];
-        }
-        const int r = bitrev(n, 9);
-        xr[r] = vx; xi[r] = 0.0;
-        yr[r] = vy; yi[r] = 0.0;
-    }
-    __syncthreads();
-    fft2_lds(xr, xi, yr, yi, 9, tb + TB_TW);
-    const int nb = (int)tb[TB_EDGES];
-    if (t < 2 * nb) {
-        const int sig = t / nb, band = t % nb;
-        const double* re = sig ? yr : xr;
-        const double* im = sig ? yi : xi;
-        const double ws = tb[TB_HSUM];
-        const int lo = (int)tb[TB_EDGES + 1 + 2 * band], hi = (int)tb[TB_EDGES + 2 + 2 * band];
-        double e = 0.0;
-        for (int k = lo; k < hi; ++k) {
-            const double r = re[k] / ws, i = im[k] / ws;
-            e += r * r + i * i;
-        }
-        a.env[(((size_t)sig * B + b) * MT_STOI_J + band) * nS + j] = sqrt(e);
-    }
+    stoi_env(a.r10, a.e10, a.N10, nS, a.src, K, j, b, tb + TB_HANN, tb + TB_HSUM, tb + TB_TW, tb + TB_EDGES, a.env, B, xr, xi,
+             yr, yi);
     double* sp = a.spec + ((size_t)b * nS + j) * (2 * SL_BINS);
     for (int k = t; k < SL_BINS; k += blockDim.x) {
         sp[2 * k] = yr[k];
@@ -413,26 +163,8 @@ __global__ __launch_bounds__(64) void sl_corr(SlArgs a, int with_grad) {
         if (t < nb) {
             const double* X = env + ((size_t)b * MT_STOI_J + t) * nS + w;
             const double* Y = env + (((size_t)B + b) * MT_STOI_J + t) * nS + w;
-            double sx2 = 0.0, sy2 = 0.0, sx = 0.0;
-            for (int i = 0; i < MT_STOI_SEG; ++i) { sx2 += X[i] * X[i]; sy2 += Y[i] * Y[i]; sx += X[i]; }
-            const double alpha = sqrt(sx2 / sy2);
-            const double mxv = sx / MT_STOI_SEG;
-            double sy = 0.0;
-            for (int i = 0; i < MT_STOI_SEG; ++i) sy += fmin_nan(Y[i] * alpha, X[i] * (1.0 + clipc));
-            const double myv = sy / MT_STOI_SEG;
-            double nx = 0.0, ny = 0.0;
-            for (int i = 0; i < MT_STOI_SEG; ++i) {
-                const double a = X[i] - mxv, c = fmin_nan(Y[i] * alpha, X[i] * (1.0 + clipc)) - myv;
-                nx += a * a;
-                ny += c * c;
-            }
-            nx = sqrt(nx);
-            ny = sqrt(ny);
-            double s = 0.0;
-            for (int i = 0; i < MT_STOI_SEG; ++i) {
-                const double a = X[i] - mxv, c = fmin_nan(Y[i] * alpha, X[i] * (1.0 + clipc)) - myv;
-                s += (a / nx) * (c / ny);
-            }
+            const BandCorr c = stoi_band_corr(X, Y, clipc);
+            const double s = c.s, alpha = c.alpha, sy2 = c.sy2, mxv = c.mx, myv = c.my, nx = c.nx, ny = c.ny;
             sc[t] = s;
             if (with_grad) {
                 // u_i = (xn_i - yn_i s) / ny;  q_i = u_i - mean u;  T = sum m_i q_i Y_i
@@ -476,8 +208,8 @@ __global__ __launch_bounds__(64) void sl_corr(SlArgs a, int with_grad) {
             for (int i = 0; i < MT_STOI_SEG; ++i) { const double u = V[i] - m; q += u * u; }
             const double n = sqrt(q);
             double* out = sig ? ya[t] : xa[t];
-            for (int i = 0; i < MT_STOI_SEG; ++i) sl_put(out + i, (V[i] - m) / n);
-            if (sig) sl_put(rown + t, n);
+            for (int i = 0; i < MT_STOI_SEG; ++i) lds_put(out + i, (V[i] - m) / n);
+            if (sig) lds_put(rown + t, n);
         }
     }
     __syncthreads();
@@ -492,12 +224,12 @@ __global__ __launch_bounds__(64) void sl_corr(SlArgs a, int with_grad) {
             double e = 0.0;
             for (int q = 0; q < nb; ++q) { const double u = in[q][t] - m; e += u * u; }
             const double n = sqrt(e);
-            for (int q = 0; q < nb; ++q) sl_put(&out[q][t], (in[q][t] - m) / n);
-            if (sig) sl_put(coln + t, n);
+            for (int q = 0; q < nb; ++q) lds_put(&out[q][t], (in[q][t] - m) / n);
+            if (sig) lds_put(coln + t, n);
         }
         double p = 0.0;
         for (int q = 0; q < nb; ++q) p += cx[q][t] * cy[q][t];
-        sl_put(sc + t, p);
+        lds_put(sc + t, p);
     }
     __syncthreads();
     if (t == 0) {
@@ -514,7 +246,7 @@ __global__ __launch_bounds__(64) void sl_corr(SlArgs a, int with_grad) {
         double su = 0.0;
         for (int q = 0; q < nb; ++q) su += (cx[q][t] / MT_STOI_SEG - cy[q][t] * dot) / n;
         const double mu = su / (double)nb;
-        for (int q = 0; q < nb; ++q) sl_put(&cx[q][t], (cx[q][t] / MT_STOI_SEG - cy[q][t] * dot) / n - mu);
+        for (int q = 0; q < nb; ++q) lds_put(&cx[q][t], (cx[q][t] / MT_STOI_SEG - cy[q][t] * dot) / n - mu);
     }
     __syncthreads();
     // back through the rows
@@ -567,7 +299,7 @@ __global__ __launch_bounds__(MT_TPB) void sl_env_grad(SlArgs a) {
     const double* tb = a.tb;
     const int nb = (int)tb[TB_EDGES];
     const int nW = K - MT_STOI_SEG;
-    for (int n = t; n < MT_STOI_NFFT; n += blockDim.x) { sl_put(xr + n, 0.0); sl_put(xi + n, 0.0); sl_put(yr + n, 0.0); sl_put(yi + n, 0.0); }
+    for (int n = t; n < MT_STOI_NFFT; n += blockDim.x) { lds_put(xr + n, 0.0); lds_put(xi + n, 0.0); lds_put(yr + n, 0.0); lds_put(yi + n, 0.0); }
     if (t < 2 * nb) {
         const int f = t / nb, band = t % nb, j = j0 + f;
         double g = 0.0;
@@ -577,7 +309,7 @@ __global__ __launch_bounds__(MT_TPB) void sl_env_grad(SlArgs a) {
             for (int w = w0; w <= w1; ++w) g += D[(size_t)w * (MT_STOI_J * MT_STOI_SEG) + (j - w)];
             g *= a.coef[b];
         }
-        sl_put(&gb[f][band], g);
+        lds_put(&gb[f][band], g);
     }
     __syncthreads();
     const double ws = tb[TB_HSUM];
@@ -593,8 +325,8 @@ __global__ __launch_bounds__(MT_TPB) void sl_env_grad(SlArgs a) {
         const double* sp = a.spec + ((size_t)b * nS + j) * (2 * SL_BINS);
         const double c = gb[f][band] / (ws * ws * e);
         const int r = bitrev(k, 9);
-        if (f == 0) { sl_put(xr + r, c * sp[2 * k]); sl_put(xi + r, -(c * sp[2 * k + 1])); }
-        else        { sl_put(yr + r, c * sp[2 * k]); sl_put(yi + r, -(c * sp[2 * k + 1])); }
+        if (f == 0) { lds_put(xr + r, c * sp[2 * k]); lds_put(xi + r, -(c * sp[2 * k + 1])); }
+        else        { lds_put(yr + r, c * sp[2 * k]); lds_put(yi + r, -(c * sp[2 * k + 1])); }
     }
     __syncthreads();
     fft2_lds(xr, xi, yr, yi, 9, tb + TB_TW);
@@ -657,8 +389,6 @@ struct SlPlan {
     size_t tb, r10, e10, level, src, inv, kept, env, spec, corr, dw, coef, z, g10, total;   // byte offsets
 };
 
-inline size_t sl_up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // null: fine; else what is wrong with the shape (code in *rc)
 inline const char* sl_plan(int B, int L, int fs, SlPlan& p, int* rc) {
     *rc = CMGAN_E_BADARG;
@@ -667,14 +397,11 @@ inline const char* sl_plan(int B, int L, int fs, SlPlan& p, int* rc) {
     if (L < 1) return "L is too short for 31 frames at 10 kHz";
     Geom g;
     geom_of(fs, g);
-    const long long n10 = ((long long)L * g.up + g.down - 1) / g.down;
-    const long long nS = n10 > MT_STOI_N ? (n10 - MT_STOI_N + MT_STOI_HOP - 1) / MT_STOI_HOP : 0;
-    if (nS < MT_STOI_SEG + 1) return "L is too short for 31 frames at 10 kHz";
+    stoi_frames(L, g, &p.N10, &p.nS);
+    if (p.nS < MT_STOI_SEG + 1) return "L is too short for 31 frames at 10 kHz";
     if (L > 2147483647 / g.up - 4096) return "rows are too long";
-    p.N10 = (int)n10;
-    p.nS = (int)nS;
     size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = sl_up256(o + bytes); return at; };
+    auto take = [&](size_t bytes) { size_t at = o; o = up256(o + bytes); return at; };
     const size_t d = sizeof(double), Bz = (size_t)B, S = (size_t)p.nS;
     p.tb = take(TB_TOTAL * d);
     p.r10 = take(Bz * p.N10 * d);
@@ -693,11 +420,6 @@ inline const char* sl_plan(int B, int L, int fs, SlPlan& p, int* rc) {
     p.total = o;
     *rc = CMGAN_OK;
     return nullptr;
-}
-
-inline bool sl_overlap(const void* p, const void* q, size_t bytes) {
-    const uintptr_t p0 = (uintptr_t)p, q0 = (uintptr_t)q;
-    return p0 < q0 + bytes && q0 < p0 + bytes;
 }
 
 }  // namespace
@@ -721,7 +443,7 @@ extern "C" int cmgan_stoi_loss(cmgan_handle* h, const float* est, const float* r
     if (extended != 0 && extended != 1) return fail(h, CMGAN_E_BADARG, "cmgan_stoi_loss: extended must be 0 or 1");
     if (!(k == k)) return fail(h, CMGAN_E_BADARG, "cmgan_stoi_loss: k must be a number");
     const size_t bytes = (size_t)B * (size_t)L * sizeof(float);
-    if (g_audio && (sl_overlap(g_audio, est, bytes) || sl_overlap(g_audio, ref, bytes)))
+    if (g_audio && (bytes_overlap(g_audio, bytes, est, bytes) || bytes_overlap(g_audio, bytes, ref, bytes)))
         return fail(h, CMGAN_E_BADARG, "cmgan_stoi_loss: g_audio overlaps est or ref; the gradient is not formed in place");
     if (!ws || ((uintptr_t)ws & 255) || ws_bytes < p.total)
         return fail(h, CMGAN_E_BADARG, "cmgan_stoi_loss: the workspace must be 256-byte aligned and hold %zu bytes (%zu given)",

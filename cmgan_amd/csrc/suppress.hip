@@ -30,11 +30,14 @@
 // E1 by two fixed formulas (the header states them): a Horner series of SP_E1_TERMS fused multiply-adds below 2, with the
 // coefficients riding in the kernel arguments (scalar registers), and from 2 on a continued fraction of depth
 // SP_E1_DEPTH run backwards as a ratio (n, d), two products and a difference per level and ONE division at the end.
+// The LDS store rule, the twiddles and the radix-2 passes are lds_f64.hip.h's, shared with auxloss.hip and stoiloss.hip.
 #include <float.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "api_internal.h"
+#include "host_ranges.h"
+#include "lds_f64.hip.h"
 
 namespace {
 
@@ -86,57 +89,13 @@ __device__ inline SpRow sp_row(const SuppressArgs& a, int b) {
     return r;
 }
 
-// a complex value into LDS as two 64-bit stores: a store of more than 64 bits keeps reading its data registers after it
-// issues, and the compiler does not guard them against the next VALU write (tools/isa_lint.py)
-typedef __attribute__((address_space(3))) volatile double lds_double;       // (volatile: not merged; LDS by name, or it goes flat)
-
-__device__ inline void sp_put(double2* p, double re, double im) {
-    lds_double* q = (lds_double*)p;
-    q[0] = re;
-    q[1] = im;
-}
-
-__device__ inline int sp_bitrev(int k, int logN) { return (int)(__brev((unsigned)k) >> (32 - logN)); }
-
-// tw[k] = e^{-2 pi i k / N}, k < N / 2: the argument 2 k / N is exact
-__device__ inline void sp_twiddles(double2* tw, int N) {
-    for (int k = threadIdx.x; k < (N >> 1); k += SP_TPB) {
-        double s, c;
-        sincospi((double)(2 * k) / (double)N, &s, &c);
-        sp_put(tw + k, c, -s);
-    }
-}
-
-// the radix-2 decimation-in-time passes over `count` bit-reversed frames of N points, SP_MAX_N apart, in LDS; sign = -1
-// conjugates the twiddles (the inverse, without its 1 / N).  Every product is a fused multiply-add by name, so the bits do
-// not hang on the build's contraction.  Ends behind a barrier.
-__device__ inline void sp_fft(double2* buf, const double2* tw, int N, int logN, double sign, int count) {
-    const int half_n = N >> 1;
-    for (int s = 1; s <= logN; ++s) {
-        __syncthreads();
-        const int half = 1 << (s - 1);
-        for (int j = threadIdx.x; j < half_n * count; j += SP_TPB) {
-            const int fr = j / half_n, jj = j - fr * half_n;
-            const int pos = jj & (half - 1);
-            const int i0 = ((jj >> (s - 1)) << s) + pos + fr * SP_MAX_N, i1 = i0 + half;
-            double2 w = tw[pos << (logN - s)];
-            w.y *= sign;
-            const double2 u = buf[i0], v = buf[i1];
-            const double vr = fma(v.x, w.x, -(v.y * w.y)), vi = fma(v.x, w.y, v.y * w.x);
-            sp_put(buf + i0, u.x + vr, u.y + vi);
-            sp_put(buf + i1, u.x - vr, u.y - vi);
-        }
-    }
-    __syncthreads();
-}
-
 __global__ __launch_bounds__(SP_TPB) void suppress_analyse(SuppressArgs a) {
     __shared__ double2 s_buf[SP_MAX_N];
     __shared__ double2 s_tw[SP_MAX_N / 2];
     const int t = blockIdx.x, b = blockIdx.y, N = a.N, h = N >> 1, F = h + 1;
     const SpRow r = sp_row(a, b);
     if (r.rule == 0 || t >= r.Tb) return;                               // block-uniform
-    sp_twiddles(s_tw, N);
+    twiddles<SP_TPB>(s_tw, N);
     const size_t at = ((size_t)b * a.T + t) * F;
     const int passes = a.key ? 2 : 1;
     for (int pass = 0; pass < passes; ++pass) {                         // ONE body for the signal and the key
@@ -145,9 +104,9 @@ __global__ __launch_bounds__(SP_TPB) void suppress_analyse(SuppressArgs a) {
         for (int k = threadIdx.x; k < N; k += SP_TPB) {
             const long long i = (long long)(t - 1) * h + k;
             const double v = (i >= 0 && i < r.n) ? (double)src[i] : 0.0;
-            sp_put(s_buf + sp_bitrev(k, a.logN), v * sinpi((double)k / (double)N), 0.0);
+            lds_put(s_buf + bitrev(k, a.logN), v * sinpi((double)k / (double)N), 0.0);
         }
-        sp_fft(s_buf, s_tw, N, a.logN, 1.0, 1);
+        fft<SP_TPB>(s_buf, s_tw, N, a.logN, 1.0, 1, SP_MAX_N);          // (one frame through the many-frames form, as ever)
         for (int f = threadIdx.x; f < F; f += SP_TPB) {
             const double2 v = s_buf[f];
             if (pass == 0) a.Y[at + f] = v;
@@ -191,7 +150,7 @@ __global__ __launch_bounds__(SP_LANES) void suppress_gain(SuppressArgs a) {
         return;
     }
     double* ag = a.AG + at;
-    lds_double* ring = (lds_double*)(s_ring + lane);                     // (64-bit stores that stay 64-bit: sp_put's reason)
+    lds_double* ring = (lds_double*)(s_ring + lane);                     // (64-bit stores that stay 64-bit: lds_f64.hip.h)
     const double oma_n = 1.0 - r.a_n, oma_dd = 1.0 - r.a_dd;
     const int D = r.D;
     double A = r.Tb > 0 ? ag[0] : 0.0;
@@ -249,7 +208,7 @@ __global__ __launch_bounds__(SP_TPB) void suppress_synth(SuppressArgs a) {
         }
         return;
     }
-    sp_twiddles(s_tw, N);
+    twiddles<SP_TPB>(s_tw, N);
     // frames j and j + 1 (both below T_b, because i0 < n): G Y on bins 0 .. N / 2, its conjugate on the mirrored bins
     for (int k = threadIdx.x; k < 2 * F; k += SP_TPB) {
         const int fr = k / F, f = k - fr * F;
@@ -258,10 +217,10 @@ __global__ __launch_bounds__(SP_TPB) void suppress_synth(SuppressArgs a) {
         const double2 v = a.Y[at];
         const bool edge = f == 0 || f == h;                             // their imaginary parts do not reach a real output
         const double re = g * v.x, im = edge ? 0.0 : g * v.y;
-        sp_put(s_buf + fr * SP_MAX_N + sp_bitrev(f, a.logN), re, im);
-        if (!edge) sp_put(s_buf + fr * SP_MAX_N + sp_bitrev(N - f, a.logN), re, -im);
+        lds_put(s_buf + fr * SP_MAX_N + bitrev(f, a.logN), re, im);
+        if (!edge) lds_put(s_buf + fr * SP_MAX_N + bitrev(N - f, a.logN), re, -im);
     }
-    sp_fft(s_buf, s_tw, N, a.logN, -1.0, 2);
+    fft<SP_TPB>(s_buf, s_tw, N, a.logN, -1.0, 2, SP_MAX_N);
     const double inv = 1.0 / (double)N;                                 // a power of two: exact
     for (int k = threadIdx.x; k < h; k += SP_TPB) {
 #pragma clang fp contract(off)
@@ -275,8 +234,6 @@ __global__ __launch_bounds__(SP_TPB) void suppress_synth(SuppressArgs a) {
         }
     }
 }
-
-inline size_t sp_up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 inline bool sp_shape_ok(int B, int L, int N) {
     return B >= 1 && B <= 65535 && L >= 1 && L <= SP_MAX_L && (N == 256 || N == 512 || N == 1024);
@@ -294,16 +251,9 @@ inline SpLayout sp_layout(int B, int L, int N) {
     l.F = h + 1;
     const size_t cells = (size_t)B * (size_t)l.T * (size_t)l.F;
     l.Y = 0;
-    l.AG = sp_up256(cells * 2 * sizeof(double));
-    l.total = l.AG + sp_up256(cells * sizeof(double));
+    l.AG = up256(cells * 2 * sizeof(double));
+    l.total = l.AG + up256(cells * sizeof(double));
     return l;
-}
-
-// do the spans [p, p + (B-1) ld + L) of two float32 batches intersect?
-inline bool sp_overlap(const float* p, long long ldp, const float* q, long long ldq, int B, int L) {
-    const uintptr_t p0 = (uintptr_t)p, p1 = p0 + ((size_t)(B - 1) * (size_t)ldp + (size_t)L) * sizeof(float);
-    const uintptr_t q0 = (uintptr_t)q, q1 = q0 + ((size_t)(B - 1) * (size_t)ldq + (size_t)L) * sizeof(float);
-    return p0 < q1 && q0 < p1;
 }
 
 }  // namespace
@@ -332,9 +282,9 @@ extern "C" int cmgan_suppress(cmgan_handle* h, const float* x, int B, int L, lon
                     "ldy=%lld ldk=%lld)", B, L, ldx, ldy, ldk);
     if (L > SP_MAX_L)
         return fail(h, CMGAN_E_BADARG, "cmgan_suppress: rows of up to %d samples are supported (L=%d)", SP_MAX_L, L);
-    if (!((const float*)y == x && ldy == ldx) && sp_overlap(x, ldx, y, ldy, B, L))   // in place is the one overlap there may be
+    if (!((const float*)y == x && ldy == ldx) && rows_overlap(x, ldx, y, ldy, B, L))   // in place is the one overlap there may be
         return fail(h, CMGAN_E_BADARG, "cmgan_suppress: x and y overlap; only y == x with ldy == ldx (in place) is allowed");
-    if (key && !((const float*)y == key && ldy == ldk) && sp_overlap(key, ldk, y, ldy, B, L))
+    if (key && !((const float*)y == key && ldy == ldk) && rows_overlap(key, ldk, y, ldy, B, L))
         return fail(h, CMGAN_E_BADARG, "cmgan_suppress: key and y overlap; only y == key with ldy == ldk is allowed");
     const SpLayout l = sp_layout(B, L, n_fft);
     if (!ws || ((uintptr_t)ws & 255) || ws_bytes < l.total)
